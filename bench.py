@@ -23,6 +23,10 @@ A "step" is one pass of the hot path over one batch of synthetic input:
       O(N^2) decoder is not part of this config (2.8e14 logits); the encoder's
       upstream gradient dZ is a fixed synthetic tensor.  Strong scaling.
 
+The timed region is exactly --steps steps, run once between barrier + synchronize; `ms_per_step` = its length /
+--steps.  `--dump-outputs DIR` writes what the last timed step left a caller (loss, parameters, Adam moments) as
+DIR/<name>.npy.
+
 value = SpMM edges aggregated per step (forward + backward launches, all ranks)
 / step time: whole-job, inputs resident in HBM, max over ranks.  `value_spmm_only`
 = the same edges / the HIP-event time of the step's SpMM launches alone.
@@ -37,7 +41,8 @@ value = SpMM edges aggregated per step (forward + backward launches, all ranks)
 `roofline_step_dominant`: the fused decoder + BCE against the measured issue rate.
 `cpu_baseline`: the CPU oracle's restatement of the same step on this host.
 `extra`     : kernel-only SpMM numbers (warm and cold) for the other BASELINE shapes,
-              whole steps of the other single-GPU configurations.
+              whole steps of the other single-GPU configurations; one JSON object on
+              stderr (`[bench] extra: {...}`), not part of the result line.
 N > 1: `rccl_ranks`, `preflight` (every collective primitive checked against known
 answers before the workload is built), `comm` (exchange vs SpMM time per step).
 """
@@ -170,7 +175,16 @@ def parse():
                          "recorded inside a replay, so the per-kernel event timings of `roofline` come from an eager "
                          "pass of the SAME steps immediately before the capture (with --no-hipgraph they sit inside "
                          "the timed region)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them left a caller -- the loss it returned, the "
+                         "model's parameters and the Adam moments -- as DIR/<name>.npy (float32 / float64, at most 64 MB "
+                         "in all: a larger array as a fixed seeded sample; with N ranks rank 0 writes, a per-rank output named as "
+                         "its shard).  The inputs depend on the arguments only, so two builds run with the same "
+                         "arguments compare output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def pmc_traffic(key):
@@ -1030,7 +1044,7 @@ def extra_steps(args, dev):
             wl.capture()
             for _ in range(a.warmup):
                 wl.step()
-        regions = timed_regions(wl, a, torch.cuda.synchronize, 1, dev, min_total_s=0.3, max_regions=50)
+        regions, _ = timed_regions(wl, a, torch.cuda.synchronize, 1, dev, min_total_s=0.3, max_regions=50)
         el = float(np.median(regions)) / a.steps
         dom_fn = wl.dominant_launch()
         t_dom = time_launches(dom_fn, iters=50, warmup=30)
@@ -1064,9 +1078,11 @@ class MockWorkload:
         self.edges_per_step = 1000 * world
         self.meta = {"workload": "mock (launcher self-test, CPU/gloo; not a measurement)", "parallelism": f"x{world}"}
         self.scaling = "weak"
+        self.calls = 0
 
     def step(self):
-        t = self.t.clone()
+        self.calls += 1
+        t = self.t * self.calls             # the output tells how many steps ran
         if self.world > 1:
             self.dist.all_reduce(t, group=self.group)
         return t
@@ -1196,17 +1212,19 @@ def launch_ranks(args):
     return subprocess.call(cmd, env=env)
 
 
-def timed_regions(wl, args, barrier, world, dev, min_total_s=0.5, max_regions=200):
+def timed_regions(wl, args, barrier, world, dev, min_total_s=0.0, max_regions=200):
     """The contract's timed region -- EXACTLY --steps steps between barrier + synchronize on both sides, MAX over
-    ranks -- repeated until the regions add up to >= min_total_s (a 20-step region of a 0.25 ms step is 5 ms: clock
-    ramp and scheduling noise).  Returns the per-region seconds (the same list on every rank)."""
+    ranks.  The headline runs it once (``min_total_s`` = 0: --steps is the number of timed steps); the extra
+    configurations repeat it until the regions add up to >= min_total_s.  Returns the per-region seconds (the same
+    list on every rank) and what the last step returned."""
     import torch.distributed as dist
     out = []
     while True:
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             wl.step()
+        last = wl.step()
         barrier()
         el = time.perf_counter() - t0
         if world > 1:
@@ -1216,7 +1234,7 @@ def timed_regions(wl, args, barrier, world, dev, min_total_s=0.5, max_regions=20
             el = float(tt)
         out.append(el)
         if sum(out) >= min_total_s or len(out) >= max_regions:      # same decision on every rank (max-reduced times)
-            return out
+            return out, last
 
 
 def region_stats(regions, steps):
@@ -1224,9 +1242,51 @@ def region_stats(regions, steps):
     return {"regions": len(regions), "steps_per_region": steps, "ms_per_step_median": float(np.median(ms)),
             "ms_per_step_min": float(ms.min()), "ms_per_step_max": float(ms.max()),
             "ms_per_step_first_region": float(ms[0]),
-            "note": "every region is the contract's timed region (barrier + synchronize, exactly --steps steps, max "
-                    "over ranks); regions are repeated until they add up to >= 0.5 s; `ms_per_step` / `value` are "
-                    "the median region"}
+            "note": "the contract's timed region (barrier + synchronize, exactly --steps steps, max over ranks), run "
+                    "once; `ms_per_step` / `value` are that region"}
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: at most this much in all, .npy headers included
+NPY_HEADER_BYTES = 4096     # room kept per file for its header (numpy writes 128 bytes for these shapes)
+
+
+def step_outputs(wl, last, rank=0, world=1):
+    """what a caller of the timed path holds after its last step: the value the step returned (the loss of a training
+    step; the encoder output Z of the rmat step -- with N ranks only this rank's row shard of it, named so), the
+    model's parameters and the Adam moments as that step left them"""
+    out = {}
+    if torch.is_tensor(last):
+        if last.numel() == 1:
+            out["loss"] = last
+        else:
+            out["output" if world == 1 else f"output.rank{rank}_of_{world}_rows"] = last
+    model, opt = getattr(wl, "model", None), getattr(wl, "opt", None)
+    for k, p in (model.named_parameters() if model is not None else ()):
+        out[f"param.{k}"] = p
+        st = opt.state.get(p, {}) if opt is not None else {}
+        for m in ("exp_avg", "exp_avg_sq"):
+            if torch.is_tensor(st.get(m)):
+                out[f"adam.{k}.{m}"] = st[m]
+    return out
+
+
+def dump_outputs(arrays, out_dir):
+    """one DIR/<name>.npy per array: float64 stays float64, integer and bool arrays are written as float64 (exact up
+    to 2^53), every other dtype as float32.  An array larger than its equal share of DUMP_BYTES is written as a fixed
+    sample -- the flat elements at distinct seeded random positions, sorted, the same positions on every run for the
+    same size -- and named on stderr"""
+    os.makedirs(out_dir, exist_ok=True)
+    n = max(len(arrays), 1)
+    cap = max(1, (DUMP_BYTES - n * NPY_HEADER_BYTES) // 8 // n)          # elements per array, counted at 8 bytes
+    for name, t in arrays.items():
+        a = t.detach()
+        a = a.double() if a.dtype == torch.float64 or not a.is_floating_point() else a.float()
+        if a.numel() > cap:
+            pos = np.sort(np.random.default_rng(0).choice(a.numel(), cap, replace=False))
+            a = a.reshape(-1)[torch.from_numpy(pos).to(a.device)]
+            print(f"[bench] --dump-outputs: {name} holds {t.numel()} elements, written as a seeded sample of {cap}",
+                  file=sys.stderr, flush=True)
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
 
 
 def main():
@@ -1288,8 +1348,11 @@ def main():
         wl = MockWorkload(args, rank, world, group)
         for _ in range(args.warmup):
             wl.step()
-        regions = timed_regions(wl, args, barrier, world, dev, min_total_s=0.05, max_regions=5)
+        regions, last = timed_regions(wl, args, barrier, world, dev)
         elapsed = float(np.median(regions))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(step_outputs(wl, last, rank, world), args.dump_outputs)
+        del last
         if dist.is_initialized():
             dist.barrier()
             dist.destroy_process_group()
@@ -1387,8 +1450,12 @@ def main():
             wl.step()
         barrier()
         ops.profiler = None
-    regions = timed_regions(wl, args, barrier, world, dev)
+    regions, last = timed_regions(wl, args, barrier, world, dev)
     elapsed = float(np.median(regions))
+    if args.dump_outputs and rank == 0:
+        # before anything else runs: the measurements below launch more steps and would move the parameters on
+        dump_outputs(step_outputs(wl, last, rank, world), args.dump_outputs)
+    del last
     dom_fn = wl.dominant_launch() if hasattr(wl, "dominant_launch") else None   # may contain a collective
     comm = wl.comm_profile() if hasattr(wl, "comm_profile") else None              # collective: every rank
     one_gpu = None
@@ -1401,7 +1468,7 @@ def main():
             w1 = RmatShardedWorkload(args, dev, 0, 1, g1)
             for _ in range(max(2, min(args.warmup, 5))):
                 w1.step()
-            r1 = timed_regions(w1, args, torch.cuda.synchronize, 1, dev)
+            r1, _ = timed_regions(w1, args, torch.cuda.synchronize, 1, dev)
             e1 = float(np.median(r1))
             one_gpu = {"value": w1.edges_per_step * args.steps / e1, "ms_per_step": e1 / args.steps * 1e3,
                        "timing": region_stats(r1, args.steps),
@@ -1617,7 +1684,9 @@ def main():
     if not args.no_extra and world == 1 and workload not in ("rmat",):
         del wl
         torch.cuda.empty_cache()
-        line["extra"] = {"steps": extra_steps(args, dev), "spmm_kernel_only": extras(dev)}
+        # stderr, not the result line: with it the line outgrows what a reader of the last stdout line takes in
+        extra = {"steps": extra_steps(args, dev), "spmm_kernel_only": extras(dev)}
+        print("[bench] extra: " + json.dumps(extra), file=sys.stderr, flush=True)
     if dist.is_initialized():
         if world > 1:
             dist.barrier()

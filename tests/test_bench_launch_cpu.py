@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -70,3 +71,57 @@ def test_gpus8_line_schema_and_collective_preflight():
         assert pf[k] == "ok", (k, pf[k])
     assert pf["ranks_agree_all_ok"] is True
     assert r.stderr.count("rccl_ranks 8") == 8       # every rank reported its device (the ranks' lines may interleave)
+
+
+def test_steps_set_the_timed_steps_and_dump_outputs(tmp_path):
+    """--steps is the number of timed steps (one timed region), and --dump-outputs writes what the last of them
+    returned: the mock's output is its step count, so after --warmup 2 and --steps 5 it holds 7 -- the same on a
+    second run with the same arguments"""
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--workload", "mock", "--dump-outputs", str(out)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 5 and line["timing"]["regions"] == 1 and line["timing"]["steps_per_region"] == 5
+        assert line["ms_per_step"] > 0
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["output.npy"], files
+        a = np.load(out / "output.npy")
+        assert a.dtype in (np.float32, np.float64) and a.shape == (16,)
+        assert np.all(a == 7.0), a
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_dump_outputs_caps_the_size(tmp_path):
+    """arrays beyond their share of 64 MB (headers included) are written as the same seeded sample of distinct
+    positions on every call; float64 stays float64, integers become float64, other floats float32"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(8 << 20, dtype=torch.float32)
+    arrays = {"big": big, "small": torch.ones(3, 4, dtype=torch.float64), "half": torch.ones(5, dtype=torch.float16),
+              "steps": torch.tensor(3)}
+    for d in ("a", "b"):
+        bench.dump_outputs(arrays, str(tmp_path / d))
+    total = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    assert total <= 64 << 20
+    s = np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and s.ndim == 1 and 0 < s.size < big.numel()
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    assert np.all(np.diff(s) > 0) and np.all(s == np.floor(s))              # distinct sorted positions of arange: its values
+    assert np.load(tmp_path / "a" / "small.npy").dtype == np.float64
+    assert np.load(tmp_path / "a" / "half.npy").dtype == np.float32
+    steps = np.load(tmp_path / "a" / "steps.npy")
+    assert steps.dtype == np.float64 and float(steps) == 3.0
+
+
+def test_dump_outputs_of_two_ranks_names_the_shard(tmp_path):
+    """with N ranks only rank 0 writes, and a per-rank output is named as rank 0's share"""
+    out = tmp_path / "out"
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "mock", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(p.name for p in out.iterdir()) == ["output.rank0_of_2_rows.npy"]
+    assert np.all(np.load(out / "output.rank0_of_2_rows.npy") == 3 * 4.0)      # 4 steps, ranks' 1 + 2 all-reduced

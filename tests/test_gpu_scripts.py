@@ -418,19 +418,23 @@ def test_sparse_features_refuse_a_near_dense_column():
     assert G.SparseFeatures.maybe_from_dense(Xd) is Xd
 
 
-def test_default_bench_line_carries_the_contract_fields():
-    """`python bench.py` (N = 1, the headline Pubmed step; short run without the extras): ONE JSON line with the contract's
-    keys; `roofline` is the SpMM aggregation with a MALL-cold fraction beside the warm one, `roofline_dense` the dense
-    layer-1 pair, `cpu_baseline` a timed CPU restatement on this host's cores"""
+def test_default_bench_line_carries_the_contract_fields(tmp_path):
+    """`python bench.py` (N = 1, the headline Pubmed step, with the extras): ONE JSON line with the contract's keys, short
+    enough for a reader of the last stdout line (the extras go to stderr); `roofline` is the SpMM aggregation with a
+    MALL-cold fraction beside the warm one, `roofline_dense` the dense layer-1 pair, `cpu_baseline` a timed CPU
+    restatement on this host's cores; --dump-outputs leaves the last timed step's loss, parameters and Adam moments"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3", "--no-extra",
-                        "--cpu-seconds", "2"], capture_output=True, text=True, timeout=900, cwd=root)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3",
+                        "--cpu-seconds", "2", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900,
+                       cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0]           # the LAST line of stdout
+    assert len(lines[0]) < 16_000 and "[bench] extra: {" in r.stderr
     line = json.loads(lines[0])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -451,3 +455,14 @@ def test_default_bench_line_carries_the_contract_fields():
     cb = line["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == "edges/s" and cb["sample"]
     assert line["roofline_step_dominant"]["kernel"].startswith("fused decoder + BCE")
+    assert line["timing"]["regions"] == 1 and line["timing"]["steps_per_region"] == 10
+    loss = np.load(dump / "loss.npy")
+    assert loss.dtype in (np.float32, np.float64) and loss.size == 1 and np.isfinite(loss).all() and float(loss) > 0
+    shapes = {"layers.0.apply_mod.linear.weight": (32, 500), "layers.0.apply_mod.linear.bias": (32,),
+              "layers.1.apply_mod.linear.weight": (16, 32), "layers.1.apply_mod.linear.bias": (16,)}
+    for k, shape in shapes.items():
+        for name in (f"param.{k}", f"adam.{k}.exp_avg", f"adam.{k}.exp_avg_sq"):
+            a = np.load(dump / f"{name}.npy")
+            assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
+        assert (np.load(dump / f"adam.{k}.exp_avg_sq.npy") > 0).any()       # the moments of steps that ran
+    assert sum(p.stat().st_size for p in dump.iterdir()) <= 64 << 20

@@ -52,6 +52,12 @@ for name in ("pubmed", "pubmed_reference_order", "cora", "citeseer", "cora_dense
     p = os.path.join(SRC, f"bench_{name}.json")
     if os.path.exists(p):
         benches[name] = last_json(p)
+        # bench.py prints `extra` on stderr (`[bench] extra: {...}`), which collect.sh keeps in bench_<name>.err
+        err = os.path.join(SRC, f"bench_{name}.err")
+        if "extra" not in benches[name] and os.path.exists(err):
+            for l in open(err):
+                if l.startswith("[bench] extra: "):
+                    benches[name]["extra"] = json.loads(l[len("[bench] extra: "):])
         json.dump(benches[name], open(os.path.join(DST, f"{TAG}_bench_{name}.json"), "w"), indent=1)
 for w in ("pubmed", "cora", "citeseer", "vgae", "zinc", "zinc128", "rmat"):
     st = os.path.join(SRC, f"prof_{w}", "bench_kernel_stats.csv")
