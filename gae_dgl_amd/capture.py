@@ -141,12 +141,18 @@ class CapturedInductiveStep:
                 ...
     """
 
-    def __init__(self, model, optimizer, dataset, batch_size, warmup=2, margin=1.005, group=None, replicas=False):
+    def __init__(self, model, optimizer, dataset, batch_size, warmup=2, margin=1.005, group=None, replicas=False,
+                 loss_scope="batch"):
         """``replicas`` (with ``group``, default process group when None): data-parallel replicas -- every rank replays
         its own batches; the parameter gradients are averaged over the ranks by ONE all-reduce (RCCL, part of the
         captured graph) between the backward pass and the optimiser launch, and the batch capacities are agreed on
         (all-reduce MAX) so that every rank captures at the same steps.  Every rank must run the same number of
-        steps per epoch (dataset.shard_order)."""
+        steps per epoch (dataset.shard_order).
+        ``loss_scope``: "batch" (the reference's loss over the whole block-diagonal batch) or "graph" (per member graph,
+        averaged over the members: GAE.reconstruction_loss(g, scope="graph")), for the captured and the tail steps."""
+        if loss_scope not in ("batch", "graph"):
+            raise ValueError(f"loss_scope: 'batch' or 'graph', not {loss_scope!r}")
+        self.loss_scope = loss_scope
         self.group, self.replicas = group, bool(replicas)
         if self.replicas:
             import torch.distributed as dist
@@ -209,7 +215,8 @@ class CapturedInductiveStep:
         g.block_diag = None                     # its cuts are host-side and batch-specific: the table kernels run here
         g._cache["plan"] = ops.table_plan(table, W)
         g._cache["plan_t"] = ops.table_plan(t_table, W)
-        g._cache["graph_ptr"] = self.ptrs[0]
+        g._cache["graph_ptr"] = self.ptrs[0]      # member offsets of the static batch (both collate paths write them)
+        g.max_member_nodes = ds.max_nodes
         g.batch_counts = self.counts
         self.g, self.x = g, feat[:, :F]
 
@@ -237,8 +244,8 @@ class CapturedInductiveStep:
             g._cache.pop(key, None)
         g.ndata.clear()
         g.ndata['h'] = self.x
-        with _defer(self.opt, True, grads=not self.replicas):
-            loss = self.model.reconstruction_loss(g)
+        with _defer(self.opt, self.loss_scope == "batch", grads=not self.replicas):
+            loss = self.model.reconstruction_loss(g, scope=self.loss_scope)
             ops.backward(loss, self._params)      # autograd.grad: no AccumulateGrad nodes (stream-bound) in the capture
             if self.replicas:                     # 1 808 floats for the 39 -> 32 -> 16 model: one small all-reduce
                 from .parallel import allreduce_grads
@@ -370,7 +377,7 @@ class CapturedInductiveStep:
             return None
         bg = self.ds._assemble(self.d_order[lo:len(order)], order[lo:])
         self.opt.zero_grad(set_to_none=True)
-        loss = self.model.reconstruction_loss(bg)
+        loss = self.model.reconstruction_loss(bg, scope=self.loss_scope)
         ops.backward(loss)
         if self.replicas:
             from .parallel import allreduce_grads

@@ -187,15 +187,27 @@ class GAE(nn.Module):
     def encode(self, g):
         return self._embed(g, write_back=False)
 
-    def reconstruction_loss(self, g, criterion="bce"):
+    def reconstruction_loss(self, g, criterion="bce", scope="batch"):
         """The training loss of train_inductive.py:44-48 (dense label from g,
         pos_weight, BCE-with-logits mean over all N^2 ordered pairs) evaluated
         by the fused HIP kernel: numerically the same quantity as
         ``BCELoss(self.forward(g), adj, pos_weight)`` without the N x N logits /
         label matrices.  Side effect on ``g.ndata['h']`` as in forward().
         ``criterion="mse"``: the hyper-parameter search's ``nn.MSELoss()(self.forward(g), adj)``
-        (optuna_gae.py:16,21), likewise without the N x N matrices (ops.decoder_mse)."""
+        (optuna_gae.py:16,21), likewise without the N x N matrices (ops.decoder_mse).
+        ``scope="graph"``: the same BCE on every member graph of a batched ``g`` alone (its own pairs, pos_weight and
+        mean), averaged over the members (ops.decoder_bce_graphs) -- the reference's loss at batch size 1, averaged
+        over the molecules of the batch; a graph that is not a batch gives exactly the ``"batch"`` loss."""
+        if scope not in ("batch", "graph"):
+            raise ValueError(f"scope: 'batch' or 'graph', not {scope!r}")
+        if scope == "graph" and criterion != "bce":
+            raise ValueError(f"scope='graph' is a BCE loss (criterion 'bce'), not {criterion!r}")
         z = g.ndata['h']
+        if scope == "graph":
+            for layer in self.layers:
+                z = layer(g, z)
+            g.ndata['h'] = z
+            return self.decoder.loss_graphs(z, g)
         if criterion == "mse":
             for layer in self.layers:
                 z = layer(g, z)
@@ -264,6 +276,19 @@ class InnerProductDecoder(nn.Module):
             raise ops.GaeHipError("InnerProductDecoder.loss_mse: the HIP path needs device tensors")
         self.last_mask = self._draw_mask(z)
         return ops.decoder_mse(z, self.last_mask, g)
+
+    def loss_graphs(self, z, g):
+        """the fused loss per member graph of a batched ``g``, averaged over the members (ops.decoder_bce_graphs).  The
+        dropout mask is drawn inside the launch (same Philox stream as loss()) and kept in ``last_mask``."""
+        if not (isinstance(z, torch.Tensor) and z.is_cuda):
+            raise ops.GaeHipError("InnerProductDecoder.loss_graphs: the HIP path needs device tensors")
+        drop = self._loss_dropout(z.device)
+        if drop is None:
+            self.last_mask = self.mask
+            return ops.decoder_bce_graphs(z, self.mask, g)
+        mask = torch.empty(tuple(z.shape), dtype=torch.float32, device=z.device)
+        self.last_mask = mask
+        return ops.decoder_bce_graphs(z, mask, g, dropout=drop)
 
     def loss(self, z, g, prepared=None):
         """fused decoder + weighted BCE (identity activation = logits, gae.py:47).  The dropout mask of this call

@@ -203,6 +203,15 @@ class Graph:
             self._cache["graph_ptr"] = torch.from_numpy(gp).to(self._device)
         return self._cache["graph_ptr"]
 
+    def max_graph_nodes(self):
+        """host-side upper bound of the member graphs' node counts (graph_ptr()): the batch's own sizes, or the bound
+        a fixed-capacity batch was given (``self.max_member_nodes``)"""
+        bound = getattr(self, "max_member_nodes", None)
+        if bound is not None:
+            return int(bound)
+        counts = self.batch_num_nodes if self.batch_num_nodes is not None else [self._n]
+        return int(max(counts)) if len(counts) else 0
+
     def set_csr(self, indptr, indices, t_indptr=None, t_indices=None):
         """adopt an already-built device CSR (used by the device dataset batcher)"""
         self._cache["csr"] = (indptr, indices)

@@ -50,6 +50,11 @@ def build_parser():
     ap.add_argument("--criterion", choices=["bce", "mse"], default="bce",
                     help="bce = train_inductive.py:44-48 (weighted BCE with logits); mse = the hyper-parameter search's "
                          "nn.MSELoss() on the same logits and label (optuna_gae.py:16,21), eager steps only")
+    ap.add_argument("--loss_scope", choices=["batch", "graph"], default="batch",
+                    help="batch = the reference's loss over the whole block-diagonal batch (one label, one pos_weight, "
+                         "the mean over all N^2 pairs); graph = the same loss on every molecule's own pairs, averaged "
+                         "over the molecules of the batch (GAE.reconstruction_loss(g, scope='graph')): training and "
+                         "validation, eager and captured; fused BCE only")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--no_plot", action="store_true")
     ap.add_argument("--capture", choices=["auto", "on", "off"], default="auto",
@@ -91,6 +96,7 @@ class Trainer:
         ``group`` before the optimiser step"""
         self.model, self.fused = model, fused
         self.criterion = getattr(args, "criterion", "bce")
+        self.scope = getattr(args, "loss_scope", "batch")
         self.replicas, self.group = bool(replicas), group
         self.optim = optim.Adam(model.parameters(), lr=args.lr)     # torch.optim.Adam's rule, one HIP launch
         self._params = list(model.parameters())
@@ -99,7 +105,7 @@ class Trainer:
 
     def loss(self, g):
         if self.fused:
-            return self.model.reconstruction_loss(g, criterion=self.criterion)
+            return self.model.reconstruction_loss(g, criterion=self.criterion, scope=self.scope)
         # the reference-shaped path (train_inductive.py:44-48): dense label, pos_weight against the imbalance, N x N logits
         label = g.adjacency_matrix().to_dense().to(device)
         if self.criterion == "mse":
@@ -190,7 +196,10 @@ def _mean_over_replicas(value):
 
 def main(argv=None):
     global args, device
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.loss_scope == "graph" and (args.criterion != "bce" or args.loss != "fused"):
+        parser.error("--loss_scope graph is the fused BCE loss: it takes neither --criterion mse nor --loss dense")
     if not torch.cuda.is_available():
         raise RuntimeError("gae_dgl_amd runs on AMD GPUs only (no CPU fallback)")
     shard = None
@@ -261,7 +270,7 @@ def main(argv=None):
     if args.capture != "off" and can_capture:
         from gae_dgl_amd.capture import CapturedInductiveStep
         captured = CapturedInductiveStep(model, trainer.optim, loaders["train"].dataset, args.batch_size,
-                                         replicas=shard is not None)
+                                         replicas=shard is not None, loss_scope=args.loss_scope)
     history = {"train": [], "val": []}
     say("Training Start")
     for epoch in range(args.n_epochs):

@@ -477,6 +477,34 @@ int gae_decoder_bce_padded(const float *Z, float *mask, int64_t ldz, int64_t n_c
                            float *loss_out, float *dZ, int64_t lddz,
                            void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- K15: the same loss PER MEMBER GRAPH of a batched graph (GAE.reconstruction_loss(g, scope="graph"))
+ * gae_dgl/train_inductive.py:44-48 applied to every member graph g ALONE, averaged over the members:
+ *   l_g  = (1 / n_g^2) sum_{i,j in g} [(1 - y_ij) x_ij + (1 + (pw_g - 1) y_ij) softplus(-x_ij)]
+ *   loss = (1 / G') sum_g l_g            over the G' members with S_g > 0
+ * x_ij = zt_i . zt_j (Zt = Z (.) mask), y_ij = #edges j -> i with BOTH ends in g (CSR rows = destination, duplicates
+ * count; an edge that leaves its member is ignored), S_g = sum_ij y_ij, pw_g = (n_g^2 - S_g) / S_g.  Pairs of two
+ * different members are never formed.  A member with no edge or no node is left out of the mean (NaN in the
+ * reference) and gets a zero gradient; no member left: loss = NaN.  Rows outside every member get a zero gradient.
+ *   node_ptr      : int64 [n_graphs + 1] member offsets on the device (graph.graph_ptr(), gae_batch_plan's
+ *                   out_node_ptr); max_graph_nodes: a host-side upper bound of n_g (sizes the grid, O(panels))
+ *   CSR and CSR of A^T: both required (also for loss only); indices may be NULL when there is no edge
+ *   counts_dev    : NULL, or the {nodes, ...} of a fixed-capacity batch: a member ending behind counts[0] is left out
+ *   loss_out      : 1 fp32; graph_loss_out (may be NULL): l_g per member, NaN for the members left out
+ *   dZ            : d loss / d Z [n, d] (ld lddz), NULL = loss only (validation)
+ *   dropout       : as gae_decoder_bce (mask drawn in the launch when dropout_p > 0, *draw_dev + 1 afterwards)
+ *   workspace     : gae_decoder_bce_graphs_workspace_bytes(n, n_graphs, max_graph_nodes, d) bytes, any content
+ *   sync_dev      : uint32 [8] counters of the launch, zero before the first call; every call leaves them zero.  One
+ *                   launch at a time per sync_dev.
+ *   d <= 64, int32 CSR.  One launch; fp64 ordered reductions: bit-identical run to run. */
+int64_t gae_decoder_bce_graphs_workspace_bytes(int64_t n, int64_t n_graphs, int64_t max_graph_nodes, int64_t d);
+int gae_decoder_bce_graphs(const float *Z, float *mask, int64_t ldz, int64_t n, int64_t d,
+                           const int64_t *node_ptr, int64_t n_graphs, int64_t max_graph_nodes,
+                           const int32_t *indptr, const int32_t *indices,
+                           const int32_t *t_indptr, const int32_t *t_indices, const int64_t *counts_dev,
+                           float dropout_p, uint64_t seed, uint64_t offset, uint64_t *draw_dev,
+                           float *loss_out, float *graph_loss_out, float *dZ, int64_t lddz,
+                           void *workspace, int64_t workspace_bytes, uint32_t *sync_dev, void *stream);
+
 /* Prepare step folded into the PRODUCER of Z.  gae_decoder_bce* start with a small launch that applies the dropout
  * mask to Z, pads it to 16 columns, splits it into bf16 hi / lo and adds up its columns.  When Z comes out of
  * gae_gcn_layer_fused (the last encoder layer of gae_dgl/gae.py:55-57 followed by the loss of
