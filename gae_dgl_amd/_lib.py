@@ -17,6 +17,7 @@ SPMM_ACCUMULATE = 4
 SPMM_SKIP_ROWS = 8
 SPMM_ELL_WIDTH = 16
 ACT_IDENTITY, ACT_RELU = 0, 1
+TOPK_EXCLUDE_SELF, TOPK_EXCLUDE_EDGES = 1, 2
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _p, _f, _int = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
@@ -161,6 +162,7 @@ SIGNATURES = {
     "gae_decoder_bce_graphs_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "gae_decoder_bce_graphs": (_int, [_p, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p, _f, _u64, _u64, _p,
                                       _p, _p, _p, _i64, _p, _i64, _p, _p]),
+    "gae_decoder_topk": (_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _int, _p, _p, _i64, _p, _p, _p]),
     "gae_decoder_bce": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _f, _f, _u64, _u64, _p, _p, _p, _i64, _p,
                                _i64, _p]),
 }

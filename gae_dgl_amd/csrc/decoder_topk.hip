@@ -1,0 +1,402 @@
+// K16: top-k link prediction without the N x N matrix (GAE.predict_links, ops.decoder_topk).
+//
+// For every row i the k candidates j with the largest logit s_ij = z_i . z_j (gae_dgl/gae.py:69-72 without dropout and
+// before the sigmoid), under the candidate rule of include/gae_hip.h: a column window (all n, or i's own member graph),
+// j != i, j not in CSR row i, s_ij neither NaN nor -inf.  Rows are sorted by (score descending, j ascending).
+//
+// Products.  One wave per 32-row panel and column split.  The panel's rows are the B operand of
+// v_mfma_f32_32x32x2_f32 and stay in registers; 32-column tiles of Z are the A operand, loaded straight from global
+// memory (L2-resident at every size measured).  With A = candidates and B = panel rows the accumulator of lane l holds
+// row i = r0 + (l & 31) against the 16 columns c0 + (r & 3) + 8 (r >> 2) + 4 (l >> 5): every lane's scores belong to ONE
+// row, so the threshold test needs no cross-lane traffic.  The f32 MFMA is bitwise a k-ordered fmaf chain; the feature
+// order is fixed (lane half h feeds features [h DH, h DH + DH) of each 2 DH-wide chunk), so s_ij depends only on the
+// bits of z_i and z_j, never on where j falls in a tile: equal rows give bit-equal scores and the tie rule is exact.
+//
+// Selection.  Each lane keeps a running top-k of its (row, lane half) in LDS as a heap with the worst entry at the root.  Per tile the
+// fast path is the max of the lane's 16 scores against the lane's k-th score (about 0.5 VALU op per pair); only lanes
+// with a passing score store the tile to an LDS scratch row and walk the passing columns: window, self, a 64-bit hash
+// of the CSR row (the row's indices are scanned only on a hash hit; any order, repeats allowed) and the heap insert.
+// One heapsort at the end turns each heap into a list sorted best first.
+// NaN and -inf never pass (the threshold starts at -FLT_MAX).
+//
+// Output.  The two lane halves of a row merge their lists in the wave.  With one column split the merged list is the
+// row of the output; with S > 1 splits every (panel, split) wave writes a sorted partial list to the workspace and a
+// second launch merges the S lists of each row by rank (binary search in the other lists): no atomics, and since the
+// total order is strict the result is unique, so every schedule gives the same bits.
+#include <float.h>
+#include <string.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kRows = 32;         // panel rows per wave
+constexpr int kTile = 32;         // columns per tile
+constexpr int kMaxK = 64;
+constexpr int kMaxSplits = 16;
+
+gae::Knob g_topk_splits{0};       // "topk_splits": column splits per panel, 0 = auto (tests force 1 or more)
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+struct TopkArgs {
+    const float *Z;
+    int64_t ldz;
+    int n, d, k, nch, S;
+    const int64_t *node_ptr;      // NULL = scope batch
+    int64_t G;
+    const int32_t *indptr, *indices;
+    int excl_self;
+    float *score_out;
+    int64_t *index_out;
+    int64_t ldo;
+    float *part_s;                // [S][n][k] (S > 1)
+    int32_t *part_j;
+};
+
+// (s, j) is better than (t, q): the total order of the output (score descending, then j ascending)
+__device__ __forceinline__ bool better(float s, int j, float t, int q) { return s > t || (s == t && j < q); }
+
+__device__ __forceinline__ unsigned hash6(int j) { return (unsigned(j) * 0x9E3779B1u) >> 26; }
+
+// the member window [w0, w1) of row i (empty when i lies outside every member)
+__device__ void member_window(const TopkArgs &a, int i, int &w0, int &w1)
+{
+    if (!a.node_ptr) { w0 = 0; w1 = a.n; return; }
+    w0 = 0; w1 = 0;
+    if (a.G <= 0 || a.node_ptr[0] > i) return;
+    int64_t l = 0, h = a.G;                       // last member g < G with node_ptr[g] <= i
+    while (h - l > 1) { const int64_t m = (l + h) >> 1; if (a.node_ptr[m] <= i) l = m; else h = m; }
+    int64_t p0 = a.node_ptr[l], p1 = a.node_ptr[l + 1];
+    p0 = p0 < 0 ? 0 : p0;                         // clipped to [0, n): a bad node_ptr never reads outside Z
+    p1 = p1 > a.n ? a.n : p1;
+    if (i >= p0 && i < p1) { w0 = int(p0); w1 = int(p1); }
+}
+
+// Each lane's running top-k is a binary heap in LDS (entry p of lane l at [p * 64 + l]) with the WORST entry at the
+// root: the threshold is the root, and an insert costs log2 k dependent LDS round trips instead of the k / 2 of a
+// shift into a sorted list.
+__device__ __forceinline__ void heap_push(float *ls, int *lj, int lane, int cnt, float s, int j)
+{
+    int p = cnt;
+    while (p > 0) {                                // sift up past every parent that is better than the new entry
+        const int q = (p - 1) >> 1;
+        const float t = ls[q * 64 + lane];
+        const int tj = lj[q * 64 + lane];
+        if (!better(t, tj, s, j)) break;
+        ls[p * 64 + lane] = t;
+        lj[p * 64 + lane] = tj;
+        p = q;
+    }
+    ls[p * 64 + lane] = s;
+    lj[p * 64 + lane] = j;
+}
+
+// replace the root of a heap of `size` entries by (s, j) and sift it down
+__device__ __forceinline__ void heap_replace_root(float *ls, int *lj, int lane, int size, float s, int j)
+{
+    int p = 0;
+    while (true) {
+        int c = 2 * p + 1;
+        if (c >= size) break;
+        float cs = ls[c * 64 + lane];
+        int cj = lj[c * 64 + lane];
+        if (c + 1 < size) {
+            const float ds = ls[(c + 1) * 64 + lane];
+            const int dj = lj[(c + 1) * 64 + lane];
+            if (better(cs, cj, ds, dj)) { cs = ds; cj = dj; c = c + 1; }     // the worse child
+        }
+        if (!better(s, j, cs, cj)) break;          // (s, j) is no better than its worse child: it stays here
+        ls[p * 64 + lane] = cs;
+        lj[p * 64 + lane] = cj;
+        p = c;
+    }
+    ls[p * 64 + lane] = s;
+    lj[p * 64 + lane] = j;
+}
+
+template <int DH, bool ONE>
+__global__ __launch_bounds__(64) void topk_kernel(const TopkArgs a)
+{
+    extern __shared__ float lds[];
+    const int lane = threadIdx.x, col = lane & 31, h = lane >> 5;
+    const int k = a.k;
+    float *ls = lds;                                       // [k][64] scores of each lane's list
+    int *lj = reinterpret_cast<int *>(lds + k * 64);       // [k][64] indices
+    float *scr = lds + 2 * k * 64;                         // [16][64] scores of a tile that has a passing lane
+    const int panel = blockIdx.x / a.S, split = blockIdx.x % a.S;
+    const int i = panel * kRows + col;
+    const bool row_ok = i < a.n;
+
+    // ---- the row: member window, CSR row, hash of its indices
+    int w0 = 0, w1 = 0;
+    if (row_ok) member_window(a, i, w0, w1);
+    int e0 = 0, e1 = 0;
+    unsigned long long hmask = 0;
+    if (row_ok && a.indptr) {
+        e0 = a.indptr[i]; e1 = a.indptr[i + 1];
+        for (int e = e0; e < e1; ++e) hmask |= 1ull << hash6(a.indices[e]);
+    }
+    // ---- the wave's column range: the union of its rows' windows, cut into S tile-aligned parts
+    int cb = w0 < w1 ? w0 : INT32_MAX, ce = w0 < w1 ? w1 : INT32_MIN;
+    for (int off = 32; off > 0; off >>= 1) {
+        const int ob = __shfl_xor(cb, off, 64), oe = __shfl_xor(ce, off, 64);
+        cb = ob < cb ? ob : cb;
+        ce = oe > ce ? oe : ce;
+    }
+    int pb = 0, pe = 0;
+    if (cb < ce) {
+        const int64_t span = int64_t(ce) - cb;
+        const int64_t L = ((span + a.S - 1) / a.S + kTile - 1) / kTile * kTile;
+        const int64_t b = cb + L * split, e = b + L;
+        pb = int(b < ce ? b : ce);
+        pe = int(e < ce ? e : ce);
+    }
+    // this lane's candidates: its row's window inside this part
+    const int lo = w0 > pb ? w0 : pb, hi = w1 < pe ? w1 : pe;
+
+    // ---- the panel rows (B operand): features q 2 DH + h DH + s
+    float zr[DH];
+    auto load_row = [&](int q) {
+#pragma unroll
+        for (int s = 0; s < DH; ++s) {
+            const int f = q * 2 * DH + h * DH + s;
+            zr[s] = (row_ok && f < a.d) ? a.Z[int64_t(i) * a.ldz + f] : 0.f;
+        }
+    };
+    if constexpr (ONE) load_row(0);
+
+    int cnt = 0;
+    float thr = -FLT_MAX;                          // score of the k-th entry once the list is full
+    int thr_j = INT32_MAX;
+    for (int64_t c0_ = pb; c0_ < pe; c0_ += kTile) {
+        const int c0 = int(c0_);
+        v16f acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        const int64_t jc = int64_t(c0) + col;      // this lane's A-operand column (int64: n may reach 2^31 - 1)
+        const bool col_ok = jc < pe;
+        for (int q = 0; q < (ONE ? 1 : a.nch); ++q) {
+            if constexpr (!ONE) load_row(q);
+            float za[DH];
+#pragma unroll
+            for (int s = 0; s < DH; ++s) {
+                const int f = q * 2 * DH + h * DH + s;
+                za[s] = (col_ok && f < a.d) ? a.Z[jc * a.ldz + f] : 0.f;
+            }
+#pragma unroll
+            for (int s = 0; s < DH; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(za[s], zr[s], acc, 0, 0, 0);
+        }
+        // ---- fast path: one max per score, one compare per tile
+        float m = acc[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) m = fmaxf(m, acc[r]);
+        if (m >= thr && lo < hi) {
+            unsigned pass = 0;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                scr[r * 64 + lane] = acc[r];
+                pass |= (acc[r] >= thr ? 1u : 0u) << r;
+            }
+            while (pass) {
+                const int r = __builtin_ctz(pass);
+                pass &= pass - 1;
+                const float s = scr[r * 64 + lane];
+                const int64_t jj = int64_t(c0) + (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (jj < lo || jj >= hi) continue;
+                const int j = int(jj);
+                if (a.excl_self && j == i) continue;
+                if (cnt == k && !better(s, j, thr, thr_j)) continue;
+                if ((hmask >> hash6(j)) & 1ull) {
+                    // a hash hit: scan the CSR row, four independent loads per round trip (clamped inside the row)
+                    bool edge = false;
+                    for (int e = e0; e < e1 && !edge; e += 4) {
+                        const int32_t v0 = a.indices[e];
+                        const int32_t v1 = a.indices[e + 1 < e1 ? e + 1 : e1 - 1];
+                        const int32_t v2 = a.indices[e + 2 < e1 ? e + 2 : e1 - 1];
+                        const int32_t v3 = a.indices[e + 3 < e1 ? e + 3 : e1 - 1];
+                        edge = v0 == j || v1 == j || v2 == j || v3 == j;
+                    }
+                    if (edge) continue;
+                }
+                if (cnt < k) {
+                    heap_push(ls, lj, lane, cnt, s, j);
+                    ++cnt;
+                } else {
+                    heap_replace_root(ls, lj, lane, k, s, j);
+                }
+                if (cnt == k) {
+                    thr = ls[lane];
+                    thr_j = lj[lane];
+                }
+            }
+        }
+    }
+    // ---- the heap into a list sorted best first: the worst entry goes to the end, k log k steps once
+    for (int e = cnt - 1; e > 0; --e) {
+        const float ts = ls[e * 64 + lane];
+        const int tj = lj[e * 64 + lane];
+        const float rs = ls[lane];
+        const int rj = lj[lane];
+        ls[e * 64 + lane] = rs;
+        lj[e * 64 + lane] = rj;
+        heap_replace_root(ls, lj, lane, e, ts, tj);
+    }
+    // ---- merge the two lane halves of each row; lane h = 0 writes the row
+    __syncthreads();
+    const int pcnt = __shfl_down(cnt, 32, 64);
+    if (h == 0 && row_ok) {
+        const bool direct = a.S == 1;
+        float *os = direct ? a.score_out + int64_t(i) * a.ldo : a.part_s + (int64_t(split) * a.n + i) * k;
+        int64_t *oj64 = a.index_out + int64_t(i) * a.ldo;
+        int32_t *oj32 = a.part_j + (int64_t(split) * a.n + i) * k;
+        int p0 = 0, p1 = 0;
+        for (int t = 0; t < k; ++t) {
+            float s = -INFINITY;
+            int j = -1;
+            const bool h0 = p0 < cnt, h1 = p1 < pcnt;
+            if (h0 || h1) {
+                const float s0 = h0 ? ls[p0 * 64 + lane] : 0.f, s1 = h1 ? ls[p1 * 64 + lane + 32] : 0.f;
+                const int j0 = h0 ? lj[p0 * 64 + lane] : 0, j1 = h1 ? lj[p1 * 64 + lane + 32] : 0;
+                if (h0 && (!h1 || better(s0, j0, s1, j1))) { s = s0; j = j0; ++p0; }
+                else { s = s1; j = j1; ++p1; }
+            }
+            os[t] = s;
+            if (direct) oj64[t] = j; else oj32[t] = j;
+        }
+    }
+}
+
+// entries of a sorted partial list (length k, padding j = -1 at the end) better than (s, j)
+__device__ __forceinline__ int rank_in(const float *ps, const int32_t *pj, int k, float s, int j)
+{
+    int l = 0, h = k;                              // first position that is not better
+    while (l < h) {
+        const int m = (l + h) >> 1;
+        const bool b = pj[m] >= 0 && better(ps[m], pj[m], s, j);
+        if (b) l = m + 1; else h = m;
+    }
+    return l;
+}
+
+__device__ __forceinline__ int valid_in(const int32_t *pj, int k)
+{
+    int l = 0, h = k;
+    while (l < h) { const int m = (l + h) >> 1; if (pj[m] >= 0) l = m + 1; else h = m; }
+    return l;
+}
+
+// one thread per (row, split, position): the entry's rank among the S lists of its row is its output slot
+__global__ __launch_bounds__(256) void topk_merge_kernel(const TopkArgs a)
+{
+    const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    const int k = a.k, S = a.S;
+    if (t >= int64_t(a.n) * S * k) return;
+    const int q = int(t % k);
+    const int s = int((t / k) % S);
+    const int64_t i = t / (int64_t(k) * S);
+    const int64_t stride = int64_t(a.n) * k;
+    const float *ps = a.part_s + i * k;
+    const int32_t *pj = a.part_j + i * k;
+    float *os = a.score_out + i * a.ldo;
+    int64_t *oj = a.index_out + i * a.ldo;
+    const int j = pj[s * stride + q];
+    if (j >= 0) {
+        const float v = ps[s * stride + q];
+        int rank = q;
+        for (int u = 0; u < S; ++u)
+            if (u != s) rank += rank_in(ps + u * stride, pj + u * stride, k, v, j);
+        if (rank < k) { os[rank] = v; oj[rank] = j; }
+    }
+    if (s == 0) {
+        int total = 0;
+        for (int u = 0; u < S; ++u) total += valid_in(pj + u * stride, k);
+        if (q >= total) { os[q] = -INFINITY; oj[q] = -1; }
+    }
+}
+
+int splits_for(int64_t n, const int64_t *node_ptr, int64_t max_graph_nodes)
+{
+    if (n <= 0) return 1;
+    const int64_t panels = (n + kRows - 1) / kRows;
+    int64_t S = g_topk_splits;
+    if (S <= 0) {
+        const int64_t span = node_ptr ? (max_graph_nodes < n ? max_graph_nodes : n) : n;
+        S = (4096 + panels - 1) / panels;                  // ~4096 waves: several per SIMD
+        const int64_t by_span = (span + 255) / 256;        // parts of >= 256 columns
+        S = S < by_span ? S : by_span;
+    }
+    return int(S < 1 ? 1 : (S > kMaxSplits ? kMaxSplits : S));
+}
+
+int64_t need_bytes(int64_t n, int64_t k, int S) { return S > 1 ? int64_t(S) * n * k * 8 + 256 : 256; }
+
+} // namespace
+
+namespace gae {
+Knob *topk_knob(const char *name) { return strcmp(name, "topk_splits") == 0 ? &g_topk_splits : nullptr; }
+} // namespace gae
+
+extern "C" int gae_decoder_topk(const float *Z, int64_t ldz, int64_t n, int64_t d, int64_t k, const int64_t *node_ptr,
+                                int64_t n_graphs, int64_t max_graph_nodes, const int32_t *indptr,
+                                const int32_t *indices, int flags, float *score_out, int64_t *index_out, int64_t ldo,
+                                void *workspace, int64_t *workspace_bytes, void *stream)
+{
+    GAE_REQUIRE(k >= 1 && k <= kMaxK, GAE_E_RANGE, "gae_decoder_topk: k = %lld outside 1..64", (long long)k);
+    GAE_REQUIRE(d >= 1 && d <= 256, GAE_E_RANGE, "gae_decoder_topk: d = %lld outside 1..256", (long long)d);
+    GAE_REQUIRE(n >= 0, GAE_E_SIZE, "gae_decoder_topk: negative n = %lld", (long long)n);
+    GAE_REQUIRE(n < (int64_t(1) << 31), GAE_E_SIZE, "gae_decoder_topk: n = %lld beyond the int32 CSR", (long long)n);
+    GAE_REQUIRE(ldz >= d && ldo >= k, GAE_E_SIZE, "gae_decoder_topk: leading dimension too small (ldz %lld < d or "
+                "ldo %lld < k)", (long long)ldz, (long long)ldo);
+    GAE_REQUIRE((flags & ~(GAE_TOPK_EXCLUDE_SELF | GAE_TOPK_EXCLUDE_EDGES)) == 0, GAE_E_RANGE,
+                "gae_decoder_topk: unknown flags 0x%x", flags);
+    GAE_REQUIRE(!node_ptr || (n_graphs >= 0 && max_graph_nodes >= 0), GAE_E_SIZE,
+                "gae_decoder_topk: negative n_graphs / max_graph_nodes");
+    GAE_REQUIRE(workspace_bytes, GAE_E_NULL, "gae_decoder_topk: workspace_bytes is NULL");
+    const int S = splits_for(n, node_ptr, max_graph_nodes);
+    const int64_t need = need_bytes(n, k, S);
+    if (!workspace) {                               // size query: no device work
+        *workspace_bytes = need;
+        return GAE_OK;
+    }
+    GAE_REQUIRE(n == 0 || Z, GAE_E_NULL, "gae_decoder_topk: Z is NULL");
+    GAE_REQUIRE(n == 0 || (score_out && index_out), GAE_E_NULL, "gae_decoder_topk: score_out / index_out is NULL");
+    GAE_REQUIRE(!(flags & GAE_TOPK_EXCLUDE_EDGES) || (indptr && indices), GAE_E_NULL,
+                "gae_decoder_topk: GAE_TOPK_EXCLUDE_EDGES without a CSR");
+    GAE_REQUIRE(*workspace_bytes >= need, GAE_E_WORKSPACE, "gae_decoder_topk: workspace of %lld bytes, %lld needed",
+                (long long)*workspace_bytes, (long long)need);
+    if (n == 0) return GAE_OK;
+    TopkArgs a;
+    a.Z = Z; a.ldz = ldz; a.n = int(n); a.d = int(d); a.k = int(k); a.S = S;
+    a.node_ptr = node_ptr; a.G = n_graphs;
+    const bool edges = (flags & GAE_TOPK_EXCLUDE_EDGES) != 0;
+    a.indptr = edges ? indptr : nullptr; a.indices = edges ? indices : nullptr;
+    a.excl_self = (flags & GAE_TOPK_EXCLUDE_SELF) ? 1 : 0;
+    a.score_out = score_out; a.index_out = index_out; a.ldo = ldo;
+    a.part_s = reinterpret_cast<float *>(static_cast<char *>(workspace) + 256);
+    a.part_j = reinterpret_cast<int32_t *>(a.part_s + (S > 1 ? int64_t(S) * n * k : 0));
+    const int64_t panels = (n + kRows - 1) / kRows;
+    const dim3 grid(unsigned(panels * S));
+    const size_t lds = size_t(2 * k + 16) * 64 * 4;
+    hipStream_t st = gae::as_stream(stream);
+    if (d <= 16) {
+        a.nch = 1;
+        hipLaunchKernelGGL((topk_kernel<8, true>), grid, dim3(64), lds, st, a);
+    } else if (d <= 32) {
+        a.nch = 1;
+        hipLaunchKernelGGL((topk_kernel<16, true>), grid, dim3(64), lds, st, a);
+    } else if (d <= 64) {
+        a.nch = 1;
+        hipLaunchKernelGGL((topk_kernel<32, true>), grid, dim3(64), lds, st, a);
+    } else {
+        a.nch = int((d + 63) / 64);
+        hipLaunchKernelGGL((topk_kernel<32, false>), grid, dim3(64), lds, st, a);
+    }
+    GAE_CHECK_LAUNCH("topk_kernel");
+    if (S > 1) {
+        const int64_t threads = n * S * k;
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(unsigned((threads + 255) / 256)), dim3(256), 0, st, a);
+        GAE_CHECK_LAUNCH("topk_merge_kernel");
+    }
+    return GAE_OK;
+}

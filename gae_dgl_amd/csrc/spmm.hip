@@ -1370,7 +1370,7 @@ extern "C" int gae_spmm_csr_blockdiag(const int32_t *indptr, const int32_t *indi
 namespace {
 } // namespace
 
-namespace gae { Knob *dense_knob(const char *name); Knob *bce_knob(const char *name); Knob *xw_knob(const char *name); Knob *optim_knob(const char *name); }
+namespace gae { Knob *dense_knob(const char *name); Knob *bce_knob(const char *name); Knob *xw_knob(const char *name); Knob *optim_knob(const char *name); Knob *topk_knob(const char *name); }
 
 namespace {
 gae::Knob *find_knob(const char *name)
@@ -1385,6 +1385,7 @@ gae::Knob *find_knob(const char *name)
     if (gae::Knob *k = gae::dense_knob(name)) return k;
     if (gae::Knob *k = gae::xw_knob(name)) return k;
     if (gae::Knob *k = gae::optim_knob(name)) return k;
+    if (gae::Knob *k = gae::topk_knob(name)) return k;
     return gae::bce_knob(name);
 }
 } // namespace

@@ -187,6 +187,16 @@ class GAE(nn.Module):
     def encode(self, g):
         return self._embed(g, write_back=False)
 
+    def predict_links(self, g, k, *, scope="batch", exclude_self=True, exclude_edges=True):
+        """(score [n, k], index [n, k]): the k most likely new neighbours of every node -- the largest logits
+        z_i . z_j of the decoder (gae.py:69-72, no dropout) among the pairs that are not edges of ``g`` -- from one
+        fused HIP launch (ops.decoder_topk) that never forms the N x N matrix.  ``sigmoid(score)`` is the probability.
+        ``scope="graph"``: only inside each member graph of a batched ``g``.  Rows with fewer than k candidates pad
+        with index -1 / score -inf.  Runs encode(g) under no_grad; g.ndata is left as encode() leaves it."""
+        with torch.no_grad():
+            z = self.encode(g)
+        return ops.decoder_topk(z, k, g, scope=scope, exclude_self=exclude_self, exclude_edges=exclude_edges)
+
     def reconstruction_loss(self, g, criterion="bce", scope="batch"):
         """The training loss of train_inductive.py:44-48 (dense label from g,
         pos_weight, BCE-with-logits mean over all N^2 ordered pairs) evaluated

@@ -80,3 +80,21 @@ def average_precision(pos_scores, neg_scores):
 def evaluate(Z, split):
     p, q = edge_scores(Z, split["pos"]), edge_scores(Z, split["neg"])
     return {"auc": roc_auc(p, q), "ap": average_precision(p, q)}
+
+
+def recall_at_k(index, pos_pairs):
+    """fraction of the held-out positive pairs (i, j) (``pos_pairs`` [2, m]) found by a top-k list: j in row i of
+    ``index`` [n, k] or i in row j (a link is undirected).  Duplicate pairs -- also (i, j) next to (j, i) -- count
+    once; -1 entries (padding) match nothing.  An empty pair list gives NaN."""
+    index = torch.as_tensor(index)
+    pairs = torch.as_tensor(pos_pairs, device=index.device).long().reshape(2, -1)
+    n = index.shape[0]
+    a, b = torch.minimum(pairs[0], pairs[1]), torch.maximum(pairs[0], pairs[1])
+    keys = torch.unique(a * n + b)
+    if keys.numel() == 0:
+        return float("nan")
+    rows = torch.arange(n, device=index.device).unsqueeze(1).expand_as(index)
+    ok = index >= 0
+    i, j = rows[ok], index[ok].long()
+    found = torch.unique(torch.minimum(i, j) * n + torch.maximum(i, j))
+    return float(torch.isin(keys, found).double().mean())

@@ -4,7 +4,7 @@ file's INTENT -- ``GAE(in_feats, [32, 16])``, Adam lr 1e-2, 500 full-graph
 epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
 59-60) -- on the HIP kernels.
 
-  python -m gae_dgl_amd.train_transductive --dataset cora [--norm both]
+  python -m gae_dgl_amd.train_transductive --dataset cora [--norm both] [--eval] [--topk 10 [--topk_out top.npz]]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -46,11 +46,30 @@ def build_parser():
     ap.add_argument("--eval", action="store_true",
                     help="hold out 5 %% / 10 %% of the edges (the reference's '# TODO: train test split', :35) and "
                          "report link-prediction ROC-AUC / AP on them after training")
+    ap.add_argument("--topk", type=int, default=None, metavar="K",
+                    help="after training, the K (1..64) most likely new neighbours of every node (GAE.predict_links, "
+                         "known edges left out); with --eval prints the test recall@K, with --topk_out saves them")
+    ap.add_argument("--topk_out", default=None, metavar="PATH",
+                    help="write the --topk lists to PATH (.npz with 'index' int64 [n, K] and 'score' fp32 [n, K])")
     return ap
 
 
+def parse_args(argv=None):
+    """the parsed flags; combinations that cannot run are refused here, before any device is touched"""
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.topk is not None:
+        if not 1 <= args.topk <= 64:
+            ap.error(f"--topk {args.topk}: K must lie in 1..64")
+        if not args.eval and args.topk_out is None:
+            ap.error("--topk needs --eval (recall@K on the held-out edges) or --topk_out PATH")
+    elif args.topk_out is not None:
+        ap.error("--topk_out needs --topk K")
+    return args
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("gae_dgl_amd runs on AMD GPUs only (no CPU fallback)")
     device = torch.device(f"cuda:{args.gpu_id}")
@@ -112,6 +131,17 @@ def main(argv=None):
             scores = metrics.evaluate(Z, pairs)
             print(f"{name} ROC-AUC: {scores['auc']:.4f} | AP: {scores['ap']:.4f}")
         main.last_eval = metrics.evaluate(Z, held_out["test"])
+    if args.topk is not None:
+        # the training graph's edges are left out, so the held-out test positives are candidates
+        g.ndata['h'] = features
+        score, index = model.predict_links(g, args.topk)
+        if held_out is not None:
+            recall = metrics.recall_at_k(index, held_out["test"]["pos"])
+            print(f"test recall@{args.topk}: {recall:.4f}")
+            main.last_recall = recall
+        if args.topk_out is not None:
+            import numpy as np
+            np.savez(args.topk_out, index=index.cpu().numpy(), score=score.cpu().numpy())
     return [float(l) for l in losses]
 
 

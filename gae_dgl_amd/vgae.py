@@ -103,6 +103,13 @@ class VGAE(nn.Module):
         self.last = {"mu": mu, "logstd": logstd, "eps": eps, "z": z, "kl": kl, "rec": rec}
         return rec + kl
 
+    def predict_links(self, g, k, *, scope="batch", exclude_self=True, exclude_edges=True):
+        """GAE.predict_links on the mean embedding mu (no noise): the k largest mu_i . mu_j per node among the
+        non-edges of ``g`` (ops.decoder_topk)"""
+        with torch.no_grad():
+            mu, _ = self.encode(g)
+        return ops.decoder_topk(mu, k, g, scope=scope, exclude_self=exclude_self, exclude_edges=exclude_edges)
+
     def forward(self, g):
         """sampled Z Z^T logits (dense parity / inference path)"""
         mu, logstd = self.encode(g)

@@ -505,6 +505,35 @@ int gae_decoder_bce_graphs(const float *Z, float *mask, int64_t ldz, int64_t n, 
                            float *loss_out, float *graph_loss_out, float *dZ, int64_t lddz,
                            void *workspace, int64_t workspace_bytes, uint32_t *sync_dev, void *stream);
 
+/* ---- K16: top-k link prediction without the N x N matrix (GAE.predict_links, ops.decoder_topk)
+ * The decoder of gae_dgl/gae.py:69-72 (no dropout, before the sigmoid) asked the question of
+ * train_transductive.py:35's "# TODO: train test split": for every row i the k candidates j with the largest
+ *   s_ij = z_i . z_j                      (returned as the logit; sigmoid(s_ij) is the probability of gae.py:71)
+ * Candidates of row i: j in its column window -- all n (node_ptr == NULL, scope "batch") or its own member
+ * [node_ptr[g], node_ptr[g + 1]) (scope "graph"; a row outside every member has none) -- and
+ *   j != i                                 when flags & GAE_TOPK_EXCLUDE_SELF,
+ *   j not in CSR row i (rows = destination, indices in any order, repeats allowed)   when flags & GAE_TOPK_EXCLUDE_EDGES,
+ *   s_ij neither NaN nor -inf.
+ * Output: score_out fp32 [n][k], index_out int64 [n][k] (leading dimension ldo), each row sorted by score descending,
+ * equal scores by ascending j (a total order: the result is unique, bit-identical run to run and across schedules).  A
+ * row with fewer than k candidates is padded with index -1, score -inf.
+ * Numerics: exact fp32 products (fp32 MFMA = a k-ordered fmaf chain in a fixed feature order): s_ij depends only on the
+ * bits of z_i and z_j, so equal rows of Z give bit-equal scores.  No logit is written to memory.
+ *   Z            : fp32 [n][d], leading dimension ldz >= d; 1 <= k <= 64, 1 <= d <= 256, n < 2^31
+ *   node_ptr     : NULL, or int64 [n_graphs + 1] member offsets on the device (graph.graph_ptr()); max_graph_nodes: a
+ *                  host-side bound of the member sizes (sizes the column split)
+ *   indptr / indices : int32 CSR, both required (non-NULL) iff GAE_TOPK_EXCLUDE_EDGES
+ *   workspace    : NULL = size query: *workspace_bytes receives the bytes needed and nothing else happens (no device
+ *                  work; works without a GPU).  Otherwise *workspace_bytes is the capacity given.  O(n k column
+ *                  splits) bytes, never O(n^2).
+ * One launch (two when the columns are split over several blocks). */
+enum { GAE_TOPK_EXCLUDE_SELF = 1, GAE_TOPK_EXCLUDE_EDGES = 2 };
+int gae_decoder_topk(const float *Z, int64_t ldz, int64_t n, int64_t d, int64_t k,
+                     const int64_t *node_ptr, int64_t n_graphs, int64_t max_graph_nodes,
+                     const int32_t *indptr, const int32_t *indices, int flags,
+                     float *score_out, int64_t *index_out, int64_t ldo,
+                     void *workspace, int64_t *workspace_bytes, void *stream);
+
 /* Prepare step folded into the PRODUCER of Z.  gae_decoder_bce* start with a small launch that applies the dropout
  * mask to Z, pads it to 16 columns, splits it into bf16 hi / lo and adds up its columns.  When Z comes out of
  * gae_gcn_layer_fused (the last encoder layer of gae_dgl/gae.py:55-57 followed by the loss of
