@@ -47,27 +47,32 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int TJ = 64;   // columns staged per iteration
 constexpr int PREP_ROWS = 64;    // rows per block of the prepare kernel
-// tuning knobs (gae_tuning_set): "bce_ri" 16-row subtiles per wave (rows / block = 64 RI),
-// "bce_s_bf16" 1 = bf16x3 S product, 0 = exact fp32 S product
-gae::Knob g_bce_ri{2};
-gae::Knob g_bce_s_bf16{3};        // S = Zt Zt^T (and P V of the symmetric kernel): 3 = two fp16 pieces per operand where the symmetric kernel runs
-                                  // (22 mantissa bits, range-guarded; default), three bf16 pieces elsewhere; 2 = three bf16 pieces
-                                  // (24 bits); 1 = two bf16 pieces (16 bits: rounds 1-3); 0 = exact fp32 MFMA
-gae::Knob g_bce_grid{2048};       // "bce_grid": target size of the (row block, column split) grid of the full-square kernel
+constexpr int kBceRi = 2;             // 16-row subtiles per wave of the full-square kernel (rows / block = 64 kBceRi)
+constexpr int64_t kBceGrid = 2048;    // target size of the (row block, column split) grid of the full-square kernel
+constexpr int64_t kBceSymGrid = 16384;    // target size of the (panel, chunk) grid of the symmetric kernel (many short
+                                          // blocks even out the triangular work: ZINC batch 3.64 -> 3.35 ms)
 constexpr int kChipCus = 256;             // MI355X: the launch-shape heuristics below are written for this part
-gae::Knob g_bce_strip_store{-1};  // "bce_strip_store": -1 auto (non-temporal from 32 k rows on: GBs of strips, 2.93 -> 2.88 ms on a ZINC
-                                          // batch; plain below: Pubmed 170 vs 174 us), 0 plain, 1 non-temporal, 2 write-through
-gae::Knob g_bce_fold_mirror{1};   // "bce_fold_mirror": 1 = the edge kernel folds the mirror strips (no separate reduction launch)
-gae::Knob g_bce_sym_tiles{0};     // "bce_sym_tiles": 64-column tiles per block of the symmetric kernel (0 = auto)
-gae::Knob g_bce_sym_grid{16384};  // "bce_sym_grid": target size of the (panel, chunk) grid of the symmetric kernel
-                             // (many short blocks even out the triangular work: ZINC batch 3.64 -> 3.35 ms)
-gae::Knob g_bce_last_kind{0}; // "bce_last_kind" (telemetry, read with gae_tuning_get): dense kernel of the last loss call on this
-                               // process -- 0 none yet, 1 full square, 2 symmetric 128-row panels, 3 symmetric 256-row panels
-gae::Knob g_bce_sym_bal{1};   // "bce_sym_bal": balanced schedule of the symmetric kernel (every block the same number of column
-                              // tiles, one resident round): 1 = below 65 536 rows, 2 = always, 0 = never (the 2-D (panel, column
-                              // chunk) grid of rounds 2-5)
-gae::Knob g_bce_sym{1};       // "bce_sym": 1 = symmetric dense kernel for full-square launches with d <= 16
-gae::Knob g_bce_pv_bf16{1};   // "bce_pv_bf16": 1 = bf16x3 for O' += P V as well (P split on the fly), 0 = exact fp32
+} // namespace
+
+namespace gae {
+Knob g_bce_s_bf16{3};    // "bce_s_bf16", S = Zt Zt^T (and P V of the symmetric kernel): 3 = two fp16 pieces per operand where the
+                         // symmetric kernel runs (22 mantissa bits, range-guarded; default), three bf16 pieces elsewhere; 2 = three
+                         // bf16 pieces (24 bits); 0 = exact fp32 MFMA
+Knob g_bce_last_kind{0}; // "bce_last_kind" (telemetry, read-only through gae_tuning_get): dense kernel of the last loss call on this
+                         // process -- 0 none yet, 1 full square, 2 symmetric 128-row panels, 3 symmetric 256-row panels
+Knob g_bce_sym_bal{1};   // "bce_sym_bal": balanced schedule of the symmetric kernel (every block the same number of column
+                         // tiles, one resident round): 1 = below 65 536 rows, 2 = always, 0 = never (the 2-D (panel, column
+                         // chunk) grid of rounds 2-5)
+Knob g_bce_sym{1};       // "bce_sym": 1 = symmetric dense kernel for full-square launches with d <= 16 (2 = from 512 rows on)
+Knob g_bce_pv_bf16{1};   // "bce_pv_bf16": 1 = bf16x3 for O' += P V as well (P split on the fly), 0 = exact fp32
+} // namespace gae
+
+namespace {
+using gae::g_bce_s_bf16;
+using gae::g_bce_last_kind;
+using gae::g_bce_sym_bal;
+using gae::g_bce_sym;
+using gae::g_bce_pv_bf16;
 
 __device__ __forceinline__ void softplus_sigmoid(float x, float &sp, float &sg)
 {
@@ -694,8 +699,14 @@ __global__ __launch_bounds__(256, MINW) void bce_dense_kernel(
 // 185 -> 194 us).  With the K = 32 fragments the fully unrolled 256-row body spilled 43 VGPRs (3.48 ms) and its
 // column-pair loop was left rolled (238 VGPRs) -- until the one-reciprocal-per-four-logits form (quad_terms) freed
 // enough registers: unrolled it now takes 234 VGPRs without a spill (ZINC step 2.853 -> 2.72 ms).
-gae::Knob g_bce_sym_ri{0};
-gae::Knob g_bce_sym_tr{1};    // "bce_sym_tr": 1 = V fragments by LDS transpose reads (ds_read_b64_tr_b16), 0 = from transposed tile copies
+} // namespace
+
+namespace gae {
+Knob g_bce_sym_ri{0};
+} // namespace gae
+
+namespace {
+using gae::g_bce_sym_ri;
 
 // the upper 16 bits of four fp32 values (exact when they are bf16 values): one v_perm_b32 per pair
 __device__ __forceinline__ s16x4 upper_halves(const f32x4 &d)
@@ -714,7 +725,7 @@ __host__ __device__ inline int64_t sym_strip_offset(int64_t I, int64_t NP, int64
 
 // TRV (default): the V fragments of O' += P V come from LDS transpose reads of the [j][k] tiles -- no second,
 // transposed copy of every tile (16 ds_write_b16 per thread and tile, 8.7 KB of LDS): Pubmed 170 -> 166 us, a ZINC
-// batch 2.92 -> 2.88 ms.  TRV = false keeps the round-2 form (knob "bce_sym_tr" = 0).
+// batch 2.92 -> 2.88 ms.  Every launch with gradients uses it; TRV = false is the form without gradients.
 template <bool WITH_GRAD, int RI, bool TRV, bool S3 = false, bool F16 = false, bool PERSIST = false, bool BAL = false>
 __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_sym_kernel(
     const float *__restrict__ Zt /*[n][16]*/, const unsigned short *__restrict__ Zhi,
@@ -1465,7 +1476,7 @@ __global__ __launch_bounds__(1024) void bce_finalize_kernel(const gae_bce_tail t
 
 struct BcePlan {
     int64_t row_blocks, n_splits, cols_per_split, edge_blocks, prep_blocks;
-    int KS, DP, LPR, VEC, RI;
+    int KS, DP, LPR, VEC;
     int64_t o_bytes, zt_bytes, zh_bytes, cs_bytes, s_bytes, n_dense, total_bytes;
     double pad_terms;
     bool sym;                     // symmetric dense kernel (full square, d <= 16, bf16x3 products)
@@ -1479,9 +1490,7 @@ inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 bool bce_plan(int64_t n, int64_t n_local, int64_t d, bool vec_ok, BcePlan &p)
 {
-    const int ri = (g_bce_ri == 1 || g_bce_ri == 4) ? g_bce_ri : 2;
-    const int64_t ROWS_PER_BLOCK = 64 * ri;
-    p.RI = ri;
+    const int64_t ROWS_PER_BLOCK = 64 * kBceRi;
     if (d > 64) return false;
     p.KS = int((d + 15) / 16);
     if (p.KS == 3) p.KS = 4;
@@ -1491,7 +1500,7 @@ bool bce_plan(int64_t n, int64_t n_local, int64_t d, bool vec_ok, BcePlan &p)
     if (p.row_blocks < 1) p.row_blocks = 1;
     int64_t col_tiles = (n + TJ - 1) / TJ;
     if (col_tiles < 1) col_tiles = 1;
-    int64_t want = (g_bce_grid + p.row_blocks - 1) / p.row_blocks;  // ~8 blocks per CU
+    int64_t want = (kBceGrid + p.row_blocks - 1) / p.row_blocks;   // ~8 blocks per CU
     if (want > col_tiles) want = col_tiles;
     if (want > 32) want = 32;                                 // each split is one more partial O' per row to add
     if (want < 1) want = 1;
@@ -1526,35 +1535,31 @@ bool bce_plan(int64_t n, int64_t n_local, int64_t d, bool vec_ok, BcePlan &p)
         const int64_t SYM_PR = (g_bce_sym_ri == 4 || (g_bce_sym_ri == 0 && (n >= 32768 || bal))) ? 256 : 128;
         p.sym_pr = int(SYM_PR);
         const int64_t T = (n + SYM_PR - 1) / SYM_PR, NP = (n + 63) / 64 * 64;
-        int64_t chunks = (g_bce_sym_grid + T - 1) / T; // half of the (panel, chunk) grid is live
+        int64_t chunks = (kBceSymGrid + T - 1) / T;    // half of the (panel, chunk) grid is live
         if (chunks > 28) chunks = 28;                  // every chunk is one more partial O' per row to write and add
         if (chunks > col_tiles) chunks = col_tiles;
         if (chunks < 1) chunks = 1;
         int64_t cpc = ((n + chunks - 1) / chunks + TJ - 1) / TJ * TJ;
-        if (g_bce_sym_tiles > 0) {
-            cpc = int64_t(g_bce_sym_tiles) * TJ;
-        } else {
-            // Launches of a few rounds of blocks (Pubmed: ~2000 live blocks on 768 slots): pick the tiles per block,
-            // within a quarter of the value above, that fills the last round best (12 -> 11 tiles: 2060 -> 2250
-            // blocks = 2.93 rounds instead of 2.68; 169 -> 166 us).  Long launches keep the value: fewer partials.
-            const int64_t slots = int64_t(kChipCus) * (SYM_PR == 128 ? 3 : 2);
-            auto live_blocks = [&](int64_t t) {
-                int64_t L = 0;
-                for (int64_t I = 0; I < T; ++I) L += (n - SYM_PR * I + t * TJ - 1) / (t * TJ);
-                return L;
-            };
-            const int64_t t0 = cpc / TJ;
-            if ((live_blocks(t0) + slots - 1) / slots <= 6) {
-                double best = -1.0;
-                int64_t best_t = t0;
-                for (int64_t t = t0 - t0 / 4; t <= t0 + t0 / 4; ++t) {
-                    if (t < 1) continue;
-                    const int64_t L = live_blocks(t), rounds = (L + slots - 1) / slots;
-                    const double fill = double(L) / double(rounds * slots) - 0.002 * double(t > t0 ? t - t0 : t0 - t);
-                    if (fill > best) { best = fill; best_t = t; }
-                }
-                cpc = best_t * TJ;
+        // Launches of a few rounds of blocks (Pubmed: ~2000 live blocks on 768 slots): pick the tiles per block,
+        // within a quarter of the value above, that fills the last round best (12 -> 11 tiles: 2060 -> 2250
+        // blocks = 2.93 rounds instead of 2.68; 169 -> 166 us).  Long launches keep the value: fewer partials.
+        const int64_t slots = int64_t(kChipCus) * (SYM_PR == 128 ? 3 : 2);
+        auto live_blocks = [&](int64_t t) {
+            int64_t L = 0;
+            for (int64_t I = 0; I < T; ++I) L += (n - SYM_PR * I + t * TJ - 1) / (t * TJ);
+            return L;
+        };
+        const int64_t t0 = cpc / TJ;
+        if ((live_blocks(t0) + slots - 1) / slots <= 6) {
+            double best = -1.0;
+            int64_t best_t = t0;
+            for (int64_t t = t0 - t0 / 4; t <= t0 + t0 / 4; ++t) {
+                if (t < 1) continue;
+                const int64_t L = live_blocks(t), rounds = (L + slots - 1) / slots;
+                const double fill = double(L) / double(rounds * slots) - 0.002 * double(t > t0 ? t - t0 : t0 - t);
+                if (fill > best) { best = fill; best_t = t; }
             }
+            cpc = best_t * TJ;
         }
         const int64_t last_len = NP - SYM_PR * T;      // strip length of the last panel (<= 0: it has no strip)
         const int64_t wfloats = sym_strip_offset(T - 1, NP, SYM_PR) + 16 * (last_len > 0 ? last_len : 0);
@@ -1602,45 +1607,22 @@ int launch_dense(const BcePlan &p, const float *Zt, const unsigned short *Zhi, c
                  hipStream_t s)
 {
     const dim3 grid(unsigned(p.row_blocks) + 1, unsigned(p.n_splits));   // + 1: the column-sum block
-#define GAE_BD(KS, RI, MW, SB)                                                                                     \
+    // SB: three bf16 pieces per operand for S (bce_s_bf16 2 or 3), else exact fp32; P V in bf16 x 3 with bce_pv_bf16
+#define GAE_BD(KS, SB)                                                                                             \
     do {                                                                                                           \
-        if (SB && g_bce_s_bf16 >= 2 && g_bce_pv_bf16 && WITH_GRAD && g_bce_sym_tr)                                  \
-            hipLaunchKernelGGL((bce_dense_kernel<KS, WITH_GRAD, RI, MW, SB, SB, SB && WITH_GRAD, SB>), grid, dim3(256), 0, s, \
-                               Zt, Zhi, Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs, p.prep_blocks, S, \
+        if (SB && g_bce_pv_bf16)                                                                                   \
+            hipLaunchKernelGGL((bce_dense_kernel<KS, WITH_GRAD, kBceRi, 1, SB, SB, SB && WITH_GRAD, SB>), grid, dim3(256), 0, \
+                               s, Zt, Zhi, Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs, p.prep_blocks, S, \
                                S_all_f, unsigned(p.row_blocks));                                                   \
-        else if (SB && g_bce_s_bf16 >= 2 && g_bce_pv_bf16)                                                          \
-            hipLaunchKernelGGL((bce_dense_kernel<KS, WITH_GRAD, RI, MW, SB, SB, false, SB>), grid, dim3(256), 0, s, \
-                               Zt, Zhi, Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs, p.prep_blocks, S, \
-                               S_all_f, unsigned(p.row_blocks));                                                   \
-        else if (SB && g_bce_s_bf16 >= 2)                                                                           \
-            hipLaunchKernelGGL((bce_dense_kernel<KS, WITH_GRAD, RI, MW, SB, false, false, SB>), grid, dim3(256), 0, s, \
-                               Zt, Zhi, Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs, p.prep_blocks, S, \
-                               S_all_f, unsigned(p.row_blocks));                                                   \
-        else if (SB && g_bce_pv_bf16 && WITH_GRAD && g_bce_sym_tr)                                                  \
-            hipLaunchKernelGGL((bce_dense_kernel<KS, WITH_GRAD, RI, MW, SB, SB, SB && WITH_GRAD>), grid, dim3(256), 0, s, \
-                               Zt, Zhi, Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs, p.prep_blocks, S, \
-                               S_all_f, unsigned(p.row_blocks));                                                   \
-        else if (SB && g_bce_pv_bf16)                                                                              \
-            hipLaunchKernelGGL((bce_dense_kernel<KS, WITH_GRAD, RI, MW, SB, SB>), grid, dim3(256), 0, s, Zt, Zhi,  \
-                               Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs, p.prep_blocks, S, S_all_f, \
-                               unsigned(p.row_blocks));                                                            \
         else                                                                                                       \
-            hipLaunchKernelGGL((bce_dense_kernel<KS, WITH_GRAD, RI, MW, SB, false>), grid, dim3(256), 0, s, Zt,    \
-                               Zhi, Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs, p.prep_blocks, S,     \
+            hipLaunchKernelGGL((bce_dense_kernel<KS, WITH_GRAD, kBceRi, 1, SB, false, false, SB>), grid, dim3(256), 0, s, \
+                               Zt, Zhi, Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs, p.prep_blocks, S, \
                                S_all_f, unsigned(p.row_blocks));                                                   \
     } while (0)
     const bool sb = g_bce_s_bf16 != 0;
-    if (p.KS == 1) {
-        if (p.RI == 1) { if (sb) GAE_BD(1, 1, 1, true); else GAE_BD(1, 1, 1, false); }
-        else if (p.RI == 4) { if (sb) GAE_BD(1, 4, 1, true); else GAE_BD(1, 4, 1, false); }
-        else { if (sb) GAE_BD(1, 2, 1, true); else GAE_BD(1, 2, 1, false); }
-    } else if (p.KS == 2) {
-        if (p.RI == 1) { if (sb) GAE_BD(2, 1, 1, true); else GAE_BD(2, 1, 1, false); }
-        else { if (sb) GAE_BD(2, 2, 1, true); else GAE_BD(2, 2, 1, false); }
-    } else {
-        if (p.RI == 1) { if (sb) GAE_BD(4, 1, 1, true); else GAE_BD(4, 1, 1, false); }
-        else { if (sb) GAE_BD(4, 2, 1, true); else GAE_BD(4, 2, 1, false); }
-    }
+    if (p.KS == 1) { if (sb) GAE_BD(1, true); else GAE_BD(1, false); }
+    else if (p.KS == 2) { if (sb) GAE_BD(2, true); else GAE_BD(2, false); }
+    else { if (sb) GAE_BD(4, true); else GAE_BD(4, false); }
 #undef GAE_BD
     GAE_CHECK_LAUNCH("bce_dense_kernel");
     return GAE_OK;
@@ -1669,26 +1651,6 @@ int launch_edges(const BcePlan &p, const float *Zt, const float *mask, int64_t l
 }
 
 } // namespace
-
-namespace gae {
-Knob *bce_knob(const char *name)
-{
-    if (strcmp(name, "bce_ri") == 0) return &g_bce_ri;
-    if (strcmp(name, "bce_s_bf16") == 0) return &g_bce_s_bf16;
-    if (strcmp(name, "bce_pv_bf16") == 0) return &g_bce_pv_bf16;
-    if (strcmp(name, "bce_sym") == 0) return &g_bce_sym;
-    if (strcmp(name, "bce_sym_bal") == 0) return &g_bce_sym_bal;
-    if (strcmp(name, "bce_last_kind") == 0) return &g_bce_last_kind;
-    if (strcmp(name, "bce_sym_grid") == 0) return &g_bce_sym_grid;
-    if (strcmp(name, "bce_grid") == 0) return &g_bce_grid;
-    if (strcmp(name, "bce_sym_tiles") == 0) return &g_bce_sym_tiles;
-    if (strcmp(name, "bce_fold_mirror") == 0) return &g_bce_fold_mirror;
-    if (strcmp(name, "bce_strip_store") == 0) return &g_bce_strip_store;
-    if (strcmp(name, "bce_sym_ri") == 0) return &g_bce_sym_ri;
-    if (strcmp(name, "bce_sym_tr") == 0) return &g_bce_sym_tr;
-    return nullptr;
-}
-} // namespace gae
 
 extern "C" int64_t gae_decoder_bce_workspace_bytes(int64_t n, int64_t n_local, int64_t d)
 {
@@ -1781,19 +1743,17 @@ int decoder_bce_impl(const float *Z, float *mask, int64_t ldz, int64_t n, int64_
 #define GAE_SYM4(WG, R, T, S3V, F16V, FM, PERS, BALV, GRID)                                                          \
     hipLaunchKernelGGL((bce_dense_sym_kernel<WG, R, T, S3V, F16V, PERS, BALV>), GRID, dim3(256), 0, s, Zt, Zhi, Zlo, n, p.cols_per_split, O, Wmir, \
                        lp, cs, p.prep_blocks, S, S_all_f, unsigned(p.row_blocks),                                    \
-                       g_bce_strip_store >= 0 ? g_bce_strip_store : (n >= 32768 ? 1 : 0), range_flag, FM, ticket,  \
+                       n >= 32768 ? 1 : 0, range_flag, FM, ticket,                                                   \
                        (p.bal_tpb ? unsigned(p.bal_blocks) + 1u : unsigned(p.n_splits)), p.bal_tpb)
-#define GAE_SYM(WG, R, T) do { if (g_bce_s_bf16 == 4) GAE_SYM3(WG, R, T, false, true, 0, false, grid);   /* experiments: fp16 pieces WITHOUT the range guard */ \
-    else if (g_bce_s_bf16 >= 3) { GAE_SYM3(WG, R, T, false, true, 1, false, grid); GAE_SYM3(WG, R, T, true, false, 2, true, (p.bal_tpb ? dim3(64) : dim3(2 * kChipCus))); } \
-    else if (g_bce_s_bf16 == 2) GAE_SYM3(WG, R, T, true, false, 0, false, grid); else GAE_SYM3(WG, R, T, false, false, 0, false, grid); } while (0)
+#define GAE_SYM(WG, R, T) do { if (g_bce_s_bf16 == 3) { GAE_SYM3(WG, R, T, false, true, 1, false, grid); GAE_SYM3(WG, R, T, true, false, 2, true, (p.bal_tpb ? dim3(64) : dim3(2 * kChipCus))); } \
+    else GAE_SYM3(WG, R, T, true, false, 0, false, grid); } while (0)
         if (!dZ) { if (p.sym_pr == 256) GAE_SYM(false, 4, false); else GAE_SYM(false, 2, false); }
-        else if (g_bce_sym_tr) { if (p.sym_pr == 256) GAE_SYM(true, 4, true); else GAE_SYM(true, 2, true); }
-        else { if (p.sym_pr == 256) GAE_SYM(true, 4, false); else GAE_SYM(true, 2, false); }
+        else { if (p.sym_pr == 256) GAE_SYM(true, 4, true); else GAE_SYM(true, 2, true); }
 #undef GAE_SYM
 #undef GAE_SYM3
 #undef GAE_SYM4
         GAE_CHECK_LAUNCH("bce_dense_sym_kernel");
-        if (dZ && !(g_bce_fold_mirror && p.LPR == 4)) {     // otherwise the edge kernel folds the strips itself
+        if (dZ && p.LPR != 4) {     // otherwise the edge kernel folds the strips itself
             hipLaunchKernelGGL(bce_mirror_reduce_kernel, dim3(unsigned((n + TJ - 1) / TJ)), dim3(256), 0, s, Wmir, n,
                                Omir, p.sym_pr);
             GAE_CHECK_LAUNCH("bce_mirror_reduce_kernel");
@@ -1807,7 +1767,7 @@ int decoder_bce_impl(const float *Z, float *mask, int64_t ldz, int64_t n, int64_
     double *lpe = lp + 2 * p.n_dense;
     rc = dZ ? launch_edges<4, true>(p, Zt, mask, ldz, row_begin, n_local, int(d), indptr, indices, t_indptr, t_indices,
                                     pos_weight, float(inv_n2), O, S_all_f, dZ, lddz, lpe, p.sym ? Omir : nullptr,
-                                    counts, scal, (p.sym && g_bce_fold_mirror && p.LPR == 4) ? Wmir : nullptr,
+                                    counts, scal, (p.sym && p.LPR == 4) ? Wmir : nullptr,
                                     p.sym ? range_flag : nullptr, s)
             : launch_edges<4, false>(p, Zt, mask, ldz, row_begin, n_local, int(d), indptr, indices, t_indptr,
                                      t_indices, pos_weight, float(inv_n2), O, S_all_f, dZ, lddz, lpe, nullptr, counts,

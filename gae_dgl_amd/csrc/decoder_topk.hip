@@ -35,7 +35,6 @@ constexpr int kTile = 32;         // columns per tile
 constexpr int kMaxK = 64;
 constexpr int kMaxSplits = 16;
 
-gae::Knob g_topk_splits{0};       // "topk_splits": column splits per panel, 0 = auto (tests force 1 or more)
 
 typedef float v16f __attribute__((ext_vector_type(16)));
 
@@ -319,7 +318,7 @@ int splits_for(int64_t n, const int64_t *node_ptr, int64_t max_graph_nodes)
 {
     if (n <= 0) return 1;
     const int64_t panels = (n + kRows - 1) / kRows;
-    int64_t S = g_topk_splits;
+    int64_t S = gae::g_topk_splits;
     if (S <= 0) {
         const int64_t span = node_ptr ? (max_graph_nodes < n ? max_graph_nodes : n) : n;
         S = (4096 + panels - 1) / panels;                  // ~4096 waves: several per SIMD
@@ -334,7 +333,7 @@ int64_t need_bytes(int64_t n, int64_t k, int S) { return S > 1 ? int64_t(S) * n 
 } // namespace
 
 namespace gae {
-Knob *topk_knob(const char *name) { return strcmp(name, "topk_splits") == 0 ? &g_topk_splits : nullptr; }
+Knob g_topk_splits{0};       // "topk_splits": column splits per panel, 0 = auto (tests force 1 or more)
 } // namespace gae
 
 extern "C" int gae_decoder_topk(const float *Z, int64_t ldz, int64_t n, int64_t d, int64_t k, const int64_t *node_ptr,

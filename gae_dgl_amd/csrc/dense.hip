@@ -21,19 +21,20 @@ using gae::kWave;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 enum { PRO_NONE = 0, PRO_RELU_MASK = 1, PRO_MUL_MASK = 2 };
-gae::Knob g_linear_depth{3};  // "linear_depth": k-steps of loads in flight + 1 in that kernel (3, 4, 5)
-gae::Knob g_linear_nw{0};     // "linear_nw": waves per block of that kernel (0 = 4, 8)
-gae::Knob g_linear_f32x16{1}; // "linear_f32x16": exact-fp32 forward Linear through the 64-byte-piece loader (0 = gemm_stream_kernel)
-gae::Knob g_gemm_stream{1};  // tuning knob: 0 = LDS-tiled kernel for every shape
-gae::Knob g_gemm_rows{1};    // "gemm_rows": 0 = never use gemm_rows_kernel, 1 = operands of >= kGemmRowsMinN rows, 2 = wherever it applies
 constexpr int64_t kGemmRowsMinN = 1 << 18;
-gae::Knob g_linear_wlds{1};  // tuning knob: 0 = never use linear_fwd_wlds_kernel, 1 = where measured faster, 2 = wherever it applies
-gae::Knob g_linear_bf16{0};  // tuning knob: 0 = exact fp32 forward Linear (default: embeddings within 2e-7 of fp64 instead of
-                        // 7e-6, tools/encode_error.py), 1 = bf16 x 3 forward where measured faster (Pubmed L1 15.4 -> 13.0 us),
-                        // 2 = wherever it applies
-gae::Knob g_atb_bf16{1};     // "atb_bf16", weight-gradient products (dW kernel where the layout allows; gae_gcn2_bwd_dense): 0 = exact fp32
-                             // MFMAs, 1 = three bf16 pieces per operand, six pairs (fp32-grade; default), 2 = two pieces, three pairs (16 bits)
-gae::Knob g_atb_rows{0};     // tuning knob: rows per block (= per partial) of the dW kernel; 0 = auto (atb_plan)
+} // namespace
+
+namespace gae {
+Knob g_gemm_rows{1};    // "gemm_rows": 0 = never use gemm_rows_kernel, 1 = operands of >= kGemmRowsMinN rows, 2 = wherever it applies
+Knob g_linear_wlds{1};  // "linear_wlds": 0 = never use linear_fwd_wlds_kernel, 1 = where measured faster, 2 = wherever it applies
+Knob g_atb_bf16{1};     // "atb_bf16", weight-gradient products (dW kernel where the layout allows; gae_gcn2_bwd_dense): 0 = exact fp32
+                        // MFMAs, 1 = three bf16 pieces per operand, six pairs (fp32-grade; default), 2 = two pieces, three pairs (16 bits)
+} // namespace gae
+
+namespace {
+using gae::g_gemm_rows;
+using gae::g_linear_wlds;
+using gae::g_atb_bf16;
 
 // ---------------------------------------------------------------------------
 // out[n, J] = epi( proA(A)[n, K] * proB(B) )      B given as [J, K] (BT) or [K, J]
@@ -202,7 +203,7 @@ int dispatch_gemm(const float *A, int64_t lda, const float *Amask, int64_t ldam,
                   const float *Bmask, int64_t ldbm, const float *bias, int act, float *out, int64_t ldo, int64_t n,
                   int K, int64_t J, hipStream_t s, float *split_ws = nullptr, int64_t split_ws_floats = 0)
 {
-    if (!MASK_B && J <= 128 && g_gemm_stream) {
+    if (!MASK_B && J <= 128) {
         if (J <= 32)
             return launch_gemm_stream<1, BT, PRO_A>(A, lda, Amask, ldam, B, ldb, bias, act, out, ldo, n, K, J, s, split_ws,
                                                     split_ws_floats);
@@ -588,22 +589,20 @@ __global__ __launch_bounds__(512) void linear_fwd_wlds_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Forward Linear with bf16 x 3 products: out[n, J <= 32] = act(A[n, K] W[J, K]^T + b), 16-byte aligned rows of A.
-// v_mfma_f32_16x16x16_bf16 wants lane (row = l15, k = 4 g + r): ONE float4 A[row][k0 + 4 g ..] per lane and 16-k
-// step, i.e. an instruction reads 64 contiguous bytes of 16 rows -- half as many requests per 128-byte line as the
-// 32-byte pieces of gemm_stream_kernel's fp32 fragments (4.3 L1->L2 requests per line there) -- and the matrix
-// pipe does the products in a fifth of the fp32 MFMA time.  A block owns 32 rows (2 row tiles); its 4 waves split
-// the block's K range (split-K over blockIdx.y as in gemm_stream_kernel) and meet in LDS in fixed order.
+// Forward Linear with exact fp32 products: out[n, J <= 32] = act(A[n, K] W[J, K]^T + b), 16-byte aligned rows of A.
+// Lane (row = l15, k = 4 g + r) loads ONE float4 A[row][k0 + 4 g ..] per 16-k step, i.e. an instruction reads 64
+// contiguous bytes of 16 rows -- 2 requests per 128-byte line instead of the 4.3 of gemm_stream_kernel's 32-byte
+// pieces -- and the 4 values a lane holds go to 4 consecutive v_mfma_f32_16x16x4_f32, each of which contracts the k
+// positions {4 g + r} of the 16-k step.  A block owns 32 rows (2 row tiles); its 4 waves split the block's K range
+// (split-K over blockIdx.y as in gemm_stream_kernel) and meet in LDS in fixed order.
 // ---------------------------------------------------------------------------
-// EXACT = true: the same loader (64-byte row pieces: 2 requests per 128-byte line instead of the 4.3 of
-// gemm_stream_kernel's 32-byte pieces) feeding v_mfma_f32_16x16x4_f32 -- exact fp32 products; the 4 values a lane
-// holds go to 4 consecutive MFMAs, each of which contracts the k positions {4 g + r} of the 16-k step.
-template <bool WVEC, bool EXACT = false, int NW = 4, int DEPTH = 3>
-__global__ __launch_bounds__(64 * NW) void linear_fwd_pieces_kernel(
+template <bool WVEC>
+__global__ __launch_bounds__(64 * 4) void linear_fwd_pieces_kernel(
     const float *__restrict__ A, int64_t lda, const float *__restrict__ W, int64_t ldw,
     const float *__restrict__ bias, int act, float *__restrict__ out, int64_t ldo, int64_t n, int K, int J,
     int ks_per_split, int64_t split_stride)
 {
+    constexpr int NW = 4, DEPTH = 3;
     __shared__ float red[NW][16 * 64];      // NW waves split the block's K range
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -659,7 +658,6 @@ __global__ __launch_bounds__(64 * NW) void linear_fwd_pieces_kernel(
         const int k = ks * 16 + 4 * g;
         const bool live = ks < ks1;
         const bool kv0 = live && k + 0 < K, kv1 = live && k + 1 < K, kv2 = live && k + 2 < K, kv3 = live && k + 3 < K;
-        gae::v4s ah[2], al[2], wh[2], wl[2];
         gae::v4f avq[2], wvq[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -668,29 +666,14 @@ __global__ __launch_bounds__(64 * NW) void linear_fwd_pieces_kernel(
             const gae::v4f wv = {(jv[q] && kv0) ? st.w[q].x : 0.f, (jv[q] && kv1) ? st.w[q].y : 0.f,
                                  (jv[q] && kv2) ? st.w[q].z : 0.f, (jv[q] && kv3) ? st.w[q].w : 0.f};
             avq[q] = av; wvq[q] = wv;
-            if (!EXACT) {
-                gae::split_bf16x4(av, ah[q], al[q]);
-                gae::split_bf16x4(wv, wh[q], wl[q]);
-            }
-        }
-        if (EXACT) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt)
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(avq[mt][r], wvq[nt][r], acc[mt][nt], 0, 0, 0);
-            return;
         }
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
+        for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(al[mt], wh[nt], acc[mt][nt], 0, 0, 0);
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ah[mt], wl[nt], acc[mt][nt], 0, 0, 0);
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ah[mt], wh[nt], acc[mt][nt], 0, 0, 0);
-            }
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(avq[mt][r], wvq[nt][r], acc[mt][nt], 0, 0, 0);
     };
     if (ks0 < ks1) {
         // ring of DEPTH stages: DEPTH - 1 k-steps of loads are in flight ahead of the MFMAs (a wave lives as long as
@@ -804,36 +787,18 @@ int launch_gemm_stream(const float *A, int64_t lda, const float *Amask, int64_t 
     if (splits > 1 && split_ws_floats < int64_t(splits) * n * J) splits = 1;
     const int kblocks = (K + 7) / 8;
     const int kbps = (kblocks + splits - 1) / splits;
-    // forward Linear with bf16 x 3 products and 64-byte row pieces (linear_fwd_pieces_kernel)
-    // (short unaligned rows of W keep gemm_stream_kernel: ZINC K = 39 measured 10.3 -> 13.2 us; knob 2 forces it)
-    const bool wvec_ok = (ldb % 4 == 0) && gae::aligned16(B) && ldb >= ((K + 3) & ~3);
-    const bool exact16 = g_linear_f32x16 && g_linear_bf16 == 0 && K >= 128;   // exact twin of the same loader
-    if (NT == 1 && BT && PRO_A == PRO_NONE &&
-        (exact16 || g_linear_bf16 > 1 || (g_linear_bf16 == 1 && (wvec_ok || K >= 128))) &&
-        avec && lda >= ((K + 3) & ~3) && K >= 16 && n > 0) {
-        const bool wvec = wvec_ok;
+    // exact-fp32 forward Linear through 64-byte row pieces (linear_fwd_pieces_kernel)
+    if (NT == 1 && BT && PRO_A == PRO_NONE && K >= 128 && avec && lda >= ((K + 3) & ~3) && n > 0) {
+        const bool wvec = (ldb % 4 == 0) && gae::aligned16(B) && ldb >= ((K + 3) & ~3);
         const int ksteps = (K + 15) / 16;
         const int kspp = (ksteps + splits - 1) / splits;
         float *dst = splits > 1 ? split_ws : out;
         const dim3 grid(unsigned((n + 31) / 32), unsigned(splits));
-#define GAE_LB(WV, EX, NW)                                                                                         \
-    if (g_linear_depth == 5)                                                                                       \
-        hipLaunchKernelGGL((linear_fwd_pieces_kernel<WV, EX, NW, 5>), grid, dim3(64 * NW), 0, s, A, lda, B, ldb,     \
-                           splits > 1 ? nullptr : bias, splits > 1 ? int(GAE_ACT_IDENTITY) : act, dst,             \
-                           splits > 1 ? J : ldo, n, K, int(J), kspp, n * J);                                       \
-    else if (g_linear_depth == 4)                                                                                  \
-        hipLaunchKernelGGL((linear_fwd_pieces_kernel<WV, EX, NW, 4>), grid, dim3(64 * NW), 0, s, A, lda, B, ldb,     \
-                           splits > 1 ? nullptr : bias, splits > 1 ? int(GAE_ACT_IDENTITY) : act, dst,             \
-                           splits > 1 ? J : ldo, n, K, int(J), kspp, n * J);                                       \
-    else                                                                                                           \
-    hipLaunchKernelGGL((linear_fwd_pieces_kernel<WV, EX, NW>), grid, dim3(64 * NW), 0, s, A, lda, B, ldb,            \
+#define GAE_LB(WV)                                                                                                 \
+    hipLaunchKernelGGL((linear_fwd_pieces_kernel<WV>), grid, dim3(256), 0, s, A, lda, B, ldb,                      \
                        splits > 1 ? nullptr : bias, splits > 1 ? int(GAE_ACT_IDENTITY) : act, dst,                 \
                        splits > 1 ? J : ldo, n, K, int(J), kspp, n * J)
-        const bool nw8 = g_linear_nw == 8;       // 8 waves per block: measured equal or slower on every layer shape
-        if (exact16 && wvec) { if (nw8) GAE_LB(true, true, 8); else GAE_LB(true, true, 4); }
-        else if (exact16) { if (nw8) GAE_LB(false, true, 8); else GAE_LB(false, true, 4); }
-        else if (wvec) GAE_LB(true, false, 4);
-        else GAE_LB(false, false, 4);
+        if (wvec) GAE_LB(true); else GAE_LB(false);
 #undef GAE_LB
         GAE_CHECK_LAUNCH("linear_fwd_pieces_kernel");
         if (splits > 1) {
@@ -1303,7 +1268,7 @@ AtbPlan atb_plan(int64_t n, int64_t O, int64_t I)
     const bool bf16 = g_atb_bf16 && O <= 32 && I > 32;                  // atb_bf16_kernel: 64 columns per block
     const int64_t cgroups = I <= 32 ? (I + 31) / 32 : bf16 ? (I + 63) / 64 : (I + 127) / 128;
     const int64_t tiles = (cgroups > 0 ? cgroups : 1) * ((O + 31) / 32 > 0 ? (O + 31) / 32 : 1);   // blocks per slot
-    int64_t rows = g_atb_rows > 0 ? g_atb_rows : (n * tiles + 207) / 208;
+    int64_t rows = (n * tiles + 207) / 208;
     rows = (rows + 127) / 128 * 128;                 // 8 waves x a multiple of 16 rows (8 for the fp32 kernel)
     if (rows < 128) rows = 128;
     int64_t want = (n + rows - 1) / rows;
@@ -1588,22 +1553,6 @@ __global__ __launch_bounds__(256) void vgae_head_bwd_kernel(const float *__restr
 }
 
 } // namespace
-
-namespace gae {
-Knob *dense_knob(const char *name)
-{
-    if (strcmp(name, "gemm_stream") == 0) return &g_gemm_stream;
-    if (strcmp(name, "gemm_rows") == 0) return &g_gemm_rows;
-    if (strcmp(name, "linear_f32x16") == 0) return &g_linear_f32x16;
-    if (strcmp(name, "linear_nw") == 0) return &g_linear_nw;
-    if (strcmp(name, "linear_depth") == 0) return &g_linear_depth;
-    if (strcmp(name, "atb_rows") == 0) return &g_atb_rows;
-    if (strcmp(name, "atb_bf16") == 0) return &g_atb_bf16;
-    if (strcmp(name, "linear_bf16") == 0) return &g_linear_bf16;
-    if (strcmp(name, "linear_wlds") == 0) return &g_linear_wlds;
-    return nullptr;
-}
-} // namespace gae
 
 // ===========================================================================
 namespace gae {

@@ -17,14 +17,6 @@ namespace {
 constexpr int kAdamMaxTensors = GAE_ADAM_MAX_TENSORS;
 constexpr int kAdamChunk = 1024;      // elements per block: 256 threads x float4
 }
-namespace gae {
-// "adam_chunk": elements per block of a tensor whose gradient is a short partial-sum list (<= 32 partials): 256 (one
-// per thread), 1024 (four per thread, one after another) or 0 = auto: 256 from 8 partials on (the sum is a chain of
-// dependent round trips: Pubmed, 32 partials, 0.232 -> 0.228 ms per step; Cora, 11: 0.083 -> 0.082), 1024 below
-// (Citeseer, 4 partials of 118 k elements: 0.105 -> 0.103 with the fewer, longer blocks)
-Knob g_adam_chunk{0};
-Knob *optim_knob(const char *name) { return strcmp(name, "adam_chunk") == 0 ? &g_adam_chunk : nullptr; }
-}
 namespace {
 
 struct AdamArgs {
@@ -167,9 +159,12 @@ extern "C" int gae_x_adam_step_tail(const gae_adam_tensor *tensors, int32_t n_te
         a.first_block[k] = int32_t(blocks);
         GAE_REQUIRE(t.n < (int64_t(1) << 31) && t.row_len < (int64_t(1) << 31), GAE_E_SIZE,
                     "gae_adam_step: tensor %d too large", k);
-        const int knob = int(gae::g_adam_chunk);
+        // elements per block of a tensor whose gradient is a short partial-sum list (<= 32 partials): 256 (one per
+        // thread) from 8 partials on (the sum is a chain of dependent round trips: Pubmed, 32 partials, 0.232 -> 0.228
+        // ms per step; Cora, 11: 0.083 -> 0.082), else 1024, four per thread one after another (Citeseer, 4 partials
+        // of 118 k elements: 0.105 -> 0.103 with the fewer, longer blocks)
         const int64_t per_block = t.n_partials > 32 ? 256 / 64
-                                  : t.n_partials > 0 ? ((knob == 256 || knob == 1024) ? knob : (t.n_partials >= 8 ? 256 : 1024))
+                                  : t.n_partials > 0 ? (t.n_partials >= 8 ? 256 : 1024)
                                                      : kAdamChunk;
         a.chunk[k] = int32_t(per_block);
         blocks += (t.n + per_block - 1) / per_block;

@@ -26,7 +26,6 @@ int spmm_ell_launch(const int32_t *indptr, const int32_t *indices, const int32_t
                     int64_t n_cols, const void *H, int64_t ldh, void *M, int64_t ldm, int F, int dtype,
                     const float *rs, const float *cs, int tile_vecs, int xcd_tiled, int store_pad, int store_mode,
                     hipStream_t s);
-Knob *spmm_ell_knob(const char *name);
 }
 
 namespace {
@@ -547,23 +546,35 @@ __global__ __launch_bounds__(256) void spmm_fill_empty_kernel(const int32_t *__r
     }
 }
 
+} // namespace
+
 // tuning knobs (gae_tuning_set): read-mostly process-wide integers
-gae::Knob g_spmm_variant{2};   // 1 = v1 rowgroup, 2 = v2 rowgroup2
-gae::Knob g_spmm_rpg{0};       // rows per lane group (v2): 0 = auto (2 for launches of >= 32768 waves, else 1), 1, 2
-gae::Knob g_spmm_parts{7};     // "spmm_parts" (experiments): which parts of a skew-plan launch run: 1 light rows | 2 segmented rows | 4 pinned rows
-gae::Knob g_spmm_light{1};     // "spmm_light": use the plan's light-row list (1) or sweep all rows with the row-group kernel (0); bit-identical
-gae::Knob g_spmm_desc{1};      // "spmm_desc": segment descriptors / identity segments (1) or the plan's index chain (0); bit-identical
-gae::Knob g_spmm_hot{1};       // "spmm_hot": use the plan's hot-column tags (streaming loads of cold rows); 0 = plain loads
-gae::Knob g_spmm_nt{-1};       // store policy of M (v2): -1 = auto (sc1 under feature tiles, else nt), 0 plain, 1 non-temporal, 2 write-through sc1
-gae::Knob g_spmm_tile_vecs{0}; // 16-byte vectors per XCD feature tile: 0 = auto when GAE_SPMM_TILE is set, -1 = never, > 0 = forced
-gae::Knob g_spmm_ell{1};       // the plan's packed neighbour table: 0 = ignore it, 1 = spmm_ell.hip kernels (row-group
+namespace gae {
+Knob g_spmm_variant{2};   // "spmm_variant": 1 = v1 rowgroup, 2 = v2 rowgroup2
+Knob g_spmm_rpg{0};       // "spmm_rpg": rows per lane group (v2): 0 = auto (2 for launches of >= 32768 waves, else 1), 1, 2
+Knob g_spmm_light{1};     // "spmm_light": use the plan's light-row list (1) or sweep all rows with the row-group kernel (0); bit-identical
+Knob g_spmm_desc{1};      // "spmm_desc": segment descriptors / identity segments (1) or the plan's index chain (0); bit-identical
+Knob g_spmm_hot{1};       // "spmm_hot": use the plan's hot-column tags (streaming loads of cold rows); 0 = plain loads
+Knob g_spmm_tile_vecs{0}; // "spmm_tile_vecs": 16-byte vectors per XCD feature tile: 0 = auto when GAE_SPMM_TILE is set, -1 = never,
+                          // > 0 = forced
+Knob g_spmm_ell{1};       // "spmm_ell": the plan's packed neighbour table: 0 = ignore it, 1 = spmm_ell.hip kernels (row-group
                           // kernel when they cannot run the launch), 2 = row-group kernel only
+} // namespace gae
+
+namespace {
+using gae::g_spmm_variant;
+using gae::g_spmm_rpg;
+using gae::g_spmm_light;
+using gae::g_spmm_desc;
+using gae::g_spmm_hot;
+using gae::g_spmm_tile_vecs;
+using gae::g_spmm_ell;
 
 constexpr int kEllWidth = 16;
 
 template <typename T, int VEC, int LPR, int CH, int RPG>
 int launch_rowgroup2(const int32_t *indptr, const int32_t *indices, int64_t n_rows, const T *H, int64_t ldh, T *M,
-                     int64_t ldm, int F, const float *rs, const float *cs, int st, int tile_vecs, int skip_deg,
+                     int64_t ldm, int F, const float *rs, const float *cs, int tile_vecs, int skip_deg,
                      int flags, const int32_t *ell, hipStream_t s, const float *ep_bias = nullptr,
                      int ep_act = GAE_ACT_IDENTITY, const int32_t *light_desc = nullptr, int64_t n_light = 0)
 {
@@ -582,9 +593,9 @@ int launch_rowgroup2(const int32_t *indptr, const int32_t *indices, int64_t n_ro
                        n_rows, H, ldh, M, ldm, F, rs, cs, nrb, nft, xt, tw * VEC, skip_deg, store_pad, store_mode, ell,        \
                        (flags & GAE_SPMM_ACCUMULATE) ? 1 : 0, ep_bias, ep_act, light_desc, n_light)
     constexpr int EW = VEC > 1 ? kEllWidth : 0;
-    // store policy: 0 plain, 1 non-temporal, 2 write-through sc1; auto (-1) = sc1 under XCD feature tiles (the
-    // output stream must not evict the tile's L2-resident slice of H), non-temporal otherwise
-    const int store_mode = sizeof(T) != 4 ? 0 : st >= 0 ? st : (tiled ? 2 : 1);
+    // store policy (0 plain, 1 non-temporal, 2 write-through sc1): sc1 under XCD feature tiles (the output stream must
+    // not evict the tile's L2-resident slice of H), non-temporal otherwise
+    const int store_mode = sizeof(T) != 4 ? 0 : (tiled ? 2 : 1);
     if (VEC > 1 && ell) {
         if (rs || cs) GAE_L2(true, EW); else GAE_L2(false, EW);
     } else {
@@ -611,7 +622,7 @@ inline int auto_tile_vecs(int nvec, int64_t n_cols)
 
 template <typename T, int VEC>
 int dispatch_rowgroup2(const int32_t *indptr, const int32_t *indices, int64_t n_rows, const T *H, int64_t ldh, T *M,
-                       int64_t ldm, int F, const float *rs, const float *cs, int rpg, int st, int64_t n_cols,
+                       int64_t ldm, int F, const float *rs, const float *cs, int rpg, int64_t n_cols,
                        int skip_deg, int flags, const int32_t *ell, int ell_width, hipStream_t s,
                        const float *ep_bias = nullptr, int ep_act = GAE_ACT_IDENTITY,
                        const int32_t *light_desc = nullptr, int64_t n_light = 0)
@@ -636,7 +647,7 @@ int dispatch_rowgroup2(const int32_t *indptr, const int32_t *indices, int64_t n_
             // write-through (sc1) under feature tiles: the launch itself is 0.4 us faster on Pubmed and the Linear that
             // reads M next finds it in the memory-side cache (non-temporal stores: 22.6 us instead of 17 us for that
             // launch inside a Pubmed step); untiled launches (molecule batches) are faster with non-temporal stores
-            const int store_mode = sizeof(T) != 4 ? 0 : st >= 0 ? st : (tile_vecs > 0 ? 2 : 1);
+            const int store_mode = sizeof(T) != 4 ? 0 : (tile_vecs > 0 ? 2 : 1);
             return gae::spmm_ell_launch(indptr, indices, ell, ell_width, n_rows, n_cols, H, ldh, M, ldm, F,
                                         sizeof(T) == 4 ? GAE_F32 : GAE_BF16, rs, cs, tv, tile_vecs > 0 ? 1 : 0,
                                         store_pad, store_mode, s);
@@ -651,10 +662,10 @@ int dispatch_rowgroup2(const int32_t *indptr, const int32_t *indices, int64_t n_
         const int64_t waves_ = (light_desc ? n_light : n_rows) * LPR / 64 * ((nvec + tw_ - 1) / tw_);            \
         const int rpg_ = rpg > 0 ? rpg : (waves_ >= 32768 ? 2 : 1);                                               \
         if (rpg_ >= 2 && CH == 1)                                                                                 \
-            return launch_rowgroup2<T, VEC, LPR, CH, 2>(indptr, indices, n_rows, H, ldh, M, ldm, F, rs, cs, st,   \
+            return launch_rowgroup2<T, VEC, LPR, CH, 2>(indptr, indices, n_rows, H, ldh, M, ldm, F, rs, cs,       \
                                                         tile_vecs, skip_deg, flags, ell, s, ep_bias, ep_act,      \
                                                         light_desc, n_light);                                     \
-        return launch_rowgroup2<T, VEC, LPR, CH, 1>(indptr, indices, n_rows, H, ldh, M, ldm, F, rs, cs, st,       \
+        return launch_rowgroup2<T, VEC, LPR, CH, 1>(indptr, indices, n_rows, H, ldh, M, ldm, F, rs, cs,           \
                                                     tile_vecs, skip_deg, flags, ell, s, ep_bias, ep_act,          \
                                                     light_desc, n_light);                                         \
     } while (0)
@@ -1107,8 +1118,7 @@ int run_spmm(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int6
     const int min_f = vec ? (sizeof(T) == 4 ? 12 : 24) : 3;
     int rc = GAE_OK;
     const bool listed = (heavy || homed) && plan->light_desc != nullptr && g_spmm_light && f > min_f;
-    if ((heavy || homed) && !(g_spmm_parts & 1)) {
-    } else if (listed) {
+    if (listed) {
         // empty rows: a pure stream; rows with 1 .. threshold edges: the plan's list (every lane group has work)
         const int nvec = (f + VEC - 1) / VEC;
         const int store_pad = ((flags & GAE_SPMM_STORE_PAD) && int64_t(nvec) * VEC <= ldm) ? 1 : 0;
@@ -1124,11 +1134,11 @@ int run_spmm(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int6
                                (flags & GAE_SPMM_SKIP_ROWS) ? plan->skip_rows : nullptr);
             GAE_CHECK_LAUNCH("spmm_fill_empty_kernel");
         }
-        rc = dispatch_rowgroup2<T, VEC>(indptr, indices, n_rows, h, ldh, m, ldm, f, rs, cs, g_spmm_rpg, g_spmm_nt, n_cols,
+        rc = dispatch_rowgroup2<T, VEC>(indptr, indices, n_rows, h, ldh, m, ldm, f, rs, cs, g_spmm_rpg, n_cols,
                                         skip, flags, nullptr, 0, s, ep_bias, ep_act, plan->light_desc, plan->n_light);
     } else if ((g_spmm_variant == 2 || epi) && f > min_f)
         rc = dispatch_rowgroup2<T, VEC>(indptr, indices, n_rows, h, ldh, m, ldm, f, rs, cs, g_spmm_rpg,
-                                        g_spmm_nt, n_cols, skip, flags,
+                                        n_cols, skip, flags,
                                         (plan && g_spmm_ell) ? plan->ell : nullptr, plan ? plan->ell_width : 0, s,
                                         ep_bias, ep_act);
     else {
@@ -1141,7 +1151,7 @@ int run_spmm(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int6
     float *partial = static_cast<float *>(workspace);
     const int ldp = plan_ldp(f);
     const int acc_flag = (flags & GAE_SPMM_ACCUMULATE) ? 1 : 0;
-    if (heavy && (g_spmm_parts & 2)) {
+    if (heavy) {
         rc = dispatch_segments<T, VEC>(indptr, indices, h, ldh, f, cs, plan, partial, ldp, rs, m, ldm, acc_flag, 1, s,
                                        ep_bias, ep_act);
         if (rc) return rc;
@@ -1152,7 +1162,7 @@ int run_spmm(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int6
                            m, ldm, acc_flag, lanes_per_row, ep_bias, ep_act);
         GAE_CHECK_LAUNCH("spmm_combine_kernel");
     }
-    if (homed && (g_spmm_parts & 4)) {
+    if (homed) {
         // XCD-pinned rows: the plan's virtual CSR (one virtual row = one segment = one (row, home, chunk) group of
         // column ids; position p is gathered by block p / 4, i.e. on XCD (p / 4) % 8 = the home of its columns) goes
         // through the same segment kernel into float partials, which are then added per real row in plan order
@@ -1370,40 +1380,3 @@ extern "C" int gae_spmm_csr_blockdiag(const int32_t *indptr, const int32_t *indi
 namespace {
 } // namespace
 
-namespace gae { Knob *dense_knob(const char *name); Knob *bce_knob(const char *name); Knob *xw_knob(const char *name); Knob *optim_knob(const char *name); Knob *topk_knob(const char *name); }
-
-namespace {
-gae::Knob *find_knob(const char *name)
-{
-    const struct { const char *k; gae::Knob *v; } knobs[] = {
-        {"spmm_variant", &g_spmm_variant}, {"spmm_rpg", &g_spmm_rpg}, {"spmm_nt", &g_spmm_nt},
-        {"spmm_tile_vecs", &g_spmm_tile_vecs}, {"spmm_ell", &g_spmm_ell}, {"spmm_hot", &g_spmm_hot},
-        {"spmm_desc", &g_spmm_desc}, {"spmm_parts", &g_spmm_parts}, {"spmm_light", &g_spmm_light}};
-    for (const auto &kv : knobs)
-        if (strcmp(kv.k, name) == 0) return kv.v;
-    if (gae::Knob *k = gae::spmm_ell_knob(name)) return k;
-    if (gae::Knob *k = gae::dense_knob(name)) return k;
-    if (gae::Knob *k = gae::xw_knob(name)) return k;
-    if (gae::Knob *k = gae::optim_knob(name)) return k;
-    if (gae::Knob *k = gae::topk_knob(name)) return k;
-    return gae::bce_knob(name);
-}
-} // namespace
-
-extern "C" int gae_tuning_set(const char *name, int64_t value)
-{
-    GAE_REQUIRE(name != nullptr, GAE_E_NULL, "gae_tuning_set: name is NULL");
-    gae::Knob *k = find_knob(name);
-    GAE_REQUIRE(k != nullptr, GAE_E_RANGE, "gae_tuning_set: unknown knob '%s'", name);
-    *k = int(value);
-    return GAE_OK;
-}
-
-extern "C" int gae_tuning_get(const char *name, int64_t *value_out)
-{
-    GAE_REQUIRE(name != nullptr && value_out != nullptr, GAE_E_NULL, "gae_tuning_get: NULL argument");
-    const gae::Knob *k = find_knob(name);
-    GAE_REQUIRE(k != nullptr, GAE_E_RANGE, "gae_tuning_get: unknown knob '%s'", name);
-    *value_out = int(*k);
-    return GAE_OK;
-}

@@ -117,12 +117,12 @@ struct Vec16<unsigned short> {   // bf16 storage, fp32 accumulation
 
 }  // namespace
 namespace gae {
-gae::Knob g_spmm_ell_rpg{0};      // rows per lane group of the ell kernels: 0 = auto (1)
+Knob g_spmm_ell_rpg{0};      // "spmm_ell_rpg": rows per lane group of the ell kernels: 0 = auto (1)
 // "ell_side": how the side work of the fused layer (gae_x_gcn_layer_fused_wgrad) forms its outer product.  Bit 3: MFMA
 // operands straight from global memory, no LDS, no barrier, when the output is at most 4 tiles of 16 x 16 (Pubmed:
 // launch 9.0 us; gather alone 7.5); bit 2: on the matrix cores from LDS tiles (9.6 us; the form for larger outputs);
 // neither: scalar LDS loop (10.4 us); bit 1: tile loads without a division per element (off: 11.9 us).  Default: all.
-gae::Knob g_ell_side{14};
+Knob g_ell_side{14};
 }
 namespace {
 
@@ -888,13 +888,6 @@ int launch_ell_t(const EllArgs &a, int lpr, int rpg, int W, bool scaled, hipStre
 } // namespace
 
 namespace gae {
-
-Knob *spmm_ell_knob(const char *name)
-{
-    if (strcmp(name, "spmm_ell_rpg") == 0) return &g_spmm_ell_rpg;
-    if (strcmp(name, "ell_side") == 0) return &g_ell_side;
-    return nullptr;
-}
 
 // Can the ell family run this launch?  (16-byte vector layout is the caller's precondition.)
 bool spmm_ell_usable(int64_t n_cols, int64_t ldh, int elem, int ell_width, int tile_vecs)

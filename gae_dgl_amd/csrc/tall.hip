@@ -76,7 +76,7 @@ __device__ __forceinline__ f32x16 mfma_split3(const s16x8 &ah, const s16x8 &al, 
 // Both products are evaluated TRANSPOSED (D1[j][row], D2[j2][row]): the rows of the tile sit in the lanes, so
 // the accumulator registers of the first product ARE the B operands of the second (step r, half h <-> j = rho(r, h)).
 // ---------------------------------------------------------------------------------------------------------------
-template <int KB, int NS = 2>
+template <int KB>
 __global__ __launch_bounds__(256, 3) void linear2_rows_kernel(const float *__restrict__ A, int64_t lda,
                                                            const float *__restrict__ W1, int64_t ldw1,
                                                            const float *__restrict__ b1, int act1,
@@ -207,8 +207,9 @@ __global__ __launch_bounds__(256, 3) void linear2_rows_kernel(const float *__res
     // requested one tile ahead of its loads.  Round 6 (tools/r06/tall_sq.sh: 38 - 54 % of the fp32 matrix pipe, the waves parked
     // at s_waitcnt for 35 - 50 % of their time): scheduling barriers keep the next tile's loads IN FRONT of this tile's MFMAs --
     // same-box A/B, same bits: list mode 0.638 -> 0.630 ms, a contiguous 5 M rows 0.324 -> 0.300 - 0.319, all 2^24 rows 1.00 ->
-    // 0.82 or 1.00 (bimodal from run to run).  NS = 3 / 4 (152 -> 168 VGPRs with 4 / 14 spilled) are slower: 1.04 ms / 0.34 -
+    // 0.82 or 1.00 (bimodal from run to run).  NS = 3 / 4 (152 -> 168 VGPRs with 4 / 14 spilled) were slower: 1.04 ms / 0.34 -
     // 0.39 / 0.66 - 0.71 ms.  The pass is neither a clean stream nor pipe-bound; see MEASUREMENTS.md, round 6.
+    constexpr int NS = 2;
     Stage st[NS];
     unsigned dnext = dead_of((t0 + NS - 1) * 32);
 #pragma unroll

@@ -26,8 +26,6 @@
 // Products: exact fp32 (v_mfma_f32_16x16x4_f32 == an fmaf chain) for fp32 storage; bf16-stored X (BASELINE config 5)
 // feeds v_mfma_f32_16x16x32_bf16 directly in the forward, with W = hi + lo split into two bf16 fragments (fp32
 // accumulation), and is widened in registers for the fp32 MFMAs of the backward.
-#include <string.h>
-
 #include "common.h"
 
 namespace {
@@ -48,7 +46,6 @@ struct XwFwdArgs {
     unsigned x_bytes, ldx_bytes, w_bytes;
     int K, J, ldw, act;
     int tiles_per_block, k_per_block;  // columns per (block, split)
-    unsigned long long *stamps;        // (experiments, DBG = 3) [block][wave][16] s_memtime stamps
 };
 
 // workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains the vector-memory
@@ -74,7 +71,7 @@ __device__ __forceinline__ u32x4 mask_tail(u32x4 v, int left)
 }
 
 // ---------------------------------------------------------------------------------------------------- forward
-template <typename TX, int NH, int SLICE_BYTES, int DBG = 0, int DEPTH = 2, bool P3 = false, int TCV = 6>
+template <typename TX, int NH, int SLICE_BYTES, bool P3 = false>
 __global__ __launch_bounds__(64 * kXwMaxWaves) void xw_fwd_kernel(const XwFwdArgs a)
 {
     // P3 (fp32 storage): the products on the bf16 matrix pipe from three bf16 pieces per operand, six piece pairs
@@ -85,24 +82,17 @@ __global__ __launch_bounds__(64 * kXwMaxWaves) void xw_fwd_kernel(const XwFwdArg
     constexpr int NL = SLICE_BYTES / 64;            // 16-byte loads per lane and row tile
     constexpr int KW = SLICE_BYTES / ES;            // columns of a wave's slice
     constexpr int CPL = 16 / ES;                    // columns per 16-byte load of one lane (4 fp32 / 8 bf16)
-    // DEPTH: row tiles in flight (this one + DEPTH - 1 ahead)
+    constexpr int DEPTH = 2;                        // row tiles in flight (this one + DEPTH - 1 ahead)
     constexpr int OUTW = 16 * NH;
     // partial tiles of up to TC row tiles x 8 waves: the waves run their tiles WITHOUT meeting (a barrier per tile kept
     // the two waves of a SIMD in lockstep and the matrix pipe idle while they reduced: 11 us for the MFMAs alone on
     // Pubmed, 4.3 us of which is issue time); one barrier and one reduction per chunk of TC tiles
-    constexpr int TC = TCV;
+    constexpr int TC = 6;
     __shared__ __attribute__((aligned(16))) float red[TC][kXwMaxWaves][NH * 256];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nw = int(blockDim.x >> 6);
     const int l15 = lane & 15, g = lane >> 4;
-    auto stamp = [&](int k) {
-        if constexpr (DBG == 3) {
-            if (lane == 0 && k < 16)
-                a.stamps[(int64_t(blockIdx.x) * kXwMaxWaves + wave) * 16 + k] = __builtin_amdgcn_s_memtime();
-        }
-    };
-    stamp(0);
     const int kb = int(blockIdx.y) * a.k_per_block + wave * KW;     // first column of this wave's slice
     const bool has_k = wave * KW < a.k_per_block && kb < a.K;
 
@@ -178,7 +168,7 @@ __global__ __launch_bounds__(64 * kXwMaxWaves) void xw_fwd_kernel(const XwFwdArg
     auto issue = [&](u32x4 (&s)[NL], int t) {
         const int64_t row = (tile0 + t) * 16 + l15;
         const bool ok = has_k && t < nt && row < a.n;
-        const unsigned base = (ok && DBG != 2) ? unsigned(row) * a.ldx_bytes + col_off : kBehind;
+        const unsigned base = ok ? unsigned(row) * a.ldx_bytes + col_off : kBehind;
 #pragma unroll
         for (int i = 0; i < NL; ++i) s[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, base + unsigned(i * 64), 0, 0);
     };
@@ -204,11 +194,6 @@ __global__ __launch_bounds__(64 * kXwMaxWaves) void xw_fwd_kernel(const XwFwdArg
                 const bf16x8 xh = __builtin_bit_cast(bf16x8, (P8{xp[0][0], xp[1][0]}));
                 const bf16x8 xm = __builtin_bit_cast(bf16x8, (P8{xp[0][1], xp[1][1]}));
                 const bf16x8 xl = __builtin_bit_cast(bf16x8, (P8{xp[0][2], xp[1][2]}));
-                if constexpr (DBG == 1) {            // (experiment: the loads and the split, no MFMAs)
-#pragma unroll
-                    for (int nh = 0; nh < NH; ++nh)
-                        acc[nh][0] += __builtin_bit_cast(float, int(xh[0]) ^ int(xm[1]) ^ int(xl[2]));
-                } else
 #pragma unroll
                 for (int nh = 0; nh < NH; ++nh) {
                     const bf16x8 wh = __builtin_bit_cast(bf16x8, (P8{w3[i][0][nh], w3[i + 1][0][nh]}));
@@ -228,10 +213,7 @@ __global__ __launch_bounds__(64 * kXwMaxWaves) void xw_fwd_kernel(const XwFwdArg
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
             const u32x4 x = mask_tail<TX>(s[i], left[i]);
-            if constexpr (DBG == 1) {
-#pragma unroll
-                for (int nh = 0; nh < NH; ++nh) acc[nh][0] += __uint_as_float(x[0] ^ x[1] ^ x[2] ^ x[3]);
-            } else if constexpr (sizeof(TX) == 4) {
+            if constexpr (sizeof(TX) == 4) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -255,7 +237,6 @@ __global__ __launch_bounds__(64 * kXwMaxWaves) void xw_fwd_kernel(const XwFwdArg
         for (int nh = 0; nh < NH; ++nh)
 #pragma unroll
             for (int q = 0; q < 4; ++q) mine[(4 * g + q) * OUTW + 16 * nh + l15] = acc[nh][q];
-        stamp(2 + t);
         if ((t + 1) % TC == 0 || t + 1 == nt) {
             const int c0 = t / TC * TC, cnt = t + 1 - c0;
             lds_barrier();
@@ -289,7 +270,6 @@ __global__ __launch_bounds__(64 * kXwMaxWaves) void xw_fwd_kernel(const XwFwdArg
                 }
             }
             if (t + 1 < nt) lds_barrier();          // the next chunk overwrites the slots
-            stamp(12);
         }
     };
 
@@ -298,7 +278,6 @@ __global__ __launch_bounds__(64 * kXwMaxWaves) void xw_fwd_kernel(const XwFwdArg
 #pragma unroll
     for (int d = 0; d < DEPTH - 1; ++d) issue(st[d], d);
     GAE_PIN();
-    stamp(1);
     if constexpr (P3) {
 #pragma unroll
         for (int i = 0; i < NL; ++i)
@@ -351,7 +330,7 @@ struct XtgArgs {
     int64_t n;
     unsigned x_bytes, ldx_bytes, g_bytes, ldg_bytes, gm_bytes, ldgm_bytes;
     int64_t ldd, lddm;
-    int K, J, kp, n_slices, xcd_map;
+    int K, J, kp, n_slices;
     int64_t rows_per_part;             // multiple of 32
 };
 
@@ -362,13 +341,13 @@ constexpr int kXtgGldsBytes = 128 * 1024;
 // there -- the main loop requests nothing but X.  (Round 4 took the kernel apart: X loads + MFMAs without the G loads
 // 9.8 us, everything 12.9 us on Pubmed -- the 8-byte G requests, one more per row group in the same in-order queue as
 // the X stream, cost the last 3 us although they all hit L2.)
-template <typename TX, int NH, bool MASKED, int DBG = 0, int NS = 4, int U = 2, bool GLDS = false>
+template <typename TX, int NH, bool MASKED, bool GLDS = false>
 __global__ __launch_bounds__(512) void xtg_kernel(const XtgArgs a)
 {
     constexpr int ES = int(sizeof(TX));
     constexpr int NQ = 16 / ES;                     // columns per lane (4 fp32 / 8 bf16): output columns NQ n + q
     constexpr int SW = 16 * NQ;                     // columns of a block's slice (64 / 128)
-    // U: 4-row groups per pipeline stage, NS: stages (NS - 1 of them in flight while one is multiplied)
+    constexpr int U = 2, NS = 4;                    // 4-row groups per pipeline stage, stages (NS - 1 in flight)
     constexpr int DBU = 8;                          // db: elements per thread in flight
     constexpr int GW = 16 * NH;                     // floats per staged row of G
     constexpr int RED_FLOATS = 8 * 16 * NH * (SW + 4);
@@ -382,7 +361,7 @@ __global__ __launch_bounds__(512) void xtg_kernel(const XtgArgs a)
     // block -> (partition, slice): consecutive (partition, slice) pairs run on ONE XCD next to each other (bijective
     // XCD remap of the block id), so the 256-byte pieces of a row are requested from one L2 at about the same time
     // (with slice = id % 8 every XCD pulled its own column stripe out of every DRAM page: 18.3 -> 17.0 us on Pubmed)
-    const unsigned lid = a.xcd_map ? gae::xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+    const unsigned lid = gae::xcd_remap(blockIdx.x, gridDim.x);
     const int part = int(lid / unsigned(a.n_slices)), slice = int(lid % unsigned(a.n_slices));
     const int64_t rbeg = int64_t(part) * a.rows_per_part;
     const int64_t rend = min(a.n, rbeg + a.rows_per_part);
@@ -430,9 +409,9 @@ __global__ __launch_bounds__(512) void xtg_kernel(const XtgArgs a)
         for (int u = 0; u < U; ++u) {
             const int64_t row = rbeg + 4 * (wave + 8 * (U * it + u)) + g;
             const bool ok = row < rend;
-            s.x[u] = __builtin_amdgcn_raw_buffer_load_b128(rx, (ok && DBG != 2) ? unsigned(row) * a.ldx_bytes + xcol : kBehind, 0, 0);
+            s.x[u] = __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? unsigned(row) * a.ldx_bytes + xcol : kBehind, 0, 0);
             if constexpr (GLDS) continue;           // the A operands come from LDS (compute)
-            const unsigned go = (ok && j_ok && DBG != 3) ? unsigned(row) * a.ldg_bytes + gcol : kBehind;
+            const unsigned go = (ok && j_ok) ? unsigned(row) * a.ldg_bytes + gcol : kBehind;
             const unsigned mo = (ok && j_ok) ? unsigned(row) * a.ldgm_bytes + gcol : kBehind;
             if constexpr (NH == 2) {
                 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -484,13 +463,9 @@ __global__ __launch_bounds__(512) void xtg_kernel(const XtgArgs a)
                     const bool on = NH * l15 + mh < a.J && (!masked || __uint_as_float(s.gm[u][mh]) > 0.f);
                     gval = on ? __uint_as_float(s.gv[u][mh]) : 0.f;
                 }
-                if constexpr (DBG == 1) {
-                    acc[mh][0][0] += gval * (xv[0] + xv[NQ - 1]);
-                } else {
 #pragma unroll
-                    for (int q = 0; q < NQ; ++q)
-                        acc[mh][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(gval, xv[q], acc[mh][q], 0, 0, 0);
-                }
+                for (int q = 0; q < NQ; ++q)
+                    acc[mh][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(gval, xv[q], acc[mh][q], 0, 0, 0);
             }
         }
     };
@@ -512,7 +487,7 @@ __global__ __launch_bounds__(512) void xtg_kernel(const XtgArgs a)
             const int e = e0 + 512 * t + tid;
             const int64_t row = rbeg + e / (GW / 4);
             const unsigned c4 = unsigned(e % (GW / 4)) * 16u;
-            const bool ok = e < n_pieces && row < rend && DBG != 3;
+            const bool ok = e < n_pieces && row < rend;
             gq[t] = __builtin_amdgcn_raw_buffer_load_b128(rg, ok ? unsigned(row) * a.ldg_bytes + c4 : kBehind, 0, 0);
             if constexpr (MASKED)
                 gmq[t] = __builtin_amdgcn_raw_buffer_load_b128(rm, ok ? unsigned(row) * a.ldgm_bytes + c4 : kBehind, 0, 0);
@@ -535,7 +510,7 @@ __global__ __launch_bounds__(512) void xtg_kernel(const XtgArgs a)
         }
     };
     Stage st[NS];
-    const bool run = iters > 0 && DBG != 4;
+    const bool run = iters > 0;
     if constexpr (GLDS) g_request(0);               // (every wave stages, also one without row groups of its own)
     if (run) {
 #pragma unroll
@@ -627,18 +602,20 @@ __global__ __launch_bounds__(256) void partials_reduce_kernel(const gae::Partial
 // ---------------------------------------------------------------------------------------------------- plans
 struct FwdPlan { int slice_bytes, nw, splits, k_per_block, tiles_per_block; int64_t row_blocks; };
 
-gae::Knob g_xw_rows{0};       // "xw_rows": rows per block of the forward (0 = auto: one block per CU)
-gae::Knob g_xw_parts{0};      // "xw_parts": row partitions of the backward (0 = auto)
-gae::Knob g_xw{1};            // "xw": 0 = never use this family (dense.hip kernels instead)
-gae::Knob g_xw_depth{0};      // "xw_depth" (experiments): other ring depths of the fp32 kernels (forward 3 / 4 / 5 tiles, default 2;
-                              // backward (stages, groups) (2, 4) / (3, 4) / (4, 4) / (6, 2), default (4, 2))
-gae::Knob g_xw_glds{1};       // "xw_glds": 1 = the backward stages its partition's rows of G in LDS (J > 16), 0 = loads them per row group
-gae::Knob g_xw_xcd{1};        // "xw_xcd": XCD-aware block order of the backward (1) or slice-major ids (0); same sums
-gae::Knob g_xw_stamps{0}, g_xw_stamps_hi{0};     // "xw_stamps" / "xw_stamps_hi" (experiments, with xw_dbg = 3): low / high half of the device address of [blocks][8][16] uint64 time stamps
-gae::Knob g_xw_tc{0};         // "xw_tc" (experiments): row tiles per reduction chunk of the forward (LDS: 16 KB each; 0 = 6)
-gae::Knob g_xw_bpc{1};        // "xw_bpc": blocks per CU the forward's grid is sized for
-gae::Knob g_xw_p3{1};         // "xw_p3": fp32-stored X, forward: 1 = bf16 x 3-piece products on the matrix pipe (six pairs, fp32-grade), 0 = exact fp32 MFMAs
-gae::Knob g_xw_dbg{0};        // "xw_dbg" (experiments, wrong results): 1 = without MFMAs, 2 = without X loads; backward also 3 = without G loads, 4 = without its main loop
+} // namespace
+
+namespace gae {
+Knob g_xw_rows{0};       // "xw_rows": rows per block of the forward (0 = auto: one block per CU)
+Knob g_xw_parts{0};      // "xw_parts": row partitions of the backward (0 = auto)
+Knob g_xw_glds{1};       // "xw_glds": 1 = the backward stages its partition's rows of G in LDS (J > 16), 0 = loads them per row group
+Knob g_xw_p3{1};         // "xw_p3": fp32-stored X, forward: 1 = bf16 x 3-piece products on the matrix pipe (six pairs, fp32-grade), 0 = exact fp32 MFMAs
+} // namespace gae
+
+namespace {
+using gae::g_xw_rows;
+using gae::g_xw_parts;
+using gae::g_xw_glds;
+using gae::g_xw_p3;
 
 FwdPlan fwd_plan(int64_t n, int K, int elem)
 {
@@ -649,7 +626,7 @@ FwdPlan fwd_plan(int64_t n, int K, int elem)
     // tiles per block and are split along K over blocks instead (partials added in split order by a second launch).
     FwdPlan p{};
     const int64_t tiles = (n + 15) / 16;
-    const int64_t slots = 256 * (g_xw_bpc > 0 ? int64_t(g_xw_bpc) : 1);
+    const int64_t slots = 256;                                      // one block per CU
     int64_t t = g_xw_rows > 0 ? (g_xw_rows + 15) / 16 : (tiles + slots - 1) / slots;
     if (g_xw_rows == 0 && t < 4) t = tiles < 4 ? tiles : 4;
     if (t < 1) t = 1;
@@ -698,27 +675,10 @@ BwdPlan bwd_plan(int64_t n, int K, int elem)
 
 namespace gae {
 
-Knob *xw_knob(const char *name)
-{
-    if (strcmp(name, "xw_rows") == 0) return &g_xw_rows;
-    if (strcmp(name, "xw_parts") == 0) return &g_xw_parts;
-    if (strcmp(name, "xw") == 0) return &g_xw;
-    if (strcmp(name, "xw_dbg") == 0) return &g_xw_dbg;
-    if (strcmp(name, "xw_xcd") == 0) return &g_xw_xcd;
-    if (strcmp(name, "xw_glds") == 0) return &g_xw_glds;
-    if (strcmp(name, "xw_depth") == 0) return &g_xw_depth;
-    if (strcmp(name, "xw_p3") == 0) return &g_xw_p3;
-    if (strcmp(name, "xw_tc") == 0) return &g_xw_tc;
-    if (strcmp(name, "xw_stamps") == 0) return &g_xw_stamps;
-    if (strcmp(name, "xw_stamps_hi") == 0) return &g_xw_stamps_hi;
-    if (strcmp(name, "xw_bpc") == 0) return &g_xw_bpc;
-    return nullptr;
-}
-
 // can the stream family run these operands?  (rows of whole 16-byte vectors, X addressable through one raw buffer)
 bool xw_usable(const void *X, int64_t ldx, int64_t n, int64_t K, int64_t J, int elem)
 {
-    return g_xw != 0 && n > 0 && K >= 193 && K < (1 << 24) && J >= 1 && J <= 32 && (ldx * elem) % 16 == 0 &&
+    return n > 0 && K >= 193 && K < (1 << 24) && J >= 1 && J <= 32 && (ldx * elem) % 16 == 0 &&
            ldx >= K && aligned16(X) && n * ldx * elem < int64_t(0xE0000000u);
 }
 
@@ -743,41 +703,18 @@ int xw_fwd_launch(const void *X, int64_t ldx, int64_t n, int K, int elem, const 
     a.x_bytes = unsigned(n * ldx * elem); a.ldx_bytes = unsigned(ldx * elem);
     a.w_bytes = unsigned(((int64_t(J) - 1) * ldw + K) * 4);
     a.tiles_per_block = p.tiles_per_block; a.k_per_block = p.k_per_block;
-    a.stamps = reinterpret_cast<unsigned long long *>((uint64_t(uint32_t(int(g_xw_stamps_hi))) << 32) | uint32_t(int(g_xw_stamps)));
-    if (g_xw_dbg == 3 && a.stamps == nullptr) {      // the stamping variant writes through this pointer
-        set_error("xw_fwd: xw_dbg=3 (s_memtime stamps) needs the stamp buffer's address in xw_stamps / xw_stamps_hi");
-        return GAE_E_NULL;
-    }
     if (p.splits > 1) { a.bias = nullptr; a.act = GAE_ACT_IDENTITY; a.out = static_cast<float *>(ws); a.ldo = J; a.split_stride = n * J; }
     else { a.bias = bias; a.act = act; a.out = out; a.ldo = ldo; a.split_stride = 0; }
     const dim3 grid(unsigned(p.row_blocks), unsigned(p.splits)), block(unsigned(64 * p.nw));
 #define GAE_XW(TX, NH, SB) hipLaunchKernelGGL((xw_fwd_kernel<TX, NH, SB>), grid, block, 0, s, a)
     const bool wide = J > 16;
     if (elem == 4) {
-        if (g_xw_p3 != 0 && p.slice_bytes == 256 && wide && (g_xw_dbg || g_xw_depth || g_xw_tc)) {     // experiments
-            const int dp = g_xw_depth ? int(g_xw_depth) : 2, tc = g_xw_tc ? int(g_xw_tc) : 6, dbg = int(g_xw_dbg);
-            bool launched = false;
-#define GAE_XWE(DB, DP, TC) if (dbg == DB && dp == DP && tc == TC) { hipLaunchKernelGGL((xw_fwd_kernel<float, 2, 256, DB, DP, true, TC>), grid, block, 0, s, a); launched = true; }
-            GAE_XWE(0, 2, 6); GAE_XWE(0, 3, 6); GAE_XWE(0, 4, 6); GAE_XWE(0, 2, 3); GAE_XWE(0, 3, 3); GAE_XWE(0, 4, 3);
-            GAE_XWE(1, 2, 6); GAE_XWE(2, 2, 6); GAE_XWE(1, 4, 3); GAE_XWE(2, 4, 3); GAE_XWE(3, 2, 6);
-#undef GAE_XWE
-            if (!launched) {      // only the instantiated (xw_dbg, xw_depth, xw_tc) combinations exist: never return uninitialised output
-                set_error("xw_fwd: no kernel for the knob combination xw_dbg=%d xw_depth=%d xw_tc=%d (with xw_p3=1: depth 2|3|4 x "
-                          "tc 3|6 at dbg 0; dbg 1|2 at (2,6) and (4,3); dbg 3 at (2,6))", dbg, dp, tc);
-                return GAE_E_RANGE;
-            }
-        }
-        else if (g_xw_p3 != 0) {
-#define GAE_XW3(NH, SB) hipLaunchKernelGGL((xw_fwd_kernel<float, NH, SB, 0, 2, true>), grid, block, 0, s, a)
+        if (g_xw_p3 != 0) {
+#define GAE_XW3(NH, SB) hipLaunchKernelGGL((xw_fwd_kernel<float, NH, SB, true>), grid, block, 0, s, a)
             if (p.slice_bytes == 256) { if (wide) GAE_XW3(2, 256); else GAE_XW3(1, 256); }
             else { if (wide) GAE_XW3(2, 512); else GAE_XW3(1, 512); }
 #undef GAE_XW3
         }
-        else if (p.slice_bytes == 256 && wide && g_xw_depth == 4) hipLaunchKernelGGL((xw_fwd_kernel<float, 2, 256, 0, 4>), grid, block, 0, s, a);
-        else if (p.slice_bytes == 256 && wide && g_xw_depth == 5) hipLaunchKernelGGL((xw_fwd_kernel<float, 2, 256, 0, 5>), grid, block, 0, s, a);
-        else if (p.slice_bytes == 256 && wide && g_xw_depth == 3) hipLaunchKernelGGL((xw_fwd_kernel<float, 2, 256, 0, 3>), grid, block, 0, s, a);
-        else if (p.slice_bytes == 256 && wide && g_xw_dbg == 1) hipLaunchKernelGGL((xw_fwd_kernel<float, 2, 256, 1>), grid, block, 0, s, a);
-        else if (p.slice_bytes == 256 && wide && g_xw_dbg == 2) hipLaunchKernelGGL((xw_fwd_kernel<float, 2, 256, 2>), grid, block, 0, s, a);
         else if (p.slice_bytes == 256) { if (wide) GAE_XW(float, 2, 256); else GAE_XW(float, 1, 256); }
         else { if (wide) GAE_XW(float, 2, 512); else GAE_XW(float, 1, 512); }
     } else {
@@ -842,7 +779,6 @@ int xtg_launch(const void *X, int64_t ldx, int64_t n, int K, int elem, const flo
     if (!want_dw) { a.x_bytes = 0; a.g_bytes = 0; a.gm_bytes = 0; a.Gmask = nullptr; }     // every load behind its buffer: zeros
     // (db alone still sweeps the slices: its rows are dealt to the slice blocks; the products of an unwanted dW go to
     // the workspace and are not reduced)
-    a.xcd_map = g_xw_xcd != 0;
     const dim3 grid(unsigned(p.n_slices) * unsigned(p.parts));
     const bool wide = J > 16;
     // staged G ("xw_glds", default on): the rows the waves read -- wave 0's stages of 2 x 32 rows -- must fit 128 KB
@@ -851,21 +787,13 @@ int xtg_launch(const void *X, int64_t ldx, int64_t n, int K, int elem, const flo
 #define GAE_XTG(TX, NH, ...) do { if (a.Gmask) hipLaunchKernelGGL((xtg_kernel<TX, NH, true, __VA_ARGS__>), grid, dim3(512), 0, s, a); \
                                    else hipLaunchKernelGGL((xtg_kernel<TX, NH, false, __VA_ARGS__>), grid, dim3(512), 0, s, a); } while (0)
     if (elem == 4) {
-        if (wide && g_xw_dbg == 1) GAE_XTG(float, 2, 1);
-        else if (wide && g_xw_dbg == 2) GAE_XTG(float, 2, 2);
-        else if (wide && g_xw_dbg == 3) GAE_XTG(float, 2, 3);
-        else if (wide && g_xw_dbg == 4) GAE_XTG(float, 2, 4);
-        else if (wide && g_xw_depth == 2) GAE_XTG(float, 2, 0, 2, 4);
-        else if (wide && g_xw_depth == 4) GAE_XTG(float, 2, 0, 4, 4);
-        else if (wide && g_xw_depth == 3) GAE_XTG(float, 2, 0, 3, 4);
-        else if (wide && g_xw_depth == 6) GAE_XTG(float, 2, 0, 6, 2);
-        else if (wide && glds) GAE_XTG(float, 2, 0, 4, 2, true);
-        else if (wide) GAE_XTG(float, 2, 0);
-        else GAE_XTG(float, 1, 0);
+        if (wide && glds) GAE_XTG(float, 2, true);
+        else if (wide) GAE_XTG(float, 2, false);
+        else GAE_XTG(float, 1, false);
     } else {
-        if (wide && glds) GAE_XTG(unsigned short, 2, 0, 4, 2, true);
-        else if (wide) GAE_XTG(unsigned short, 2, 0);
-        else GAE_XTG(unsigned short, 1, 0);
+        if (wide && glds) GAE_XTG(unsigned short, 2, true);
+        else if (wide) GAE_XTG(unsigned short, 2, false);
+        else GAE_XTG(unsigned short, 1, false);
     }
 #undef GAE_XTG
     GAE_CHECK_LAUNCH("xtg_kernel");

@@ -85,21 +85,25 @@ int gae_device_info_get(int device, gae_device_info *out_host);
 /* Tuning / test knobs: ONE integer per process and knob (relaxed atomics, read at launch time).  Process-wide on
  * purpose: PyTorch runs the backward of an autograd Function on its engine's worker thread, so a per-thread value
  * would not reach the launches made in backward() (dW, A^T products).  Meant to be set once, before the launches
- * they should affect; every other piece of library state is per call.  Three kinds:
- *  - select among kernels with bit-identical results: "spmm_variant", "spmm_rpg", "spmm_nt", "spmm_tile_vecs",
- *    "spmm_ell", "spmm_ell_rpg", "spmm_hot", "spmm_desc", "spmm_parts" (bit mask of the parts of a skew-plan
- *    launch that run; experiments only), "bce_strip_store", "bce_fold_mirror";
+ * they should affect; every other piece of library state is per call.  gae_tuning_set refuses an unknown name
+ * and a value outside the knob's allowed set (GAE_E_RANGE; gae_last_error names the allowed values).  The knobs,
+ * as "name" = default {allowed values}:
+ *  - select among kernels with bit-identical results: "spmm_variant" = 2 {1, 2}, "spmm_rpg" = 0 {0, 1, 2},
+ *    "spmm_tile_vecs" = 0 {-1 .. 256}, "spmm_ell" = 1 {0, 1, 2}, "spmm_ell_rpg" = 0 {0, 1, 2}, "spmm_hot" = 1
+ *    {0, 1}, "spmm_desc" = 1 {0, 1}, "spmm_light" = 1 {0, 1}, "xw_glds" = 1 {0, 1} (whether gae_xw_wgrad stages
+ *    its rows of G in LDS), "topk_splits" = 0 {0 .. 16} (column splits of gae_decoder_topk, 0 = auto);
  *  - change the ORDER in which partial sums are added (results agree within the fp32 tolerance of DESIGN.md
- *    section 6, not bit for bit): "atb_rows", "gemm_stream", "gemm_rows", "linear_wlds", "linear_f32x16", "linear_nw", "linear_depth", "bce_ri", "bce_sym", "bce_sym_ri",
- *    "bce_sym_grid", "bce_sym_tiles", "bce_grid"; a skew
- *    plan (gae_spmm_plan with heavy rows) and GAE_SPMM_ACCUMULATE do the same for the rows they touch;
- *    "xw" (0 = the layer-1 stream kernels of gae_xw_fwd are never used by gae_linear_fwd), "xw_rows" (rows per block
- *    of gae_xw_fwd, 0 = auto), "xw_parts" (row partitions of gae_xw_wgrad, 0 = auto) likewise; "xw_depth" / "xw_xcd" /
- *    "xw_glds" select pipeline depths / the block order of those kernels / whether gae_xw_wgrad stages its rows of G
- *    in LDS (same sums, bit for bit); "xw_dbg" (experiments: WRONG results --
- *    1 = no MFMAs, 2 = no loads of X);
- *  - select the ARITHMETIC of matrix-core products: "bce_s_bf16" / "bce_pv_bf16" / "atb_bf16" (1 = bf16 x 3 split
- *    products, default; 0 = exact fp32 MFMA) and "linear_bf16" (default 0 = exact fp32 forward Linear). */
+ *    section 6, not bit for bit): "gemm_rows" = 1 {0, 1, 2}, "linear_wlds" = 1 {0, 1, 2}, "ell_side" = 14
+ *    {0 .. 15}, "bce_sym" = 1 {0, 1, 2}, "bce_sym_ri" = 0 {0, 2, 4}, "bce_sym_bal" = 1 {0, 1, 2}, "xw_rows" = 0
+ *    {0 .. 2^24} (rows per block of gae_xw_fwd, 0 = auto), "xw_parts" = 0 {0 .. 2^20} (row partitions of
+ *    gae_xw_wgrad, 0 = auto); a skew plan (gae_spmm_plan with heavy rows) and GAE_SPMM_ACCUMULATE do the same
+ *    for the rows they touch;
+ *  - select the ARITHMETIC of matrix-core products: "bce_s_bf16" = 3 {0, 2, 3} (3 = range-guarded fp16 pieces
+ *    where the symmetric loss kernel runs, bf16 x 3 elsewhere; 2 = bf16 x 3; 0 = exact fp32 MFMA), "bce_pv_bf16"
+ *    = 1 {0, 1}, "xw_p3" = 1 {0, 1} and "atb_bf16" = 1 {0, 1, 2} (1 = bf16 x 3 split products; 0 = exact fp32
+ *    MFMA; atb_bf16 = 2: two pieces, 16 bits).
+ * Read-only (gae_tuning_get): "bce_last_kind", the dense kernel of the last loss call (0 none yet, 1 full square,
+ * 2 / 3 symmetric with 128- / 256-row panels). */
 int gae_tuning_set(const char *name, int64_t value);
 int gae_tuning_get(const char *name, int64_t *value_out);
 

@@ -182,3 +182,63 @@ def test_tuning_knobs_round_trip_and_are_process_wide():
     assert lib.gae_tuning_set(b"spmm_tile_vecs", default) == 0
     assert lib.gae_tuning_get(b"no_such_knob", ctypes.byref(ctypes.c_int64())) != 0
     assert lib.gae_tuning_set(b"no_such_knob", 1) != 0 and b"unknown knob" in lib.gae_last_error()
+
+
+def _header_knobs():
+    """the knobs include/gae_hip.h documents: name -> (default, allowed values or None for a range, range)"""
+    text = open(HEADER).read()
+    block = text[text.index("int gae_device_info_get("):text.index("int gae_tuning_set(")]
+    block = re.sub(r"\s*\n\s*\*\s*", " ", block)
+    knobs = {}
+    for name, default, allowed in re.findall(r'"([a-z0-9_]+)" = (-?\d+) \{([^}]*)\}', block):
+        if ".." in allowed:
+            lo, hi = (2 ** int(x.split("^")[1]) if "^" in x else int(x) for x in allowed.split(".."))
+            knobs[name] = (int(default), None, (lo, hi))
+        else:
+            knobs[name] = (int(default), [int(v) for v in allowed.split(",")], None)
+    return knobs
+
+
+RETIRED_KNOBS = ["xw", "xw_dbg", "xw_depth", "xw_tc", "xw_stamps", "xw_stamps_hi", "xw_xcd", "xw_bpc",
+                 "linear_depth", "linear_nw", "linear_f32x16", "linear_bf16", "gemm_stream", "atb_rows",
+                 "bce_ri", "bce_grid", "bce_sym_grid", "bce_sym_tiles", "bce_strip_store", "bce_fold_mirror",
+                 "bce_sym_tr", "spmm_parts", "spmm_nt", "adam_chunk"]
+
+
+def test_tuning_knobs_match_the_header_and_check_their_values():
+    """every knob the header lists reads back its stated default and takes exactly its stated values; retired
+    knobs are unknown; the telemetry value bce_last_kind is read-only"""
+    import ctypes
+    from gae_dgl_amd import _lib
+    lib = _lib.load()
+    GAE_E_RANGE = -6
+
+    def get(name):
+        v = ctypes.c_int64(-99)
+        assert lib.gae_tuning_get(name.encode(), ctypes.byref(v)) == 0, name
+        return v.value
+    knobs = _header_knobs()
+    assert len(knobs) == 22, sorted(knobs)
+    for name, (default, values, rng) in knobs.items():
+        assert get(name) == default, name
+        lo, hi = rng if rng else (min(values), max(values))
+        try:
+            for v in (values if values else [lo, hi]):
+                assert lib.gae_tuning_set(name.encode(), v) == 0 and get(name) == v, (name, v)
+            for v in [lo - 1, hi + 1] + [v for v in range(lo, hi + 1) if values and v not in values]:
+                assert lib.gae_tuning_set(name.encode(), v) == GAE_E_RANGE, (name, v)
+                assert name.encode() in lib.gae_last_error() and b"allowed" in lib.gae_last_error()
+        finally:
+            assert lib.gae_tuning_set(name.encode(), default) == 0
+        assert get(name) == default
+    for name, v in (("bce_s_bf16", 1), ("bce_s_bf16", 4), ("spmm_rpg", 9)):
+        assert lib.gae_tuning_set(name.encode(), v) == GAE_E_RANGE
+        assert lib.gae_last_error().startswith(f"gae_tuning_set: {name} = {v} is out of range".encode())
+    assert b"allowed: 0, 2, 3" in (lib.gae_tuning_set(b"bce_s_bf16", 1), lib.gae_last_error())[1]
+    assert get("bce_s_bf16") == 3 and get("spmm_rpg") == 0
+
+    assert get("bce_last_kind") in (0, 1, 2, 3)
+    assert lib.gae_tuning_set(b"bce_last_kind", 1) == GAE_E_RANGE and b"read-only" in lib.gae_last_error()
+    for name in RETIRED_KNOBS:
+        assert lib.gae_tuning_set(name.encode(), 0) == GAE_E_RANGE and b"unknown knob" in lib.gae_last_error(), name
+        assert lib.gae_tuning_get(name.encode(), ctypes.byref(ctypes.c_int64())) == GAE_E_RANGE, name

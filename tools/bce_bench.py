@@ -30,17 +30,10 @@ ref = None
 for rnd in range(a.rounds + 1):
     for v in a.variants.split(";"):
         kv = dict(x.split("=") for x in v.split(","))
-        _lib.call("gae_tuning_set", b"bce_ri", int(kv.get("ri", 2)))
         _lib.call("gae_tuning_set", b"bce_s_bf16", int(kv.get("sb", 3)))
         _lib.call("gae_tuning_set", b"bce_pv_bf16", int(kv.get("pb", 1)))
         _lib.call("gae_tuning_set", b"bce_sym", int(kv.get("sym", 1)))
-        _lib.call("gae_tuning_set", b"bce_sym_grid", int(kv.get("grid", 16384)))
         _lib.call("gae_tuning_set", b"bce_sym_ri", int(kv.get("sri", 0)))
-        _lib.call("gae_tuning_set", b"bce_grid", int(kv.get("fgrid", 2048)))
-        _lib.call("gae_tuning_set", b"bce_sym_tiles", int(kv.get("tiles", 0)))
-        _lib.call("gae_tuning_set", b"bce_strip_store", int(kv.get("strip", -1)))
-        _lib.call("gae_tuning_set", b"bce_fold_mirror", int(kv.get("fold", 1)))
-        _lib.call("gae_tuning_set", b"bce_sym_tr", int(kv.get("tr", 1)))
         _lib.call("gae_tuning_set", b"bce_sym_bal", int(kv.get("bal", 1)))
         fn = lambda: ops.decoder_bce_raw(Z, mask, g.csr(), g.csc(), pw, True)
         loss, dz = fn(); torch.cuda.synchronize()

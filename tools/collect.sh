@@ -28,8 +28,8 @@ done
 PMC_TIMEOUT=300 tools/pmc.sh $TAG/pmc_rmat32 tools/spmm_one.py --shape rmat32 --rmat-scale 24 --iters 3 > $O/pmc_rmat32.txt
 tools/pmc.sh $TAG/pmc_pubmed500_plain tools/spmm_one.py --shape pubmed500 --iters 5 --plain > $O/pmc_pubmed500_plain.txt
 timeout 300 python tools/linear_bench.py --rows 256 2>/dev/null > $O/linear_bench.txt
-timeout 300 python tools/spmm_bench.py --shapes pubmed500a,pband500 --variants v2:0:1:0:p,v2:0:1:0:pt,v2:0:1:0:pEt,v2:1:1:0:pet --rounds 5 2>/dev/null > $O/spmm_bench_pubmed.txt
-timeout 300 python tools/spmm_bench.py --shapes pdiag_zero,pdiag_col2k --variants v2:0:1:0:p,v2:1:1:16:pet --rounds 5 2>/dev/null > $O/spmm_bench_diag.txt
+timeout 300 python tools/spmm_bench.py --shapes pubmed500a,pband500 --variants v2:0:0:p,v2:0:0:pt,v2:0:0:pEt,v2:1:0:pet --rounds 5 2>/dev/null > $O/spmm_bench_pubmed.txt
+timeout 300 python tools/spmm_bench.py --shapes pdiag_zero,pdiag_col2k --variants v2:0:0:p,v2:1:16:pet --rounds 5 2>/dev/null > $O/spmm_bench_diag.txt
 timeout 300 python tools/bce_bench.py --variants "sym=1;sym=0;sym=0,sb=0,pb=0" --rounds 5 2>/dev/null > $O/bce_bench_pubmed.txt
 timeout 300 python tools/bce_bench.py --n 94752 --variants "sym=1;sym=1,sri=2;sym=0" --rounds 3 2>/dev/null > $O/bce_bench_zinc.txt
 timeout 200 tools/probes/bin/gather_l2 > $O/probe_gather_l2.txt 2>&1

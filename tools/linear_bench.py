@@ -25,7 +25,6 @@ def t_(fn, iters=50):
 
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--rows", default="0,128,256,512")
 ap.add_argument("--knobs", default="")
 ap.add_argument("--only", default="")
 a = ap.parse_args()
@@ -43,9 +42,6 @@ for (name, n, fin, fout) in shapes:
     mb = n * fin * 4 / 1e6
     tf = t_(lambda: ops.linear_fwd_raw(M, W, b, 1))
     print(f"{name}: {n} x {fin} -> {fout}  (M = {mb:.1f} MB)   fwd {tf:.1f} us ({mb / tf:.2f} TB/s of M)")
-    for rows in (int(r) for r in a.rows.split(",")):
-        _lib.call("gae_tuning_set", b"atb_rows", rows)
-        t1 = t_(lambda: ops.linear_bwd_raw(dY, Y, 1, M, W, True, True, False))
-        t2 = t_(lambda: ops.linear_bwd_raw(dY, Y, 1, M, W, True, True, True))
-        print(f"   atb_rows={rows}: bwd(dW,db) {t1:.1f} us ({mb / t1:.2f} TB/s)   bwd(dW,db,dM) {t2:.1f} us")
-    _lib.call("gae_tuning_set", b"atb_rows", 0)
+    t1 = t_(lambda: ops.linear_bwd_raw(dY, Y, 1, M, W, True, True, False))
+    t2 = t_(lambda: ops.linear_bwd_raw(dY, Y, 1, M, W, True, True, True))
+    print(f"   bwd(dW,db) {t1:.1f} us ({mb / t1:.2f} TB/s)   bwd(dW,db,dM) {t2:.1f} us")

@@ -38,8 +38,6 @@ pmc)
   PMC_TIMEOUT=300 tools/pmc.sh r03/pmc_rmat32 tools/spmm_one.py --shape rmat32 --rmat-scale 24 --iters 3 > $O/pmc_rmat32.txt
   ;;
 micro)
-  timeout 300 python tools/r03/xw_bench.py 2>/dev/null > $O/xw_bench.txt
-  timeout 300 python tools/r03/xw_sweep.py pubmed 2>/dev/null > $O/xw_sweep_pubmed.txt
   timeout 300 python tools/bce_bench.py --variants "sym=1;sym=0;sym=0,sb=0,pb=0" --rounds 5 2>/dev/null > $O/bce_bench_pubmed.txt
   ;;
 esac

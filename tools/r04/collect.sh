@@ -40,15 +40,13 @@ pmc)
   PMC_TIMEOUT=400 tools/pmc.sh r04c/pmc_rmat16 tools/spmm_one.py --shape rmat16 --rmat-scale 24 --iters 3 > $O/pmc_rmat16.txt
   ;;
 micro)
-  timeout 300 python tools/r03/xw_bench.py 2>/dev/null > $O/xw_bench.txt
-  timeout 300 python tools/r04/xtg_probe.py 2>/dev/null > $O/xtg_probe.txt
   timeout 300 python tools/r04/spx_bench.py 2>/dev/null > $O/spx_bench.txt
   timeout 300 python tools/r04/tall_bench.py 2>/dev/null > $O/tall_bench.txt
   timeout 300 python tools/r04/zinc_l1.py 2>/dev/null > $O/zinc_l1.txt
   timeout 300 python tools/r04/loss_condition.py --sym 2>/dev/null > $O/loss_condition.txt
-  timeout 300 python tools/bce_bench.py --variants "sym=1,sb=3;sym=1,sb=2;sym=1,sb=1;sym=1,sb=0;sym=0,sb=0,pb=0" --rounds 5 2>/dev/null > $O/bce_bench_pubmed.txt
-  timeout 300 python tools/bce_bench.py --n 95000 --variants "sym=1,sb=3;sym=1,sb=2;sym=1,sb=1" --rounds 3 2>/dev/null > $O/bce_bench_zinc.txt
-  timeout 300 python tools/bce_bench.py --graph cora --variants "sym=0,sb=3;sym=0,sb=1;sym=0,sb=0" --rounds 5 2>/dev/null > $O/bce_bench_cora.txt
+  timeout 300 python tools/bce_bench.py --variants "sym=1,sb=3;sym=1,sb=2;sym=1,sb=0;sym=0,sb=0,pb=0" --rounds 5 2>/dev/null > $O/bce_bench_pubmed.txt
+  timeout 300 python tools/bce_bench.py --n 95000 --variants "sym=1,sb=3;sym=1,sb=2" --rounds 3 2>/dev/null > $O/bce_bench_zinc.txt
+  timeout 300 python tools/bce_bench.py --graph cora --variants "sym=0,sb=3;sym=0,sb=0" --rounds 5 2>/dev/null > $O/bce_bench_cora.txt
   timeout 300 python tools/r04/plan_build_time.py 2>/dev/null > $O/plan_build_time.txt
   ;;
 esac

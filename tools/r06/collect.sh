@@ -45,8 +45,6 @@ micro)
   timeout 300 python tools/bce_bench.py --variants "sri=2,bal=0;sri=2,bal=1;sri=4,bal=0;sri=4,bal=1" --rounds 5 2>/dev/null > $O/bce_bench_pubmed.txt
   for n in 3327 5000 8000 26000 40000; do echo "== N = $n" >> $O/bce_bench_sizes.txt; timeout 300 python tools/bce_bench.py --n $n --variants "sym=1,bal=0,sri=2;sym=2,sri=2,bal=0;sym=2,sri=2,bal=1;sym=2,sri=4,bal=0;sym=2,sri=4,bal=1" --rounds 4 2>/dev/null | grep median >> $O/bce_bench_sizes.txt; done
   timeout 300 python tools/bce_bench.py --n 95000 --variants "sri=2,bal=0;sri=2,bal=2;sri=4,bal=0;sri=4,bal=2" --rounds 3 2>/dev/null > $O/bce_bench_zinc.txt
-  timeout 600 python tools/r06/spmm_tile_sweep.py --shape pubmed 2>/dev/null > $O/spmm_tile_sweep_pubmed.txt
-  timeout 600 python tools/r06/spmm_tile_sweep.py --shape cora --tiles 0,8,16,32,64,-1 --stores -1 2>/dev/null > $O/spmm_tile_sweep_cora.txt
   [ -s $O/rmat_windows.txt ] || timeout 900 python tools/r06/rmat_windows.py 2>/dev/null > $O/rmat_windows.txt
   ;;
 esac

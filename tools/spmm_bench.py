@@ -45,7 +45,7 @@ def main():
     ap.add_argument("--homed-sweep", type=int, default=-1, help="ops.HOMED_COLUMN_SWEEP (0 / 1; -1 = default)")
     ap.add_argument("--thr", type=int, default=64)
     ap.add_argument("--seg", type=int, default=512)
-    ap.add_argument("--variants", default="v1:1:0,v2:1:0,v2:2:0,v2:1:1,v2:2:1")
+    ap.add_argument("--variants", default="v1:1,v2:1,v2:2")
     ap.add_argument("--shapes", default="pubmed500,pubmed32,zincb39,zincb32,zinc39,zinc32,rmat32")
     ap.add_argument("--knobs", default="", help="comma-separated gae_tuning_set name=value pairs applied to every variant")
     args = ap.parse_args()
@@ -133,14 +133,14 @@ def main():
         print(f"rmat plan: thr={args.thr} seg={args.seg} heavy rows={pl.n_heavy} segments={pl.n_segments}")
     variants = []
     for v in args.variants.split(","):
-        # name:rpg:nt:tile_vecs:opts   opts = letters: e = packed neighbour table + spmm_ell.hip kernels (w4 / w8 =
+        # name:rpg:tile_vecs:opts   opts = letters: e = packed neighbour table + spmm_ell.hip kernels (w4 / w8 =
         #                              table width, default 16), E = table + row-group kernel, t = GAE_SPMM_TILE,
         #                              p = store pad, b = block-diagonal kernel
         parts = v.split(":")
-        name, rpg, nt = parts[:3]
-        tv = int(parts[3]) if len(parts) > 3 else 0
-        opts = parts[4] if len(parts) > 4 else ""
-        variants.append((v, 1 if name == "v1" else 2, int(rpg), int(nt), tv, opts))
+        name, rpg = parts[:2]
+        tv = int(parts[2]) if len(parts) > 2 else 0
+        opts = parts[3] if len(parts) > 3 else ""
+        variants.append((v, 1 if name == "v1" else 2, int(rpg), tv, opts))
     ell_plans = {}
     for sname in want:
         ip, ix, n, F, ld = shapes[sname]
@@ -152,8 +152,8 @@ def main():
         res = {v[0]: [] for v in variants}
         ref = None
         for rnd in range(args.rounds + 1):
-            for (label, var, rpg, nt, tv, opts) in variants:
-                knob("spmm_variant", var); knob("spmm_rpg", rpg); knob("spmm_nt", nt); knob("spmm_tile_vecs", tv)
+            for (label, var, rpg, tv, opts) in variants:
+                knob("spmm_variant", var); knob("spmm_rpg", rpg); knob("spmm_tile_vecs", tv)
                 knob("spmm_ell", 2 if "E" in opts else 1); knob("spmm_ell_rpg", rpg)
                 plan = plans.get(sname)
                 if ("e" in opts or "E" in opts) and plan is None:
