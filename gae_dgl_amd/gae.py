@@ -197,7 +197,7 @@ class GAE(nn.Module):
             z = self.encode(g)
         return ops.decoder_topk(z, k, g, scope=scope, exclude_self=exclude_self, exclude_edges=exclude_edges)
 
-    def reconstruction_loss(self, g, criterion="bce", scope="batch"):
+    def reconstruction_loss(self, g, criterion="bce", scope="batch", samples=None):
         """The training loss of train_inductive.py:44-48 (dense label from g,
         pos_weight, BCE-with-logits mean over all N^2 ordered pairs) evaluated
         by the fused HIP kernel: numerically the same quantity as
@@ -207,12 +207,27 @@ class GAE(nn.Module):
         (optuna_gae.py:16,21), likewise without the N x N matrices (ops.decoder_mse).
         ``scope="graph"``: the same BCE on every member graph of a batched ``g`` alone (its own pairs, pos_weight and
         mean), averaged over the members (ops.decoder_bce_graphs) -- the reference's loss at batch size 1, averaged
-        over the molecules of the batch; a graph that is not a batch gives exactly the ``"batch"`` loss."""
+        over the molecules of the batch; a graph that is not a batch gives exactly the ``"batch"`` loss.
+        ``samples=m``: the unbiased sampled estimate of the BCE loss (ops.decoder_bce_sampled): the edge term exactly,
+        the all-pairs term from m keyed-random partners per node, O((E + N m) d) instead of O(N^2 d); the decoder's
+        dropout and draw counter as for the exact loss, fresh partners every call.  BCE over the whole batch only."""
         if scope not in ("batch", "graph"):
             raise ValueError(f"scope: 'batch' or 'graph', not {scope!r}")
         if scope == "graph" and criterion != "bce":
             raise ValueError(f"scope='graph' is a BCE loss (criterion 'bce'), not {criterion!r}")
+        if samples is not None:
+            if criterion != "bce":
+                raise ValueError(f"samples: the sampled loss is the BCE loss (criterion 'bce'), not {criterion!r}")
+            if scope != "batch":
+                raise ValueError("samples: the sampled loss covers the whole batch (scope 'batch'), not 'graph'")
+            if isinstance(samples, bool) or int(samples) != samples or samples < 1:
+                raise ValueError(f"samples: a positive number of partners per node, not {samples!r}")
         z = g.ndata['h']
+        if samples is not None:
+            for layer in self.layers:
+                z = layer(g, z)
+            g.ndata['h'] = z
+            return self.decoder.loss_sampled(z, g, int(samples))
         if scope == "graph":
             for layer in self.layers:
                 z = layer(g, z)
@@ -299,6 +314,23 @@ class InnerProductDecoder(nn.Module):
         mask = torch.empty(tuple(z.shape), dtype=torch.float32, device=z.device)
         self.last_mask = mask
         return ops.decoder_bce_graphs(z, mask, g, dropout=drop)
+
+    def loss_sampled(self, z, g, samples):
+        """the unbiased sampled estimate of loss() (ops.decoder_bce_sampled) from ``samples`` partners per node.  The
+        draw counter advances every call (the partners change), the dropout mask is drawn in the launch as loss() draws
+        it and kept in ``last_mask``."""
+        if not (isinstance(z, torch.Tensor) and z.is_cuda):
+            raise ops.GaeHipError("InnerProductDecoder.loss_sampled: the HIP path needs device tensors")
+        seed = self.seed if self.seed is not None else int(torch.initial_seed())
+        if self._draws is None or self._draws.device != z.device:
+            self._draws = torch.zeros(1, dtype=torch.int64, device=z.device)
+        drop = self._loss_dropout(z.device)
+        if drop is None:
+            self.last_mask = self.mask
+            return ops.decoder_bce_sampled(z, self.mask, g, samples, dropout=(0.0, seed, 0, self._draws))
+        mask = torch.empty(tuple(z.shape), dtype=torch.float32, device=z.device)
+        self.last_mask = mask
+        return ops.decoder_bce_sampled(z, mask, g, samples, dropout=drop)
 
     def loss(self, z, g, prepared=None):
         """fused decoder + weighted BCE (identity activation = logits, gae.py:47).  The dropout mask of this call

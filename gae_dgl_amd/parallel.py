@@ -646,12 +646,16 @@ def sharded_encode(model, sg, x_local, transform_first=False):
     return h
 
 
-def sharded_loss(model, sg, x_local, mask_local=None, transform_first=False):
+def sharded_loss(model, sg, x_local, mask_local=None, transform_first=False, samples=None):
     """train_inductive.py:44-48 on a row-sharded graph: each rank evaluates its
     row block of the N x N loss against the all-gathered Z and the partial
-    sums are all-reduced.  Returns the global mean loss (same on every rank)."""
+    sums are all-reduced.  Returns the global mean loss (same on every rank).
+    ``samples=m``: the unbiased sampled estimate instead (ops.sharded_decoder_bce_sampled, m partners per node, a draw
+    counter on ``sg``): O((E + N m) d) per step, each rank's dZ rows bit-identical to one GPU's."""
     from . import ops
     z_local = sharded_encode(model, sg, x_local, transform_first)
+    if samples is not None:
+        return ops.sharded_decoder_bce_sampled(z_local, mask_local, sg, samples)
     return ops.sharded_decoder_bce(z_local, mask_local, sg)
 
 
@@ -681,11 +685,13 @@ class ShardedTrainStep:
     ``capture=True``: after ``warmup`` eager steps (they create the communicators, the structures, the optimiser
     state) the step -- collectives included -- is captured into one HIP graph and replayed; RCCL's work is then part
     of the graph, the host issues one launch per step.  ``mask_local``: the rank's rows of a fixed dropout mask (None
-    = no dropout)."""
+    = no dropout).  ``loss_samples=m``: the sampled loss (sharded_loss(..., samples=m)) instead of the N^2 one."""
 
-    def __init__(self, model, optimizer, sg, x_local, mask_local=None, transform_first=True, capture=False, warmup=2):
+    def __init__(self, model, optimizer, sg, x_local, mask_local=None, transform_first=True, capture=False, warmup=2,
+                 loss_samples=None):
         self.model, self.opt, self.sg, self.x, self.mask = model, optimizer, sg, x_local, mask_local
         self.transform_first = transform_first
+        self.loss_samples = loss_samples
         self.params = [p for g in optimizer.param_groups for p in g["params"]]
         self.graph = None
         self.loss = None
@@ -695,7 +701,7 @@ class ShardedTrainStep:
 
     def _step(self):
         from . import ops
-        loss = sharded_loss(self.model, self.sg, self.x, self.mask, self.transform_first)
+        loss = sharded_loss(self.model, self.sg, self.x, self.mask, self.transform_first, samples=self.loss_samples)
         ops.backward(loss, self.params)                    # autograd.grad: no stream-bound AccumulateGrad nodes
         if not isinstance(self.sg.group, LocalGroup):      # (a 1-rank process group still runs the collective)
             allreduce_grads(self.params, self.sg.group)

@@ -5,6 +5,7 @@ epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
 59-60) -- on the HIP kernels.
 
   python -m gae_dgl_amd.train_transductive --dataset cora [--norm both] [--eval] [--topk 10 [--topk_out top.npz]]
+      [--loss_samples M]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -51,6 +52,9 @@ def build_parser():
                          "known edges left out); with --eval prints the test recall@K, with --topk_out saves them")
     ap.add_argument("--topk_out", default=None, metavar="PATH",
                     help="write the --topk lists to PATH (.npz with 'index' int64 [n, K] and 'score' fp32 [n, K])")
+    ap.add_argument("--loss_samples", type=int, default=None, metavar="M",
+                    help="train on the unbiased sampled loss (GAE.reconstruction_loss(g, samples=M)): the edge term "
+                         "exactly, the all-pairs term from M random partners per node, O((E + N M) d) per step")
     return ap
 
 
@@ -65,6 +69,8 @@ def parse_args(argv=None):
             ap.error("--topk needs --eval (recall@K on the held-out edges) or --topk_out PATH")
     elif args.topk_out is not None:
         ap.error("--topk_out needs --topk K")
+    if args.loss_samples is not None and args.loss_samples < 1:
+        ap.error(f"--loss_samples {args.loss_samples}: M must be at least 1")
     return args
 
 
@@ -105,7 +111,7 @@ def main(argv=None):
 
     def eager_step():
         g.ndata['h'] = features
-        loss = model.reconstruction_loss(g)
+        loss = model.reconstruction_loss(g, samples=args.loss_samples)
         optimiser.zero_grad()
         ops.backward(loss)                # loss.backward() with a cached unit gradient
         optimiser.step()
@@ -118,7 +124,9 @@ def main(argv=None):
     print("Training Start")
     for epoch in range(args.n_epochs):
         if epoch == 1 and not args.no_hipgraph:
-            step = CapturedTrainStep(model, optimiser, g, features, warmup=0)
+            step = CapturedTrainStep(model, optimiser, g, features, warmup=0) if args.loss_samples is None else \
+                CapturedTrainStep(model, optimiser, g, features, warmup=0,
+                                  loss_fn=lambda m, gr: m.reconstruction_loss(gr, samples=args.loss_samples))
         losses.append(step().clone())
         if epoch % args.log_every == 0 or epoch + 1 == args.n_epochs:
             print(f"Epoch: {epoch:02d} | Loss: {float(losses[-1]):.5f}")

@@ -77,14 +77,17 @@ class VGAE(nn.Module):
             noise = (seed, 0, self._draws)
         return ops.vgae_head_loss(ml, g, self.eps, noise)
 
-    def loss(self, g):
-        """reconstruction BCE (train_inductive.py:44-48 semantics, fused) + KL"""
+    def loss(self, g, samples=None):
+        """reconstruction BCE (train_inductive.py:44-48 semantics, fused) + KL.  ``samples=m``: the reconstruction term
+        is the unbiased sampled estimate (InnerProductDecoder.loss_sampled, m partners per node)"""
+        if samples is not None and (isinstance(samples, bool) or int(samples) != samples or samples < 1):
+            raise ValueError(f"samples: a positive number of partners per node, not {samples!r}")
         h = self.shared(g, g.ndata['h'])
         ml = self._heads_packed(g, h)
         if ml is not None:                       # both heads in one launch, [mu | logstd] packed end to end
             d = ml.shape[1] // 2
             mu, logstd = ml[:, :d], ml[:, d:]
-            fused = self._fused_loss(g, ml)
+            fused = self._fused_loss(g, ml) if samples is None else None
             if fused is not None:
                 loss, z, kl, rec, eps = fused
                 g.ndata['h'] = z
@@ -99,7 +102,7 @@ class VGAE(nn.Module):
             eps = self._noise(mu)
             z, kl = ops.vgae_head(mu, logstd, eps)
         g.ndata['h'] = z
-        rec = self.decoder.loss(z, g)
+        rec = self.decoder.loss(z, g) if samples is None else self.decoder.loss_sampled(z, g, int(samples))
         self.last = {"mu": mu, "logstd": logstd, "eps": eps, "z": z, "kl": kl, "rec": rec}
         return rec + kl
 

@@ -8,6 +8,7 @@
  *                               plan construction and the specialised aggregation kernels gae_spmm_csr dispatches to
  *   gae_spx_*, gae_dense_to_csr_*   layer 1 from the non-zeros of constant input features (gae_dgl_amd.SparseFeatures)
  *   gae_linear2_*, gae_gcn2_*   the dense halves of a two-layer encoder on millions of rows (row-sharded RMAT path)
+ * and gae_decoder_bce_sampled, an unbiased stochastic estimate of gae_decoder_bce's loss for graphs beyond the N^2 sum.
  * Same conventions as gae_hip.h: caller-owned buffers, 0 / negative / hipError_t return codes, asynchronous launches on
  * the stream passed last.  These signatures may change between versions without a GAE_VERSION major bump. */
 #ifndef GAE_HIP_EXPERIMENTAL_H
@@ -274,6 +275,50 @@ int gae_x_decoder_bce_prepared(float *mask, int64_t ldz, int64_t n, int64_t d, c
 int gae_x_vgae_head_prep(const float *mu, const float *logstd, int64_t ldm, float *eps, int draw_eps, uint64_t seed,
                        uint64_t offset, const uint64_t *draw_dev, int64_t n, int64_t d, float *z, const gae_bce_prep *prep,
                        double *kl_partial, int64_t kl_capacity, int64_t *n_blocks_out, void *stream);
+
+/* (from gae_hip.h: K7+K8+K9, the fused loss) */
+/* ---- K17: unbiased sampled estimate of gae_decoder_bce's loss, O((E + n_local m) d) per call
+ * The loss of gae_decoder_bce splits exactly (sp = softplus, x_ij = zt_i . zt_j, Zt = Z (.) mask, y_ij = #edges j->i,
+ * pw = pos_weight):
+ *   L = (1/N^2) [ sum_{all i,j} sp(x_ij) + sum_{edges e=(i,j)} (pw sp(-x_e) - sp(x_e)) ]
+ * For the rows r in [row_begin, row_begin + n_local) and m in [1, N] samples per row this call returns
+ *   Lhat = (1/N^2) [ (N/m) sum_r sum_{s<m} sp(x_{r,pi_s(r)}) + sum_{edges (r,j) in the rows} (pw sp(-x_rj) - sp(x_rj)) ]
+ * and dZ = d Lhat / d Z exactly (the mask included).  E[Lhat] = L (each partner is uniform over [0, N)); at m = N every
+ * pair appears once and Lhat = L up to rounding.
+ * SAMPLER of draw t = offset + *draw_dev (0 when draw_dev is NULL):
+ *   keys      philox4x32_10(counter = 0 | 1, draw = t, key = seed ^ 0xD1B54A32D192ED03) -> words k0..k3 of sigma | tau
+ *             (a stream of its own: the dropout mask uses key = seed)
+ *   domain    b = smallest integer with 2^b >= N; h = b >> 1; widths (wl, wr) = (b - h, h)
+ *   F(R, k)   x = R ^ k; x *= 0x9E3779B1; x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13   (uint32 arithmetic)
+ *   E(v)      4 rounds q = 0..3: L = v >> wr, R = v & (2^wr - 1), v = (R << wl) | (L ^ (F(R, k_q) & (2^wl - 1))),
+ *             then swap(wl, wr): a bijection of [0, 2^b)
+ *   perm(i)   v = E(i); while v >= N: v = E(v)         (cycle walking: a bijection of [0, N)); perm^-1 walks E^-1
+ *   o_s       = tau(s), s < m                            (m distinct offsets)
+ *   pi_s(i)   = sigma^-1((sigma(i) + o_s) mod N)         (a bijection for every s; row i gets m distinct partners)
+ *   the partner of column j in slot s is i = sigma^-1((sigma(j) - o_s) mod N): a gather, no scatter, no atomics.
+ * Every local row owns its gradient row and sums, in this order: its edges (CSR of A), its transposed edges (CSR of
+ * A^T), its m samples, its m inverse partners.  dZ has the same bits whatever the grid and the row partition; the loss
+ * is an ordered fp64 reduction (deterministic run to run).
+ *   Z / mask     the full [n, d] arrays (ld ldz); d <= 64.  dropout_p > 0: the mask of this draw is drawn in the launch
+ *                (the stream of gae_dropout_mask / gae_decoder_bce at *draw_dev) and written to mask; dropout_p == 0:
+ *                mask is an optional input
+ *   CSRs         the local row blocks (n_local + 1 entries) with global column ids, as gae_decoder_bce_rows; the CSR
+ *                of A^T is required iff dZ != NULL
+ *   loss_out     this block's share of Lhat (1 fp32; the shares of a row partition sum to Lhat)
+ *   dZ           [n_local, d] (ld lddz), NULL = loss only
+ *   partners_out int32 [n_local, m] (may be NULL): pi_s(r) (tests, diagnosis)
+ *   draw_dev     device uint64, may be NULL: *draw_dev += 1 once per call, also without dropout, so a replayed HIP
+ *                graph draws fresh pairs every time
+ *   workspace    NULL = size query: *workspace_bytes receives the bytes needed and nothing else happens (no device
+ *                work; works without a GPU).  Otherwise *workspace_bytes is the capacity given.  O(n d + n_local) bytes.
+ * Argument errors are returned before any launch: n, d <= 0, n_local or row_begin negative, the row window outside
+ * [0, n), d > 64, m outside [1, n], dropout_p outside [0, 1), dZ without the CSR of A^T. */
+int gae_decoder_bce_sampled(const float *Z, float *mask, int64_t ldz, int64_t n, int64_t d, int64_t row_begin,
+                            int64_t n_local, int64_t m, const int32_t *indptr, const int32_t *indices,
+                            const int32_t *t_indptr, const int32_t *t_indices, float pos_weight, float dropout_p,
+                            uint64_t seed, uint64_t offset, uint64_t *draw_dev, float *loss_out, float *dZ,
+                            int64_t lddz, int32_t *partners_out, void *workspace, int64_t *workspace_bytes,
+                            void *stream);
 
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
