@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the GCN-encoder hot path on MI355X (metric / configs: BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W [--workload pubmed|cora|citeseer|zinc|vgae|rmat]
+  python bench.py --gpus N --steps K --warmup W [--workload pubmed|cora|citeseer|zinc|vgae|rmat] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started without a launcher (no WORLD_SIZE in the environment), `--gpus N` with N > 1 starts its N ranks itself (one
@@ -28,7 +28,13 @@ The timed region is exactly --steps steps, run once between barrier + synchroniz
 DIR/<name>.npy.
 
 value = SpMM edges aggregated per step (forward + backward launches, all ranks)
-/ step time: whole-job, inputs resident in HBM, max over ranks.  `value_spmm_only`
+/ step time: whole-job, inputs resident in HBM, max over ranks.
+N > 1: `rccl_ranks`, `preflight` (every collective primitive checked against known
+answers before the workload is built).
+
+A plain run sets up, warms up, times the steps, writes the outputs and prints the line with `value`, `ms_per_step`,
+`timing`, `config` and the fields above.  What follows is measured after the timed steps, and only with `--full`:
+`value_spmm_only`
 = the same edges / the HIP-event time of the step's SpMM launches alone.
 `roofline`  : the metric's kernel, the SpMM aggregation, HIP-event timed on the
               launch stream against SURVEY.md 8(d)'s B_alg.  Pubmed (default): the
@@ -43,8 +49,8 @@ value = SpMM edges aggregated per step (forward + backward launches, all ranks)
 `extra`     : kernel-only SpMM numbers (warm and cold) for the other BASELINE shapes,
               whole steps of the other single-GPU configurations; one JSON object on
               stderr (`[bench] extra: {...}`), not part of the result line.
-N > 1: `rccl_ranks`, `preflight` (every collective primitive checked against known
-answers before the workload is built), `comm` (exchange vs SpMM time per step).
+N > 1: `comm` (exchange vs SpMM time per step), `same_workload_1gpu` (the rmat workload
+timed on one GPU in the same invocation).
 """
 import argparse
 import json
@@ -114,8 +120,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: per-kernel and roofline "
+                         "figures, the exact-fp32 step, the CPU baseline, the extra configurations and (N > 1) the "
+                         "exchange profile and the same workload on one GPU")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra configurations")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--loss", choices=["fused", "dense"], default="fused",
                     help="fused = HIP decoder+BCE kernel (never materialises N x N); dense = reference-shaped "
@@ -1404,7 +1414,9 @@ def main():
         wl = CitationWorkload(workload, args, dev)
 
     graphed = getattr(wl, "use_graph", False)
-    prof = ops.EventProfiler()
+    # The pass of --steps profiled steps below runs with or without --full, so that the timed steps start from the
+    # same state either way; only --full records its HIP events (ops.profiler = None records nothing).
+    prof = ops.EventProfiler() if args.full else None
     if graphed:
         # Events cannot be recorded inside a graph replay: the per-kernel HIP-event timings come from an eager
         # pass of the SAME steps right before the capture; the timed regions then replay the captured graph.
@@ -1456,6 +1468,19 @@ def main():
         # before anything else runs: the measurements below launch more steps and would move the parameters on
         dump_outputs(step_outputs(wl, last, rank, world), args.dump_outputs)
     del last
+    value = wl.edges_per_step * args.steps / elapsed
+    line = {
+        "metric": "edges aggregated/sec (SpMM fwd+bwd)", "value": value, "unit": "edges/s",
+        "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "rccl_ranks": n_gpus if dist.is_initialized() else 0, "preflight": preflight,
+        "higher_is_better": True, "scaling": wl.scaling, "vs_baseline": None, "dtype": getattr(wl, "dtype", "f32"), "data": "synthetic",
+        "config": wl.meta,
+        "epoch_time_s": elapsed / args.steps * (wl.meta.get("batches_per_epoch_at_239455_graphs", 1)),
+        "timing": region_stats(regions, args.steps),
+    }
+    if not args.full:
+        finish(line, rank, world)
+        return
     dom_fn = wl.dominant_launch() if hasattr(wl, "dominant_launch") else None   # may contain a collective
     comm = wl.comm_profile() if hasattr(wl, "comm_profile") else None              # collective: every rank
     one_gpu = None
@@ -1477,9 +1502,7 @@ def main():
             del w1
             torch.cuda.empty_cache()
     if rank != 0:
-        if dist.is_initialized():
-            dist.barrier()
-            dist.destroy_process_group()
+        finish(line, rank, world)
         return
     times = prof.summary()
     spmm_keys = [k for k in times if k[0] == "spmm"]
@@ -1502,18 +1525,11 @@ def main():
     t_dom = time_launches(dom_fn, iters=50 if wl.alg_bytes < 1e9 else 10) if dom_fn is not None else t_dom_instep
     spmm_t = sum(sum(times[k]) for k in spmm_keys)
     copy_gbs = copy_bandwidth(wl.alg_bytes, dev) if dom_fn is not None else None
-    value = wl.edges_per_step * args.steps / elapsed
-    line = {
-        "metric": "edges aggregated/sec (SpMM fwd+bwd)", "value": value, "unit": "edges/s",
-        "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "rccl_ranks": n_gpus if dist.is_initialized() else 0, "preflight": preflight,
-        "higher_is_better": True, "scaling": wl.scaling, "vs_baseline": None, "dtype": getattr(wl, "dtype", "f32"), "data": "synthetic",
-        "config": wl.meta,
+    line.update({
         "value_spmm_only": wl.edges_per_step / max(world, 1) * args.steps / spmm_t if spmm_t else None,
         "value_note": "value = SpMM edges of a step / WHOLE-step time (encoder + fused N^2 loss + backward + Adam: the loss is "
                       "two thirds of a Pubmed step); value_spmm_only = the same edges / the HIP-event time of the step's SpMM "
                       "launches alone (see spmm_only) -- the figure to set beside an SpMM-only CPU rate (cpu_baseline.spmm)",
-        "epoch_time_s": elapsed / args.steps * (wl.meta.get("batches_per_epoch_at_239455_graphs", 1)),
         "spmm_only": {"edges_per_s": wl.edges_per_step / max(world, 1) * args.steps / spmm_t if spmm_t else None,
                       "sum_event_time_s": spmm_t, "launches": sum(len(times[k]) for k in spmm_keys),
                       "note": "rank-0 HIP-event time of its SpMM launches inside the timed steps"
@@ -1529,7 +1545,7 @@ def main():
                                   "(read + write), same timing method: the second denominator of SURVEY 8(d)",
                      "alg_bytes_per_launch": wl.alg_bytes, "avg_launch_us": t_dom * 1e6,
                      "avg_launch_us_event_pairs_inside_steps": t_dom_instep * 1e6, "launches_timed_inside_steps": len(dom)},
-    }
+    })
     if comm is not None:
         t, calls = comm
         ex = t.get("exchange", 0.0) * calls.get("exchange", 0) + \
@@ -1545,7 +1561,6 @@ def main():
             "note": "rank-0 HIP-event times over 5 extra steps outside the timed region; exchange_wait is what the "
                     "own-column SpMM did not hide; SpMM-only edges/s assumes every rank takes as long as rank 0 "
                     "(nnz-balanced blocks)"}
-    line["timing"] = region_stats(regions, args.steps)
     if one_gpu is not None:
         one_gpu["speedup"] = value / one_gpu["value"]
         line["same_workload_1gpu"] = one_gpu
@@ -1687,10 +1702,18 @@ def main():
         # stderr, not the result line: with it the line outgrows what a reader of the last stdout line takes in
         extra = {"steps": extra_steps(args, dev), "spmm_kernel_only": extras(dev)}
         print("[bench] extra: " + json.dumps(extra), file=sys.stderr, flush=True)
+    finish(line, rank, world)
+
+
+def finish(line, rank, world):
+    """every rank: close the process group; rank 0: print the result line"""
+    import torch.distributed as dist
     if dist.is_initialized():
         if world > 1:
             dist.barrier()
         dist.destroy_process_group()
+    if rank != 0:
+        return
     # RCCL prints a version banner through C stdio; flush it first so the JSON line is the LAST line of stdout
     try:
         import ctypes

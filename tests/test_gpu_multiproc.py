@@ -226,7 +226,7 @@ def test_bench_two_ranks_oversubscribed_prints_a_valid_line():
     env = dict(os.environ)
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "rmat",
-                        "--rmat-scale", "20", "--oversubscribe", "--steps", "3", "--warmup", "2"],
+                        "--rmat-scale", "20", "--oversubscribe", "--steps", "3", "--warmup", "2", "--full"],
                        capture_output=True, text=True, timeout=1400, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -419,7 +419,7 @@ def test_sparse_features_refuse_a_near_dense_column():
 
 
 def test_default_bench_line_carries_the_contract_fields(tmp_path):
-    """`python bench.py` (N = 1, the headline Pubmed step, with the extras): ONE JSON line with the contract's keys, short
+    """`python bench.py --full` (N = 1, the headline Pubmed step, with the extras): ONE JSON line with the contract's keys, short
     enough for a reader of the last stdout line (the extras go to stderr); `roofline` is the SpMM aggregation with a
     MALL-cold fraction beside the warm one, `roofline_dense` the dense layer-1 pair, `cpu_baseline` a timed CPU
     restatement on this host's cores; --dump-outputs leaves the last timed step's loss, parameters and Adam moments"""
@@ -428,7 +428,7 @@ def test_default_bench_line_carries_the_contract_fields(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     dump = tmp_path / "outputs"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "10", "--warmup", "3",
                         "--cpu-seconds", "2", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900,
                        cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -466,3 +466,38 @@ def test_default_bench_line_carries_the_contract_fields(tmp_path):
             assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
         assert (np.load(dump / f"adam.{k}.exp_avg_sq.npy") > 0).any()       # the moments of steps that ran
     assert sum(p.stat().st_size for p in dump.iterdir()) <= 64 << 20
+
+
+def test_plain_bench_line_is_the_headline_alone(tmp_path):
+    """`python bench.py` without --full sets up, warms up, times the steps, writes the outputs and prints the headline:
+    no roofline, CPU baseline or extras.  --full measures those only after the timed steps, so a run with it leaves
+    the same outputs and a line with the same headline fields"""
+    import json
+    import subprocess
+    runs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-extra", "--no-cpu-baseline"])):
+        dump = tmp_path / mode
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3",
+                            "--dump-outputs", str(dump)] + extra, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0]
+        runs[mode] = (json.loads(lines[0]), r.stderr, dump)
+    line, err, dump = runs["plain"]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "timing"):
+        assert k in line, k
+    assert line["steps"] == 10 and line["warmup"] == 3 and line["timing"]["steps_per_region"] == 10
+    assert 0.05 < line["ms_per_step"] < 5 and line["value"] > 0 and line["config"]["workload"].startswith("pubmed")
+    for k in ("roofline", "roofline_dense", "roofline_step_dominant", "cpu_baseline", "value_spmm_only", "spmm_only",
+              "ms_per_step_exact_fp32", "decoder_loss"):
+        assert k not in line, k
+    assert "[bench] extra" not in err
+    full = runs["full"][0]
+    assert "roofline" in full and "value_spmm_only" in full
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "data"):
+        assert line[k] == full[k], k
+    names = sorted(p.name for p in dump.iterdir())
+    assert "loss.npy" in names and names == sorted(p.name for p in runs["full"][2].iterdir())
+    for name in names:
+        assert np.array_equal(np.load(dump / name), np.load(runs["full"][2] / name)), name

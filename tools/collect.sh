@@ -6,15 +6,15 @@ TAG=${1:-r02}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-timeout 900 python bench.py > $O/bench_pubmed.json 2> $O/bench_pubmed.err
-for w in cora citeseer zinc; do timeout 600 python bench.py --workload $w --no-extra 2>/dev/null | tail -1 > $O/bench_$w.json; done
+timeout 900 python bench.py --full > $O/bench_pubmed.json 2> $O/bench_pubmed.err
+for w in cora citeseer zinc; do timeout 600 python bench.py --full --workload $w --no-extra 2>/dev/null | tail -1 > $O/bench_$w.json; done
 # BASELINE config 5: VGAE on Citeseer, bf16 feature storage
-timeout 600 python bench.py --workload vgae --no-extra 2>/dev/null | tail -1 > $O/bench_vgae.json
-timeout 600 python bench.py --workload zinc --batch-graphs 128 --steps 300 --warmup 30 --no-extra 2>/dev/null | tail -1 > $O/bench_zinc128.json
+timeout 600 python bench.py --full --workload vgae --no-extra 2>/dev/null | tail -1 > $O/bench_vgae.json
+timeout 600 python bench.py --full --workload zinc --batch-graphs 128 --steps 300 --warmup 30 --no-extra 2>/dev/null | tail -1 > $O/bench_zinc128.json
 # the same inductive steps launched eagerly (no captured step): what the HIP graph buys
-timeout 600 python bench.py --workload zinc --no-hipgraph --no-extra --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_zinc_eager.json
-timeout 600 python bench.py --workload zinc --batch-graphs 128 --steps 300 --warmup 30 --no-hipgraph --no-extra --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_zinc128_eager.json
-MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 timeout 900 python bench.py --workload rmat --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_rmat_s24_1gpu.json
+timeout 600 python bench.py --full --workload zinc --no-hipgraph --no-extra --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_zinc_eager.json
+timeout 600 python bench.py --full --workload zinc --batch-graphs 128 --steps 300 --warmup 30 --no-hipgraph --no-extra --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_zinc128_eager.json
+MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 timeout 900 python bench.py --full --workload rmat --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_rmat_s24_1gpu.json
 for w in pubmed cora zinc; do
   timeout 600 tools/prof_bench.sh $TAG/prof_$w --workload $w --steps 30 --warmup 3 > $O/${w}_step_kernel_stats_top.txt
 done

@@ -9,11 +9,11 @@ PARTS=${@:-bench prof pmc micro}
 for part in $PARTS; do
 case $part in
 bench)
-  timeout 900 python bench.py > $O/bench_pubmed.json 2> $O/bench_pubmed.err
-  timeout 600 python bench.py --layer1 reference --no-extra --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_pubmed_reference_order.json
-  for w in cora citeseer zinc vgae; do timeout 600 python bench.py --workload $w --no-extra 2>/dev/null | tail -1 > $O/bench_$w.json; done
-  timeout 600 python bench.py --workload zinc --batch-graphs 128 --steps 300 --warmup 30 --no-extra 2>/dev/null | tail -1 > $O/bench_zinc128.json
-  MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 timeout 900 python bench.py --workload rmat --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_rmat_s24_1gpu.json
+  timeout 900 python bench.py --full > $O/bench_pubmed.json 2> $O/bench_pubmed.err
+  timeout 600 python bench.py --full --layer1 reference --no-extra --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_pubmed_reference_order.json
+  for w in cora citeseer zinc vgae; do timeout 600 python bench.py --full --workload $w --no-extra 2>/dev/null | tail -1 > $O/bench_$w.json; done
+  timeout 600 python bench.py --full --workload zinc --batch-graphs 128 --steps 300 --warmup 30 --no-extra 2>/dev/null | tail -1 > $O/bench_zinc128.json
+  MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 timeout 900 python bench.py --full --workload rmat --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_rmat_s24_1gpu.json
   ;;
 prof)
   for w in pubmed cora citeseer vgae zinc; do
