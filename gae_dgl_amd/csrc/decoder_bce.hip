@@ -23,11 +23,11 @@
 //   ~8 VALU ops (2 transcendental: v_exp, v_rcp; the logs are taken of products of 16 t's) per logit.  Zero-padded columns contribute exactly log2(2) = 1 to
 //   sum log2(t) and 0 to everything else: corrected analytically, no masking in the loop.
 //
-// Dense kernel: flash-style.  A wave owns RI 16-row subtiles and streams 64-column tiles of Zt through
+// Dense kernel: flash-style.  A wave owns kBceRi 16-row subtiles and streams 64-column tiles of Zt through
 // double-buffered LDS.  S^T = Zj Zi^T on the matrix cores, either
-//   * bf16 x 3 (default): Zt = hi + lo (two bf16), S = hi.hi + hi.lo + lo.hi on v_mfma_f32_16x16x16_bf16
-//     (fp32 accumulate; the dropped lo.lo term is 2^-16 relative), which runs on the matrix pipe proper and
-//     leaves the fp32 FMA lanes to the VALU work; or
+//   * three bf16 pieces per operand (default): Zt = hi + lo + lo2, all products down to 2^-24 relative on
+//     v_mfma_f32_16x16x32_bf16 (fp32 accumulate), which runs on the matrix pipe proper and leaves the fp32 FMA
+//     lanes to the VALU work; or
 //   * exact fp32 v_mfma_f32_16x16x4_f32 (knob bce_s_bf16 = 0), which shares the fp32 lanes with the VALU.
 // O' += P Zj on v_mfma_f32_16x16x4_f32: the S^T accumulator registers are directly the A fragments (lane =
 // row i, reg r <-> j = 4 (lane >> 4) + r), so P never leaves registers.
@@ -375,32 +375,28 @@ __device__ __forceinline__ s16x4 exact_f16(const f32x4 &d)
     return __builtin_bit_cast(s16x4, u);
 }
 
-template <int KS, bool WITH_GRAD, int RI, int MINW, bool SBF16, bool PBF16, bool TRV = false, bool S3 = false>
-__global__ __launch_bounds__(256, MINW) void bce_dense_kernel(
+// SBF16: S from three bf16 pieces per operand (else exact fp32).  PBF16: O' += P V in bf16 x 3 as well, its V fragments
+// read from the bf16 [j][k] tiles by LDS transpose reads (else exact fp32).
+template <int KS, bool WITH_GRAD, bool SBF16, bool PBF16>
+__global__ __launch_bounds__(256, 1) void bce_dense_kernel(
     const float *__restrict__ Zt /*[n][16 KS]*/, const unsigned short *__restrict__ Zhi,
     const unsigned short *__restrict__ Zlo, int64_t n, int64_t row_begin, int64_t n_local, int64_t cols_per_split,
     float *__restrict__ O_partial /*[splits][n_local][KS*16]*/, double *__restrict__ loss_partial /*[blocks][2]*/,
     const double *__restrict__ colsum_partial, int64_t n_prep_blocks, double *__restrict__ S,
     float *__restrict__ S_all_f, unsigned n_row_blocks)
 {
+    constexpr int RI = kBceRi;
     constexpr int ROWS_PER_BLOCK = 4 * RI * 16;
     constexpr int DP = KS * 16;          // padded feature width
     constexpr int LDA = DP + 4;          // fp32 LDS row stride (floats): 16-byte aligned, breaks the power of two
     constexpr int LDH = DP + 4;          // bf16 LDS row stride (elements): 8-byte aligned rows
     constexpr int V4 = TJ * DP / 4 / 256;  // float4 per thread and staged tile (1, 2, 4)
-    constexpr int LDT = TJ + 4;          // transposed bf16 tile row stride (elements), 8-byte aligned rows
-    static_assert(!S3 || SBF16, "the three-piece S product is a bf16 form");
+    static_assert(!PBF16 || SBF16, "the bf16 P V product reads its V fragments from the bf16 S tiles");
     constexpr bool NEED_F32 = !SBF16 || (WITH_GRAD && !PBF16);
-    constexpr bool LOAD_F32 = NEED_F32 || S3;            // S3: the staged fp32 values give the third piece
-    constexpr bool NEED_BF = SBF16 || (WITH_GRAD && PBF16);
-    static_assert(!TRV || (SBF16 && PBF16 && WITH_GRAD), "transpose reads take the V fragments from the bf16 [j][k] tiles");
-    constexpr bool NEED_T = WITH_GRAD && PBF16 && !TRV;
     __shared__ __attribute__((aligned(16))) float Zs[2][NEED_F32 ? TJ * LDA : 4];            // fp32 column tile [j][k]
     __shared__ __attribute__((aligned(16))) unsigned short Hs[2][SBF16 ? TJ * LDH : 4];      // bf16 hi [j][k]
     __shared__ __attribute__((aligned(16))) unsigned short Ls[2][SBF16 ? TJ * LDH : 4];      // bf16 lo [j][k]
-    __shared__ __attribute__((aligned(16))) unsigned short L2s[2][S3 ? TJ * LDH : 4];        // bf16 lo2 [j][k]
-    __shared__ __attribute__((aligned(16))) unsigned short HT[2][NEED_T ? DP * LDT : 4];     // bf16 hi [k][j]
-    __shared__ __attribute__((aligned(16))) unsigned short LT[2][NEED_T ? DP * LDT : 4];     // bf16 lo [k][j]
+    __shared__ __attribute__((aligned(16))) unsigned short L2s[2][SBF16 ? TJ * LDH : 4];     // bf16 lo2 [j][k]
     __shared__ double red[4][2];
 
     if (blockIdx.x >= n_row_blocks) {   // the extra block column: column sums of Zt for the kernels that follow
@@ -424,12 +420,12 @@ __global__ __launch_bounds__(256, MINW) void bce_dense_kernel(
     // accumulator is y = x log2(e) and exp(-|x|) = exp2(-|y|) needs no multiply per logit (sign and |.|
     // sums are rescaled at the end).
     constexpr float LOG2E = 1.44269504088896341f;
-    // bf16 x 3 on K = 32 MFMAs (see bce_dense_sym_kernel): K2 fragments per row subtile, each two K = 16 fragments
+    // bf16 pieces on K = 32 MFMAs (see bce_dense_sym_kernel): K2 fragments per row subtile, each two K = 16 fragments
     // side by side -- chunk pairs [c | c + 1] for d > 16, the same chunk twice for d <= 16.
     constexpr int K2 = KS == 1 ? 1 : KS / 2;
     f32x4 bfrag[RI][KS];
     s16x8 bhh[RI][K2], bll[RI][K2];
-    s16x8 b3[RI][S3 ? K2 : 1];        // S3: KS == 1: [bhi | blo2]; chunk pairs: [blo2 | blo2']
+    s16x8 b3[RI][SBF16 ? K2 : 1];     // KS == 1: [bhi | blo2]; chunk pairs: [blo2 | blo2']
 #pragma unroll
     for (int ri = 0; ri < RI; ++ri) {
         const int64_t i = row_base + ri * 16 + l15;
@@ -442,16 +438,15 @@ __global__ __launch_bounds__(256, MINW) void bce_dense_kernel(
             bfrag[ri][c] = b;
             if (SBF16) {
                 s16x4 bh, bl, bl2;
-                if (S3) split_bf16x4_3(b, bh, bl, bl2);
-                else split_bf16x4(b, bh, bl);
+                split_bf16x4_3(b, bh, bl, bl2);
                 if (KS == 1) {
                     bhh[ri][0] = cat(bh, bh);
                     bll[ri][0] = cat(bl, bl);
-                    if (S3) b3[ri][0] = cat(bh, bl2);
+                    b3[ri][0] = cat(bh, bl2);
                 } else {
                     put_half(bhh[ri][c / 2], c & 1, bh);
                     put_half(bll[ri][c / 2], c & 1, bl);
-                    if (S3) put_half(b3[ri][c / 2], c & 1, bl2);
+                    put_half(b3[ri][c / 2], c & 1, bl2);
                 }
             }
         }
@@ -476,11 +471,9 @@ __global__ __launch_bounds__(256, MINW) void bce_dense_kernel(
             const int jj = idx / (DP / 4), kk = (idx % (DP / 4)) * 4;
             const bool jv = j0 + jj < col_end;
             const int64_t j = jv ? j0 + jj : col_begin;
-            if (LOAD_F32) {
-                st.f[q] = *reinterpret_cast<const f32x4 *>(Zt + j * DP + kk);
-                if (!jv) st.f[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            if (NEED_BF) {
+            st.f[q] = *reinterpret_cast<const f32x4 *>(Zt + j * DP + kk);   // (SBF16: they give the third piece)
+            if (!jv) st.f[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (SBF16) {
                 st.h[q] = *reinterpret_cast<const s16x4 *>(Zhi + j * DP + kk);
                 st.l[q] = *reinterpret_cast<const s16x4 *>(Zlo + j * DP + kk);
                 if (!jv) { st.h[q] = s16x4{0, 0, 0, 0}; st.l[q] = s16x4{0, 0, 0, 0}; }
@@ -496,14 +489,7 @@ __global__ __launch_bounds__(256, MINW) void bce_dense_kernel(
             if (SBF16) {
                 *reinterpret_cast<s16x4 *>(&Hs[buf][jj * LDH + kk]) = st.h[q];
                 *reinterpret_cast<s16x4 *>(&Ls[buf][jj * LDH + kk]) = st.l[q];
-                if (S3) *reinterpret_cast<s16x4 *>(&L2s[buf][jj * LDH + kk]) = third_piece(st.f[q], st.h[q], st.l[q]);
-            }
-            if (NEED_T) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    HT[buf][(kk + e) * LDT + jj] = (unsigned short)st.h[q][e];
-                    LT[buf][(kk + e) * LDT + jj] = (unsigned short)st.l[q][e];
-                }
+                *reinterpret_cast<s16x4 *>(&L2s[buf][jj * LDH + kk]) = third_piece(st.f[q], st.h[q], st.l[q]);
             }
         }
     };
@@ -529,28 +515,26 @@ __global__ __launch_bounds__(256, MINW) void bce_dense_kernel(
                     auto frag = [&](const unsigned short *base, int c) {
                         return *reinterpret_cast<const s16x4 *>(&base[(jt * 16 + l15) * LDH + 16 * c + 4 * g]);
                     };
-                    if (KS == 1) {        // S = [ah | al] x [bhi | bhi] + [ah | al] x [blo | blo]  (+ [al2 | ah] x [bhi | blo2])
+                    if (KS == 1) {        // S = [al2 | ah] x [bhi | blo2] + [ah | al] x [blo | blo] + [ah | al] x [bhi | bhi]
                         const s16x4 fh = frag(Hs[buf], 0);
                         const s16x8 ahl = cat(fh, frag(Ls[buf], 0));
 #pragma unroll
                         for (int ri = 0; ri < RI; ++ri) {
-                            if (S3) sacc[ri] = mfma32(cat(frag(L2s[buf], 0), fh), b3[ri][0], sacc[ri]);
+                            sacc[ri] = mfma32(cat(frag(L2s[buf], 0), fh), b3[ri][0], sacc[ri]);
                             sacc[ri] = mfma32(ahl, bll[ri][0], sacc[ri]);
                             sacc[ri] = mfma32(ahl, bhh[ri][0], sacc[ri]);
                         }
-                    } else {              // chunk pairs: lo.hi + hi.lo + hi.hi, 3 MFMAs per 32 features (S3: + lo.lo, hi.lo2, lo2.hi)
+                    } else {              // chunk pairs, 6 MFMAs per 32 features: lo2.hi + hi.lo2 + lo.lo, then lo.hi + hi.lo + hi.hi
 #pragma unroll
                         for (int c2 = 0; c2 < K2; ++c2) {
                             const s16x8 ah = cat(frag(Hs[buf], 2 * c2), frag(Hs[buf], 2 * c2 + 1));
                             const s16x8 al = cat(frag(Ls[buf], 2 * c2), frag(Ls[buf], 2 * c2 + 1));
-                            if (S3) {
-                                const s16x8 al2 = cat(frag(L2s[buf], 2 * c2), frag(L2s[buf], 2 * c2 + 1));
+                            const s16x8 al2 = cat(frag(L2s[buf], 2 * c2), frag(L2s[buf], 2 * c2 + 1));
 #pragma unroll
-                                for (int ri = 0; ri < RI; ++ri) {
-                                    sacc[ri] = mfma32(al2, bhh[ri][c2], sacc[ri]);
-                                    sacc[ri] = mfma32(ah, b3[ri][c2], sacc[ri]);
-                                    sacc[ri] = mfma32(al, bll[ri][c2], sacc[ri]);
-                                }
+                            for (int ri = 0; ri < RI; ++ri) {
+                                sacc[ri] = mfma32(al2, bhh[ri][c2], sacc[ri]);
+                                sacc[ri] = mfma32(ah, b3[ri][c2], sacc[ri]);
+                                sacc[ri] = mfma32(al, bll[ri][c2], sacc[ri]);
                             }
 #pragma unroll
                             for (int ri = 0; ri < RI; ++ri) {
@@ -601,21 +585,13 @@ __global__ __launch_bounds__(256, MINW) void bce_dense_kernel(
             }
             if (WITH_GRAD && PBF16) {
                 // B fragments: lane (nn = l15, g) -> bf16 V[j][16 c + nn] for the 4 + 4 columns j this lane group
-                // holds of the two subtiles, read from the transposed tiles; O' += lo.hi + hi.lo + hi.hi, K = 32
+                // holds of the two subtiles, LDS transpose reads of the [j][k] tiles (see lds_read_tr);
+                // O' += lo.hi + hi.lo + hi.hi, K = 32
 #pragma unroll
                 for (int c = 0; c < KS; ++c) {
-                    s16x8 vh, vl;
-                    if constexpr (TRV) {      // LDS transpose reads of the [j][k] tiles (see lds_read_tr)
-                        const int o = (jp * 32 + 4 * g + (l15 >> 2)) * LDH + 16 * c + 4 * (l15 & 3);
-                        vh = cat(lds_read_tr(&Hs[buf][o]), lds_read_tr(&Hs[buf][o + 16 * LDH]));
-                        vl = cat(lds_read_tr(&Ls[buf][o]), lds_read_tr(&Ls[buf][o + 16 * LDH]));
-                    } else {
-                        const int at = (16 * c + l15) * LDT + jp * 32 + 4 * g;
-                        vh = cat(*reinterpret_cast<const s16x4 *>(&HT[buf][at]),
-                                 *reinterpret_cast<const s16x4 *>(&HT[buf][at + 16]));
-                        vl = cat(*reinterpret_cast<const s16x4 *>(&LT[buf][at]),
-                                 *reinterpret_cast<const s16x4 *>(&LT[buf][at + 16]));
-                    }
+                    const int o = (jp * 32 + 4 * g + (l15 >> 2)) * LDH + 16 * c + 4 * (l15 & 3);
+                    const s16x8 vh = cat(lds_read_tr(&Hs[buf][o]), lds_read_tr(&Hs[buf][o + 16 * LDH]));
+                    const s16x8 vl = cat(lds_read_tr(&Ls[buf][o]), lds_read_tr(&Ls[buf][o + 16 * LDH]));
 #pragma unroll
                     for (int ri = 0; ri < RI; ++ri) {
                         oacc[ri][c] = mfma32(pl[ri], vh, oacc[ri][c]);
@@ -723,11 +699,15 @@ __host__ __device__ inline int64_t sym_strip_offset(int64_t I, int64_t NP, int64
     return 16 * (I * NP - PR * (I * (I + 1) / 2));
 }
 
-// TRV (default): the V fragments of O' += P V come from LDS transpose reads of the [j][k] tiles -- no second,
-// transposed copy of every tile (16 ds_write_b16 per thread and tile, 8.7 KB of LDS): Pubmed 170 -> 166 us, a ZINC
-// batch 2.92 -> 2.88 ms.  Every launch with gradients uses it; TRV = false is the form without gradients.
-template <bool WITH_GRAD, int RI, bool TRV, bool S3 = false, bool F16 = false, bool PERSIST = false, bool BAL = false>
-__global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_sym_kernel(
+// The products of the symmetric kernel: two fp16 pieces per operand behind the range guard (knob bce_s_bf16 = 3),
+// three bf16 pieces (any other nonzero value), and the three bf16 pieces again as the guard's fallback launch (a few
+// blocks that walk the whole grid; see the kernel).
+enum class SymForm { kF16, kBf16x3, kBf16x3Fallback };
+
+// The V fragments of O' += P V come from LDS transpose reads of the [j][k] tiles -- no second, transposed copy of
+// every tile (16 ds_write_b16 per thread and tile, 8.7 KB of LDS): Pubmed 170 -> 166 us, a ZINC batch 2.92 -> 2.88 ms.
+template <bool WITH_GRAD, int RI, SymForm FORM, bool BAL>
+__global__ __launch_bounds__(256, (RI == 2 && FORM != SymForm::kBf16x3Fallback) ? 3 : 2) void bce_dense_sym_kernel(
     const float *__restrict__ Zt /*[n][16]*/, const unsigned short *__restrict__ Zhi,
     const unsigned short *__restrict__ Zlo, int64_t n, int64_t cols_per_chunk,
     float *__restrict__ O_partial /*[chunks][n][16]*/, float *__restrict__ Wmir,
@@ -745,13 +725,12 @@ __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_
     // occur in a trained GAE: in practice the second launch costs the start of its few blocks (PERSIST: a 1-D grid of
     // a few hundred blocks that would walk the (panel, chunk) units of the first launch's 2-D grid).
     if (flag_mode == 2 && *range_flag != ticket) return;
-    static_assert(!(S3 && F16), "three bf16 pieces OR two fp16 pieces");
+    constexpr bool F16 = FORM == SymForm::kF16;    // else three bf16 pieces
+    constexpr bool PERSIST = FORM == SymForm::kBf16x3Fallback;
     bool out_of_range = false;
-    constexpr bool STAGE32 = S3 || F16;  // the column tiles are staged as fp32 and split at LDS-store time
     constexpr int DP = 16, SYM_PR = 64 * RI;
     constexpr int LDH = DP + 4;          // bf16 LDS row stride (elements): 8-byte aligned rows
     constexpr int V4 = TJ * DP / 4 / 256;  // = 1
-    constexpr int LDT = TJ + 4;          // transposed bf16 tile row stride (elements)
     constexpr int LDM = TJ + 4;          // mirror tile row stride (floats)
     // hi and lo pieces of a column tile INTERLEAVED per row: [hi k 0..3 | lo k 0..3 | hi k 4..7 | lo k 4..7 | ...], rows of
     // 2 DP + 8 elements (80 bytes: the 16-byte pieces of 16 consecutive rows fall on disjoint banks).  A lane's [ah | al]
@@ -759,9 +738,7 @@ __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_
     // arrays needed four v_mov per subtile to line them up); the LDS transpose reads take the pieces at stride 16 bytes.
     constexpr int LDHL = 2 * DP + 8;
     __shared__ __attribute__((aligned(16))) unsigned short HLs[2][TJ * LDHL];
-    __shared__ __attribute__((aligned(16))) unsigned short L2s[2][S3 ? TJ * LDH : 4];       // bf16 lo2 [j][k] (three-piece S)
-    __shared__ __attribute__((aligned(16))) unsigned short HT[2][TRV ? 4 : DP * LDT];       // bf16 hi [k][j]
-    __shared__ __attribute__((aligned(16))) unsigned short LT[2][TRV ? 4 : DP * LDT];       // bf16 lo [k][j]
+    __shared__ __attribute__((aligned(16))) unsigned short L2s[2][F16 ? 4 : TJ * LDH];       // bf16 lo2 [j][k] (three-piece S)
     // mirror tiles [buffer][wave][f][j].  Two buffers (round 4): the tile after next rewrites a buffer only behind the NEXT tile's
     // barrier, which every thread passes after it has flushed this one -- the second block barrier per tile is gone.  (Round 2
     // tried this with the transposed tile copies still in LDS: 54 KB per block, 2 instead of 3 blocks per CU, 157 -> 179 us; since
@@ -785,7 +762,7 @@ __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_
     static_assert(RI % 2 == 0, "row subtiles are paired into K = 32 mirror products");
     s16x8 bhh[RI];               // B fragments of S^T = Zj Zi^T (row operand, log2(e) folded in): [hi | hi]
     s16x8 bll[RI];               // ... and [lo | lo]: S = (ah + al)(bhi + blo), all four partial products
-    s16x8 b3[S3 ? RI : 1];       // S3: [hi | lo2] against [al2 | ah]: + al2.bhi + ah.blo2
+    s16x8 b3[F16 ? 1 : RI];      // bf16: [hi | lo2] against [al2 | ah]: + al2.bhi + ah.blo2
     s16x8 zTh[RI / 2], zTl[RI / 2];   // B fragments of the mirror product, row subtiles (2 rp, 2 rp + 1) concatenated:
                                       // lane (f = l15, g) -> Zt[i = 4 g + r][f]
 #pragma unroll
@@ -795,11 +772,13 @@ __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_
         if (i >= n) b = f32x4{0.f, 0.f, 0.f, 0.f};
         b *= LOG2E;
         s16x4 bhi, blo, blo2;
-        if (S3) { split_bf16x4_3(b, bhi, blo, blo2); b3[ri] = cat(bhi, blo2); }
-        else if (F16) {
+        if (F16) {
             out_of_range |= !(fmaxf(fmaxf(fabsf(b[0]), fabsf(b[1])), fmaxf(fabsf(b[2]), fabsf(b[3]))) <= kF16Max * LOG2E);
             split_f16x4(b, bhi, blo);
-        } else split_bf16x4(b, bhi, blo);
+        } else {
+            split_bf16x4_3(b, bhi, blo, blo2);
+            b3[ri] = cat(bhi, blo2);
+        }
         bhh[ri] = cat(bhi, bhi);
         bll[ri] = cat(blo, blo);
         s16x4 th, tl;
@@ -843,9 +822,9 @@ __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_
             for (int r = 0; r < 4; ++r) pad_lane += (pad_j0 + jt * 16 + 4 * g + r >= n) ? 1.f : 0.f;
     }
 
-    // S3: only the fp32 values are staged (4 registers instead of 4 + 4 + 4); hi / lo / lo2 are split off at store time
-    // with the prepare step's own roundings (v_cvt_pk_bf16_f32 = round to nearest even: the same hi / lo bits)
-    struct Stage { s16x4 h[STAGE32 ? 1 : V4], l[STAGE32 ? 1 : V4]; f32x4 f[STAGE32 ? V4 : 1]; };
+    // only the fp32 values are staged (4 registers instead of 4 + 4 + 4); the pieces are split off at store time (bf16:
+    // with the prepare step's own roundings, v_cvt_pk_bf16_f32 = round to nearest even: the same hi / lo bits)
+    struct Stage { f32x4 f[V4]; };
     auto load_tile = [&](int64_t j0, Stage &st) {
 #pragma unroll
         for (int q = 0; q < V4; ++q) {
@@ -853,14 +832,8 @@ __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_
             const int jj = idx / (DP / 4), kk = (idx % (DP / 4)) * 4;
             const bool jv = j0 + jj < col_end;
             const int64_t j = jv ? j0 + jj : col_begin;
-            if (STAGE32) {
-                st.f[q] = *reinterpret_cast<const f32x4 *>(Zt + j * DP + kk);
-                if (!jv) st.f[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-                st.h[q] = *reinterpret_cast<const s16x4 *>(Zhi + j * DP + kk);
-                st.l[q] = *reinterpret_cast<const s16x4 *>(Zlo + j * DP + kk);
-                if (!jv) { st.h[q] = s16x4{0, 0, 0, 0}; st.l[q] = s16x4{0, 0, 0, 0}; }
-            }
+            st.f[q] = *reinterpret_cast<const f32x4 *>(Zt + j * DP + kk);
+            if (!jv) st.f[q] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
     auto store_tile = [&](int buf, const Stage &st) {
@@ -869,25 +842,16 @@ __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_
             const int idx = tid + 256 * q;
             const int jj = idx / (DP / 4), kk = (idx % (DP / 4)) * 4;
             s16x4 h4, l4;
-            if (S3) {
-                s16x4 l24;
-                split_bf16x4_3(st.f[q], h4, l4, l24);
-                *reinterpret_cast<s16x4 *>(&L2s[buf][jj * LDH + kk]) = l24;
-            } else if (F16) {
+            if (F16) {
                 const f32x4 f = st.f[q];
                 out_of_range |= !(fmaxf(fmaxf(fabsf(f[0]), fabsf(f[1])), fmaxf(fabsf(f[2]), fabsf(f[3]))) <= kF16Max);
                 split_f16x4(f, h4, l4);
             } else {
-                h4 = st.h[q]; l4 = st.l[q];
+                s16x4 l24;
+                split_bf16x4_3(st.f[q], h4, l4, l24);
+                *reinterpret_cast<s16x4 *>(&L2s[buf][jj * LDH + kk]) = l24;
             }
             *reinterpret_cast<s16x8 *>(&HLs[buf][jj * LDHL + 2 * kk]) = cat(h4, l4);
-            if (WITH_GRAD && !TRV) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    HT[buf][(kk + e) * LDT + jj] = (unsigned short)h4[e];
-                    LT[buf][(kk + e) * LDT + jj] = (unsigned short)l4[e];
-                }
-            }
         }
     };
     // sum the 4 waves' mirror tiles of the tile that started at column j0 and store it to this panel's strip
@@ -918,8 +882,9 @@ __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_
         float tA[RI], tP[RI];
 #pragma unroll
         for (int ri = 0; ri < RI; ++ri) { tA[ri] = 0.f; tP[ri] = 1.f; }
-        // (256-row panels: unrolled since the four-logit form -- 234 VGPRs; the three-piece fallback stays rolled: it spills unrolled)
-#pragma unroll((RI == 4 && S3) ? 1 : TJ / 32)
+        // (256-row panels: unrolled since the four-logit form -- 234 VGPRs; the three-piece forms stay rolled: the fallback spills unrolled)
+        constexpr int JP_UNROLL = (RI == 4 && !F16) ? 1 : TJ / 32;
+#pragma unroll JP_UNROLL
         for (int jp = 0; jp < TJ / 32; ++jp) {           // pairs of 16-column subtiles
             s16x8 ph[RI], pl[RI];                        // P of the pair: [subtile 2 jp | subtile 2 jp + 1]
 #pragma unroll
@@ -931,7 +896,7 @@ __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_
 #pragma unroll
                 for (int ri = 0; ri < RI; ++ri) {
                     sacc[ri] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (S3)       // the smallest terms first: al2.bhi + ah.blo2
+                    if (!F16)     // the smallest terms first: al2.bhi + ah.blo2
                         sacc[ri] = mfma32(cat(*reinterpret_cast<const s16x4 *>(&L2s[buf][(jt * 16 + l15) * LDH + 4 * g]), ah),
                                           b3[ri], sacc[ri]);
                     sacc[ri] = mfma_k32<F16>(ahl, bll[ri], sacc[ri]);
@@ -952,17 +917,10 @@ __global__ __launch_bounds__(256, (RI == 2 && !PERSIST) ? 3 : 2) void bce_dense_
             }
             if (WITH_GRAD) {
                 const int jc = jp * 32 + 4 * g;
-                s16x8 vh, vl;                // lane (f = l15, g): Z[j = jc + r][f] | Z[j = jc + 16 + r][f]
-                if constexpr (TRV) {
-                    const int o = (jc + (l15 >> 2)) * LDHL + 8 * (l15 & 3);
-                    vh = cat(lds_read_tr(&HLs[buf][o]), lds_read_tr(&HLs[buf][o + 16 * LDHL]));
-                    vl = cat(lds_read_tr(&HLs[buf][o + 4]), lds_read_tr(&HLs[buf][o + 4 + 16 * LDHL]));
-                } else {
-                    vh = cat(*reinterpret_cast<const s16x4 *>(&HT[buf][l15 * LDT + jc]),
-                             *reinterpret_cast<const s16x4 *>(&HT[buf][l15 * LDT + jc + 16]));
-                    vl = cat(*reinterpret_cast<const s16x4 *>(&LT[buf][l15 * LDT + jc]),
-                             *reinterpret_cast<const s16x4 *>(&LT[buf][l15 * LDT + jc + 16]));
-                }
+                // lane (f = l15, g): Z[j = jc + r][f] | Z[j = jc + 16 + r][f]
+                const int o = (jc + (l15 >> 2)) * LDHL + 8 * (l15 & 3);
+                const s16x8 vh = cat(lds_read_tr(&HLs[buf][o]), lds_read_tr(&HLs[buf][o + 16 * LDHL]));
+                const s16x8 vl = cat(lds_read_tr(&HLs[buf][o + 4]), lds_read_tr(&HLs[buf][o + 4 + 16 * LDHL]));
 #pragma unroll
                 for (int ri = 0; ri < RI; ++ri) {
                     oacc[ri] = mfma_k32<F16>(pl[ri], vh, oacc[ri]);
@@ -1184,7 +1142,7 @@ __global__ __launch_bounds__(256) void bce_mirror_reduce_kernel(const float *__r
 // give the loss terms and G_s Zt, out-edges from the CSR of A^T give G_s^T Zt; then
 //   dZ[i] = mask[i] * ( 2 (sum_splits O'[s][i] + S_all / 2) + sparse ) / N^2.
 // ---------------------------------------------------------------------------
-template <int VEC, int LPR, bool WITH_GRAD>
+template <int LPR, bool WITH_GRAD>
 __global__ __launch_bounds__(256) void bce_edges_kernel(
     const float *__restrict__ Zt /*[n][DP] = Z (.) mask, zero padded*/, const float *__restrict__ mask, int64_t ldz,
     int64_t row_begin, int64_t n_local, int d, const int32_t *__restrict__ indptr,
@@ -1196,7 +1154,7 @@ __global__ __launch_bounds__(256) void bce_edges_kernel(
     const float *__restrict__ Wmir /*mirror strips: fold them here instead of reading O_mirror (LPR == 4), or NULL*/,
     unsigned *__restrict__ range_flag /*the dense launches' range guard, cleared here for the next call (or NULL)*/)
 {
-    static_assert(VEC == 4, "edge kernel reads the padded Zt rows as float4");
+    constexpr int VEC = 4;      // features per lane: the padded Zt rows are read as float4
     if (range_flag != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *range_flag = 0u;
     // Block b owns rows [64 b, 64 b + 64).  When it also folds the mirror strips its work grows with b (column tile b
     // has a strip from every panel left of it: up to N / SYM_PR tiles of 4 KB): the heaviest blocks go FIRST, so the
@@ -1476,7 +1434,7 @@ __global__ __launch_bounds__(1024) void bce_finalize_kernel(const gae_bce_tail t
 
 struct BcePlan {
     int64_t row_blocks, n_splits, cols_per_split, edge_blocks, prep_blocks;
-    int KS, DP, LPR, VEC;
+    int KS, DP, LPR;
     int64_t o_bytes, zt_bytes, zh_bytes, cs_bytes, s_bytes, n_dense, total_bytes;
     double pad_terms;
     bool sym;                     // symmetric dense kernel (full square, d <= 16, bf16x3 products)
@@ -1488,7 +1446,7 @@ struct BcePlan {
 
 inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
-bool bce_plan(int64_t n, int64_t n_local, int64_t d, bool vec_ok, BcePlan &p)
+bool bce_plan(int64_t n, int64_t n_local, int64_t d, BcePlan &p)
 {
     const int64_t ROWS_PER_BLOCK = 64 * kBceRi;
     if (d > 64) return false;
@@ -1508,8 +1466,6 @@ bool bce_plan(int64_t n, int64_t n_local, int64_t d, bool vec_ok, BcePlan &p)
     p.cols_per_split = tiles_per_split * TJ;
     p.n_splits = (col_tiles + tiles_per_split - 1) / tiles_per_split;
     p.pad_terms = double(col_tiles * TJ - n) * double(n_local);   // zero columns: log2(1 + e^0) = 1 each
-    (void)vec_ok;
-    p.VEC = 4;
     const int nvec = p.DP / 4;   // the edge kernel reads the padded Zt rows
     int lpr = 1;
     while (lpr < nvec) lpr <<= 1;
@@ -1601,53 +1557,58 @@ bool bce_plan(int64_t n, int64_t n_local, int64_t d, bool vec_ok, BcePlan &p)
     return true;
 }
 
+// the full-square kernel of the knobs: S in three bf16 pieces per operand (bce_s_bf16 != 0) or exact fp32, P V in bf16 x 3
+// as well with bce_pv_bf16
+template <int KS, bool WITH_GRAD>
+auto dense_kernel()
+{
+    if (!g_bce_s_bf16) return bce_dense_kernel<KS, WITH_GRAD, false, false>;
+    return g_bce_pv_bf16 ? bce_dense_kernel<KS, WITH_GRAD, true, true> : bce_dense_kernel<KS, WITH_GRAD, true, false>;
+}
+
 template <bool WITH_GRAD>
 int launch_dense(const BcePlan &p, const float *Zt, const unsigned short *Zhi, const unsigned short *Zlo, int64_t n,
                  int64_t row_begin, int64_t n_local, float *O, double *lp, const double *cs, double *S, float *S_all_f,
                  hipStream_t s)
 {
     const dim3 grid(unsigned(p.row_blocks) + 1, unsigned(p.n_splits));   // + 1: the column-sum block
-    // SB: three bf16 pieces per operand for S (bce_s_bf16 2 or 3), else exact fp32; P V in bf16 x 3 with bce_pv_bf16
-#define GAE_BD(KS, SB)                                                                                             \
-    do {                                                                                                           \
-        if (SB && g_bce_pv_bf16)                                                                                   \
-            hipLaunchKernelGGL((bce_dense_kernel<KS, WITH_GRAD, kBceRi, 1, SB, SB, SB && WITH_GRAD, SB>), grid, dim3(256), 0, \
-                               s, Zt, Zhi, Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs, p.prep_blocks, S, \
-                               S_all_f, unsigned(p.row_blocks));                                                   \
-        else                                                                                                       \
-            hipLaunchKernelGGL((bce_dense_kernel<KS, WITH_GRAD, kBceRi, 1, SB, false, false, SB>), grid, dim3(256), 0, s, \
-                               Zt, Zhi, Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs, p.prep_blocks, S, \
-                               S_all_f, unsigned(p.row_blocks));                                                   \
-    } while (0)
-    const bool sb = g_bce_s_bf16 != 0;
-    if (p.KS == 1) { if (sb) GAE_BD(1, true); else GAE_BD(1, false); }
-    else if (p.KS == 2) { if (sb) GAE_BD(2, true); else GAE_BD(2, false); }
-    else { if (sb) GAE_BD(4, true); else GAE_BD(4, false); }
-#undef GAE_BD
+    const auto kernel = p.KS == 1 ? dense_kernel<1, WITH_GRAD>() : p.KS == 2 ? dense_kernel<2, WITH_GRAD>()
+                                                                             : dense_kernel<4, WITH_GRAD>();
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, Zt, Zhi, Zlo, n, row_begin, n_local, p.cols_per_split, O, lp, cs,
+                       p.prep_blocks, S, S_all_f, unsigned(p.row_blocks));
     GAE_CHECK_LAUNCH("bce_dense_kernel");
     return GAE_OK;
 }
 
-template <int VEC, bool WITH_GRAD>
+template <bool WITH_GRAD>
 int launch_edges(const BcePlan &p, const float *Zt, const float *mask, int64_t ldz, int64_t row_begin, int64_t n, int d,
                  const int32_t *ip, const int32_t *ix, const int32_t *tp, const int32_t *tx, float pw, float inv_n2,
                  const float *O, const float *S_all_f, float *dZ, int64_t lddz, double *lp, const float *Omir,
                  const int64_t *counts, const double *scal, const float *Wmir, unsigned *range_flag, hipStream_t s)
 {
-#define GAE_EDGE(LPR)                                                                                              \
-    hipLaunchKernelGGL((bce_edges_kernel<VEC, LPR, WITH_GRAD>), dim3(unsigned(p.edge_blocks)), dim3(256), 0, s, Zt, \
-                       mask, ldz, row_begin, n, d, ip, ix, tp, tx, pw, inv_n2, O, int(p.n_splits), p.DP, S_all_f,  \
-                       dZ, lddz, lp, Omir, (p.bal_tpb ? -int64_t(p.bal_tpb) : p.cols_per_split), p.sym_pr, counts, scal, Wmir, range_flag)
-    switch (p.LPR) {
-    case 1: GAE_EDGE(1); break;
-    case 2: GAE_EDGE(2); break;
-    case 4: GAE_EDGE(4); break;
-    case 8: GAE_EDGE(8); break;
-    default: GAE_EDGE(16); break;
-    }
-#undef GAE_EDGE
+    const auto kernel = p.LPR == 1 ? bce_edges_kernel<1, WITH_GRAD>
+                        : p.LPR == 2 ? bce_edges_kernel<2, WITH_GRAD>
+                        : p.LPR == 4 ? bce_edges_kernel<4, WITH_GRAD>
+                        : p.LPR == 8 ? bce_edges_kernel<8, WITH_GRAD>
+                                     : bce_edges_kernel<16, WITH_GRAD>;
+    hipLaunchKernelGGL(kernel, dim3(unsigned(p.edge_blocks)), dim3(256), 0, s, Zt, mask, ldz, row_begin, n, d, ip, ix, tp,
+                       tx, pw, inv_n2, O, int(p.n_splits), p.DP, S_all_f, dZ, lddz, lp, Omir,
+                       (p.bal_tpb ? -int64_t(p.bal_tpb) : p.cols_per_split), p.sym_pr, counts, scal, Wmir, range_flag);
     GAE_CHECK_LAUNCH("bce_edges_kernel");
     return GAE_OK;
+}
+
+// the symmetric kernel of the plan: panels of sym_pr = 64 RI rows, the balanced schedule when bal_tpb is set
+template <SymForm FORM>
+auto sym_kernel(const BcePlan &p, bool with_grad)
+{
+    const bool tall = p.sym_pr == 256, bal = p.bal_tpb != 0;
+    if (with_grad) {
+        if (tall) return bal ? bce_dense_sym_kernel<true, 4, FORM, true> : bce_dense_sym_kernel<true, 4, FORM, false>;
+        return bal ? bce_dense_sym_kernel<true, 2, FORM, true> : bce_dense_sym_kernel<true, 2, FORM, false>;
+    }
+    if (tall) return bal ? bce_dense_sym_kernel<false, 4, FORM, true> : bce_dense_sym_kernel<false, 4, FORM, false>;
+    return bal ? bce_dense_sym_kernel<false, 2, FORM, true> : bce_dense_sym_kernel<false, 2, FORM, false>;
 }
 
 } // namespace
@@ -1656,7 +1617,7 @@ extern "C" int64_t gae_decoder_bce_workspace_bytes(int64_t n, int64_t n_local, i
 {
     if (n < 0 || d < 0 || n_local < 0 || n_local > n) return GAE_E_SIZE;
     BcePlan p;
-    if (!bce_plan(n, n_local, d, true, p)) return GAE_E_RANGE;
+    if (!bce_plan(n, n_local, d, p)) return GAE_E_RANGE;
     return p.total_bytes + 256;
 }
 
@@ -1693,7 +1654,7 @@ int decoder_bce_impl(const float *Z, float *mask, int64_t ldz, int64_t n, int64_
     GAE_REQUIRE((Z || prepared) && loss_out && workspace && (n_local == 0 || indptr), GAE_E_NULL, "gae_decoder_bce: NULL pointer");
     GAE_REQUIRE(!dZ || n_local == 0 || t_indptr, GAE_E_NULL, "gae_decoder_bce: the gradient needs the CSR of A^T");
     BcePlan p;
-    bce_plan(n, n_local, d, true, p);
+    bce_plan(n, n_local, d, p);
     GAE_REQUIRE(workspace_bytes >= p.total_bytes, GAE_E_WORKSPACE, "gae_decoder_bce: workspace %lld < %lld bytes",
                 (long long)workspace_bytes, (long long)p.total_bytes);
     if (prepared) {
@@ -1736,22 +1697,19 @@ int decoder_bce_impl(const float *Z, float *mask, int64_t ldz, int64_t n, int64_
         const dim3 grid = p.bal_tpb ? dim3(unsigned(p.bal_blocks) + 1) : dim3(unsigned(p.row_blocks) + 1, unsigned(p.n_splits));
         static std::atomic<unsigned> call_counter{0};
         const unsigned ticket = (call_counter.fetch_add(1) * 2654435761u) | 0x80000001u;    // never 0 (= cleared)
+        auto launch_sym = [&](auto kernel, dim3 g, int flag_mode) {
+            hipLaunchKernelGGL(kernel, g, dim3(256), 0, s, Zt, Zhi, Zlo, n, p.cols_per_split, O, Wmir, lp, cs, p.prep_blocks, S,
+                               S_all_f, unsigned(p.row_blocks), n >= 32768 ? 1 : 0, range_flag, flag_mode, ticket,
+                               (p.bal_tpb ? unsigned(p.bal_blocks) + 1u : unsigned(p.n_splits)), p.bal_tpb);
+        };
         // fp16 pieces (knob bce_s_bf16 = 3, the default): the F16 launch reports out-of-range embeddings through
         // range_flag, the three-piece bf16 launch behind it runs only then (see the kernel)
-#define GAE_SYM3(WG, R, T, S3V, F16V, FM, PERS, GRID)                                                                \
-    do { if (p.bal_tpb) GAE_SYM4(WG, R, T, S3V, F16V, FM, PERS, true, GRID); else GAE_SYM4(WG, R, T, S3V, F16V, FM, PERS, false, GRID); } while (0)
-#define GAE_SYM4(WG, R, T, S3V, F16V, FM, PERS, BALV, GRID)                                                          \
-    hipLaunchKernelGGL((bce_dense_sym_kernel<WG, R, T, S3V, F16V, PERS, BALV>), GRID, dim3(256), 0, s, Zt, Zhi, Zlo, n, p.cols_per_split, O, Wmir, \
-                       lp, cs, p.prep_blocks, S, S_all_f, unsigned(p.row_blocks),                                    \
-                       n >= 32768 ? 1 : 0, range_flag, FM, ticket,                                                   \
-                       (p.bal_tpb ? unsigned(p.bal_blocks) + 1u : unsigned(p.n_splits)), p.bal_tpb)
-#define GAE_SYM(WG, R, T) do { if (g_bce_s_bf16 == 3) { GAE_SYM3(WG, R, T, false, true, 1, false, grid); GAE_SYM3(WG, R, T, true, false, 2, true, (p.bal_tpb ? dim3(64) : dim3(2 * kChipCus))); } \
-    else GAE_SYM3(WG, R, T, true, false, 0, false, grid); } while (0)
-        if (!dZ) { if (p.sym_pr == 256) GAE_SYM(false, 4, false); else GAE_SYM(false, 2, false); }
-        else { if (p.sym_pr == 256) GAE_SYM(true, 4, true); else GAE_SYM(true, 2, true); }
-#undef GAE_SYM
-#undef GAE_SYM3
-#undef GAE_SYM4
+        if (g_bce_s_bf16 == 3) {
+            launch_sym(sym_kernel<SymForm::kF16>(p, dZ != nullptr), grid, 1);
+            launch_sym(sym_kernel<SymForm::kBf16x3Fallback>(p, dZ != nullptr), p.bal_tpb ? dim3(64) : dim3(2 * kChipCus), 2);
+        } else {
+            launch_sym(sym_kernel<SymForm::kBf16x3>(p, dZ != nullptr), grid, 0);
+        }
         GAE_CHECK_LAUNCH("bce_dense_sym_kernel");
         if (dZ && p.LPR != 4) {     // otherwise the edge kernel folds the strips itself
             hipLaunchKernelGGL(bce_mirror_reduce_kernel, dim3(unsigned((n + TJ - 1) / TJ)), dim3(256), 0, s, Wmir, n,
@@ -1765,11 +1723,11 @@ int decoder_bce_impl(const float *Z, float *mask, int64_t ldz, int64_t n, int64_
     }
     if (rc) return rc;
     double *lpe = lp + 2 * p.n_dense;
-    rc = dZ ? launch_edges<4, true>(p, Zt, mask, ldz, row_begin, n_local, int(d), indptr, indices, t_indptr, t_indices,
+    rc = dZ ? launch_edges<true>(p, Zt, mask, ldz, row_begin, n_local, int(d), indptr, indices, t_indptr, t_indices,
                                     pos_weight, float(inv_n2), O, S_all_f, dZ, lddz, lpe, p.sym ? Omir : nullptr,
                                     counts, scal, (p.sym && p.LPR == 4) ? Wmir : nullptr,
                                     p.sym ? range_flag : nullptr, s)
-            : launch_edges<4, false>(p, Zt, mask, ldz, row_begin, n_local, int(d), indptr, indices, t_indptr,
+            : launch_edges<false>(p, Zt, mask, ldz, row_begin, n_local, int(d), indptr, indices, t_indptr,
                                      t_indices, pos_weight, float(inv_n2), O, S_all_f, dZ, lddz, lpe, nullptr, counts,
                                      scal, nullptr, p.sym ? range_flag : nullptr, s);
     if (rc) return rc;
@@ -1851,7 +1809,7 @@ extern "C" int gae_x_decoder_bce_prep_layout(int64_t n, int64_t d, void *workspa
     GAE_REQUIRE(out && workspace, GAE_E_NULL, "gae_x_decoder_bce_prep_layout: NULL pointer");
     GAE_REQUIRE(n > 0 && d > 0 && d <= 64, GAE_E_RANGE, "gae_x_decoder_bce_prep_layout: n, d out of range");
     BcePlan p;
-    bce_plan(n, n, d, true, p);
+    bce_plan(n, n, d, p);
     GAE_REQUIRE(workspace_bytes >= p.total_bytes && gae::aligned16(workspace), GAE_E_WORKSPACE,
                 "gae_x_decoder_bce_prep_layout: workspace %lld < %lld bytes (or not 16-byte aligned)",
                 (long long)workspace_bytes, (long long)p.total_bytes);

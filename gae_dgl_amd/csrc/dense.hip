@@ -862,14 +862,14 @@ int launch_gemm_stream(const float *A, int64_t lda, const float *Amask, int64_t 
 // out[O, I] (+)= sum_r proP(P)[r, O]^T Q[r, I]   -- reduction over rows.
 // Both operands are read in their natural row-major layout straight into the
 // MFMA fragments (lane = column, k = row parity): no LDS in the row loop.  A block
-// of NW waves owns one row slot and one 32 x (IT*32) output tile: the waves split
-// the slot's rows (NW = 8: twice the loads in flight per partial of the 4-wave
-// form, and a second wave per SIMD whose MFMAs cover the other's memory waits),
+// of 8 waves owns one row slot and one 32 x (IT*32) output tile: the waves split
+// the slot's rows (twice the loads in flight per partial of a 4-wave block, and
+// a second wave per SIMD whose MFMAs cover the other's memory waits),
 // meet in LDS in a fixed tree order and write ONE partial; a second kernel sums
 // the partials in slot order (deterministic, no float atomics).
 // ---------------------------------------------------------------------------
-template <int IT, int PRO_P, bool QVEC, int NW>
-__global__ __launch_bounds__(NW * 64) void atb_partial_kernel(
+template <int IT, int PRO_P, bool QVEC>
+__global__ __launch_bounds__(512) void atb_partial_kernel(
     const float *__restrict__ P, int64_t ldp, const float *__restrict__ Pmask, int64_t ldpm,
     const float *__restrict__ Q, int64_t ldq, int64_t n, int O, int I, int64_t rows_per_slot,
     float *__restrict__ partial, int64_t slot_stride, int64_t colsum_offset)
@@ -878,7 +878,7 @@ __global__ __launch_bounds__(NW * 64) void atb_partial_kernel(
     //          column 4j + t);  IT == 1: lane j owns column j of a 32-column group (narrow outputs).
     static_assert(IT == 4 || IT == 1, "IT is 1 or 4");
     static_assert(!QVEC || IT == 4, "the float4 path needs IT == 4");
-    static_assert(NW == 4 || NW == 8, "4 or 8 waves");
+    constexpr int NW = 8;
     constexpr int PARK = IT * 16 * 64 + 64;          // accumulators + column sums of one parked wave
     __shared__ float red[NW / 2][PARK];
     const int lane = threadIdx.x & 63;
@@ -1313,7 +1313,7 @@ int launch_atb(const float *P, int64_t ldp, const float *Pmask, int64_t ldpm, co
                       gae::aligned16(partial);
     const int64_t cso = colsum ? int64_t(O) * I : -1;
 #define GAE_ATB(IT, QV)                                                                                             \
-    hipLaunchKernelGGL((atb_partial_kernel<IT, PRO_P, QV, 8>), grid, dim3(512), 0, s, P, ldp, Pmask, ldpm, Q, ldq, n, \
+    hipLaunchKernelGGL((atb_partial_kernel<IT, PRO_P, QV>), grid, dim3(512), 0, s, P, ldp, Pmask, ldpm, Q, ldq, n, \
                        O, I, pl.rows_per_slot, partial, pl.slot_stride, cso)
     if (narrow) GAE_ATB(1, false);
     else if (qvec) GAE_ATB(4, true);
