@@ -699,6 +699,220 @@ __host__ __device__ inline int64_t sym_strip_offset(int64_t I, int64_t NP, int64
     return 16 * (I * NP - PR * (I * (I + 1) / 2));
 }
 
+// ---------------------------------------------------------------------------
+// Sparse part of the loss: a group of LPR lanes owns node i (4 features per lane); its in-edges from the CSR give the
+// loss terms and G_s Zt, its out-edges from the CSR of A^T give G_s^T Zt.  It reads Zt and the two CSR tables only, so
+// it runs in bce_edges_kernel or, on the balanced schedule of the symmetric kernel, in blocks appended to the dense
+// launch (the same code: the same terms in the same order).  start() requests the row of Zt and both edge ranges; the
+// caller may ask for more before run() begins the chain of dependent round trips.
+// ---------------------------------------------------------------------------
+template <int LPR, bool WITH_GRAD>
+struct EdgeWalk {
+    static constexpr int VEC = 4;      // features per lane: the padded Zt rows are read as float4
+    // rows with more than kLongRow edges in a list (the hubs of the real citation graphs: 100 - 170) are left out of the
+    // lane group's own walk -- 8 edges per pair of round trips: a 156-edge row held its block for 40 us -- and taken by
+    // the whole wave afterwards, one row at a time
+    static constexpr int kLongRow = 16;
+    float zi[VEC], acc_in[VEC], acc_out[VEC];
+    int32_t posA, endA, posB, endB, longA0, longA1, longB0, longB1;
+    bool is_long;
+
+    __device__ __forceinline__ void start(const float *__restrict__ Zt, int DP, int64_t i, int64_t gi, bool rowv,
+                                          int f0, bool fv, const int32_t *__restrict__ indptr,
+                                          const int32_t *__restrict__ t_indptr)
+    {
+        const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+        const f32x4 t = (rowv && fv) ? *reinterpret_cast<const f32x4 *>(Zt + gi * DP + f0) : zero4;
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) { acc_in[q] = acc_out[q] = 0.f; zi[q] = t[q]; }
+        posA = rowv ? indptr[i] : 0;
+        endA = rowv ? indptr[i + 1] : 0;
+        posB = (WITH_GRAD && rowv) ? t_indptr[i] : 0;
+        endB = (WITH_GRAD && rowv) ? t_indptr[i + 1] : 0;
+        is_long = max(endA - posA, endB - posB) > kLongRow;
+        longA0 = posA; longA1 = endA; longB0 = posB; longB1 = endB;
+        if (is_long) { endA = posA; endB = posB; }
+    }
+
+    // the walk; returns this lane's share of sum_edges [-x + (pw - 1) softplus(-x)]
+    __device__ __forceinline__ double run(const float *__restrict__ Zt, int DP, int f0, bool fv, float pw,
+                                          const int32_t *__restrict__ indices, const int32_t *__restrict__ t_indices)
+    {
+        const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+        const int lane = threadIdx.x & 63, lig = threadIdx.x % LPR;
+        double lsum = 0.0;
+        // In-edges (CSR: loss + G_s Zt) and out-edges (CSR of A^T: G_s^T Zt) of node i advance TOGETHER, NE edges of
+        // each per trip: the ids come from two coalesced loads per list, the 2 NE neighbour rows are all in flight
+        // before the first dot product (one memory round trip per trip for both lists; rows of <= 8 edges: one trip).
+        constexpr int NE = LPR >= 4 ? 8 : 4;
+        const int glane0 = (lane / LPR) * LPR;
+        while (posA < endA || posB < endB) {
+            int32_t mineA[NE / 4], mineB[NE / 4];
+#pragma unroll
+            for (int h = 0; h < NE / 4; ++h) {
+                const int32_t eA = posA + 4 * h + (LPR >= 4 ? (lig & 3) : 0), eB = posB + 4 * h + (LPR >= 4 ? (lig & 3) : 0);
+                mineA[h] = eA < endA ? indices[eA] : 0;
+                mineB[h] = (WITH_GRAD && eB < endB) ? t_indices[eB] : 0;
+            }
+            float zj[2 * NE][VEC], dot[2 * NE];
+#pragma unroll
+            for (int u = 0; u < 2 * NE; ++u) {
+                const bool second = u >= NE;
+                if (second && !WITH_GRAD) { dot[u] = 0.f; continue; }
+                const int32_t pos = second ? posB : posA, end = second ? endB : endA;
+                const int uu = u % NE;
+                const int32_t mine = second ? mineB[uu / 4] : mineA[uu / 4];
+                const int32_t j = LPR >= 4 ? __shfl(mine, glane0 + (uu & 3), 64)
+                                           : (pos + uu < end ? (second ? t_indices : indices)[pos + uu] : 0);
+                const bool ev = pos + uu < end;
+                dot[u] = 0.f;
+                const f32x4 t = (ev && fv) ? *reinterpret_cast<const f32x4 *>(Zt + int64_t(j) * DP + f0) : zero4;
+#pragma unroll
+                for (int q = 0; q < VEC; ++q) {
+                    zj[u][q] = t[q];
+                    dot[u] = fmaf(zi[q], t[q], dot[u]);
+                }
+            }
+#pragma unroll
+            for (int off = LPR / 2; off > 0; off >>= 1)
+#pragma unroll
+                for (int u = 0; u < (WITH_GRAD ? 2 * NE : NE); ++u) dot[u] += __shfl_xor(dot[u], off, 64);
+#pragma unroll
+            for (int u = 0; u < (WITH_GRAD ? 2 * NE : NE); ++u) {
+                const bool second = u >= NE;
+                const int32_t pos = second ? posB : posA, end = second ? endB : endA;
+                if (pos + (u % NE) < end) {
+                    const float x = dot[u];
+                    float spn, sgn;               // softplus(-x), sigmoid(-x)
+                    softplus_sigmoid(-x, spn, sgn);
+                    const float sg = 1.0f - sgn;  // sigmoid(x)
+                    if (!second && lig == 0) lsum += double(-x + (pw - 1.0f) * spn);
+                    const float c = (pw - 1.0f) * sg - pw;
+#pragma unroll
+                    for (int q = 0; q < VEC; ++q) {
+                        if (second) acc_out[q] = fmaf(c, zj[u][q], acc_out[q]);
+                        else acc_in[q] = fmaf(c, zj[u][q], acc_in[q]);
+                    }
+                }
+            }
+            posA = min(posA + NE, endA);
+            posB = min(posB + NE, endB);
+        }
+        // ---- long rows: CH edges of each list per trip (ids: one coalesced load per list), lane group g takes ids g,
+        //      g + G, ... -- up to 4 of each list, 8 rows of Zt in flight per lane --, its shares of the two sums meet in a
+        //      butterfly over the lane bits above the group; the loss terms stay where they were computed (lsum is summed
+        //      over the wave by the caller anyway).  Same terms as the walk above, added in another order.
+        {
+            // (requesting the first long row's first ids in front of the short rows' walk: measured, no gain)
+            constexpr int G = 64 / LPR, CU = LPR < 4 ? LPR : 4, CH = CU * G;      // CH <= 64: one id per lane
+            unsigned long long todo = __builtin_amdgcn_ballot_w64(is_long && lig == 0);
+            const int grp = lane / LPR;
+            while (todo != 0) {                                            // scalar
+                const int hl = __builtin_ctzll(todo);
+                todo &= todo - 1;
+                const int32_t eA = __builtin_amdgcn_readlane(longA1, hl), eB = __builtin_amdgcn_readlane(longB1, hl);
+                int32_t a0 = __builtin_amdgcn_readlane(longA0, hl), b0 = __builtin_amdgcn_readlane(longB0, hl);
+                float zr[VEC], pin[VEC], pout[VEC];
+#pragma unroll
+                for (int q = 0; q < VEC; ++q) {
+                    zr[q] = __shfl(zi[q], hl + lig, 64);
+                    pin[q] = pout[q] = 0.f;
+                }
+                for (; a0 < eA || b0 < eB; a0 += CH, b0 += CH) {
+                    const int32_t idA = (lane < CH && a0 + lane < eA) ? indices[a0 + lane] : 0;
+                    const int32_t idB = (WITH_GRAD && lane < CH && b0 + lane < eB) ? t_indices[b0 + lane] : 0;
+                    float zj[2 * CU][VEC], dot[2 * CU];
+#pragma unroll
+                    for (int u = 0; u < 2 * CU; ++u) {
+                        const bool second = u >= CU;
+                        dot[u] = 0.f;
+                        if (second && !WITH_GRAD) continue;
+                        const int slot = grp + G * (u % CU);
+                        const int32_t j = __shfl(second ? idB : idA, slot, 64);
+                        const bool ev = (second ? b0 : a0) + slot < (second ? eB : eA);
+                        const f32x4 t = (ev && fv) ? *reinterpret_cast<const f32x4 *>(Zt + int64_t(j) * DP + f0) : zero4;
+#pragma unroll
+                        for (int q = 0; q < VEC; ++q) {
+                            zj[u][q] = t[q];
+                            dot[u] = fmaf(zr[q], t[q], dot[u]);
+                        }
+                    }
+#pragma unroll
+                    for (int off = LPR / 2; off > 0; off >>= 1)
+#pragma unroll
+                        for (int u = 0; u < (WITH_GRAD ? 2 * CU : CU); ++u) dot[u] += __shfl_xor(dot[u], off, 64);
+#pragma unroll
+                    for (int u = 0; u < (WITH_GRAD ? 2 * CU : CU); ++u) {
+                        const bool second = u >= CU;
+                        const int slot = grp + G * (u % CU);
+                        if ((second ? b0 : a0) + slot < (second ? eB : eA)) {
+                            const float x = dot[u];
+                            float spn, sgn;
+                            softplus_sigmoid(-x, spn, sgn);
+                            const float sg = 1.0f - sgn;
+                            if (!second && lig == 0) lsum += double(-x + (pw - 1.0f) * spn);
+                            const float c = (pw - 1.0f) * sg - pw;
+#pragma unroll
+                            for (int q = 0; q < VEC; ++q) {
+                                if (second) pout[q] = fmaf(c, zj[u][q], pout[q]);
+                                else pin[q] = fmaf(c, zj[u][q], pin[q]);
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int off = LPR; off < 64; off <<= 1)
+#pragma unroll
+                    for (int q = 0; q < VEC; ++q) {
+                        pin[q] += __shfl_xor(pin[q], off, 64);
+                        if (WITH_GRAD) pout[q] += __shfl_xor(pout[q], off, 64);
+                    }
+                if ((lane & ~(LPR - 1)) == hl) {
+#pragma unroll
+                    for (int q = 0; q < VEC; ++q) { acc_in[q] += pin[q]; acc_out[q] += pout[q]; }
+                }
+            }
+        }
+        return lsum;
+    }
+};
+
+// what the walk blocks of the balanced symmetric launch need (WITH_GRAD; see bce_dense_sym_kernel)
+struct SymWalkArgs {
+    const int32_t *indptr, *indices, *t_indptr, *t_indices;
+    float pw;
+    const double *scal;          // fixed-capacity batch: pos_weight on the device (or NULL)
+    float *s;                    // [n][16]: acc_in + acc_out per row, for the combine (bce_edges_kernel<4, true, false>)
+    double *loss_partial;        // [ceil(n / 64)]: the edge loss partials, one per 64 rows
+    unsigned n_walk;             // walk blocks after the dense ones (0: none, the edge kernel walks)
+};
+
+// one walk block of the balanced symmetric launch: rows [64 w, 64 w + 64), 4 lanes per row (DP = 16)
+__device__ __forceinline__ void sym_walk_block(const float *__restrict__ Zt, int64_t n, unsigned w, const SymWalkArgs &wk,
+                                               double (*red)[2])
+{
+    constexpr int LPR = 4, DP = 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t i = int64_t(w) * (256 / LPR) + tid / LPR;
+    const bool rowv = i < n;
+    const int f0 = (tid % LPR) * 4;
+    const float pw = wk.scal ? float(wk.scal[0]) : wk.pw;
+    EdgeWalk<LPR, true> ew;
+    ew.start(Zt, DP, i, i, rowv, f0, true, wk.indptr, wk.t_indptr);
+    double lsum = ew.run(Zt, DP, f0, true, pw, wk.indices, wk.t_indices);
+    if (rowv) {
+        f32x4 v;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = ew.acc_in[q] + ew.acc_out[q];
+        *reinterpret_cast<f32x4 *>(wk.s + i * DP + f0) = v;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) lsum += __shfl_down(lsum, off, 64);
+    if (lane == 0) red[wave][0] = lsum;
+    __syncthreads();
+    if (tid == 0) wk.loss_partial[w] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+}
+
 // The products of the symmetric kernel: two fp16 pieces per operand behind the range guard (knob bce_s_bf16 = 3),
 // three bf16 pieces (any other nonzero value), and the three bf16 pieces again as the guard's fallback launch (a few
 // blocks that walk the whole grid; see the kernel).
@@ -713,7 +927,8 @@ __global__ __launch_bounds__(256, (RI == 2 && FORM != SymForm::kBf16x3Fallback) 
     float *__restrict__ O_partial /*[chunks][n][16]*/, float *__restrict__ Wmir,
     double *__restrict__ loss_partial /*[chunks * panels][2]*/, const double *__restrict__ colsum_partial,
     int64_t n_prep_blocks, double *__restrict__ S, float *__restrict__ S_all_f, unsigned n_panels, int exp_strip,
-    unsigned *__restrict__ range_flag, int flag_mode, unsigned ticket, unsigned n_chunks, int bal_tpb)
+    unsigned *__restrict__ range_flag, int flag_mode, unsigned ticket, unsigned n_chunks, int bal_tpb,
+    const SymWalkArgs wk)
 {
     // Range guard of the fp16 pieces.  flag_mode 1 (the F16 launch): a thread that meets |Zt| > kF16Max (or a NaN)
     // writes this call's ticket to *range_flag; the launch's results are then meaningless.  flag_mode 2 (the
@@ -1095,6 +1310,13 @@ __global__ __launch_bounds__(256, (RI == 2 && FORM != SymForm::kBf16x3Fallback) 
                 vblock(vb);
                 __syncthreads();                       // red and the LDS tiles are reused by the next virtual block
             }
+        } else if (WITH_GRAD && blockIdx.x >= n_vb) {
+            // ---- walk blocks (wk.n_walk of them, after the column-sum block): the sparse part of the loss, which reads
+            //      only Zt and the CSR tables.  Dispatched as the dense blocks retire, they fill the launch's tail; the
+            //      edge kernel behind it keeps the strip fold and the assembly of dZ (bce_edges_kernel<4, true, false>).
+            //      Rows and loss slot of block w as those of block w of bce_edges_kernel<4>: the same terms, same order.
+            const unsigned w = blockIdx.x - n_vb;
+            if (w < wk.n_walk) sym_walk_block(Zt, n, w, wk, red);
         } else {
             vblock(blockIdx.x);
         }
@@ -1138,11 +1360,13 @@ __global__ __launch_bounds__(256) void bce_mirror_reduce_kernel(const float *__r
 }
 
 // ---------------------------------------------------------------------------
-// Sparse part + assembly.  A group of LPR lanes owns node i (4 features per lane): in-edges from the CSR
-// give the loss terms and G_s Zt, out-edges from the CSR of A^T give G_s^T Zt; then
+// Sparse part + assembly.  A group of LPR lanes owns node i (4 features per lane): the edge walk (EdgeWalk) gives
+// the loss terms and G_s Zt + G_s^T Zt; then
 //   dZ[i] = mask[i] * ( 2 (sum_splits O'[s][i] + S_all / 2) + sparse ) / N^2.
+// WALK = false (the balanced symmetric launch, which walked the edges in blocks of its own): the combine alone --
+// sparse = s[i] as those blocks wrote it, no index loads, no loss partial.
 // ---------------------------------------------------------------------------
-template <int LPR, bool WITH_GRAD>
+template <int LPR, bool WITH_GRAD, bool WALK = true>
 __global__ __launch_bounds__(256) void bce_edges_kernel(
     const float *__restrict__ Zt /*[n][DP] = Z (.) mask, zero padded*/, const float *__restrict__ mask, int64_t ldz,
     int64_t row_begin, int64_t n_local, int d, const int32_t *__restrict__ indptr,
@@ -1152,9 +1376,11 @@ __global__ __launch_bounds__(256) void bce_edges_kernel(
     const float *__restrict__ O_mirror /*[n][16] or NULL*/, int64_t sym_cols_per_chunk, int SYM_PR,
     const int64_t *__restrict__ counts, const double *__restrict__ scal,
     const float *__restrict__ Wmir /*mirror strips: fold them here instead of reading O_mirror (LPR == 4), or NULL*/,
-    unsigned *__restrict__ range_flag /*the dense launches' range guard, cleared here for the next call (or NULL)*/)
+    unsigned *__restrict__ range_flag /*the dense launches' range guard, cleared here for the next call (or NULL)*/,
+    const float *__restrict__ s_walk /*WALK = false: [n][16] sparse rows of the walk blocks*/)
 {
-    constexpr int VEC = 4;      // features per lane: the padded Zt rows are read as float4
+    static_assert(WALK || (LPR == 4 && WITH_GRAD), "the combine follows the walk blocks of the balanced symmetric launch");
+    constexpr int VEC = EdgeWalk<LPR, WITH_GRAD>::VEC;
     if (range_flag != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *range_flag = 0u;
     // Block b owns rows [64 b, 64 b + 64).  When it also folds the mirror strips its work grows with b (column tile b
     // has a strip from every panel left of it: up to N / SYM_PR tiles of 4 KB): the heaviest blocks go FIRST, so the
@@ -1181,6 +1407,8 @@ __global__ __launch_bounds__(256) void bce_edges_kernel(
         //  a ZINC batch 236 -> 245 us -- eight plain loads per batch it stays.  The fold is a byte stream, not a latency chain:
         //  as a launch of its own, cut into four pieces per column tile (1232 blocks), it takes 18.0 us = 97 MB at 5.4 TB/s
         //  and the edge kernel 13.2 us behind it -- 31.2 us against 28.6 us fused; profiles/r05_loss_fold.txt)
+        //  (The combine, WALK = false, with 16 strips per batch or the ragged tail as one predicated batch: 15.1 / 14.7 us
+        //  against 14.6 us as below -- no gain, same sums.)
         int64_t I = 0;
         for (; I + 8 <= n_left; I += 8) {
             f32x4 v[8];
@@ -1209,13 +1437,11 @@ __global__ __launch_bounds__(256) void bce_edges_kernel(
 
     // Everything that does not depend on the neighbour gathers is requested first (row of Zt, both edge ranges,
     // the dense kernel's partial O' rows): the kernel is a chain of dependent round trips, not a byte stream.
-    float zi[VEC], acc_in[VEC], acc_out[VEC];
+    EdgeWalk<LPR, WITH_GRAD> ew;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    {
-        const f32x4 t = (rowv && fv) ? *reinterpret_cast<const f32x4 *>(Zt + gi * DP + f0) : zero4;
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) { acc_in[q] = acc_out[q] = 0.f; zi[q] = t[q]; }
-    }
+    f32x4 sw = zero4;            // WALK = false: the walk blocks' acc_in + acc_out of this row
+    if constexpr (WALK) ew.start(Zt, DP, i, gi, rowv, f0, fv, indptr, t_indptr);
+    else if (rowv) sw = *reinterpret_cast<const f32x4 *>(s_walk + i * 16 + f0);
     // ... and what the LAST lines of the kernel need (the column sums' share of dZ, the dropout multipliers): asked for
     // there, inside `if (f < d)`, they came out as eight dependent round trips at the end of every wave
     float sall[VEC], mk[VEC];
@@ -1225,17 +1451,6 @@ __global__ __launch_bounds__(256) void bce_edges_kernel(
         sall[q] = WITH_GRAD ? S_all_f[in ? f0 + q : 0] : 0.f;
         mk[q] = (WITH_GRAD && mask != nullptr) ? mask[in ? gi * ldz + f0 + q : 0] : 1.f;
     }
-    int32_t posA = rowv ? indptr[i] : 0;
-    int32_t endA = rowv ? indptr[i + 1] : 0;
-    int32_t posB = (WITH_GRAD && rowv) ? t_indptr[i] : 0;
-    int32_t endB = (WITH_GRAD && rowv) ? t_indptr[i + 1] : 0;
-    // rows with more than kLongRow edges in a list (the hubs of the real citation graphs: 100 - 170) are left out of the
-    // lane group's own walk below -- 8 edges per pair of round trips: a 156-edge row held its block for 40 us -- and
-    // taken by the whole wave afterwards, one row at a time
-    constexpr int kLongRow = 16;
-    const bool is_long = max(endA - posA, endB - posB) > kLongRow;
-    const int32_t longA0 = posA, longA1 = endA, longB0 = posB, longB1 = endB;
-    if (is_long) { endA = posA; endB = posB; }
     f32x4 osum = zero4;
     if (WITH_GRAD && rowv && fv) {
         const float *op = O_partial + i * DP + f0;
@@ -1272,151 +1487,22 @@ __global__ __launch_bounds__(256) void bce_edges_kernel(
         }
     }
     double lsum = 0.0;
-    // In-edges (CSR: loss + G_s Zt) and out-edges (CSR of A^T: G_s^T Zt) of node i advance TOGETHER, NE edges of
-    // each per trip: the ids come from two coalesced loads per list, the 2 NE neighbour rows are all in flight
-    // before the first dot product (one memory round trip per trip for both lists; rows of <= 8 edges: one trip).
-    constexpr int NE = LPR >= 4 ? 8 : 4;
-    const int glane0 = (lane / LPR) * LPR;
-    while (posA < endA || posB < endB) {
-        int32_t mineA[NE / 4], mineB[NE / 4];
-#pragma unroll
-        for (int h = 0; h < NE / 4; ++h) {
-            const int32_t eA = posA + 4 * h + (LPR >= 4 ? (lig & 3) : 0), eB = posB + 4 * h + (LPR >= 4 ? (lig & 3) : 0);
-            mineA[h] = eA < endA ? indices[eA] : 0;
-            mineB[h] = (WITH_GRAD && eB < endB) ? t_indices[eB] : 0;
-        }
-        float zj[2 * NE][VEC], dot[2 * NE];
-#pragma unroll
-        for (int u = 0; u < 2 * NE; ++u) {
-            const bool second = u >= NE;
-            if (second && !WITH_GRAD) { dot[u] = 0.f; continue; }
-            const int32_t pos = second ? posB : posA, end = second ? endB : endA;
-            const int uu = u % NE;
-            const int32_t mine = second ? mineB[uu / 4] : mineA[uu / 4];
-            const int32_t j = LPR >= 4 ? __shfl(mine, glane0 + (uu & 3), 64)
-                                       : (pos + uu < end ? (second ? t_indices : indices)[pos + uu] : 0);
-            const bool ev = pos + uu < end;
-            dot[u] = 0.f;
-            const f32x4 t = (ev && fv) ? *reinterpret_cast<const f32x4 *>(Zt + int64_t(j) * DP + f0) : zero4;
-#pragma unroll
-            for (int q = 0; q < VEC; ++q) {
-                zj[u][q] = t[q];
-                dot[u] = fmaf(zi[q], t[q], dot[u]);
-            }
-        }
-#pragma unroll
-        for (int off = LPR / 2; off > 0; off >>= 1)
-#pragma unroll
-            for (int u = 0; u < (WITH_GRAD ? 2 * NE : NE); ++u) dot[u] += __shfl_xor(dot[u], off, 64);
-#pragma unroll
-        for (int u = 0; u < (WITH_GRAD ? 2 * NE : NE); ++u) {
-            const bool second = u >= NE;
-            const int32_t pos = second ? posB : posA, end = second ? endB : endA;
-            if (pos + (u % NE) < end) {
-                const float x = dot[u];
-                float spn, sgn;               // softplus(-x), sigmoid(-x)
-                softplus_sigmoid(-x, spn, sgn);
-                const float sg = 1.0f - sgn;  // sigmoid(x)
-                if (!second && lig == 0) lsum += double(-x + (pw - 1.0f) * spn);
-                const float c = (pw - 1.0f) * sg - pw;
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) {
-                    if (second) acc_out[q] = fmaf(c, zj[u][q], acc_out[q]);
-                    else acc_in[q] = fmaf(c, zj[u][q], acc_in[q]);
-                }
-            }
-        }
-        posA = min(posA + NE, endA);
-        posB = min(posB + NE, endB);
-    }
-    // ---- long rows: CH edges of each list per trip (ids: one coalesced load per list), lane group g takes ids g,
-    //      g + G, ... -- up to 4 of each list, 8 rows of Zt in flight per lane --, its shares of the two sums meet in a
-    //      butterfly over the lane bits above the group; the loss terms stay where they were computed (lsum is summed
-    //      over the wave below anyway).  Same terms as the walk above, added in another order.
-    {
-        // (requesting the first long row's first ids in front of the short rows' walk: measured, no gain)
-        constexpr int G = 64 / LPR, CU = LPR < 4 ? LPR : 4, CH = CU * G;      // CH <= 64: one id per lane
-        unsigned long long todo = __builtin_amdgcn_ballot_w64(is_long && lig == 0);
-        const int grp = lane / LPR;
-        while (todo != 0) {                                            // scalar
-            const int hl = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const int32_t eA = __builtin_amdgcn_readlane(longA1, hl), eB = __builtin_amdgcn_readlane(longB1, hl);
-            int32_t a0 = __builtin_amdgcn_readlane(longA0, hl), b0 = __builtin_amdgcn_readlane(longB0, hl);
-            float zr[VEC], pin[VEC], pout[VEC];
-#pragma unroll
-            for (int q = 0; q < VEC; ++q) {
-                zr[q] = __shfl(zi[q], hl + lig, 64);
-                pin[q] = pout[q] = 0.f;
-            }
-            for (; a0 < eA || b0 < eB; a0 += CH, b0 += CH) {
-                const int32_t idA = (lane < CH && a0 + lane < eA) ? indices[a0 + lane] : 0;
-                const int32_t idB = (WITH_GRAD && lane < CH && b0 + lane < eB) ? t_indices[b0 + lane] : 0;
-                float zj[2 * CU][VEC], dot[2 * CU];
-#pragma unroll
-                for (int u = 0; u < 2 * CU; ++u) {
-                    const bool second = u >= CU;
-                    dot[u] = 0.f;
-                    if (second && !WITH_GRAD) continue;
-                    const int slot = grp + G * (u % CU);
-                    const int32_t j = __shfl(second ? idB : idA, slot, 64);
-                    const bool ev = (second ? b0 : a0) + slot < (second ? eB : eA);
-                    const f32x4 t = (ev && fv) ? *reinterpret_cast<const f32x4 *>(Zt + int64_t(j) * DP + f0) : zero4;
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) {
-                        zj[u][q] = t[q];
-                        dot[u] = fmaf(zr[q], t[q], dot[u]);
-                    }
-                }
-#pragma unroll
-                for (int off = LPR / 2; off > 0; off >>= 1)
-#pragma unroll
-                    for (int u = 0; u < (WITH_GRAD ? 2 * CU : CU); ++u) dot[u] += __shfl_xor(dot[u], off, 64);
-#pragma unroll
-                for (int u = 0; u < (WITH_GRAD ? 2 * CU : CU); ++u) {
-                    const bool second = u >= CU;
-                    const int slot = grp + G * (u % CU);
-                    if ((second ? b0 : a0) + slot < (second ? eB : eA)) {
-                        const float x = dot[u];
-                        float spn, sgn;
-                        softplus_sigmoid(-x, spn, sgn);
-                        const float sg = 1.0f - sgn;
-                        if (!second && lig == 0) lsum += double(-x + (pw - 1.0f) * spn);
-                        const float c = (pw - 1.0f) * sg - pw;
-#pragma unroll
-                        for (int q = 0; q < VEC; ++q) {
-                            if (second) pout[q] = fmaf(c, zj[u][q], pout[q]);
-                            else pin[q] = fmaf(c, zj[u][q], pin[q]);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int off = LPR; off < 64; off <<= 1)
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) {
-                    pin[q] += __shfl_xor(pin[q], off, 64);
-                    if (WITH_GRAD) pout[q] += __shfl_xor(pout[q], off, 64);
-                }
-            if ((lane & ~(LPR - 1)) == hl) {
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) { acc_in[q] += pin[q]; acc_out[q] += pout[q]; }
-            }
-        }
-    }
+    if constexpr (WALK) lsum = ew.run(Zt, DP, f0, fv, pw, indices, t_indices);
     if (WITH_GRAD && rowv) {
 #pragma unroll
         for (int q = 0; q < VEC; ++q) {
             const int f = f0 + q;
             if (f < d) {
                 const float o = 0.5f * sall[q] + osum[q];
-                float v = (2.0f * o + (acc_in[q] + acc_out[q])) * inv_n2;
+                const float sparse = WALK ? ew.acc_in[q] + ew.acc_out[q] : sw[q];
+                float v = (2.0f * o + sparse) * inv_n2;
                 if (mask) v *= mk[q];
                 if (i >= n_valid) v = 0.f;                     // padding rows receive no gradient
                 dZ[i * lddz + f] = v;
             }
         }
     }
+    if constexpr (!WALK) return;                               // (the walk blocks wrote the loss partials)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) lsum += __shfl_down(lsum, off, 64);
     if (lane == 0) red[wave] = lsum;
@@ -1442,6 +1528,7 @@ struct BcePlan {
     int bal_tpb;                  // balanced schedule: column tiles per block (0 = the 2-D grid)
     int64_t bal_blocks;           // ... and the blocks that have tiles
     int64_t wmir_bytes, omir_bytes;
+    int64_t sw_bytes;             // balanced schedule: the [n][16] sparse rows of its walk blocks (with the gradient)
 };
 
 inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
@@ -1479,6 +1566,7 @@ bool bce_plan(int64_t n, int64_t n_local, int64_t d, BcePlan &p)
     p.bal_tpb = 0;
     p.bal_blocks = 0;
     p.wmir_bytes = p.omir_bytes = 0;
+    p.sw_bytes = 0;
     // balanced schedule (round 6): every block the same number of column tiles, one resident round.  It removes the
     // quantisation of the 2-D grid into rounds of blocks, which is what kept 256-row panels from paying below ~32 k rows:
     // with it they win from ~5 k rows on (whole loss sequence, 2-D grid + 128-row panels -> balanced + 256-row panels:
@@ -1543,6 +1631,9 @@ bool bce_plan(int64_t n, int64_t n_local, int64_t d, BcePlan &p)
                 p.bal_tpb = int(tpb);
                 p.bal_blocks = (W + tpb - 1) / tpb;
                 p.n_splits = most;
+                // the launch also walks the edges (blocks of 64 rows: edge_blocks, LPR = 4 at d <= 16) and leaves
+                // acc_in + acc_out of every row here for the combine
+                p.sw_bytes = align256(n * 16 * 4);
             }
         }
     }
@@ -1553,7 +1644,7 @@ bool bce_plan(int64_t n, int64_t n_local, int64_t d, BcePlan &p)
     p.s_bytes = align256(2 * p.DP * 8 + p.DP * 4 + 4 * 8);       // column sums (double x 2, float) + 3 scalars
     p.n_dense = p.bal_tpb ? p.bal_blocks : p.row_blocks * p.n_splits;
     p.total_bytes = p.o_bytes + p.zt_bytes + 2 * p.zh_bytes + p.cs_bytes + p.s_bytes +
-                    align256((2 * p.n_dense + p.edge_blocks) * 8) + p.wmir_bytes + p.omir_bytes;
+                    align256((2 * p.n_dense + p.edge_blocks) * 8) + p.wmir_bytes + p.omir_bytes + p.sw_bytes;
     return true;
 }
 
@@ -1584,8 +1675,16 @@ template <bool WITH_GRAD>
 int launch_edges(const BcePlan &p, const float *Zt, const float *mask, int64_t ldz, int64_t row_begin, int64_t n, int d,
                  const int32_t *ip, const int32_t *ix, const int32_t *tp, const int32_t *tx, float pw, float inv_n2,
                  const float *O, const float *S_all_f, float *dZ, int64_t lddz, double *lp, const float *Omir,
-                 const int64_t *counts, const double *scal, const float *Wmir, unsigned *range_flag, hipStream_t s)
+                 const int64_t *counts, const double *scal, const float *Wmir, unsigned *range_flag,
+                 const float *s_walk /*the balanced launch walked the edges: the combine alone (or NULL)*/, hipStream_t s)
 {
+    if (WITH_GRAD && s_walk) {
+        hipLaunchKernelGGL((bce_edges_kernel<4, true, false>), dim3(unsigned(p.edge_blocks)), dim3(256), 0, s, Zt, mask,
+                           ldz, row_begin, n, d, ip, ix, tp, tx, pw, inv_n2, O, int(p.n_splits), p.DP, S_all_f, dZ, lddz,
+                           lp, Omir, -int64_t(p.bal_tpb), p.sym_pr, counts, scal, Wmir, range_flag, s_walk);
+        GAE_CHECK_LAUNCH("bce_edges_kernel (combine)");
+        return GAE_OK;
+    }
     const auto kernel = p.LPR == 1 ? bce_edges_kernel<1, WITH_GRAD>
                         : p.LPR == 2 ? bce_edges_kernel<2, WITH_GRAD>
                         : p.LPR == 4 ? bce_edges_kernel<4, WITH_GRAD>
@@ -1593,7 +1692,8 @@ int launch_edges(const BcePlan &p, const float *Zt, const float *mask, int64_t l
                                      : bce_edges_kernel<16, WITH_GRAD>;
     hipLaunchKernelGGL(kernel, dim3(unsigned(p.edge_blocks)), dim3(256), 0, s, Zt, mask, ldz, row_begin, n, d, ip, ix, tp,
                        tx, pw, inv_n2, O, int(p.n_splits), p.DP, S_all_f, dZ, lddz, lp, Omir,
-                       (p.bal_tpb ? -int64_t(p.bal_tpb) : p.cols_per_split), p.sym_pr, counts, scal, Wmir, range_flag);
+                       (p.bal_tpb ? -int64_t(p.bal_tpb) : p.cols_per_split), p.sym_pr, counts, scal, Wmir, range_flag,
+                       nullptr);
     GAE_CHECK_LAUNCH("bce_edges_kernel");
     return GAE_OK;
 }
@@ -1677,7 +1777,8 @@ int decoder_bce_impl(const float *Z, float *mask, int64_t ldz, int64_t n, int64_
     w += p.s_bytes;
     double *lp = reinterpret_cast<double *>(w); w += align256((2 * p.n_dense + p.edge_blocks) * 8);
     float *Wmir = reinterpret_cast<float *>(w); w += p.wmir_bytes;
-    float *Omir = reinterpret_cast<float *>(w);
+    float *Omir = reinterpret_cast<float *>(w); w += p.omir_bytes;
+    float *s_walk = reinterpret_cast<float *>(w);
     const double inv_n2 = 1.0 / (double(n) * double(n));
     if (n_local == 0) {
         GAE_HIP(hipMemsetAsync(loss_out, 0, sizeof(float), s));
@@ -1691,16 +1792,23 @@ int decoder_bce_impl(const float *Z, float *mask, int64_t ldz, int64_t n, int64_
         GAE_CHECK_LAUNCH("bce_prepare_kernel");
     }
     int rc;
+    double *lpe = lp + 2 * p.n_dense;
+    // balanced symmetric launch with the gradient: it walks the edges as well (blocks after its column-sum block), the
+    // edge kernel behind it only combines
+    const bool walk_in_dense = p.sym && p.bal_tpb && p.LPR == 4 && dZ != nullptr;    // (d <= 16: 64 rows per walk block)
     g_bce_last_kind = p.sym ? (p.sym_pr == 256 ? 3 : 2) : 1;
     if (p.sym) {
         // 2-D grid: + 1 block column for the column sums; balanced schedule: 1-D, + 1 block for them
-        const dim3 grid = p.bal_tpb ? dim3(unsigned(p.bal_blocks) + 1) : dim3(unsigned(p.row_blocks) + 1, unsigned(p.n_splits));
+        SymWalkArgs wk{indptr, indices, t_indptr, t_indices, pos_weight, scal, s_walk, lpe,
+                       walk_in_dense ? unsigned(p.edge_blocks) : 0u};
+        const dim3 grid = p.bal_tpb ? dim3(unsigned(p.bal_blocks) + 1 + wk.n_walk)
+                                    : dim3(unsigned(p.row_blocks) + 1, unsigned(p.n_splits));
         static std::atomic<unsigned> call_counter{0};
         const unsigned ticket = (call_counter.fetch_add(1) * 2654435761u) | 0x80000001u;    // never 0 (= cleared)
         auto launch_sym = [&](auto kernel, dim3 g, int flag_mode) {
             hipLaunchKernelGGL(kernel, g, dim3(256), 0, s, Zt, Zhi, Zlo, n, p.cols_per_split, O, Wmir, lp, cs, p.prep_blocks, S,
                                S_all_f, unsigned(p.row_blocks), n >= 32768 ? 1 : 0, range_flag, flag_mode, ticket,
-                               (p.bal_tpb ? unsigned(p.bal_blocks) + 1u : unsigned(p.n_splits)), p.bal_tpb);
+                               (p.bal_tpb ? unsigned(p.bal_blocks) + 1u : unsigned(p.n_splits)), p.bal_tpb, wk);
         };
         // fp16 pieces (knob bce_s_bf16 = 3, the default): the F16 launch reports out-of-range embeddings through
         // range_flag, the three-piece bf16 launch behind it runs only then (see the kernel)
@@ -1722,14 +1830,13 @@ int decoder_bce_impl(const float *Z, float *mask, int64_t ldz, int64_t n, int64_
                 : launch_dense<false>(p, Zt, Zhi, Zlo, n, row_begin, n_local, O, lp, cs, S, S_all_f, s);
     }
     if (rc) return rc;
-    double *lpe = lp + 2 * p.n_dense;
     rc = dZ ? launch_edges<true>(p, Zt, mask, ldz, row_begin, n_local, int(d), indptr, indices, t_indptr, t_indices,
                                     pos_weight, float(inv_n2), O, S_all_f, dZ, lddz, lpe, p.sym ? Omir : nullptr,
                                     counts, scal, (p.sym && p.LPR == 4) ? Wmir : nullptr,
-                                    p.sym ? range_flag : nullptr, s)
+                                    p.sym ? range_flag : nullptr, walk_in_dense ? s_walk : nullptr, s)
             : launch_edges<false>(p, Zt, mask, ldz, row_begin, n_local, int(d), indptr, indices, t_indptr,
                                      t_indices, pos_weight, float(inv_n2), O, S_all_f, dZ, lddz, lpe, nullptr, counts,
-                                     scal, nullptr, p.sym ? range_flag : nullptr, s);
+                                     scal, nullptr, p.sym ? range_flag : nullptr, nullptr, s);
     if (rc) return rc;
     gae_bce_tail tail;
     memset(&tail, 0, sizeof(tail));
