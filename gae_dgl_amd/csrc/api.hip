@@ -53,6 +53,7 @@ const KnobEntry kKnobs[] = {
     {"bce_sym_bal", &gae::g_bce_sym_bal, 0, 2, 0, true},
     {"bce_last_kind", &gae::g_bce_last_kind, 0, 3, 0, false},
     {"topk_splits", &gae::g_topk_splits, 0, 16, 0, true},
+    {"rank_splits", &gae::g_rank_splits, 0, 16, 0, true},
 };
 
 const KnobEntry *find_knob(const char *name)

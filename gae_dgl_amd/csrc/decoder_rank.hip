@@ -1,0 +1,434 @@
+// K18: filtered link ranking without the N x N matrix (GAE.rank_links, ops.decoder_rank).
+//
+// For query q = (i, j) = (src[q], dst[q]) and t = s_ij = z_i . z_j: how many candidates c of row i, the target left out,
+// score above t and how many score exactly t -- the rank of j among all candidates of i (MRR, Hits@K, mean rank, the
+// exact all-negatives AUC; metrics.rank_metrics).  The candidate rule is K16's (include/gae_hip.h): a column window,
+// c != i, c not in CSR row i, s_ic neither NaN nor -inf.
+//
+// Products.  K16's, operand for operand: one wave per 32-query panel and column split; panel row r holds z_{src[q0 + r]}
+// (gathered) as the B operand of v_mfma_f32_32x32x2_f32, 32-column tiles of Z are the A operand, lane half h feeds
+// features [h DH, h DH + DH) of each 2 DH-wide chunk, same d -> DH / chunk dispatch.  The accumulator of lane l holds
+// query q0 + (l & 31) against the 16 columns c0 + (r & 3) + 8 (r >> 2) + 4 (l >> 5).  s_ic is therefore the number
+// gae_decoder_topk computes for that pair: a function of the bits of z_i and z_c only.
+// The threshold t comes out of the same instruction: one extra tile whose A operand is the gathered dst rows; the lane
+// that owns the diagonal element (row r against column r) hands it to the other half of its row.  No score is computed
+// by a second route, so "s_ic == t" is an equality of bits of one and the same chain.
+//
+// Counting.  Each lane keeps three int32 counts of its (query, lane half): scores above t, scores at or above t, valid
+// scores.  A tile that lies inside the lane's window, holds neither i (when self is excluded) nor j, and whose 16
+// scores add up to something above -inf (no NaN, no -inf among them) takes the fast path: two compares and two adds
+// per score plus the sum.  Every other tile takes the masked path (window, self, target, validity per column).
+//
+// Known edges.  The sweep counts them like any column; a second sweep takes them out again.  The CSR rows of the
+// panel's 32 sources are laid end to end, 32 entries per tile: the A operand gathers those columns, the same MFMA
+// gives their scores, and a lane looks only at the slots of its own row.  A repeated entry counts once: the lane
+// that gathers entry e tells whether e is the first occurrence of its column -- from its left neighbour when the
+// row is sorted (checked once per row), by a scan of the entries before it otherwise (quadratic in the degree of an
+// UNSORTED row only).  Tiles of the second sweep are dealt round-robin to the column splits.
+//
+// Output.  The two lane halves of a query add up in the wave.  With one column split the wave writes the result; with
+// S > 1 every (panel, split) wave stores its three partial counts in the workspace and a second launch adds the S
+// parts: integers, so every schedule gives the same bits.
+//
+// Measured (tools/rank_bench.py, profiles/r09_decoder_rank.json; d = 16, m = n, a 5-regular graph excluded): 0.25 ms at
+// n = 19 717 and 19.2 ms at n = 200 000 (66 Tflop/s of fp32 MFMA, 42 % of peak) -- 0.27 x and 0.52 x the time of
+// gae_decoder_topk(k = 10) on the same Z.  What buys that: operand loads without branches (row and feature clamped, two
+// 16-byte loads per tile at d = 16) and the next tile's loads issued before the current tile is counted.  118 VGPRs at
+// d <= 16 (4 waves per SIMD), accumulators in VGPRs (-amdgpu-mfma-vgpr-form, _build.py): the epilogue reads each one.
+#include "common.h"
+
+namespace {
+
+constexpr int kRows = 32;         // queries per wave
+constexpr int kTile = 32;         // columns per tile
+constexpr int kMaxSplits = 16;
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+struct RankArgs {
+    const float *Z;
+    int64_t ldz;
+    int n, d, m, nch, S;
+    const int64_t *src, *dst;
+    const int64_t *node_ptr;      // NULL = scope batch
+    int64_t G;
+    const int32_t *indptr, *indices;
+    int excl_self;
+    float *score_out;
+    int64_t *greater_out, *equal_out, *cand_out;
+    int32_t *part;                // [S][m][3] (S > 1): above, at-or-above, valid
+};
+
+// the member window [w0, w1) of row i (empty when i lies outside every member): K16's rule
+__device__ void member_window(const RankArgs &a, int i, int &w0, int &w1)
+{
+    if (!a.node_ptr) { w0 = 0; w1 = a.n; return; }
+    w0 = 0; w1 = 0;
+    if (a.G <= 0 || a.node_ptr[0] > i) return;
+    int64_t l = 0, h = a.G;                       // last member g < G with node_ptr[g] <= i
+    while (h - l > 1) { const int64_t m = (l + h) >> 1; if (a.node_ptr[m] <= i) l = m; else h = m; }
+    int64_t p0 = a.node_ptr[l], p1 = a.node_ptr[l + 1];
+    p0 = p0 < 0 ? 0 : p0;                         // clipped to [0, n): a bad node_ptr never reads outside Z
+    p1 = p1 > a.n ? a.n : p1;
+    if (i >= p0 && i < p1) { w0 = int(p0); w1 = int(p1); }
+}
+
+__device__ __forceinline__ void write_result(const RankArgs &a, int64_t q, bool ok, float t, int gt, int ge, int valid)
+{
+    int64_t g = -1, e = -1, c = -1;
+    if (ok) {
+        const bool tnan = t != t;                 // a NaN target ranks last
+        g = tnan ? valid : gt;
+        e = tnan ? 0 : ge - gt;
+        c = valid;
+    }
+    a.score_out[q] = ok ? t : __builtin_nanf("");
+    a.greater_out[q] = g;
+    a.equal_out[q] = e;
+    a.cand_out[q] = c;
+}
+
+template <int DH, bool ONE>
+__global__ __launch_bounds__(64) void rank_kernel(const RankArgs a)
+{
+    __shared__ int64_t s_pref[kRows + 1];          // CSR rows of the panel laid end to end: first slot of row r
+    __shared__ int s_e0[kRows];
+    __shared__ int s_sorted[kRows];
+    __shared__ int s_col[kTile];                   // second sweep: the column each slot gathered, -1 = not counted
+    const int lane = threadIdx.x, col = lane & 31, h = lane >> 5;
+    const int panel = blockIdx.x / a.S, split = blockIdx.x % a.S;
+    const int64_t q = int64_t(panel) * kRows + col;
+    const bool q_in = q < a.m;
+    const int64_t si = q_in ? a.src[q] : -1, sj = q_in ? a.dst[q] : -1;
+    const bool ok = si >= 0 && si < a.n && sj >= 0 && sj < a.n;      // an index outside [0, n) loads nothing
+    const int i = ok ? int(si) : 0, j = ok ? int(sj) : 0;
+
+    // ---- the query's row: member window, CSR row
+    int w0 = 0, w1 = 0;
+    if (ok) member_window(a, i, w0, w1);
+    int e0 = 0, e1 = 0;
+    if (ok && a.indptr) { e0 = a.indptr[i]; e1 = a.indptr[i + 1]; }
+    // ---- the wave's column range: the union of its rows' windows, cut into S tile-aligned parts
+    int cb = w0 < w1 ? w0 : INT32_MAX, ce = w0 < w1 ? w1 : INT32_MIN;
+    for (int off = 32; off > 0; off >>= 1) {
+        const int ob = __shfl_xor(cb, off, 64), oe = __shfl_xor(ce, off, 64);
+        cb = ob < cb ? ob : cb;
+        ce = oe > ce ? oe : ce;
+    }
+    int pb = 0, pe = 0;
+    if (cb < ce) {
+        const int64_t span = int64_t(ce) - cb;
+        const int64_t L = ((span + a.S - 1) / a.S + kTile - 1) / kTile * kTile;
+        const int64_t b = cb + L * split, e = b + L;
+        pb = int(b < ce ? b : ce);
+        pe = int(e < ce ? e : ce);
+    }
+    pb = __builtin_amdgcn_readfirstlane(pb);       // the same in every lane: scalar loop control
+    pe = __builtin_amdgcn_readfirstlane(pe);
+    // this lane's columns: its row's window inside this part
+    const int lo = w0 > pb ? w0 : pb, hi = w1 < pe ? w1 : pe;
+
+    // ---- operand loads: DH features f = ch 2 DH + h DH + s of one row of Z per lane.  The caller clamps the row into
+    // [0, n) (the host launches nothing when n = 0) and the feature index is clamped here, so no load carries a branch.
+    // A feature past d is zeroed: it would enter every product.  A clamped ROW is not: row c of the A operand reaches
+    // only the scores of column c, row r of the B operand only those of query r, and neither is counted.
+    const bool full = a.d == a.nch * 2 * DH;       // no feature tail: the common d = 16, 32, 64, 128, 256
+    auto load_feats = [&](float (&z)[DH], int64_t row, int ch) {
+        const float *p = a.Z + row * a.ldz;
+        const int f0 = ch * 2 * DH + h * DH;
+        if (full) {
+#pragma unroll
+            for (int s = 0; s < DH; ++s) z[s] = p[f0 + s];
+        } else {
+#pragma unroll
+            for (int s = 0; s < DH; ++s) {
+                const int f = f0 + s;
+                const float v = p[f < a.d ? f : a.d - 1];
+                z[s] = f < a.d ? v : 0.f;
+            }
+        }
+    };
+    auto mma = [&](v16f acc, const float (&za)[DH], const float (&zb)[DH]) {
+#pragma unroll
+        for (int s = 0; s < DH; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(za[s], zb[s], acc, 0, 0, 0);
+        return acc;
+    };
+    // the panel rows (B operand) stay in registers when one chunk holds all of d
+    float zr[DH];
+    if constexpr (ONE) load_feats(zr, i, 0);
+    // one tile: rows of Z picked by `row` (in [0, n)) against the panel
+    auto tile = [&](int64_t row) {
+        v16f acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int ch = 0; ch < (ONE ? 1 : a.nch); ++ch) {
+            if constexpr (!ONE) load_feats(zr, i, ch);
+            float za[DH];
+            load_feats(za, row, ch);
+            acc = mma(acc, za, zr);
+        }
+        return acc;
+    };
+
+    // ---- the threshold: the diagonal of (gathered dst rows) x (panel); column `col` of this tile sits in lane half
+    // (col >> 2) & 1, register (col & 3) + 4 (col >> 3)
+    float t;
+    {
+        const v16f acc = tile(j);
+        const int dr = (col & 3) + 4 * (col >> 3);
+        float dv = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dv = r == dr ? acc[r] : dv;
+        const int owner = col + 32 * ((col >> 2) & 1);
+        t = __shfl(dv, owner, 64);
+    }
+
+    int gt = 0, ge = 0, valid = 0;
+    const int xs = a.excl_self ? i : -1;           // the column left out as "self" (-1: none)
+    // counts of one tile at c0; everything relative to c0, so no column index leaves int32 (n may reach 2^31 - 1)
+    auto count = [&](const v16f &acc, int c0) {
+        const int lo_r = lo > c0 ? lo - c0 : 0, hi_r = hi - c0 < kTile ? hi - c0 : kTile;
+        if (lo_r >= hi_r) return;                  // nothing of this lane's window in the tile
+        const int j_r = j >= c0 ? j - c0 : -1, x_r = xs >= c0 ? xs - c0 : -1;     // >= 32: not in the tile
+        float sum = acc[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) sum += acc[r];
+        const bool clean = lo_r == 0 && hi_r == kTile && unsigned(j_r) >= unsigned(kTile) &&
+                           unsigned(x_r) >= unsigned(kTile);
+        if (clean && sum > -INFINITY) {
+            // ---- fast path: 16 valid scores of candidates (a NaN or a -inf among them makes the sum NaN or -inf)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                gt += acc[r] > t ? 1 : 0;
+                ge += acc[r] >= t ? 1 : 0;
+            }
+            valid += 16;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int c = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const bool cand = c >= lo_r && c < hi_r && c != j_r && c != x_r && acc[r] > -INFINITY;
+                gt += (cand && acc[r] > t) ? 1 : 0;
+                ge += (cand && acc[r] >= t) ? 1 : 0;
+                valid += cand ? 1 : 0;
+            }
+        }
+    };
+    if constexpr (ONE) {
+        // the next tile's A operand is in flight while this tile is multiplied and counted
+        float za[DH];
+        const int64_t last = int64_t(pe) - 1;      // a column past the part is clamped into it
+        if (pb < pe) load_feats(za, int64_t(pb) + col < last ? int64_t(pb) + col : last, 0);
+        for (int64_t c0 = pb; c0 < pe; c0 += kTile) {
+            v16f acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            acc = mma(acc, za, zr);
+            const int64_t jn = c0 + kTile + col;
+            if (c0 + kTile < pe) load_feats(za, jn < last ? jn : last, 0);
+            count(acc, int(c0));
+        }
+    } else {
+        for (int64_t c0 = pb; c0 < pe; c0 += kTile) {
+            const int64_t jc = c0 + col;           // this lane's A-operand column
+            const v16f acc = tile(jc < pe ? jc : int64_t(pe) - 1);
+            count(acc, int(c0));
+        }
+    }
+
+    // ---- known edges: take the distinct neighbours the sweep counted out again
+    if (a.indptr) {
+        const int deg = e1 > e0 ? e1 - e0 : 0;
+        int64_t incl = deg;                        // inclusive prefix over the 32 rows (both halves compute the same)
+        for (int off = 1; off < 32; off <<= 1) {
+            const int64_t o = __shfl_up(incl, off, 32);
+            if (col >= off) incl += o;
+        }
+        const int64_t pref = incl - deg;
+        const int64_t total = __shfl(incl, 31, 64);
+        // is the row sorted (non-decreasing)?  each half checks half of it
+        int sorted = 1;
+        {
+            const int xb = e0 + 1, xe = e1 > e0 ? e1 : e0 + 1;  // pairs (x - 1, x), x in [xb, xe)
+            const int xm = xb + (xe - xb) / 2;
+            for (int x = h == 0 ? xb : xm; x < (h == 0 ? xm : xe); ++x)
+                sorted &= a.indices[x - 1] <= a.indices[x] ? 1 : 0;
+            sorted &= __shfl_xor(sorted, 32, 64);
+        }
+        if (h == 0) {
+            s_pref[col] = pref;
+            s_e0[col] = e0;
+            s_sorted[col] = sorted;
+            if (col == 31) s_pref[32] = total;
+        }
+        __syncthreads();
+        const int64_t ntiles = (total + kTile - 1) / kTile;
+        for (int64_t tix = split; tix < ntiles; tix += a.S) {
+            // slot p of the concatenation: owner row, entry, column; is it the first occurrence in its row?
+            const int64_t p = tix * kTile + col;
+            int c = -1;
+            if (p < total) {
+                int l = 0, u = kRows;              // last row o with s_pref[o] <= p (it has an entry: s_pref[o + 1] > p)
+                while (u - l > 1) { const int mid = (l + u) >> 1; if (s_pref[mid] <= p) l = mid; else u = mid; }
+                const int b = s_e0[l];
+                const int e = b + int(p - s_pref[l]);
+                const int v = a.indices[e];
+                bool first;
+                if (s_sorted[l]) {
+                    first = e == b || a.indices[e - 1] != v;
+                } else {
+                    first = true;
+                    for (int x = b; x < e && first; x += 4) {      // four independent loads per round trip
+                        const int32_t v0 = a.indices[x];
+                        const int32_t v1 = a.indices[x + 1 < e ? x + 1 : e - 1];
+                        const int32_t v2 = a.indices[x + 2 < e ? x + 2 : e - 1];
+                        const int32_t v3 = a.indices[x + 3 < e ? x + 3 : e - 1];
+                        first = !(v0 == v || v1 == v || v2 == v || v3 == v);
+                    }
+                }
+                if (first && v >= 0 && v < a.n) c = v;             // a bad CSR entry never reads outside Z
+            }
+            __syncthreads();                       // the previous tile's readers are done with s_col
+            if (h == 0) s_col[col] = c;
+            __syncthreads();
+            const v16f acc = tile(c >= 0 ? c : 0);
+            const int64_t base = tix * kTile;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int s = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int64_t ps = base + s;
+                const int cs = s_col[s];
+                // mine, and counted by the sweep: inside the row's whole window, neither the target nor self, valid
+                const bool cand = ps >= pref && ps < pref + deg && cs >= w0 && cs < w1 && cs != j && cs != xs &&
+                                  acc[r] > -INFINITY;
+                gt -= (cand && acc[r] > t) ? 1 : 0;
+                ge -= (cand && acc[r] >= t) ? 1 : 0;
+                valid -= cand ? 1 : 0;
+            }
+        }
+    }
+
+    // ---- the two lane halves of each query; lane half 0 writes
+    gt += __shfl_down(gt, 32, 64);
+    ge += __shfl_down(ge, 32, 64);
+    valid += __shfl_down(valid, 32, 64);
+    if (h == 0 && q_in) {
+        if (a.S == 1) {
+            write_result(a, q, ok, t, gt, ge, valid);
+        } else {
+            int32_t *p = a.part + (int64_t(split) * a.m + q) * 3;
+            p[0] = gt; p[1] = ge; p[2] = valid;
+            if (split == 0) a.score_out[q] = t;
+        }
+    }
+}
+
+// one thread per query: the S partial counts added up (a part may be negative: the second sweep of one split takes
+// out what the first sweep of another counted).  S = 0 (n = 0: no row of Z exists) only marks every query invalid.
+__global__ __launch_bounds__(256) void rank_combine_kernel(const RankArgs a)
+{
+    const int64_t q = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (q >= a.m) return;
+    const int64_t si = a.src[q], sj = a.dst[q];
+    const bool ok = si >= 0 && si < a.n && sj >= 0 && sj < a.n;
+    int gt = 0, ge = 0, valid = 0;
+    for (int s = 0; s < a.S; ++s) {
+        const int32_t *p = a.part + (int64_t(s) * a.m + q) * 3;
+        gt += p[0]; ge += p[1]; valid += p[2];
+    }
+    write_result(a, q, ok, ok ? a.score_out[q] : 0.f, gt, ge, valid);
+}
+
+int splits_for(int64_t n, int64_t m, const int64_t *node_ptr, int64_t max_graph_nodes)
+{
+    if (n <= 0 || m <= 0) return 1;
+    const int64_t panels = (m + kRows - 1) / kRows;
+    int64_t S = gae::g_rank_splits;
+    if (S <= 0) {
+        const int64_t span = node_ptr ? (max_graph_nodes < n ? max_graph_nodes : n) : n;
+        S = (4096 + panels - 1) / panels;                  // ~4096 waves: several per SIMD
+        const int64_t by_span = (span + 255) / 256;        // parts of >= 256 columns
+        S = S < by_span ? S : by_span;
+    }
+    return int(S < 1 ? 1 : (S > kMaxSplits ? kMaxSplits : S));
+}
+
+int64_t need_bytes(int64_t m, int S) { return S > 1 ? int64_t(S) * m * 12 + 256 : 256; }
+
+} // namespace
+
+namespace gae {
+Knob g_rank_splits{0};       // "rank_splits": column splits per query panel, 0 = auto (tests force 1 or more)
+} // namespace gae
+
+extern "C" int gae_decoder_rank(const float *Z, int64_t ldz, int64_t n, int64_t d, const int64_t *src,
+                                const int64_t *dst, int64_t m, const int64_t *node_ptr, int64_t n_graphs,
+                                int64_t max_graph_nodes, const int32_t *indptr, const int32_t *indices, int flags,
+                                float *score_out, int64_t *greater_out, int64_t *equal_out, int64_t *candidates_out,
+                                void *workspace, int64_t *workspace_bytes, void *stream)
+{
+    GAE_REQUIRE(d >= 1 && d <= 256, GAE_E_RANGE, "gae_decoder_rank: d = %lld outside 1..256", (long long)d);
+    GAE_REQUIRE(n >= 0 && m >= 0, GAE_E_SIZE, "gae_decoder_rank: negative n = %lld or m = %lld", (long long)n,
+                (long long)m);
+    GAE_REQUIRE(n < (int64_t(1) << 31), GAE_E_SIZE, "gae_decoder_rank: n = %lld beyond the int32 CSR", (long long)n);
+    GAE_REQUIRE(m < (int64_t(1) << 31), GAE_E_SIZE, "gae_decoder_rank: m = %lld queries, 2^31 - 1 at most",
+                (long long)m);
+    GAE_REQUIRE(ldz >= d, GAE_E_SIZE, "gae_decoder_rank: leading dimension too small (ldz %lld < d)", (long long)ldz);
+    GAE_REQUIRE((flags & ~(GAE_TOPK_EXCLUDE_SELF | GAE_TOPK_EXCLUDE_EDGES)) == 0, GAE_E_RANGE,
+                "gae_decoder_rank: unknown flags 0x%x", flags);
+    GAE_REQUIRE(!node_ptr || (n_graphs >= 0 && max_graph_nodes >= 0), GAE_E_SIZE,
+                "gae_decoder_rank: negative n_graphs / max_graph_nodes");
+    GAE_REQUIRE(workspace_bytes, GAE_E_NULL, "gae_decoder_rank: workspace_bytes is NULL");
+    const int S = splits_for(n, m, node_ptr, max_graph_nodes);
+    const int64_t need = need_bytes(m, S);
+    if (!workspace) {                               // size query: no device work
+        *workspace_bytes = need;
+        return GAE_OK;
+    }
+    GAE_REQUIRE(n == 0 || Z, GAE_E_NULL, "gae_decoder_rank: Z is NULL");
+    GAE_REQUIRE(m == 0 || (src && dst), GAE_E_NULL, "gae_decoder_rank: src / dst is NULL");
+    GAE_REQUIRE(m == 0 || (score_out && greater_out && equal_out && candidates_out), GAE_E_NULL,
+                "gae_decoder_rank: score_out / greater_out / equal_out / candidates_out is NULL");
+    GAE_REQUIRE(!(flags & GAE_TOPK_EXCLUDE_EDGES) || (indptr && indices), GAE_E_NULL,
+                "gae_decoder_rank: GAE_TOPK_EXCLUDE_EDGES without a CSR");
+    GAE_REQUIRE(*workspace_bytes >= need, GAE_E_WORKSPACE, "gae_decoder_rank: workspace of %lld bytes, %lld needed",
+                (long long)*workspace_bytes, (long long)need);
+    if (m == 0) return GAE_OK;
+    RankArgs a;
+    a.Z = Z; a.ldz = ldz; a.n = int(n); a.d = int(d); a.m = int(m); a.S = S;
+    a.src = src; a.dst = dst;
+    a.node_ptr = node_ptr; a.G = n_graphs;
+    const bool edges = (flags & GAE_TOPK_EXCLUDE_EDGES) != 0;
+    a.indptr = edges ? indptr : nullptr; a.indices = edges ? indices : nullptr;
+    a.excl_self = (flags & GAE_TOPK_EXCLUDE_SELF) ? 1 : 0;
+    a.score_out = score_out; a.greater_out = greater_out; a.equal_out = equal_out; a.cand_out = candidates_out;
+    a.part = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + 256);
+    const int64_t panels = (m + kRows - 1) / kRows;
+    const dim3 grid(unsigned(panels * S));
+    hipStream_t st = gae::as_stream(stream);
+    if (n == 0) {
+        a.S = 0;
+        hipLaunchKernelGGL(rank_combine_kernel, dim3(unsigned((m + 255) / 256)), dim3(256), 0, st, a);
+        GAE_CHECK_LAUNCH("rank_combine_kernel");
+        return GAE_OK;
+    }
+    if (d <= 16) {
+        a.nch = 1;
+        hipLaunchKernelGGL((rank_kernel<8, true>), grid, dim3(64), 0, st, a);
+    } else if (d <= 32) {
+        a.nch = 1;
+        hipLaunchKernelGGL((rank_kernel<16, true>), grid, dim3(64), 0, st, a);
+    } else if (d <= 64) {
+        a.nch = 1;
+        hipLaunchKernelGGL((rank_kernel<32, true>), grid, dim3(64), 0, st, a);
+    } else {
+        a.nch = int((d + 63) / 64);
+        hipLaunchKernelGGL((rank_kernel<32, false>), grid, dim3(64), 0, st, a);
+    }
+    GAE_CHECK_LAUNCH("rank_kernel");
+    if (S > 1) {
+        hipLaunchKernelGGL(rank_combine_kernel, dim3(unsigned((m + 255) / 256)), dim3(256), 0, st, a);
+        GAE_CHECK_LAUNCH("rank_combine_kernel");
+    }
+    return GAE_OK;
+}

@@ -197,6 +197,19 @@ class GAE(nn.Module):
             z = self.encode(g)
         return ops.decoder_topk(z, k, g, scope=scope, exclude_self=exclude_self, exclude_edges=exclude_edges)
 
+    def rank_links(self, g, pairs, *, filter_graph=None, scope="batch", exclude_self=True, exclude_edges=True):
+        """RankResult(score, greater, equal, candidates), one entry per query pair (i, j) of ``pairs`` [2, m]: the logit
+        z_i . z_j and how many candidates c of i (the candidate rule of predict_links, j itself left out) score above /
+        exactly at it -- the filtered rank of j among ALL candidates of i, from one fused HIP launch
+        (ops.decoder_rank) that never forms an m x N matrix.  ``filter_graph`` (default ``g``) supplies the edges that
+        are left out: pass the full graph to filter the held-out edges too; the target itself is always ranked.
+        ``metrics.rank_metrics`` gives MRR, Hits@K, mean rank and the all-negatives AUC.  Runs encode(g) under
+        no_grad; g.ndata is left as encode() leaves it."""
+        with torch.no_grad():
+            z = self.encode(g)
+        return ops.decoder_rank(z, pairs, g, filter_graph=filter_graph, scope=scope, exclude_self=exclude_self,
+                                exclude_edges=exclude_edges)
+
     def reconstruction_loss(self, g, criterion="bce", scope="batch", samples=None):
         """The training loss of train_inductive.py:44-48 (dense label from g,
         pos_weight, BCE-with-logits mean over all N^2 ordered pairs) evaluated

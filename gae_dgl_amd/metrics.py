@@ -98,3 +98,31 @@ def recall_at_k(index, pos_pairs):
     i, j = rows[ok], index[ok].long()
     found = torch.unique(torch.minimum(i, j) * n + torch.maximum(i, j))
     return float(torch.isin(keys, found).double().mean())
+
+
+def rank_metrics(greater, equal, candidates, ks=(1, 10, 50, 100)):
+    """The filtered ranking protocol from the counts of ``GAE.rank_links`` / ``ops.decoder_rank`` (one entry per query):
+    ``rank = 1 + greater + equal / 2`` (ties share the mean rank).  Returns a dict with ``mrr`` = mean(1 / rank),
+    ``mean_rank``, ``hits@K`` = mean(rank <= K) for every K of ``ks``, ``auc`` = mean(1 - (greater + equal / 2) /
+    candidates) over the queries that have a candidate (the exact per-source AUC against ALL filtered non-edges) and
+    ``queries``.  A count of -1 (a query whose index was out of range) raises ValueError; no query gives NaN."""
+    greater, equal, candidates = (torch.as_tensor(x).reshape(-1) for x in (greater, equal, candidates))
+    if not (greater.numel() == equal.numel() == candidates.numel()):
+        raise ValueError("rank_metrics: greater, equal and candidates must have one length")
+    if any(bool((x < 0).any()) for x in (greater, equal, candidates)):
+        raise ValueError("rank_metrics: a negative count (a query with an index outside [0, n))")
+    m = greater.numel()
+    out = {"queries": m}
+    nan = float("nan")
+    if m == 0:
+        out.update(mrr=nan, mean_rank=nan, auc=nan, **{f"hits@{int(k)}": nan for k in ks})
+        return out
+    above = greater.double() + equal.double() / 2
+    rank = 1 + above
+    out["mrr"] = float((1 / rank).mean())
+    out["mean_rank"] = float(rank.mean())
+    for k in ks:
+        out[f"hits@{int(k)}"] = float((rank <= k).double().mean())
+    has = candidates > 0
+    out["auc"] = float((1 - above[has] / candidates[has].double()).mean()) if bool(has.any()) else nan
+    return out

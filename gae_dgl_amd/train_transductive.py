@@ -4,7 +4,7 @@ file's INTENT -- ``GAE(in_feats, [32, 16])``, Adam lr 1e-2, 500 full-graph
 epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
 59-60) -- on the HIP kernels.
 
-  python -m gae_dgl_amd.train_transductive --dataset cora [--norm both] [--eval] [--topk 10 [--topk_out top.npz]]
+  python -m gae_dgl_amd.train_transductive --dataset cora [--norm both] [--eval [--rank]] [--topk 10 [--topk_out top.npz]]
       [--loss_samples M]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
@@ -52,6 +52,10 @@ def build_parser():
                          "known edges left out); with --eval prints the test recall@K, with --topk_out saves them")
     ap.add_argument("--topk_out", default=None, metavar="PATH",
                     help="write the --topk lists to PATH (.npz with 'index' int64 [n, K] and 'score' fp32 [n, K])")
+    ap.add_argument("--rank", action="store_true",
+                    help="with --eval: rank both directions of every held-out test pair among ALL candidates of its "
+                         "source (GAE.rank_links, every edge of the input graph filtered) and print the test MRR, "
+                         "Hits@10 / @100, mean rank and the all-non-edges AUC")
     ap.add_argument("--loss_samples", type=int, default=None, metavar="M",
                     help="train on the unbiased sampled loss (GAE.reconstruction_loss(g, samples=M)): the edge term "
                          "exactly, the all-pairs term from M random partners per node, O((E + N M) d) per step")
@@ -69,6 +73,8 @@ def parse_args(argv=None):
             ap.error("--topk needs --eval (recall@K on the held-out edges) or --topk_out PATH")
     elif args.topk_out is not None:
         ap.error("--topk_out needs --topk K")
+    if args.rank and not args.eval:
+        ap.error("--rank needs --eval (it ranks the held-out test edges)")
     if args.loss_samples is not None and args.loss_samples < 1:
         ap.error(f"--loss_samples {args.loss_samples}: M must be at least 1")
     return args
@@ -139,6 +145,21 @@ def main(argv=None):
             scores = metrics.evaluate(Z, pairs)
             print(f"{name} ROC-AUC: {scores['auc']:.4f} | AP: {scores['ap']:.4f}")
         main.last_eval = metrics.evaluate(Z, held_out["test"])
+    if args.rank:
+        # filtered protocol: train, validation and test edges are all left out of the candidates; the target of a query
+        # is exempt from the filter (gae_decoder_rank), so every held-out test edge still gets its rank
+        import numpy as np
+        pos = held_out["test"]["pos"]
+        queries = np.concatenate([pos, pos[::-1]], axis=1)
+        every = [np.concatenate([np.asarray(kept[k], dtype=np.int64), held_out["val"]["pos"][k],
+                                 held_out["val"]["pos"][1 - k], pos[k], pos[1 - k]]) for k in (0, 1)]
+        full = DGLGraph((every[0], every[1]), num_nodes=n_nodes).to(device)
+        g.ndata['h'] = features
+        res = model.rank_links(g, queries, filter_graph=full)
+        rm = metrics.rank_metrics(res.greater, res.equal, res.candidates, ks=(1, 10, 50, 100))
+        print(f"test MRR: {rm['mrr']:.4f} | Hits@10: {rm['hits@10']:.4f} | Hits@100: {rm['hits@100']:.4f} | "
+              f"mean rank: {rm['mean_rank']:.1f} | AUC (all non-edges): {rm['auc']:.4f}")
+        main.last_rank = rm
     if args.topk is not None:
         # the training graph's edges are left out, so the held-out test positives are candidates
         g.ndata['h'] = features

@@ -113,6 +113,14 @@ class VGAE(nn.Module):
             mu, _ = self.encode(g)
         return ops.decoder_topk(mu, k, g, scope=scope, exclude_self=exclude_self, exclude_edges=exclude_edges)
 
+    def rank_links(self, g, pairs, *, filter_graph=None, scope="batch", exclude_self=True, exclude_edges=True):
+        """GAE.rank_links on the mean embedding mu (no noise): the filtered rank counts of the pairs (i, j) among all
+        candidates of i (ops.decoder_rank)"""
+        with torch.no_grad():
+            mu, _ = self.encode(g)
+        return ops.decoder_rank(mu, pairs, g, filter_graph=filter_graph, scope=scope, exclude_self=exclude_self,
+                                exclude_edges=exclude_edges)
+
     def forward(self, g):
         """sampled Z Z^T logits (dense parity / inference path)"""
         mu, logstd = self.encode(g)

@@ -8,7 +8,8 @@
  *                               plan construction and the specialised aggregation kernels gae_spmm_csr dispatches to
  *   gae_spx_*, gae_dense_to_csr_*   layer 1 from the non-zeros of constant input features (gae_dgl_amd.SparseFeatures)
  *   gae_linear2_*, gae_gcn2_*   the dense halves of a two-layer encoder on millions of rows (row-sharded RMAT path)
- * and gae_decoder_bce_sampled, an unbiased stochastic estimate of gae_decoder_bce's loss for graphs beyond the N^2 sum.
+ * and gae_decoder_bce_sampled, an unbiased stochastic estimate of gae_decoder_bce's loss for graphs beyond the N^2 sum,
+ * and gae_decoder_rank, the filtered rank of given pairs among all candidates of gae_decoder_topk's rule.
  * Same conventions as gae_hip.h: caller-owned buffers, 0 / negative / hipError_t return codes, asynchronous launches on
  * the stream passed last.  These signatures may change between versions without a GAE_VERSION major bump. */
 #ifndef GAE_HIP_EXPERIMENTAL_H
@@ -319,6 +320,49 @@ int gae_decoder_bce_sampled(const float *Z, float *mask, int64_t ldz, int64_t n,
                             uint64_t seed, uint64_t offset, uint64_t *draw_dev, float *loss_out, float *dZ,
                             int64_t lddz, int32_t *partners_out, void *workspace, int64_t *workspace_bytes,
                             void *stream);
+
+/* (from gae_hip.h: K16, top-k link prediction) */
+/* ---- K18: filtered link ranking without the N x N matrix (GAE.rank_links, ops.decoder_rank, metrics.rank_metrics)
+ * For query q with i = src[q], j = dst[q] and the threshold t = s_ij = z_i . z_j: where j stands among ALL candidates
+ * of row i -- the filtered ranking protocol (MRR, Hits@K for any K, mean rank, the exact all-negatives AUC) that
+ * train_transductive.py:35's "# TODO: train test split" needs to say how good a link predictor is.
+ * s_ic is the SAME fp32 number gae_decoder_topk computes for that pair and that d: the fp32 MFMA chain in K16's fixed
+ * feature order, a function of the bits of z_i and z_c only.  t is produced by the same instruction, never by a second
+ * route, so the counts below are defined by equality of bits.
+ * Candidates C(i): exactly K16's -- c in i's column window (all n, or i's member [node_ptr[g], node_ptr[g + 1])),
+ *   c != i                                 when flags & GAE_TOPK_EXCLUDE_SELF,
+ *   c not in CSR row i (indices in any order, repeats counted once)   when flags & GAE_TOPK_EXCLUDE_EDGES,
+ *   s_ic neither NaN nor -inf.             Same flags values as gae_decoder_topk.
+ * Output, one entry per query:
+ *   score_out[q]      = t                                          (fp32)
+ *   greater_out[q]    = |{c in C(i) \ {j} : s_ic >  t}|            (int64)
+ *   equal_out[q]      = |{c in C(i) \ {j} : s_ic == t}|
+ *   candidates_out[q] = |C(i) \ {j}|
+ * The target is never counted against itself and NEED NOT be a candidate: it may sit in CSR row i, be i itself or lie
+ * outside i's window.  A caller can therefore filter with the full graph, held-out edges included, and still rank each
+ * of them.  rank = 1 + greater + equal / 2 (ties share the mean rank).
+ *   t NaN                      : greater = candidates, equal = 0 (worst rank); t = +-inf needs no special case
+ *   src[q] or dst[q] outside [0, n) : score = NaN, the three counts -1; nothing outside Z is read
+ * Several queries may share a source; any order; m = 0 and n = 0 are valid.  1 <= d <= 256, n < 2^31, m < 2^31.
+ * Results are integers and one fp32 per query: bit-identical run to run and under any column split.
+ *   src / dst    : int64 [m] on the device
+ *   node_ptr, max_graph_nodes, indptr / indices : as gae_decoder_topk
+ *   workspace    : NULL = size query: *workspace_bytes receives the bytes needed and nothing else happens (no device
+ *                  work; works without a GPU).  Otherwise *workspace_bytes is the capacity given.  O(m column splits)
+ *                  bytes, never O(m n) or O(n^2).  No logit is written to memory.
+ * Cost: the m x n products of the sweep plus, under GAE_TOPK_EXCLUDE_EDGES, one product per CSR entry of the queried
+ * rows; the first-occurrence test of a repeated entry is O(1) in a sorted CSR row and O(degree) in an unsorted one.
+ * Tuning knob (gae_tuning_set, bit-identical results): "rank_splits" = 0 {0 .. 16}: column splits per panel of 32
+ * queries, 0 = auto (the twin of "topk_splits").
+ * Argument errors are returned before any launch: d outside 1..256, negative n / m, n or m >= 2^31, ldz < d, unknown
+ * flag bits, NULL Z (n > 0), NULL src / dst / output (m > 0), GAE_TOPK_EXCLUDE_EDGES without a CSR, a short workspace.
+ * One launch (two when the columns are split over several blocks). */
+int gae_decoder_rank(const float *Z, int64_t ldz, int64_t n, int64_t d,
+                     const int64_t *src, const int64_t *dst, int64_t m,
+                     const int64_t *node_ptr, int64_t n_graphs, int64_t max_graph_nodes,
+                     const int32_t *indptr, const int32_t *indices, int flags,
+                     float *score_out, int64_t *greater_out, int64_t *equal_out, int64_t *candidates_out,
+                     void *workspace, int64_t *workspace_bytes, void *stream);
 
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
