@@ -18,6 +18,7 @@ SPMM_SKIP_ROWS = 8
 SPMM_ELL_WIDTH = 16
 ACT_IDENTITY, ACT_RELU = 0, 1
 TOPK_EXCLUDE_SELF, TOPK_EXCLUDE_EDGES = 1, 2
+EMBED_NORM_NONE, EMBED_NORM_BOTH = 0, 1
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _p, _f, _int = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
@@ -169,6 +170,9 @@ SIGNATURES = {
                                 _p]),
     "gae_decoder_bce": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _f, _f, _u64, _u64, _p, _p, _p, _i64, _p,
                                _i64, _p]),
+    "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
+    "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
+                                _p, _i64, _p, _i64, _p]),
 }
 
 _lib = None

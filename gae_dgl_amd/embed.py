@@ -1,0 +1,102 @@
+"""Turn a pre-trained checkpoint into the molecule features of the reference's chemistry table (README.md:54: "GAE
+feature is a concatenation of mean, sum, and max aggregation of the hidden vector", 48 numbers per molecule for
+``--hidden_dims 32 16``):
+
+  python -m gae_dgl_amd.embed --checkpoint result/ep09.pkl --hidden_dims 32 16 -d data/zinc.npz --out features.npy
+  python -m gae_dgl_amd.embed --checkpoint result/ep09.pkl --hidden_dims 32 16 --synthetic 20000 --out features.npy
+
+The checkpoint is the state dict ``train_inductive`` (and the reference's Trainer.save, train_inductive.py:56-57)
+writes.  The whole set is embedded by ``GAE.embed_graphs``: one fused launch where the kernel takes the shapes
+(``--fused auto|on``), the chunked batch -> encode -> readout route otherwise (``--fused off``).  Writes fp32
+[G, 3 d] as .npy and prints the graph count, the route taken and the time of the embedding call."""
+import argparse
+import os
+import time
+
+import numpy as np
+import torch
+
+from gae_dgl_amd import _lib, ops
+from gae_dgl_amd.dataset import DeviceGraphDataset
+from gae_dgl_amd.gae import GAE
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Embed a molecule set with a pre-trained GAE")
+    ap.add_argument("--checkpoint", "-c", type=str, default=None, help="state dict written by train_inductive (ep{NN}.pkl)")
+    ap.add_argument("--hidden_dims", type=int, nargs="+", metavar="N", help="encoder widths, e.g. 32 16")
+    ap.add_argument("--in_dim", "-i", type=int, default=39, help="atom feature width")
+    ap.add_argument("--data_file", "-d", type=str, default=None, help="dataset (flat .npz of DeviceGraphDataset.save)")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="G",
+                    help="generate G ZINC-shaped molecules instead of reading --data_file")
+    ap.add_argument("--out", "-o", type=str, default=None, help="where the [G, 3 d] fp32 features go (.npy)")
+    ap.add_argument("--norm", choices=["none", "both"], default="none",
+                    help="none = the reference's plain in-edge sums; both = D^-1/2 A D^-1/2")
+    ap.add_argument("--fused", choices=["auto", "on", "off"], default="auto",
+                    help="on = the one-launch kernel or an error; off = batch -> encode -> readout in chunks of "
+                         "--batch_size; auto = the kernel for every molecule it takes")
+    ap.add_argument("--batch_size", "-b", type=int, default=4096, help="molecules per chunk of the chunked route")
+    ap.add_argument("--seed", type=int, default=None, help="seed of --synthetic")
+    ap.add_argument("--gpu_id", type=int, default=0, help="which GPU")
+    return ap
+
+
+def parse_args(argv=None):
+    """the arguments, checked: combinations that cannot work fail here, with a message, before any GPU is touched"""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if not args.checkpoint:
+        parser.error("--checkpoint is required: the state dict train_inductive saved (ep{NN}.pkl)")
+    if not args.hidden_dims:
+        parser.error("--hidden_dims is required: the encoder widths the checkpoint was trained with, e.g. 32 16")
+    if not args.out:
+        parser.error("--out is required: the .npy file the features are written to")
+    if bool(args.data_file) == bool(args.synthetic):
+        parser.error("give exactly one of --data_file and --synthetic G")
+    if args.synthetic < 0 or args.batch_size < 1 or args.in_dim < 1 or min(args.hidden_dims) < 1:
+        parser.error("--synthetic, --batch_size, --in_dim and --hidden_dims take positive numbers")
+    if args.fused == "on" and not ops.embed_graphs_usable(args.in_dim, args.hidden_dims, 0):
+        parser.error(f"--fused on: the kernel takes 1..{ops.EMBED_MAX_LAYERS} layers of widths <= {ops.EMBED_MAX_WIDTH}, "
+                     f"not {args.in_dim} -> {args.hidden_dims}; use --fused auto or off")
+    return args
+
+
+def load_dataset(args, device):
+    if args.synthetic:
+        return DeviceGraphDataset.synthetic_zinc(args.synthetic, seed=args.seed or 0, device=device)
+    if not os.path.exists(args.data_file):
+        raise FileNotFoundError(f"{args.data_file} not found (use --synthetic G for ZINC-shaped synthetic data)")
+    return DeviceGraphDataset.load(args.data_file, device=device)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("gae_dgl_amd runs on AMD GPUs only (no CPU fallback)")
+    device = torch.device(f"cuda:{args.gpu_id}")
+    torch.cuda.set_device(device)
+    model = GAE(args.in_dim, args.hidden_dims, norm=None if args.norm == "none" else args.norm)
+    model.load_state_dict(torch.load(args.checkpoint, map_location="cpu"))
+    model = model.to(device).eval()
+    graphs = load_dataset(args, device)
+    print(f"Loaded {len(graphs)} molecules")
+    fused = {"auto": "auto", "on": True, "off": False}[args.fused]
+    before = _lib.CALLS["gae_embed_graphs"]
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    feats = model.embed_graphs(graphs, fused=fused, batch_size=args.batch_size)
+    torch.cuda.synchronize(device)
+    seconds = time.perf_counter() - t0
+    in_kernel = ops.embed_graphs.last_request["n_out"] if _lib.CALLS["gae_embed_graphs"] > before else 0
+    route = "fused kernel" if in_kernel == len(graphs) else \
+        "chunked route" if in_kernel == 0 else f"fused kernel for {in_kernel}, chunked route for {len(graphs) - in_kernel}"
+    out = feats.cpu().numpy().astype(np.float32, copy=False)
+    np.save(args.out, out)
+    print(f"Embedded {out.shape[0]} molecules -> {tuple(out.shape)} fp32 | route: {route} | "
+          f"{seconds * 1e3:.3f} ms | wrote {args.out}")
+    main.features = feats
+    return out
+
+
+if __name__ == '__main__':
+    main()

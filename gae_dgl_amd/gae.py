@@ -210,6 +210,106 @@ class GAE(nn.Module):
         return ops.decoder_rank(z, pairs, g, filter_graph=filter_graph, scope=scope, exclude_self=exclude_self,
                                 exclude_edges=exclude_edges)
 
+    def embed_graphs(self, data, *, fused="auto", batch_size=4096):
+        """fp32 [n_graphs, 3 d]: the molecule feature of the reference's chemistry table (README.md:54: mean | sum |
+        max of the hidden vectors, 48 numbers for ``--hidden_dims 32 16``) of every graph of ``data`` -- a
+        ``DeviceGraphDataset`` or a ``subset()`` view (rows in the order of ``data.ids``), or a batched graph with
+        ``graph_ptr()`` and ``ndata['h']`` (rows in member order).  Runs under no_grad; parameters and ``g.ndata`` are
+        left as they were.  The norm follows the model as in encode(): ``GAE(norm=...)`` if given, else the graph's
+        ``norm_mode`` (the batches of a dataset carry "none").
+        ``fused=True``: one launch for the whole set (ops.embed_graphs: encoder and readout per molecule, nothing of
+        width N written); raises when the model or a graph lies outside the kernel's shapes (1..4 layers, widths <= 64,
+        graphs <= 64 nodes).  ``fused=False``: ``batch`` -> ``encode`` -> ``readout_nodes`` in chunks of ``batch_size``
+        graphs.  ``"auto"``: the kernel for every graph it takes, the chunked route for the rest."""
+        if fused not in ("auto", True, False):
+            raise ValueError(f"fused: 'auto', True or False, not {fused!r}")
+        if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
+            raise ValueError(f"batch_size: a positive number of graphs, not {batch_size!r}")
+        with torch.no_grad():
+            return self._embed_graphs(data, fused, int(batch_size))
+
+    def _embed_graphs(self, data, fused, batch_size):
+        import numpy as np
+        is_set = hasattr(data, "subset") and hasattr(data, "sizes_host")
+        lins = [layer.apply_mod.linear for layer in self.layers]
+        widths = [lin.out_features for lin in lins]
+        d = widths[-1]
+        if is_set:
+            ids = np.asarray(data.ids, dtype=np.int64)
+            sizes = data.sizes_host[ids] if len(ids) else np.zeros(0, np.int64)
+            gp, (indptr, indices), feat, mode0 = data.graph_ptr, (data.indptr, data.indices), data.feat, "none"
+            n_all = len(data.sizes_host)
+            identity_ids = len(ids) == n_all and bool((ids == np.arange(n_all)).all())
+        else:
+            feat = data.ndata['h']
+            if not (isinstance(feat, torch.Tensor) and feat.is_cuda):
+                raise ops.GaeHipError("GAE.embed_graphs: the HIP path needs device tensors")
+            data._follow(feat)
+            counts = data.batch_num_nodes if data.batch_num_nodes is not None else [data.number_of_nodes()]
+            sizes = np.asarray(counts, dtype=np.int64)
+            ids, identity_ids, mode0 = np.arange(len(sizes), dtype=np.int64), True, data.norm_mode
+        dev = feat.device
+        B = len(ids)
+        modes = {mode0 if layer.norm is None else layer.norm for layer in self.layers}
+        codes = [_act_code(layer.apply_mod.activation) for layer in self.layers]
+        why = None
+        if len(modes) != 1 or next(iter(modes)) not in ("none", "both"):
+            why = f"norm modes {sorted(map(str, modes))}: one of 'none' / 'both' for all layers"
+        elif any(c is None for c in codes):
+            why = "an activation that is neither identity nor ReLU"
+        elif feat.dtype not in (torch.uint8, torch.float32):
+            why = f"{feat.dtype} features (uint8 or fp32)"
+        elif not ops.embed_graphs_usable(lins[0].in_features, widths, 0):
+            why = f"the encoder {lins[0].in_features} -> {widths}: 1..{ops.EMBED_MAX_LAYERS} layers of widths <= " \
+                  f"{ops.EMBED_MAX_WIDTH}"
+        take = sizes <= ops.EMBED_MAX_NODES if why is None else np.zeros(B, dtype=bool)
+        if fused is True:
+            if why is None and not take.all():
+                why = f"{int((~take).sum())} graph(s) above {ops.EMBED_MAX_NODES} nodes (largest: {int(sizes.max())})"
+            if why is not None:
+                raise ops.GaeHipError(f"GAE.embed_graphs(fused=True): the kernel does not take {why}")
+        if fused is False:
+            take = np.zeros(B, dtype=bool)
+        out = None
+        n_take = int(take.sum())
+        if n_take:
+            if n_take == B and identity_ids:
+                gids = None
+            else:
+                gids = torch.from_numpy(np.ascontiguousarray(ids[take])).to(dev)
+            if not is_set:
+                gp, (indptr, indices) = data.graph_ptr(), data.csr()
+            out = ops.embed_graphs(gp, indptr, indices, feat, [lin.weight for lin in lins], [lin.bias for lin in lins],
+                                   codes, norm=next(iter(modes)), graph_ids=gids, max_graph_nodes=int(sizes[take].max()))
+            if n_take == B:
+                return out
+        full = torch.empty(B, 3 * d, dtype=torch.float32, device=dev)
+        if out is not None:
+            full[torch.from_numpy(np.nonzero(take)[0]).to(dev)] = out
+        rest = np.nonzero(~take)[0]
+        if B == 0:
+            return full
+        if not is_set:
+            # a batched graph is one batch: the existing route embeds all of it, the rows still missing are kept
+            from .graph import readout_nodes
+            try:
+                rows = readout_nodes(data, self.encode(data))
+            finally:
+                data.ndata['h'] = feat
+            if len(rest):
+                sel = torch.from_numpy(rest).to(dev)
+                full[sel] = rows[sel]
+            return full
+        from .graph import readout_nodes
+        for lo in range(0, len(rest), batch_size):
+            sel = rest[lo:lo + batch_size]
+            bg = data.batch(ids[sel])
+            rows = readout_nodes(bg, self.encode(bg))
+            if len(sel) == B:
+                return rows
+            full[torch.from_numpy(sel).to(dev)] = rows
+        return full
+
     def reconstruction_loss(self, g, criterion="bce", scope="batch", samples=None):
         """The training loss of train_inductive.py:44-48 (dense label from g,
         pos_weight, BCE-with-logits mean over all N^2 ordered pairs) evaluated

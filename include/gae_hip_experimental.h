@@ -364,6 +364,56 @@ int gae_decoder_rank(const float *Z, int64_t ldz, int64_t n, int64_t d,
                      float *score_out, int64_t *greater_out, int64_t *equal_out, int64_t *candidates_out,
                      void *workspace, int64_t *workspace_bytes, void *stream);
 
+/* (from gae_hip.h: graph-level readout) */
+/* ---- K19: the molecule feature of a whole resident set in ONE launch (GAE.embed_graphs, ops.embed_graphs)
+ * For every selected member graph: the complete GCN encoder of gae.py:26-31,36-45 on that graph's own rows -- per layer
+ * aggregate over in-edges, Linear + bias, activation -- followed by gae_segment_readout's [mean | sum | max] over its
+ * nodes.  The node embeddings never reach memory.  Every array is read in the layout a resident dataset holds; nothing
+ * is copied or re-batched.
+ *   graph_ptr    int64 [n_graphs + 1] node offsets of the member graphs; n_nodes rows in all
+ *   indptr / indices   int32 CSR of the whole set (rows = destination, GLOBAL column ids, n_edges entries, repeated
+ *                entries add); every entry of a row lies inside the row's own member graph
+ *   feat         feat_dtype GAE_U8: [n_nodes, ldf] bytes; GAE_F32: [n_nodes, ldf] floats; f_in columns are data, the rest of
+ *                a row is padding that is never used as data (it may hold anything, NaN included).  Rows are read with
+ *                16-byte loads: feat and the row pitch must be multiples of 16 bytes and hold whole vectors
+ *                (ldf >= f_in rounded up to 16 bytes), else GAE_E_ALIGN / GAE_E_SIZE
+ *   layers       HOST arrays of n_layers entries: widths[l] = output width of layer l, weights[l] = device pointer to
+ *                [widths[l], input width] row-major with leading dimension ldw[l], biases[l] (biases or an entry may be
+ *                NULL = no bias), acts[l] = GAE_ACT_IDENTITY / GAE_ACT_RELU (GAE: ReLU on all but the last layer)
+ *   norm         GAE_EMBED_NORM_NONE: plain in-edge sums (the reference); GAE_EMBED_NORM_BOTH: D^-1/2 A D^-1/2 with
+ *                in_degree^-1/2 (inf -> 0; gae_degree_norm's vector, taken here from the row lengths) as row AND column
+ *                scale of every layer
+ *   graph_ids    int64 [n_out] on the device, or NULL = graphs 0 .. n_out - 1 (n_out <= n_graphs is the caller's
+ *                business): output row k belongs to graph graph_ids[k]; any order, repeats allowed
+ *   out          fp32 [n_out, ldo], ldo >= 3 d (d = widths[n_layers - 1]): [mean | sum | max]; an empty graph gives
+ *                zeros in all three, as gae_segment_readout
+ *   max_graph_nodes   host-side upper bound of the node counts of the selected graphs
+ * SHAPES TAKEN: 1 <= n_layers <= 4, f_in and every width in 1..64, max_graph_nodes <= 64 (rows of any length: the
+ * neighbour walk follows the CSR).  Anything else returns GAE_E_RANGE, with a message naming the quantity, before any
+ * launch; gae_embed_graphs_usable answers the same question (1 = taken) without a launch or a GPU.
+ * INDEPENDENCE: a graph's output row is a function of that graph's rows alone -- aggregation sums in CSR order, every
+ * product is one fp32 fmaf chain in ascending feature order, the readout adds the graph's nodes first to last.  The
+ * row has the same bits whether the graph is embedded with the whole set, in any subset, at any position of graph_ids,
+ * twice in one call, or in another run.  No atomics.
+ * NUMERICAL CONTRACT: fp32 throughout (products as exact as v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain); within the
+ * library's 1e-5 of an fp64 evaluation, measured as everywhere against max(1, max |reference|).
+ * ROBUSTNESS: a graph id outside [0, n_graphs), a node range outside [0, n_nodes] or longer than 64 rows (a wrong
+ * max_graph_nodes) gives a row of NaN; a row pointer outside [0, n_edges] reads as an empty row; a column id outside
+ * the row's own graph is skipped.  Nothing outside the arrays is read or written.
+ * Argument errors are returned before any launch: NULL widths / weights / ldw / acts / a layer's weight (GAE_E_NULL),
+ * negative sizes, ldo < 3 d, ldw below the input width, short feature rows (GAE_E_SIZE), unknown norm (GAE_E_RANGE),
+ * unknown activation or feature dtype (GAE_E_DTYPE), then, when n_out > 0, NULL arrays.  One launch, no workspace. */
+enum { GAE_EMBED_NORM_NONE = 0, GAE_EMBED_NORM_BOTH = 1 };
+
+int gae_embed_graphs_usable(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes);
+
+int gae_embed_graphs(const int64_t *graph_ptr, int64_t n_graphs, int64_t n_nodes, int64_t n_edges,
+                     int64_t max_graph_nodes, const int32_t *indptr, const int32_t *indices,
+                     const void *feat, int feat_dtype, int64_t ldf, int64_t f_in, int64_t n_layers,
+                     const int64_t *widths, const float *const *weights, const int64_t *ldw,
+                     const float *const *biases, const int *acts, int norm, const int64_t *graph_ids,
+                     int64_t n_out, float *out, int64_t ldo, void *stream);
+
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
 int gae_x_decoder_bce_finalize(const gae_bce_tail *tail, void *stream);
