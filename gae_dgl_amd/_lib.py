@@ -173,6 +173,9 @@ SIGNATURES = {
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),
+    "gae_score_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
+    "gae_score_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
+                                _p, _i64, _int, _p, _p, _p, _p]),
 }
 
 _lib = None

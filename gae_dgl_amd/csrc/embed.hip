@@ -34,6 +34,33 @@
 // the ZINC-sized set in 2.43 ms of kernel time (3.1 ms per call) against 15.5 ms for batch -> encode -> readout in chunks
 // of 4096 and 389 ms in chunks of 128; 9 Tflop/s, 6 % of the fp32 peak -- LDS sets 1.5 waves per SIMD and feeds every
 // FMA (DESIGN.md K19 lists the levers).  175 VGPRs, no scratch (uint8 form).
+//
+// K20: how well every selected member graph is reconstructed (GAE.score_graphs, ops.score_graphs).  The same walk and
+// the same encoder -- graphs_body below is the body of both kernels, aggregate / transform are called by both -- with
+// a second tail in place of the readout: the decoder on each graph's own ordered pairs, ranked and scored in LDS.
+//   logits      lane r computes row r of its graph's n x n block: s_rb = the fmaf chain over k ascending, from 0.f, of
+//               z_r[k] z_b[k] (Z rows from LDS, 16 bytes at a time), into the buffer the last layer no longer needs,
+//               rows max_graph_nodes | 1 floats apart (odd: a column walk of a graph's lanes hits distinct banks)
+//   labels      lane r walks its CSR row once more: a 64-bit mask of the columns that occur (a repeat counts once),
+//               and S, the entries with repeats, for pos_weight
+//   counting    lane r owns the positives of ITS row, in entry order: for the threshold t = s_rc it reads every pair
+//               above the diagonal of its graph's block once (s_ab == s_ba bit for bit, so a hit counts twice; the
+//               lanes of a graph read the same address: a broadcast) for all_ge / all_gt, and the pairs the masks mark
+//               for pos_ge / pos_gt.  No cross-lane step per positive; the fp64 quotient pos_ge / all_ge is added in
+//               the lane, neg_ge = all_ge - pos_ge and neg_gt are summed as integers
+//   fold        lane m adds the rows of slot m first to last (tables in the buffer that held Z): integers, and the
+//               fp64 sums of the AP terms and of the three loss sums (softplus(s) over all pairs; softplus(-s) and s
+//               over the entries) in row order; wins = n_pos n_neg - sum neg_ge, ties = sum neg_ge - sum neg_gt
+// Every number is a function of the graph's own rows in an order the graph alone fixes; integers are exact.  No atomics.
+// The load of a lane is its row's positives times n (n - 1) / 2: a molecule's lanes are busy unevenly (2.2 bonds per
+// atom on average, 4 at most), which is what the tail pays for needing no segmented reduction per positive.
+//
+// LDS (K20).  Per wave: the buffer that ends up holding Z (>= 64 x 16 floats: it takes the 896 floats of tables), the
+// other buffer = the logit block, max(its K19 size, 64 x (max_graph_nodes | 1) floats), and K19's 192 floats of tables.
+// 39 -> 32 -> 16 on ZINC (max 38 atoms): 64 x 39 = 2 496 floats fit the 64 x 44 the encoder needs anyway -- 53.8 KB per
+// block as K19, 3 blocks = 6 waves per CU = 1.5 per SIMD, unchanged.  max_graph_nodes = 64 needs 64 x 65 floats: 64.6 KB
+// per block for this model, 2 blocks = 1 wave per SIMD.  Registers: 227 VGPRs (uint8 form, 2 waves per SIMD), 270 (fp32
+// form, 1 wave per SIMD, as K19's 261), no scratch.
 #include "common.h"
 
 namespace {
@@ -158,8 +185,176 @@ __device__ __forceinline__ void transform(const float *Wt, const float *bl, int 
     }
 }
 
-template <bool U8>
-__global__ __launch_bounds__(kWaves * 64) void embed_graphs_kernel(const EmbedArgs a)
+// ---- K20: the decoder tail (see the header comment) ------------------------------------------------------------------
+struct ScoreArgs {
+    int64_t *counts;              // [B][4]: n_pos, n_neg, wins, ties
+    double *ap;                   // [B]
+    float *loss;                  // [B]
+    int exclude_self;
+    int max_nodes;                // the host's bound of a graph's rows: a larger graph is refused (the block is sized for it)
+    int rs;                       // floats between two rows of the logit block: max_nodes | 1
+    int z_in_b;                   // odd layer count: Z ends in buffer B, which then comes first
+    int block_floats;             // floats of the second buffer = the logit block
+};
+
+// float offsets of the per-lane tables inside the buffer that held Z (dead once the logits are in the block)
+enum { kTabLab = 0, kTabGe = 128, kTabGt = 192, kTabS = 256, kTabBad = 320, kTabAp = 384, kTabSp = 512, kTabA = 640,
+       kTabB = 768, kTabFloats = 896 };
+
+__device__ __forceinline__ void score_invalid(const ScoreArgs &t, int64_t k)
+{
+    int64_t *c = t.counts + 4 * k;
+    c[0] = c[1] = c[2] = c[3] = -1;
+    t.ap[k] = __builtin_nan("");
+    t.loss[k] = __builtin_nanf("");
+}
+
+__device__ __forceinline__ float softplus(float x)
+{
+    return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x)));
+}
+
+// Z [64 rows][sz] of the group is final.  Lane r: its row of logits into the block, its label mask from its CSR row,
+// then for each positive of its row (entry order, first occurrence) the counts over all pairs of its graph.
+__device__ __forceinline__ void score_tail(const EmbedArgs &a, const ScoreArgs &t, const Lane &me, int lane, int d,
+                                           float *Z, int sz, float *blk, const int *mbase, const int *mcount, int ccnt,
+                                           int64_t slot0)
+{
+    const int RS = t.rs, n = me.mn, mb = me.mb, li = lane - mb;
+    float *myrow = blk + lane * RS;
+    // ---- logits of the lane's row against the rows of its own graph: fmaf chains from 0.f, k ascending
+    double sp = 0.0;
+    bool bad = false;
+    if (me.active) {
+        const float *zi = Z + lane * sz;
+        const int d4 = d & ~3;
+        for (int b = 0; b < n; ++b) {
+            const float *zb = Z + (mb + b) * sz;
+            float s = 0.f;
+            for (int k = 0; k < d4; k += 4) {
+                const v4f x = *reinterpret_cast<const v4f *>(zi + k), y = *reinterpret_cast<const v4f *>(zb + k);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) s = fmaf(x[i], y[i], s);
+            }
+            for (int k = d4; k < d; ++k) s = fmaf(zi[k], zb[k], s);
+            myrow[b] = s;
+            bad = bad || !(fabsf(s) < INFINITY);
+            sp += double(softplus(s));               // the loss sees all n^2 ordered pairs, self pairs included
+        }
+    }
+    wave_sync();                                     // Z is dead from here on: its buffer holds the tables
+    // ---- label mask of the lane's row: bit c = column g0 + c occurs in it; S counts the entries with repeats
+    uint64_t *tlab = reinterpret_cast<uint64_t *>(Z + kTabLab);
+    uint64_t lab = 0;
+    unsigned S = 0;
+    if (me.active) {
+        for (int e = me.e0; e < me.e1; ++e) {
+            const int c = a.indices[e] - me.g0;
+            if (c >= 0 && c < n) { lab |= 1ull << c; ++S; }
+        }
+        if (t.exclude_self) lab &= ~(1ull << li);
+    }
+    tlab[lane] = lab;
+    wave_sync();
+    // ---- the lane's positives, in CSR order.  all = ordered pairs of the graph (s_rb == s_br bit for bit: the pairs
+    // above the diagonal are read once and count twice), pos = the pairs the masks mark
+    unsigned sge = 0, sgt = 0;                       // sums over the lane's positives of neg_ge, neg_gt (<= 64 * 4096)
+    double ap = 0.0, la = 0.0, lb = 0.0;
+    if (me.active) {
+        uint64_t seen = 0;
+        for (int e = me.e0; e < me.e1; ++e) {
+            const int c = a.indices[e] - me.g0;
+            if (c < 0 || c >= n) continue;
+            const float x = myrow[c];
+            la += double(softplus(-x));              // y_ij counts every entry, repeats and self loops included
+            lb += double(x);
+            const uint64_t bit = 1ull << c;
+            if (!(lab & bit) || (seen & bit)) continue;
+            seen |= bit;
+            unsigned ge = 0, gt = 0;
+            for (int r = 0; r < n; ++r) {
+                const float *ra = blk + (mb + r) * RS;
+                for (int b = r + 1; b < n; ++b) {
+                    const float s = ra[b];
+                    ge += s >= x;
+                    gt += s > x;
+                }
+            }
+            ge *= 2; gt *= 2;
+            if (!t.exclude_self)
+                for (int r = 0; r < n; ++r) {
+                    const float s = blk[(mb + r) * RS + r];
+                    ge += s >= x;
+                    gt += s > x;
+                }
+            unsigned pge = 0, pgt = 0;
+            for (int r = 0; r < n; ++r) {
+                const float *ra = blk + (mb + r) * RS;
+                uint64_t m = tlab[mb + r];
+                while (m) {
+                    const int b = __builtin_ctzll(m);
+                    m &= m - 1;
+                    const float s = ra[b];
+                    pge += s >= x;
+                    pgt += s > x;
+                }
+            }
+            ap += double(pge) / double(ge);
+            sge += ge - pge;
+            sgt += gt - pgt;
+        }
+    }
+    reinterpret_cast<unsigned *>(Z + kTabGe)[lane] = sge;
+    reinterpret_cast<unsigned *>(Z + kTabGt)[lane] = sgt;
+    reinterpret_cast<unsigned *>(Z + kTabS)[lane] = S;
+    reinterpret_cast<unsigned *>(Z + kTabBad)[lane] = bad ? 1u : 0u;
+    reinterpret_cast<double *>(Z + kTabAp)[lane] = ap;
+    reinterpret_cast<double *>(Z + kTabSp)[lane] = sp;
+    reinterpret_cast<double *>(Z + kTabA)[lane] = la;
+    reinterpret_cast<double *>(Z + kTabB)[lane] = lb;
+    wave_sync();
+    // ---- lane m folds the rows of slot m first to last: integers, and fp64 sums in row order
+    if (lane < ccnt) {
+        const int b0 = mbase[lane], gn = mcount[lane];
+        int64_t n_pos = 0, tge = 0, tgt = 0, tS = 0;
+        unsigned anybad = 0;
+        double tap = 0.0, tsp = 0.0, ta = 0.0, tb = 0.0;
+        for (int r = b0; r < b0 + gn; ++r) {
+            n_pos += __builtin_popcountll(tlab[r]);
+            tge += reinterpret_cast<const unsigned *>(Z + kTabGe)[r];
+            tgt += reinterpret_cast<const unsigned *>(Z + kTabGt)[r];
+            tS += reinterpret_cast<const unsigned *>(Z + kTabS)[r];
+            anybad |= reinterpret_cast<const unsigned *>(Z + kTabBad)[r];
+            tap += reinterpret_cast<const double *>(Z + kTabAp)[r];
+            tsp += reinterpret_cast<const double *>(Z + kTabSp)[r];
+            ta += reinterpret_cast<const double *>(Z + kTabA)[r];
+            tb += reinterpret_cast<const double *>(Z + kTabB)[r];
+        }
+        const int64_t k = slot0 + lane;
+        if (anybad) {
+            score_invalid(t, k);
+        } else {
+            const int64_t nn = int64_t(gn) * gn, n_neg = nn - (t.exclude_self ? gn : 0) - n_pos;
+            int64_t *c = t.counts + 4 * k;
+            c[0] = n_pos;
+            c[1] = n_neg;
+            c[2] = n_pos * n_neg - tge;              // wins = sum_p (n_neg - neg_ge(p))
+            c[3] = tge - tgt;                        // ties = sum_p (neg_ge(p) - neg_gt(p))
+            t.ap[k] = n_pos > 0 && n_neg > 0 ? tap / double(n_pos) : __builtin_nan("");
+            float l = __builtin_nanf("");
+            if (n_pos > 0) {
+                const double pw = (double(nn) - double(tS)) / double(tS);      // train_inductive.py:46
+                l = float((tsp + (pw - 1.0) * ta - tb) / double(nn));
+            }
+            t.loss[k] = l;
+        }
+    }
+}
+
+// The walk both kernels share: the slots of a wave, their groups, the encoder of a group in LDS.  SCORE = false ends a
+// group with K19's readout, SCORE = true with K20's decoder tail (score_tail).
+template <bool U8, bool SCORE>
+__device__ __forceinline__ void graphs_body(const EmbedArgs &a, const ScoreArgs &t)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -184,6 +379,13 @@ __global__ __launch_bounds__(kWaves * 64) void embed_graphs_kernel(const EmbedAr
     float *bufA = lds + a.wfloats + wave * a.wave_floats;
     float *bufB = bufA + kRows * a.sa;
     float *scale = bufB + kRows * a.sb;
+    if constexpr (SCORE) {
+        // the buffer that ends up holding Z comes first; the other one is the logit block and may be longer
+        float *base = bufA;
+        bufA = base + (t.z_in_b ? kRows * a.sb : 0);
+        bufB = base + (t.z_in_b ? 0 : kRows * a.sa);
+        scale = base + kRows * (t.z_in_b ? a.sb : a.sa) + t.block_floats;
+    }
     int *mbase = reinterpret_cast<int *>(scale + kRows);
     int *mcount = mbase + kRows;
 
@@ -202,6 +404,7 @@ __global__ __launch_bounds__(kWaves * 64) void embed_graphs_kernel(const EmbedAr
         int64_t r0 = 0, r1 = 0;
         if (ok) { r0 = a.graph_ptr[gid]; r1 = a.graph_ptr[gid + 1]; }
         ok = ok && r0 >= 0 && r1 >= r0 && r1 <= a.N && r1 - r0 <= kRows;
+        if constexpr (SCORE) ok = ok && r1 - r0 <= t.max_nodes;      // the logit block is sized for max_graph_nodes
         sn = ok ? int(r1 - r0) : kRows + 1;        // a slot that cannot be taken never fits a group
         sr0 = ok ? int(r0) : 0;
     }
@@ -246,8 +449,12 @@ __global__ __launch_bounds__(kWaves * 64) void embed_graphs_kernel(const EmbedAr
     while (pos < avail) {
         if (cnt == 0) {
             // a slot that cannot be taken (bad id, bad range, above 64 rows): a row of NaN
-            float *o = a.out + (k0 + pos) * a.ldo;
-            for (int c = lane; c < 3 * d; c += 64) o[c] = __builtin_nanf("");
+            if constexpr (SCORE) {
+                if (lane == 0) score_invalid(t, k0 + pos);
+            } else {
+                float *o = a.out + (k0 + pos) * a.ldo;
+                for (int c = lane; c < 3 * d; c += 64) o[c] = __builtin_nanf("");
+            }
             issue(pos + 1);
             continue;
         }
@@ -323,7 +530,9 @@ __global__ __launch_bounds__(kWaves * 64) void embed_graphs_kernel(const EmbedAr
             const int ts = sin; sin = sout; sout = ts;
         }
         // ---- readout: Z = `in` now; lane (slot, c) walks the rows of its graphs first to last
-        {
+        if constexpr (SCORE) {
+            score_tail(a, t, me, lane, d, const_cast<float *>(in), sin, out, mbase, mcount, ccnt, k0 + cpos);
+        } else {
             int DP = 1;
             while (DP < d) DP <<= 1;
             const int c = lane & (DP - 1), slot = lane / DP, RS = 64 / DP;
@@ -347,13 +556,27 @@ __global__ __launch_bounds__(kWaves * 64) void embed_graphs_kernel(const EmbedAr
     }
 }
 
+template <bool U8>
+__global__ __launch_bounds__(kWaves * 64) void embed_graphs_kernel(const EmbedArgs a)
+{
+    graphs_body<U8, false>(a, ScoreArgs{});
+}
+
+template <bool U8>
+__global__ __launch_bounds__(kWaves * 64) void score_graphs_kernel(const EmbedArgs a, const ScoreArgs t)
+{
+    graphs_body<U8, true>(a, t);
+}
+
 int round_up(int v, int q) { return (v + q - 1) / q * q; }
 
-// the shapes the kernel takes; `what` (may be NULL) receives the offending quantity
-bool shape_taken(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes, char *what, size_t cap)
+// the shapes the kernels take (K20 also the encoder of no layers: the feature rows are Z); `what` (may be NULL)
+// receives the offending quantity
+bool shape_taken(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes, int min_layers,
+                 char *what, size_t cap)
 {
-    if (n_layers < 1 || n_layers > kMaxLayers) {
-        if (what) snprintf(what, cap, "n_layers = %lld outside 1..%d", (long long)n_layers, kMaxLayers);
+    if (n_layers < min_layers || n_layers > kMaxLayers) {
+        if (what) snprintf(what, cap, "n_layers = %lld outside %d..%d", (long long)n_layers, min_layers, kMaxLayers);
         return false;
     }
     if (f_in < 1 || f_in > kMaxWidth) {
@@ -375,12 +598,130 @@ bool shape_taken(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t 
     return true;
 }
 
+// what gae_embed_graphs and gae_score_graphs ask of their common arguments, in this order; `fn` names the caller
+struct Request {
+    const int64_t *graph_ptr;
+    int64_t n_graphs, n_nodes, n_edges, max_graph_nodes;
+    const int32_t *indptr, *indices;
+    const void *feat;
+    int feat_dtype;
+    int64_t ldf, f_in, n_layers;
+    const int64_t *widths;
+    const float *const *weights;
+    const int64_t *ldw;
+    const float *const *biases;
+    const int *acts;
+    int norm;
+    const int64_t *graph_ids;
+    int64_t n_out;
+};
+
+int check_layers(const char *fn, const Request &r, int min_layers)
+{
+    GAE_REQUIRE((min_layers == 0 && r.n_layers == 0) || (r.widths && r.weights && r.ldw && r.acts), GAE_E_NULL,
+                "%s: widths / weights / ldw / acts is NULL", fn);
+    GAE_REQUIRE(r.n_graphs >= 0 && r.n_nodes >= 0 && r.n_edges >= 0 && r.n_out >= 0 && r.max_graph_nodes >= 0, GAE_E_SIZE,
+                "%s: negative n_graphs = %lld, n_nodes = %lld, n_edges = %lld, n_out = %lld or "
+                "max_graph_nodes = %lld", fn, (long long)r.n_graphs, (long long)r.n_nodes, (long long)r.n_edges,
+                (long long)r.n_out, (long long)r.max_graph_nodes);
+    GAE_REQUIRE(r.n_nodes < (int64_t(1) << 31) && r.n_edges < (int64_t(1) << 31), GAE_E_SIZE,
+                "%s: n_nodes = %lld or n_edges = %lld beyond the int32 CSR", fn, (long long)r.n_nodes,
+                (long long)r.n_edges);
+    char what[160];
+    GAE_REQUIRE(shape_taken(r.f_in, r.n_layers, r.widths, r.max_graph_nodes, min_layers, what, sizeof what), GAE_E_RANGE,
+                "%s: %s", fn, what);
+    GAE_REQUIRE(r.norm == GAE_EMBED_NORM_NONE || r.norm == GAE_EMBED_NORM_BOTH, GAE_E_RANGE,
+                "%s: unknown norm code %d (0 = none, 1 = both)", fn, r.norm);
+    GAE_REQUIRE(r.feat_dtype == GAE_F32 || r.feat_dtype == GAE_U8, GAE_E_DTYPE,
+                "%s: feature dtype %d (GAE_F32 or GAE_U8)", fn, r.feat_dtype);
+    for (int64_t l = 0; l < r.n_layers; ++l) {
+        GAE_REQUIRE(r.acts[l] == GAE_ACT_IDENTITY || r.acts[l] == GAE_ACT_RELU, GAE_E_DTYPE,
+                    "%s: unknown activation code %d of layer %lld", fn, r.acts[l], (long long)l);
+        GAE_REQUIRE(r.weights[l], GAE_E_NULL, "%s: the weight of layer %lld is NULL", fn, (long long)l);
+        GAE_REQUIRE(r.ldw[l] >= (l ? r.widths[l - 1] : r.f_in), GAE_E_SIZE,
+                    "%s: leading dimension ldw = %lld of layer %lld below its input width", fn,
+                    (long long)r.ldw[l], (long long)l);
+    }
+    return GAE_OK;
+}
+
+int check_feature_rows(const char *fn, const Request &r)
+{
+    const int64_t row_elems = r.feat_dtype == GAE_U8 ? (r.f_in + 15) / 16 * 16 : (r.f_in + 3) / 4 * 4;
+    GAE_REQUIRE(r.ldf >= row_elems, GAE_E_SIZE,
+                "%s: feature rows of ldf = %lld elements, %lld needed (whole 16-byte vectors)", fn,
+                (long long)r.ldf, (long long)row_elems);
+    return GAE_OK;
+}
+
+int check_arrays(const char *fn, const Request &r)
+{
+    GAE_REQUIRE(r.n_nodes == 0 || (r.indptr && r.feat), GAE_E_NULL, "%s: indptr / feat is NULL", fn);
+    GAE_REQUIRE(r.n_edges == 0 || r.indices, GAE_E_NULL, "%s: indices is NULL", fn);
+    const int64_t row_bytes = r.ldf * (r.feat_dtype == GAE_U8 ? 1 : 4);
+    GAE_REQUIRE(r.n_nodes == 0 || (gae::aligned16(r.feat) && row_bytes % 16 == 0), GAE_E_ALIGN,
+                "%s: feature rows must start on 16-byte boundaries (pointer and ldf)", fn);
+    return GAE_OK;
+}
+
+// the kernel arguments of a checked request: staged weights, row strides of the two buffers, slots per wave.  The LDS
+// of a wave (wave_floats) is K19's; gae_score_graphs replaces it.
+int64_t fill_args(const Request &r, EmbedArgs &a)
+{
+    a.graph_ptr = r.graph_ptr; a.indptr = r.indptr; a.indices = r.indices; a.feat = r.feat; a.ldf = r.ldf;
+    a.G = r.n_graphs; a.N = r.n_nodes; a.E = r.n_edges; a.B = r.n_out;
+    a.L = int(r.n_layers);
+    a.width[0] = int(r.f_in);
+    for (int l = 0; l < a.L; ++l) a.width[l + 1] = int(r.widths[l]);
+    for (int l = a.L + 1; l <= kMaxLayers; ++l) a.width[l] = 0;
+    int off = 0;
+    for (int l = 0; l < kMaxLayers; ++l) {
+        a.jp[l] = a.w_off[l] = a.b_off[l] = a.act[l] = 0;
+        a.W[l] = nullptr; a.bias[l] = nullptr; a.ldw[l] = 0;
+    }
+    int sa = round_up(a.width[0], 4), sb = 0;      // (no layers: buffer A holds the feature rows and nothing else)
+    for (int l = 0; l < a.L; ++l) {
+        const int fq = round_up(a.width[l], 4);    // the input (and its aggregate) in whole 16-byte vectors
+        a.jp[l] = round_up(a.width[l + 1], 8);
+        a.w_off[l] = off; off += a.width[l] * a.jp[l];
+        a.b_off[l] = off; off += a.jp[l];
+        a.W[l] = r.weights[l]; a.ldw[l] = r.ldw[l]; a.bias[l] = r.biases ? r.biases[l] : nullptr; a.act[l] = r.acts[l];
+        int &s_in = l % 2 ? sb : sa, &s_out = l % 2 ? sa : sb;
+        s_in = s_in > fq ? s_in : fq;
+        s_out = s_out > fq ? s_out : fq;           // the aggregate is written to the lane's row of the output buffer
+        s_out = s_out > a.jp[l] ? s_out : a.jp[l];
+    }
+    a.sa = sa + 4; a.sb = sb + 4;                  // + 16 bytes: rows start on different banks
+    a.wfloats = round_up(off, 4);
+    a.wave_floats = kRows * (a.sa + a.sb) + 3 * kRows;
+    a.norm_both = r.norm == GAE_EMBED_NORM_BOTH;
+    a.graph_ids = r.graph_ids; a.out = nullptr; a.ldo = 0;
+    int64_t S = (r.n_out + 8191) / 8192;           // ~8 000 waves on a large set, several groups per wave on a small one
+    a.S = int(S < 4 ? 4 : (S > 64 ? 64 : S));
+    const int64_t waves = (r.n_out + a.S - 1) / a.S;
+    return (waves + kWaves - 1) / kWaves;
+}
+
+// a launch of `kernel` with `lds` bytes of dynamic LDS; the attribute is raised once per (kernel, device)
+#define GAE_GRAPHS_LAUNCH(kernel, ...)                                                                                 \
+    do {                                                                                                               \
+        static int configured[16] = {0};   /* per (instantiation, device): raised when a launch needs more LDS */      \
+        int dev_ = 0;                                                                                                  \
+        GAE_HIP(hipGetDevice(&dev_));                                                                                  \
+        if (lds > 48 * 1024 && (dev_ < 0 || dev_ >= 16 || configured[dev_] < int(lds))) {                              \
+            GAE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&kernel),                                       \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));                        \
+            if (dev_ >= 0 && dev_ < 16) configured[dev_] = int(lds);                                                   \
+        }                                                                                                              \
+        hipLaunchKernelGGL(kernel, dim3(unsigned(blocks)), dim3(kWaves * 64), lds, st, __VA_ARGS__);                   \
+    } while (0)
+
 } // namespace
 
 extern "C" int gae_embed_graphs_usable(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes)
 {
     if (!widths || max_graph_nodes < 0) return 0;
-    return shape_taken(f_in, n_layers, widths, max_graph_nodes, nullptr, 0) ? 1 : 0;
+    return shape_taken(f_in, n_layers, widths, max_graph_nodes, 1, nullptr, 0) ? 1 : 0;
 }
 
 extern "C" int gae_embed_graphs(const int64_t *graph_ptr, int64_t n_graphs, int64_t n_nodes, int64_t n_edges,
@@ -390,95 +731,78 @@ extern "C" int gae_embed_graphs(const int64_t *graph_ptr, int64_t n_graphs, int6
                                 const float *const *biases, const int *acts, int norm, const int64_t *graph_ids,
                                 int64_t n_out, float *out, int64_t ldo, void *stream)
 {
-    GAE_REQUIRE(widths && weights && ldw && acts, GAE_E_NULL,
-                "gae_embed_graphs: widths / weights / ldw / acts is NULL");
-    GAE_REQUIRE(n_graphs >= 0 && n_nodes >= 0 && n_edges >= 0 && n_out >= 0 && max_graph_nodes >= 0, GAE_E_SIZE,
-                "gae_embed_graphs: negative n_graphs = %lld, n_nodes = %lld, n_edges = %lld, n_out = %lld or "
-                "max_graph_nodes = %lld", (long long)n_graphs, (long long)n_nodes, (long long)n_edges, (long long)n_out,
-                (long long)max_graph_nodes);
-    GAE_REQUIRE(n_nodes < (int64_t(1) << 31) && n_edges < (int64_t(1) << 31), GAE_E_SIZE,
-                "gae_embed_graphs: n_nodes = %lld or n_edges = %lld beyond the int32 CSR", (long long)n_nodes,
-                (long long)n_edges);
-    char what[160];
-    GAE_REQUIRE(shape_taken(f_in, n_layers, widths, max_graph_nodes, what, sizeof what), GAE_E_RANGE,
-                "gae_embed_graphs: %s", what);
-    GAE_REQUIRE(norm == GAE_EMBED_NORM_NONE || norm == GAE_EMBED_NORM_BOTH, GAE_E_RANGE,
-                "gae_embed_graphs: unknown norm code %d (0 = none, 1 = both)", norm);
-    GAE_REQUIRE(feat_dtype == GAE_F32 || feat_dtype == GAE_U8, GAE_E_DTYPE,
-                "gae_embed_graphs: feature dtype %d (GAE_F32 or GAE_U8)", feat_dtype);
-    for (int64_t l = 0; l < n_layers; ++l) {
-        GAE_REQUIRE(acts[l] == GAE_ACT_IDENTITY || acts[l] == GAE_ACT_RELU, GAE_E_DTYPE,
-                    "gae_embed_graphs: unknown activation code %d of layer %lld", acts[l], (long long)l);
-        GAE_REQUIRE(weights[l], GAE_E_NULL, "gae_embed_graphs: the weight of layer %lld is NULL", (long long)l);
-        GAE_REQUIRE(ldw[l] >= (l ? widths[l - 1] : f_in), GAE_E_SIZE,
-                    "gae_embed_graphs: leading dimension ldw = %lld of layer %lld below its input width",
-                    (long long)ldw[l], (long long)l);
-    }
+    static const char fn[] = "gae_embed_graphs";
+    const Request r = {graph_ptr, n_graphs, n_nodes, n_edges, max_graph_nodes, indptr, indices, feat, feat_dtype, ldf,
+                       f_in, n_layers, widths, weights, ldw, biases, acts, norm, graph_ids, n_out};
+    if (const int rc = check_layers(fn, r, 1)) return rc;
     const int64_t d = widths[n_layers - 1];
     GAE_REQUIRE(ldo >= 3 * d, GAE_E_SIZE, "gae_embed_graphs: leading dimension too small (ldo %lld < 3 d = %lld)",
                 (long long)ldo, (long long)(3 * d));
-    const int64_t row_elems = feat_dtype == GAE_U8 ? (f_in + 15) / 16 * 16 : (f_in + 3) / 4 * 4;
-    GAE_REQUIRE(ldf >= row_elems, GAE_E_SIZE,
-                "gae_embed_graphs: feature rows of ldf = %lld elements, %lld needed (whole 16-byte vectors)",
-                (long long)ldf, (long long)row_elems);
+    if (const int rc = check_feature_rows(fn, r)) return rc;
     if (n_out == 0) return GAE_OK;
     GAE_REQUIRE(graph_ptr && out, GAE_E_NULL, "gae_embed_graphs: graph_ptr / out is NULL");
-    GAE_REQUIRE(n_nodes == 0 || (indptr && feat), GAE_E_NULL, "gae_embed_graphs: indptr / feat is NULL");
-    GAE_REQUIRE(n_edges == 0 || indices, GAE_E_NULL, "gae_embed_graphs: indices is NULL");
-    const int64_t row_bytes = ldf * (feat_dtype == GAE_U8 ? 1 : 4);
-    GAE_REQUIRE(n_nodes == 0 || (gae::aligned16(feat) && row_bytes % 16 == 0), GAE_E_ALIGN,
-                "gae_embed_graphs: feature rows must start on 16-byte boundaries (pointer and ldf)");
+    if (const int rc = check_arrays(fn, r)) return rc;
 
     EmbedArgs a;
-    a.graph_ptr = graph_ptr; a.indptr = indptr; a.indices = indices; a.feat = feat; a.ldf = ldf;
-    a.G = n_graphs; a.N = n_nodes; a.E = n_edges; a.B = n_out;
-    a.L = int(n_layers);
-    a.width[0] = int(f_in);
-    for (int l = 0; l < a.L; ++l) a.width[l + 1] = int(widths[l]);
-    int off = 0;
-    for (int l = 0; l < kMaxLayers; ++l) {
-        a.jp[l] = a.w_off[l] = a.b_off[l] = a.act[l] = 0;
-        a.W[l] = nullptr; a.bias[l] = nullptr; a.ldw[l] = 0;
-    }
-    int sa = 0, sb = 0;
-    for (int l = 0; l < a.L; ++l) {
-        const int fq = round_up(a.width[l], 4);    // the input (and its aggregate) in whole 16-byte vectors
-        a.jp[l] = round_up(a.width[l + 1], 8);
-        a.w_off[l] = off; off += a.width[l] * a.jp[l];
-        a.b_off[l] = off; off += a.jp[l];
-        a.W[l] = weights[l]; a.ldw[l] = ldw[l]; a.bias[l] = biases ? biases[l] : nullptr; a.act[l] = acts[l];
-        int &s_in = l % 2 ? sb : sa, &s_out = l % 2 ? sa : sb;
-        s_in = s_in > fq ? s_in : fq;
-        s_out = s_out > fq ? s_out : fq;           // the aggregate is written to the lane's row of the output buffer
-        s_out = s_out > a.jp[l] ? s_out : a.jp[l];
-    }
-    a.sa = sa + 4; a.sb = sb + 4;                  // + 16 bytes: rows start on different banks
-    a.wfloats = round_up(off, 4);
-    a.wave_floats = kRows * (a.sa + a.sb) + 3 * kRows;
-    a.norm_both = norm == GAE_EMBED_NORM_BOTH;
-    a.graph_ids = graph_ids; a.out = out; a.ldo = ldo;
-    int64_t S = (n_out + 8191) / 8192;             // ~8 000 waves on a large set, several groups per wave on a small one
-    a.S = int(S < 4 ? 4 : (S > 64 ? 64 : S));
-    const int64_t waves = (n_out + a.S - 1) / a.S;
-    const int64_t blocks = (waves + kWaves - 1) / kWaves;
+    const int64_t blocks = fill_args(r, a);
+    a.out = out; a.ldo = ldo;
     GAE_REQUIRE(blocks < (int64_t(1) << 31), GAE_E_SIZE, "gae_embed_graphs: n_out = %lld is too large", (long long)n_out);
     const size_t lds = size_t(a.wfloats + kWaves * a.wave_floats) * 4;
     hipStream_t st = gae::as_stream(stream);
-#define GAE_EMBED_LAUNCH(U8)                                                                                           \
-    do {                                                                                                               \
-        static int configured[16] = {0};   /* per (instantiation, device): raised when a launch needs more LDS */      \
-        int dev_ = 0;                                                                                                  \
-        GAE_HIP(hipGetDevice(&dev_));                                                                                  \
-        if (lds > 48 * 1024 && (dev_ < 0 || dev_ >= 16 || configured[dev_] < int(lds))) {                              \
-            GAE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&embed_graphs_kernel<U8>),                      \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));                        \
-            if (dev_ >= 0 && dev_ < 16) configured[dev_] = int(lds);                                                   \
-        }                                                                                                              \
-        hipLaunchKernelGGL((embed_graphs_kernel<U8>), dim3(unsigned(blocks)), dim3(kWaves * 64), lds, st, a);          \
-    } while (0)
-    if (feat_dtype == GAE_U8) GAE_EMBED_LAUNCH(true);
-    else GAE_EMBED_LAUNCH(false);
-#undef GAE_EMBED_LAUNCH
+    if (feat_dtype == GAE_U8) GAE_GRAPHS_LAUNCH(embed_graphs_kernel<true>, a);
+    else GAE_GRAPHS_LAUNCH(embed_graphs_kernel<false>, a);
     GAE_CHECK_LAUNCH("embed_graphs_kernel");
+    return GAE_OK;
+}
+
+extern "C" int gae_score_graphs_usable(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes)
+{
+    if ((!widths && n_layers != 0) || max_graph_nodes < 0) return 0;
+    return shape_taken(f_in, n_layers, widths, max_graph_nodes, 0, nullptr, 0) ? 1 : 0;
+}
+
+extern "C" int gae_score_graphs(const int64_t *graph_ptr, int64_t n_graphs, int64_t n_nodes, int64_t n_edges,
+                                int64_t max_graph_nodes, const int32_t *indptr, const int32_t *indices,
+                                const void *feat, int feat_dtype, int64_t ldf, int64_t f_in, int64_t n_layers,
+                                const int64_t *widths, const float *const *weights, const int64_t *ldw,
+                                const float *const *biases, const int *acts, int norm, const int64_t *graph_ids,
+                                int64_t n_out, int exclude_self, int64_t *counts_out, double *ap_out, float *loss_out,
+                                void *stream)
+{
+    static const char fn[] = "gae_score_graphs";
+    const Request r = {graph_ptr, n_graphs, n_nodes, n_edges, max_graph_nodes, indptr, indices, feat, feat_dtype, ldf,
+                       f_in, n_layers, widths, weights, ldw, biases, acts, norm, graph_ids, n_out};
+    if (const int rc = check_layers(fn, r, 0)) return rc;
+    GAE_REQUIRE(n_layers > 0 || feat_dtype == GAE_F32, GAE_E_DTYPE,
+                "gae_score_graphs: n_layers = 0 takes the feature rows as the fp32 embedding, not dtype %d", feat_dtype);
+    GAE_REQUIRE(exclude_self == 0 || exclude_self == 1, GAE_E_RANGE, "gae_score_graphs: exclude_self = %d (0 or 1)",
+                exclude_self);
+    if (const int rc = check_feature_rows(fn, r)) return rc;
+    if (n_out == 0) return GAE_OK;
+    GAE_REQUIRE(graph_ptr && counts_out && ap_out && loss_out, GAE_E_NULL,
+                "gae_score_graphs: graph_ptr / counts_out / ap_out / loss_out is NULL");
+    if (const int rc = check_arrays(fn, r)) return rc;
+
+    EmbedArgs a;
+    const int64_t blocks = fill_args(r, a);
+    GAE_REQUIRE(blocks < (int64_t(1) << 31), GAE_E_SIZE, "gae_score_graphs: n_out = %lld is too large", (long long)n_out);
+    ScoreArgs t;
+    t.counts = counts_out; t.ap = ap_out; t.loss = loss_out;
+    t.exclude_self = exclude_self;
+    t.max_nodes = int(max_graph_nodes);
+    t.rs = t.max_nodes | 1;
+    t.z_in_b = a.L % 2;
+    // the buffer that held Z takes the per-lane tables afterwards; the other buffer becomes the logit block
+    int &s_z = t.z_in_b ? a.sb : a.sa;
+    const int s_other = t.z_in_b ? a.sa : a.sb;
+    if (kRows * s_z < kTabFloats) s_z = round_up((kTabFloats + kRows - 1) / kRows, 4);
+    const int block = kRows * t.rs > kRows * s_other ? kRows * t.rs : kRows * s_other;
+    t.block_floats = round_up(block, 4);
+    a.wave_floats = kRows * s_z + t.block_floats + 3 * kRows;
+    const size_t lds = size_t(a.wfloats + kWaves * a.wave_floats) * 4;
+    hipStream_t st = gae::as_stream(stream);
+    if (feat_dtype == GAE_U8) GAE_GRAPHS_LAUNCH(score_graphs_kernel<true>, a, t);
+    else GAE_GRAPHS_LAUNCH(score_graphs_kernel<false>, a, t);
+    GAE_CHECK_LAUNCH("score_graphs_kernel");
     return GAE_OK;
 }

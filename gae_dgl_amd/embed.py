@@ -8,7 +8,9 @@ feature is a concatenation of mean, sum, and max aggregation of the hidden vecto
 The checkpoint is the state dict ``train_inductive`` (and the reference's Trainer.save, train_inductive.py:56-57)
 writes.  The whole set is embedded by ``GAE.embed_graphs``: one fused launch where the kernel takes the shapes
 (``--fused auto|on``), the chunked batch -> encode -> readout route otherwise (``--fused off``).  Writes fp32
-[G, 3 d] as .npy and prints the graph count, the route taken and the time of the embedding call."""
+[G, 3 d] as .npy and prints the graph count, the route taken and the time of the embedding call.
+``--scores PATH`` also writes how well each molecule is reconstructed (``GAE.score_graphs``): fp64 [G, 5] .npy with the
+columns loss, auc, ap, n_pos, n_neg; the feature output is the same with and without it."""
 import argparse
 import os
 import time
@@ -30,6 +32,9 @@ def build_parser():
     ap.add_argument("--synthetic", type=int, default=0, metavar="G",
                     help="generate G ZINC-shaped molecules instead of reading --data_file")
     ap.add_argument("--out", "-o", type=str, default=None, help="where the [G, 3 d] fp32 features go (.npy)")
+    ap.add_argument("--scores", type=str, default=None, metavar="PATH",
+                    help="also write the per-molecule reconstruction scores (.npy, [G, 5] fp64: loss, auc, ap, n_pos, "
+                         "n_neg)")
     ap.add_argument("--norm", choices=["none", "both"], default="none",
                     help="none = the reference's plain in-edge sums; both = D^-1/2 A D^-1/2")
     ap.add_argument("--fused", choices=["auto", "on", "off"], default="auto",
@@ -95,6 +100,16 @@ def main(argv=None):
     print(f"Embedded {out.shape[0]} molecules -> {tuple(out.shape)} fp32 | route: {route} | "
           f"{seconds * 1e3:.3f} ms | wrote {args.out}")
     main.features = feats
+    main.scores = None
+    if args.scores:
+        from gae_dgl_amd import metrics
+        sc = model.score_graphs(graphs, fused=fused, batch_size=args.batch_size)
+        table = torch.stack([sc.loss.double(), sc.auc, sc.ap, sc.n_pos.double(), sc.n_neg.double()], 1).cpu().numpy()
+        np.save(args.scores, table)
+        summary = metrics.graph_score_summary(sc)
+        print(f"Scored {table.shape[0]} molecules | AUC {summary['auc']:.4f} | AP {summary['ap']:.4f} | "
+              f"loss (no dropout) {summary['loss']:.4f} | {summary['left_out']} without both classes | wrote {args.scores}")
+        main.scores = sc
     return out
 
 

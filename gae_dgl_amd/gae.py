@@ -160,6 +160,59 @@ class GCN(nn.Module):
         return g.ndata.pop('h')
 
 
+def _empty_scores(B, dev):
+    f64 = lambda: torch.empty(B, dtype=torch.float64, device=dev)       # noqa: E731
+    i64 = lambda: torch.empty(B, dtype=torch.int64, device=dev)         # noqa: E731
+    return ops.GraphScores(torch.empty(B, dtype=torch.float32, device=dev), f64(), f64(), i64(), i64(), i64(), i64())
+
+
+def _put_scores(full, where, part):
+    for dst, src in zip(full, part):
+        dst[where] = src
+
+
+def score_embedding(z, g, exclude_self=True, members=None):
+    """``ops.GraphScores`` of the member graphs of the batched graph ``g`` (``members``: their positions, default all)
+    for a GIVEN node embedding ``z`` [N, d]: members of at most 64 nodes through the no-layer mode of ops.score_graphs
+    (d <= 64), the others one by one through metrics.graph_scores_dense.  What GAE.score_graphs does with the Z of its
+    chunked route and VGAE.score_graphs with mu."""
+    import numpy as np
+    from . import metrics
+    z = z.detach()
+    if z.dtype != torch.float32:
+        z = z.float()
+    g._follow(z)
+    dev = z.device
+    counts = g.batch_num_nodes if g.batch_num_nodes is not None else [g.number_of_nodes()]
+    sizes = np.asarray(counts, dtype=np.int64)
+    members = np.arange(len(sizes), dtype=np.int64) if members is None else np.asarray(members, dtype=np.int64)
+    B = len(members)
+    gp, (indptr, indices) = g.graph_ptr(), g.csr()
+    small = sizes[members] <= ops.EMBED_MAX_NODES
+    if not ops.score_graphs_usable(z.shape[1], [], 0):
+        small[:] = False
+    out = None
+    if small.any():
+        whole = bool(small.all()) and B == len(sizes) and bool((members == np.arange(B)).all())
+        gids = None if whole else torch.from_numpy(np.ascontiguousarray(members[small])).to(dev)
+        out = ops.score_graphs(gp, indptr, indices, z, graph_ids=gids, max_graph_nodes=int(sizes[members][small].max()),
+                               exclude_self=exclude_self)
+        if small.all():
+            return out
+    full = _empty_scores(B, dev)
+    if out is not None:
+        _put_scores(full, torch.from_numpy(np.nonzero(small)[0]).to(dev), out)
+    gp_host = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=gp_host[1:])
+    for k in np.nonzero(~small)[0]:
+        r0, r1 = int(gp_host[members[k]]), int(gp_host[members[k] + 1])
+        e0, e1 = int(indptr[r0]), int(indptr[r1])
+        row = metrics.graph_scores_dense(z[r0:r1], (indptr[r0:r1 + 1].long() - e0, indices[e0:e1].long() - r0), exclude_self)
+        for name, t in zip(full._fields, full):
+            t[k] = row[name]
+    return full
+
+
 class GAE(nn.Module):
     """gae.py:33-61.  ReLU on layers 0..L-2, identity on the last layer; a
     single hidden dim gives one identity layer (gae.py:36-45)."""
@@ -228,28 +281,28 @@ class GAE(nn.Module):
         with torch.no_grad():
             return self._embed_graphs(data, fused, int(batch_size))
 
-    def _embed_graphs(self, data, fused, batch_size):
+    def _graph_set(self, data, who):
+        """what embed_graphs / score_graphs read of ``data`` (a resident set or a batched graph) and what the model
+        allows: (is_set, ids, sizes, identity_ids, feat, mode, codes, why) -- ``why`` names what keeps the model out of
+        the fused kernels (None: taken)"""
         import numpy as np
         is_set = hasattr(data, "subset") and hasattr(data, "sizes_host")
         lins = [layer.apply_mod.linear for layer in self.layers]
         widths = [lin.out_features for lin in lins]
-        d = widths[-1]
         if is_set:
             ids = np.asarray(data.ids, dtype=np.int64)
             sizes = data.sizes_host[ids] if len(ids) else np.zeros(0, np.int64)
-            gp, (indptr, indices), feat, mode0 = data.graph_ptr, (data.indptr, data.indices), data.feat, "none"
+            feat, mode0 = data.feat, "none"
             n_all = len(data.sizes_host)
             identity_ids = len(ids) == n_all and bool((ids == np.arange(n_all)).all())
         else:
             feat = data.ndata['h']
             if not (isinstance(feat, torch.Tensor) and feat.is_cuda):
-                raise ops.GaeHipError("GAE.embed_graphs: the HIP path needs device tensors")
+                raise ops.GaeHipError(f"GAE.{who}: the HIP path needs device tensors")
             data._follow(feat)
             counts = data.batch_num_nodes if data.batch_num_nodes is not None else [data.number_of_nodes()]
             sizes = np.asarray(counts, dtype=np.int64)
             ids, identity_ids, mode0 = np.arange(len(sizes), dtype=np.int64), True, data.norm_mode
-        dev = feat.device
-        B = len(ids)
         modes = {mode0 if layer.norm is None else layer.norm for layer in self.layers}
         codes = [_act_code(layer.apply_mod.activation) for layer in self.layers]
         why = None
@@ -262,6 +315,17 @@ class GAE(nn.Module):
         elif not ops.embed_graphs_usable(lins[0].in_features, widths, 0):
             why = f"the encoder {lins[0].in_features} -> {widths}: 1..{ops.EMBED_MAX_LAYERS} layers of widths <= " \
                   f"{ops.EMBED_MAX_WIDTH}"
+        return is_set, ids, sizes, identity_ids, feat, next(iter(modes)), codes, why
+
+    def _embed_graphs(self, data, fused, batch_size):
+        import numpy as np
+        is_set, ids, sizes, identity_ids, feat, mode, codes, why = self._graph_set(data, "embed_graphs")
+        lins = [layer.apply_mod.linear for layer in self.layers]
+        d = lins[-1].out_features
+        if is_set:
+            gp, (indptr, indices) = data.graph_ptr, (data.indptr, data.indices)
+        dev = feat.device
+        B = len(ids)
         take = sizes <= ops.EMBED_MAX_NODES if why is None else np.zeros(B, dtype=bool)
         if fused is True:
             if why is None and not take.all():
@@ -280,7 +344,7 @@ class GAE(nn.Module):
             if not is_set:
                 gp, (indptr, indices) = data.graph_ptr(), data.csr()
             out = ops.embed_graphs(gp, indptr, indices, feat, [lin.weight for lin in lins], [lin.bias for lin in lins],
-                                   codes, norm=next(iter(modes)), graph_ids=gids, max_graph_nodes=int(sizes[take].max()))
+                                   codes, norm=mode, graph_ids=gids, max_graph_nodes=int(sizes[take].max()))
             if n_take == B:
                 return out
         full = torch.empty(B, 3 * d, dtype=torch.float32, device=dev)
@@ -308,6 +372,73 @@ class GAE(nn.Module):
             if len(sel) == B:
                 return rows
             full[torch.from_numpy(sel).to(dev)] = rows
+        return full
+
+    def score_graphs(self, data, *, fused="auto", exclude_self=True, batch_size=4096):
+        """``ops.GraphScores(loss, auc, ap, n_pos, n_neg, wins, ties)``, device tensors with one entry per graph of
+        ``data`` (the kinds and the order of embed_graphs): how well the encoder reconstructs each molecule -- the
+        ROC-AUC and the average precision of z_i . z_j against the molecule's own adjacency over its ordered pairs
+        (i != j when ``exclude_self``), the exact counts behind them, and the reference's per-molecule weighted BCE
+        (train_inductive.py:44-48) WITHOUT the decoder's dropout.  NaN where a class is missing.
+        ``metrics.graph_score_summary`` condenses them.  Runs under no_grad; parameters and ``g.ndata`` are left as
+        they were; the norm follows the model as in embed_graphs.
+        ``fused=True``: one launch for the whole set (ops.score_graphs: encoder, decoder and ranking per molecule in
+        LDS); raises outside the kernel's shapes (1..4 layers, widths <= 64, graphs <= 64 nodes).  ``"auto"``: that
+        launch for every graph it takes; a model it does not take runs ``batch`` -> ``encode`` in chunks of
+        ``batch_size`` graphs and scores that Z with the kernel's no-layer mode; graphs above 64 nodes are scored one by
+        one (metrics.graph_scores_dense).  ``False``: the chunked route for everything."""
+        if fused not in ("auto", True, False):
+            raise ValueError(f"fused: 'auto', True or False, not {fused!r}")
+        if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
+            raise ValueError(f"batch_size: a positive number of graphs, not {batch_size!r}")
+        with torch.no_grad():
+            return self._score_graphs(data, fused, bool(exclude_self), int(batch_size))
+
+    def _score_graphs(self, data, fused, exclude_self, batch_size):
+        import numpy as np
+        is_set, ids, sizes, identity_ids, feat, mode, codes, why = self._graph_set(data, "score_graphs")
+        lins = [layer.apply_mod.linear for layer in self.layers]
+        dev = feat.device
+        B = len(ids)
+        take = sizes <= ops.EMBED_MAX_NODES if why is None else np.zeros(B, dtype=bool)
+        if fused is True:
+            if why is None and not take.all():
+                why = f"{int((~take).sum())} graph(s) above {ops.EMBED_MAX_NODES} nodes (largest: {int(sizes.max())})"
+            if why is not None:
+                raise ops.GaeHipError(f"GAE.score_graphs(fused=True): the kernel does not take {why}")
+        if fused is False:
+            take = np.zeros(B, dtype=bool)
+        out = None
+        n_take = int(take.sum())
+        if n_take:
+            if n_take == B and identity_ids:
+                gids = None
+            else:
+                gids = torch.from_numpy(np.ascontiguousarray(ids[take])).to(dev)
+            gp, (indptr, indices) = (data.graph_ptr, (data.indptr, data.indices)) if is_set else \
+                (data.graph_ptr(), data.csr())
+            out = ops.score_graphs(gp, indptr, indices, feat, [lin.weight for lin in lins], [lin.bias for lin in lins],
+                                   codes, norm=mode, graph_ids=gids, max_graph_nodes=int(sizes[take].max()),
+                                   exclude_self=exclude_self)
+            if n_take == B:
+                return out
+        full = _empty_scores(B, dev)
+        if out is not None:
+            _put_scores(full, torch.from_numpy(np.nonzero(take)[0]).to(dev), out)
+        rest = np.nonzero(~take)[0]
+        if not is_set:
+            if len(rest):
+                # a batched graph is one batch: encode() embeds all of it, the members still missing are scored
+                try:
+                    z = self.encode(data)
+                finally:
+                    data.ndata['h'] = feat
+                _put_scores(full, torch.from_numpy(rest).to(dev), score_embedding(z, data, exclude_self, members=rest))
+            return full
+        for lo in range(0, len(rest), batch_size):
+            sel = rest[lo:lo + batch_size]
+            bg = data.batch(ids[sel])
+            _put_scores(full, torch.from_numpy(sel).to(dev), score_embedding(self.encode(bg), bg, exclude_self))
         return full
 
     def reconstruction_loss(self, g, criterion="bce", scope="batch", samples=None):

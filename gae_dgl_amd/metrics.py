@@ -126,3 +126,90 @@ def rank_metrics(greater, equal, candidates, ks=(1, 10, 50, 100)):
     has = candidates > 0
     out["auc"] = float((1 - above[has] / candidates[has].double()).mean()) if bool(has.any()) else nan
     return out
+
+
+def graph_scores_dense(z_g, csr_g, exclude_self=True):
+    """The per-graph scores of ``GAE.score_graphs`` / ``ops.score_graphs`` for ONE graph of any size, by the definitions
+    taken literally with torch ops on the device of ``z_g`` [n, d]: the route of graphs above the fused kernel's 64
+    nodes, and a cross-check of it.  ``csr_g`` = (indptr [n + 1], indices) of the graph alone, local column ids (entries
+    outside [0, n) are ignored, a repeated entry is one positive).  Logits: the k-ascending chain from 0 of
+    z_i[k] z_j[k], every step rounded to fp32 (through an exact fp64 product: the fmaf chain up to double rounding).
+    Returns a dict of Python numbers: loss, auc, ap (NaN where a class is missing), n_pos, n_neg, wins, ties (-1, and
+    NaN, when a logit is not finite)."""
+    nan = float("nan")
+    z = torch.as_tensor(z_g).detach().float()
+    n, d = z.shape
+    dev = z.device
+    indptr, indices = (torch.as_tensor(t, device=dev).long() for t in csr_g)
+    rows = torch.repeat_interleave(torch.arange(n, device=dev), indptr[1:] - indptr[:-1])
+    cols = indices[int(indptr[0]):int(indptr[-1])]
+    inside = (cols >= 0) & (cols < n)
+    rows, cols = rows[inside], cols[inside]
+    s = torch.zeros(n, n, dtype=torch.float32, device=dev)
+    zd = z.double()
+    for k in range(d):
+        s = (s.double() + zd[:, k:k + 1] * zd[None, :, k]).float()
+    if not bool(torch.isfinite(s).all()):
+        return {"loss": nan, "auc": nan, "ap": nan, "n_pos": -1, "n_neg": -1, "wins": -1, "ties": -1}
+    # the loss of train_inductive.py:44-48 on this graph alone: all n^2 pairs, y_ij = the number of entries j in row i
+    y = torch.zeros(n * n, dtype=torch.float64, device=dev)
+    y.index_put_((rows * n + cols,), torch.ones(rows.numel(), dtype=torch.float64, device=dev), accumulate=True)
+    y = y.view(n, n)
+    S = float(y.sum())
+    x = s.double()
+    sp = torch.nn.functional.softplus
+    # the positives in CSR order, first occurrences
+    keys = rows * n + cols
+    if exclude_self:
+        keys = keys[rows != cols]
+    if keys.numel():
+        uniq, inv = torch.unique(keys, return_inverse=True)
+        first = torch.full((uniq.numel(),), keys.numel(), dtype=torch.long, device=dev)
+        first.scatter_reduce_(0, inv, torch.arange(keys.numel(), device=dev), reduce="amin")
+        keys = keys[torch.sort(first).values]
+    flat = s.view(-1)
+    member = torch.ones(n, n, dtype=torch.bool, device=dev)
+    if exclude_self:
+        member.fill_diagonal_(False)
+    is_pos = torch.zeros(n * n, dtype=torch.bool, device=dev)
+    is_pos[keys] = True
+    P = flat[keys]
+    Q = flat[member.view(-1) & ~is_pos]
+    n_pos, n_neg = int(P.numel()), int(Q.numel())
+    out = {"n_pos": n_pos, "n_neg": n_neg, "wins": 0, "ties": 0, "auc": nan, "ap": nan, "loss": nan}
+    if n_pos > 0:
+        pw = (float(n) * n - S) / S
+        out["loss"] = float((sp(x) + y * ((pw - 1) * sp(-x) - x)).sum() / (float(n) * n))
+    if n_pos > 0 and n_neg > 0:
+        qs, ps = torch.sort(Q).values, torch.sort(P).values
+        lo, hi = torch.searchsorted(qs, P, right=False), torch.searchsorted(qs, P, right=True)
+        out["wins"], out["ties"] = int(lo.sum()), int((hi - lo).sum())
+        out["auc"] = (out["wins"] + out["ties"] / 2) / (float(n_pos) * n_neg)
+        pos_ge = n_pos - torch.searchsorted(ps, P, right=False)
+        all_ge = pos_ge + (n_neg - lo)
+        out["ap"] = float((pos_ge.double() / all_ge.double()).sum() / n_pos)
+    return out
+
+
+def graph_score_summary(scores):
+    """What a set of per-graph scores says in a few numbers.  ``scores``: a ``GraphScores`` (or anything with auc, ap,
+    loss, n_pos, n_neg, wins, ties of one length).  Over the graphs that have both classes (n_pos > 0 and n_neg > 0;
+    refused graphs carry -1): the means ``auc``, ``ap``, ``loss``; ``micro_auc`` = (sum wins + sum ties / 2) / sum
+    n_pos n_neg -- every (positive, negative) pair of the set weighs the same; ``graphs`` = how many they are,
+    ``left_out`` = the others.  NaN when no graph has both classes."""
+    n_pos, n_neg, wins, ties = (torch.as_tensor(getattr(scores, k)).reshape(-1).long()
+                                for k in ("n_pos", "n_neg", "wins", "ties"))
+    auc, ap, loss = (torch.as_tensor(getattr(scores, k)).reshape(-1).double() for k in ("auc", "ap", "loss"))
+    both = (n_pos > 0) & (n_neg > 0)
+    m = int(both.sum())
+    out = {"graphs": m, "left_out": int(both.numel()) - m}
+    nan = float("nan")
+    if m == 0:
+        out.update(auc=nan, ap=nan, loss=nan, micro_auc=nan)
+        return out
+    out["auc"] = float(auc[both].mean())
+    out["ap"] = float(ap[both].mean())
+    out["loss"] = float(loss[both].mean())
+    pairs = float((n_pos[both].double() * n_neg[both].double()).sum())
+    out["micro_auc"] = (float(wins[both].double().sum()) + float(ties[both].double().sum()) / 2) / pairs
+    return out

@@ -70,6 +70,10 @@ def build_parser():
                          "trains on its share (dataset.shard_order); the parameter gradients are averaged by one small "
                          "all-reduce per step (1 808 floats for 39 -> 32 -> 16), inside the captured step -- the update "
                          "of one process whose loss is the mean of the replicas' batch losses.  Rank 0 saves and plots")
+    ap.add_argument("--val_metrics", action="store_true",
+                    help="after each epoch, score the validation molecules (GAE.score_graphs, one launch for the whole "
+                         "split): mean per-molecule ROC-AUC and average precision of the reconstruction and the "
+                         "validation loss WITHOUT the decoder's dropout; --distributed: rank 0 scores the whole split")
     ap.add_argument("--dataloader", action="store_true",
                     help="batch through torch's DataLoader + collate exactly like the reference (one small pinned "
                          "copy of the graph ids per batch) instead of the device-resident epoch iterator")
@@ -272,6 +276,8 @@ def main(argv=None):
         captured = CapturedInductiveStep(model, trainer.optim, loaders["train"].dataset, args.batch_size,
                                          replicas=shard is not None, loss_scope=args.loss_scope)
     history = {"train": [], "val": []}
+    main.val_metrics = {"auc": [], "ap": [], "loss": []} if args.val_metrics else None
+    val_set = graphs.subset(graphs.ids[order[:n_val]])
     say("Training Start")
     for epoch in range(args.n_epochs):
         model.train()
@@ -280,8 +286,15 @@ def main(argv=None):
             trainer.save(epoch, args.save_dir)
         model.eval()         # no effect on the decoder's dropout, exactly like the reference (gae.py:70)
         history["val"].append(_mean_over_replicas(_run_epoch(trainer, loaders["val"], train=False)))
-        say(f"Epoch: {epoch:02d} | Train Loss: {history['train'][-1]:.4f} | "
-            f"Validation Loss: {history['val'][-1]:.4f}")
+        line = f"Epoch: {epoch:02d} | Train Loss: {history['train'][-1]:.4f} | Validation Loss: {history['val'][-1]:.4f}"
+        if args.val_metrics and _rank() == 0:
+            from gae_dgl_amd import metrics
+            summary = metrics.graph_score_summary(model.score_graphs(val_set))
+            for k in main.val_metrics:
+                main.val_metrics[k].append(summary[k])
+            line += f" | Val AUC: {summary['auc']:.4f} | Val AP: {summary['ap']:.4f} | " \
+                    f"Val loss (no dropout): {summary['loss']:.4f}"
+        say(line)
     if not args.no_plot and _rank() == 0:
         plot(history["train"], history["val"], args.save_dir)
     main.final_state = {k: v.detach().clone() for k, v in model.state_dict().items()}
@@ -292,6 +305,9 @@ def main(argv=None):
         torch.cuda.synchronize()
         dist.destroy_process_group()
     return history["train"], history["val"]
+
+
+main.val_metrics = None      # --val_metrics: {"auc", "ap", "loss"} -> one value per epoch
 
 
 if __name__ == '__main__':

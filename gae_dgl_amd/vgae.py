@@ -12,7 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .gae import GCN, InnerProductDecoder, identity
+from .gae import GCN, InnerProductDecoder, identity, score_embedding
 
 
 # mu and log sigma heads as ONE fused launch on the shared aggregate (gae_x_gcn_layer_fused2) and one packed gradient
@@ -120,6 +120,17 @@ class VGAE(nn.Module):
             mu, _ = self.encode(g)
         return ops.decoder_rank(mu, pairs, g, filter_graph=filter_graph, scope=scope, exclude_self=exclude_self,
                                 exclude_edges=exclude_edges)
+
+    def score_graphs(self, g, *, exclude_self=True):
+        """GAE.score_graphs on the mean embedding mu (no noise) of a batched graph ``g``: ``ops.GraphScores`` per member
+        graph, mu scored through the no-layer mode of ops.score_graphs (gae.score_embedding)"""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                mu, _ = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return score_embedding(mu, g, exclude_self)
 
     def forward(self, g):
         """sampled Z Z^T logits (dense parity / inference path)"""

@@ -9,7 +9,8 @@
  *   gae_spx_*, gae_dense_to_csr_*   layer 1 from the non-zeros of constant input features (gae_dgl_amd.SparseFeatures)
  *   gae_linear2_*, gae_gcn2_*   the dense halves of a two-layer encoder on millions of rows (row-sharded RMAT path)
  * and gae_decoder_bce_sampled, an unbiased stochastic estimate of gae_decoder_bce's loss for graphs beyond the N^2 sum,
- * and gae_decoder_rank, the filtered rank of given pairs among all candidates of gae_decoder_topk's rule.
+ * and gae_decoder_rank, the filtered rank of given pairs among all candidates of gae_decoder_topk's rule,
+ * and gae_score_graphs, the per-molecule reconstruction scores (AUC counts, average precision, loss) of a resident set.
  * Same conventions as gae_hip.h: caller-owned buffers, 0 / negative / hipError_t return codes, asynchronous launches on
  * the stream passed last.  These signatures may change between versions without a GAE_VERSION major bump. */
 #ifndef GAE_HIP_EXPERIMENTAL_H
@@ -413,6 +414,46 @@ int gae_embed_graphs(const int64_t *graph_ptr, int64_t n_graphs, int64_t n_nodes
                      const int64_t *widths, const float *const *weights, const int64_t *ldw,
                      const float *const *biases, const int *acts, int norm, const int64_t *graph_ids,
                      int64_t n_out, float *out, int64_t ldo, void *stream);
+
+/* ---- K20: how well a molecule set is reconstructed, per graph, in ONE launch (GAE.score_graphs, ops.score_graphs)
+ * K19's pipeline with a second tail: for every selected member graph the same encoder on the graph's own rows (the Z
+ * that is ranked has the bits of the Z gae_embed_graphs reads out), then the inner-product decoder on the graph's own
+ * ordered pairs, ranked and scored in LDS.  Nothing of width n_nodes and nothing of size n^2 reaches memory.
+ * Arguments up to n_out: exactly gae_embed_graphs's, with one more mode: n_layers = 0 takes the fp32 feature rows AS
+ * the embedding Z (f_in = its width, 1..64; feat_dtype must be GAE_F32; widths .. acts may be NULL) -- a Z produced by
+ * any other route (VGAE's mu, a wide model) is scored through it.
+ * For graph g with rows [r0, r0 + n):
+ *   logits     s_ij = the fmaf chain over k = 0 .. d-1 ascending, from 0.f, of z_i[k] z_j[k]; no dropout.  A function of
+ *              the bits of z_i and z_j only; s_ij == s_ji bit for bit
+ *   pairs      the ordered pairs (i, j) of the graph, i != j when exclude_self = 1.  (i, j) is a POSITIVE iff column
+ *              r0 + j occurs in CSR row r0 + i (a repeated entry counts once; columns outside the graph's own rows are
+ *              ignored); every other pair is a NEGATIVE
+ *   counts_out int64 [n_out][4] = n_pos, n_neg, wins, ties: wins / ties = the number of (positive p, negative q) with
+ *              s_p > s_q / s_p == s_q.  Exact integers: AUC = (wins + ties / 2) / (n_pos n_neg) is the host's division
+ *   ap_out     fp64 [n_out] = (1 / n_pos) sum_p pos_ge(p) / all_ge(p), pos_ge / all_ge = the positives / all pairs with
+ *              score >= s_p (average precision, ties grouped: sklearn's definition).  fp64 quotients; the positives of a
+ *              CSR row are added in entry order (first occurrences), then the rows' sums first row to last
+ *   loss_out   fp32 [n_out] = gae_decoder_bce_graphs's l_g without dropout (train_inductive.py:44-48 on this graph
+ *              alone): all n^2 ordered pairs, self pairs included, y_ij = the number of entries j in row i,
+ *              pos_weight = (n^2 - S) / S; fp32 terms, fp64 sums per row, rows added first to last
+ * DEGENERATE SLOTS: n_pos = 0: loss NaN; n_pos = 0 or n_neg = 0: ap NaN (wins = ties = 0; an empty graph gives zeros).
+ * A graph id outside [0, n_graphs), a node range outside [0, n_nodes], a graph of more than max_graph_nodes (<= 64)
+ * rows, or a non-finite logit anywhere in the graph: the four counts -1, ap and loss NaN.  Row pointers and column ids
+ * as gae_embed_graphs: nothing outside the arrays is read or written.
+ * INDEPENDENCE: a graph's outputs are functions of that graph's rows alone, with the same bits in any subset, order,
+ * position, repeat or run.  No float atomics.
+ * SHAPES TAKEN: 0 <= n_layers <= 4, f_in and every width in 1..64, max_graph_nodes <= 64: gae_score_graphs_usable
+ * (1 = taken; agrees with gae_embed_graphs_usable for n_layers >= 1).  Argument errors as gae_embed_graphs, plus
+ * exclude_self outside {0, 1} (GAE_E_RANGE) and n_layers = 0 with uint8 rows (GAE_E_DTYPE).  One launch, no workspace. */
+int gae_score_graphs_usable(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes);
+
+int gae_score_graphs(const int64_t *graph_ptr, int64_t n_graphs, int64_t n_nodes, int64_t n_edges,
+                     int64_t max_graph_nodes, const int32_t *indptr, const int32_t *indices,
+                     const void *feat, int feat_dtype, int64_t ldf, int64_t f_in, int64_t n_layers,
+                     const int64_t *widths, const float *const *weights, const int64_t *ldw,
+                     const float *const *biases, const int *acts, int norm, const int64_t *graph_ids,
+                     int64_t n_out, int exclude_self, int64_t *counts_out, double *ap_out, float *loss_out,
+                     void *stream);
 
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
