@@ -173,6 +173,11 @@ SIGNATURES = {
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),
+    "gae_embed_graphs_bwd_usable": (_int, [_i64, _i64, _p, _i64]),
+    "gae_embed_graphs_bwd_workspace_bytes": (_i64, [_i64, _i64, _p, _i64]),
+    "gae_embed_graphs_bwd": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
+                                    _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p]),
+    "gae_segment_readout_bwd": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p]),
     "gae_score_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_score_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _int, _p, _p, _p, _p]),

@@ -263,23 +263,31 @@ class GAE(nn.Module):
         return ops.decoder_rank(z, pairs, g, filter_graph=filter_graph, scope=scope, exclude_self=exclude_self,
                                 exclude_edges=exclude_edges)
 
-    def embed_graphs(self, data, *, fused="auto", batch_size=4096):
+    def embed_graphs(self, data, *, fused="auto", batch_size=4096, grad=False):
         """fp32 [n_graphs, 3 d]: the molecule feature of the reference's chemistry table (README.md:54: mean | sum |
         max of the hidden vectors, 48 numbers for ``--hidden_dims 32 16``) of every graph of ``data`` -- a
         ``DeviceGraphDataset`` or a ``subset()`` view (rows in the order of ``data.ids``), or a batched graph with
-        ``graph_ptr()`` and ``ndata['h']`` (rows in member order).  Runs under no_grad; parameters and ``g.ndata`` are
-        left as they were.  The norm follows the model as in encode(): ``GAE(norm=...)`` if given, else the graph's
-        ``norm_mode`` (the batches of a dataset carry "none").
+        ``graph_ptr()`` and ``ndata['h']`` (rows in member order).  Parameters and ``g.ndata`` are left as they were.
+        The norm follows the model as in encode(): ``GAE(norm=...)`` if given, else the graph's ``norm_mode`` (the
+        batches of a dataset carry "none").
         ``fused=True``: one launch for the whole set (ops.embed_graphs: encoder and readout per molecule, nothing of
         width N written); raises when the model or a graph lies outside the kernel's shapes (1..4 layers, widths <= 64,
         graphs <= 64 nodes).  ``fused=False``: ``batch`` -> ``encode`` -> ``readout_nodes`` in chunks of ``batch_size``
-        graphs.  ``"auto"``: the kernel for every graph it takes, the chunked route for the rest."""
+        graphs.  ``"auto"``: the kernel for every graph it takes, the chunked route for the rest.
+        ``grad=False`` (default) runs under no_grad.  ``grad=True`` runs with autograd, for fine-tuning the encoder
+        through the features: the same forward values bit for bit, and a result whose backward reaches the encoder's
+        parameters -- through the kernel pair gae_embed_graphs / gae_embed_graphs_bwd (K19 / K21) where ``fused`` says
+        so (``True``: the pair or an error; ``"auto"``: the pair for every graph BOTH kernels take), through the
+        chunked route and the readout's own backward elsewhere; the rows are scattered into place with differentiable
+        indexing."""
         if fused not in ("auto", True, False):
             raise ValueError(f"fused: 'auto', True or False, not {fused!r}")
         if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
             raise ValueError(f"batch_size: a positive number of graphs, not {batch_size!r}")
-        with torch.no_grad():
-            return self._embed_graphs(data, fused, int(batch_size))
+        if grad not in (True, False):
+            raise ValueError(f"grad: True or False, not {grad!r}")
+        with torch.set_grad_enabled(bool(grad)):
+            return self._embed_graphs(data, fused, int(batch_size), grad=bool(grad))
 
     def _graph_set(self, data, who):
         """what embed_graphs / score_graphs read of ``data`` (a resident set or a batched graph) and what the model
@@ -317,11 +325,15 @@ class GAE(nn.Module):
                   f"{ops.EMBED_MAX_WIDTH}"
         return is_set, ids, sizes, identity_ids, feat, next(iter(modes)), codes, why
 
-    def _embed_graphs(self, data, fused, batch_size):
+    def _embed_graphs(self, data, fused, batch_size, grad=False):
         import numpy as np
         is_set, ids, sizes, identity_ids, feat, mode, codes, why = self._graph_set(data, "embed_graphs")
         lins = [layer.apply_mod.linear for layer in self.layers]
         d = lins[-1].out_features
+        if grad and why is None and any(p.requires_grad for p in self.parameters()) and \
+                not ops.embed_graphs_bwd_usable(lins[0].in_features, [lin.out_features for lin in lins], 0):
+            why = f"the encoder {lins[0].in_features} -> {[lin.out_features for lin in lins]} in its backward " \
+                  f"(ops.embed_graphs_bwd_usable)"
         if is_set:
             gp, (indptr, indices) = data.graph_ptr, (data.indptr, data.indices)
         dev = feat.device

@@ -12,7 +12,8 @@ from .. import _lib
 from .._lib import GaeHipError
 from ._base import _gpu, _on_device, _ptr, _stream
 
-__all__ = ['EMBED_MAX_LAYERS', 'EMBED_MAX_WIDTH', 'EMBED_MAX_NODES', 'embed_graphs_usable', 'embed_graphs']
+__all__ = ['EMBED_MAX_LAYERS', 'EMBED_MAX_WIDTH', 'EMBED_MAX_NODES', 'embed_graphs_usable', 'embed_graphs',
+           'embed_graphs_bwd_usable', 'embed_graphs_bwd']
 
 EMBED_MAX_LAYERS, EMBED_MAX_WIDTH, EMBED_MAX_NODES = 4, 64, 64      # the shapes gae_embed_graphs takes
 
@@ -113,19 +114,16 @@ def _request(who, graph_ptr, indptr, indices, feat, weights, biases, acts, norm,
     return args, keep, dev, B, widths, N, code, f_in
 
 
-def embed_graphs(graph_ptr, indptr, indices, feat, weights, biases, acts, norm="none", graph_ids=None,
-                 max_graph_nodes=None):
-    """[B, 3 d] fp32: row k = [mean | sum | max] over the nodes of member graph ``graph_ids[k]`` (None: every graph in
-    order) of the embedding the encoder ``weights`` / ``biases`` / ``acts`` (per layer: [out, in] fp32, [out] or None,
-    ACT_IDENTITY / ACT_RELU) gives on that graph alone.  ``graph_ptr`` int64 [G + 1], ``indptr`` / ``indices`` the int32
-    CSR of the whole set (rows = destination, global column ids), ``feat`` uint8 or fp32 [N, F]: the arrays of a
-    ``DeviceGraphDataset`` as they are.  ``norm``: "none" or "both" (D^-1/2 A D^-1/2 from the row lengths).
-    ``max_graph_nodes``: host-side bound of the selected graphs' node counts (None: computed from ``graph_ptr``, one
-    device read-back).  One launch; a graph's row has the same bits whatever else is embedded with it.
-    Raises GaeHipError for CPU tensors and for shapes the kernel does not take (``embed_graphs_usable``); there is no
-    other route behind this function."""
-    head, keep, dev, B, widths, N, code, _ = _request("embed_graphs", graph_ptr, indptr, indices, feat, weights, biases,
-                                                      acts, norm, graph_ids, max_graph_nodes)
+def embed_graphs_bwd_usable(f_in, widths, max_graph_nodes=0):
+    """does gae_embed_graphs_bwd (K21) take the encoder ``f_in -> widths[0] -> ...``?  Narrower than
+    ``embed_graphs_usable``: every layer's aggregated input and the weights in both orientations must fit the LDS, the
+    weight-gradient tiles the registers.  Asks the library; no launch, no GPU."""
+    widths = [int(w) for w in widths]
+    arr = (ctypes.c_int64 * max(len(widths), 1))(*widths)
+    return bool(_lib.load().gae_embed_graphs_bwd_usable(int(f_in), len(widths), arr, int(max_graph_nodes)))
+
+
+def _launch_forward(head, dev, B, widths, N, code, norm):
     d = widths[-1] if widths else 0
     out = torch.empty(B, 3 * d, dtype=torch.float32, device=dev)
     args = head + (_ptr(out), max(3 * d, 1))
@@ -137,6 +135,124 @@ def embed_graphs(graph_ptr, indptr, indices, feat, weights, biases, acts, norm="
             _ops.profiler.wrap(("embed_graphs", N, B, tuple(widths)), launch)
         else:
             launch()
+    return out
+
+
+def embed_graphs_bwd(graph_ptr, indptr, indices, feat, weights, biases, acts, d_out, norm="none", graph_ids=None,
+                     max_graph_nodes=None, want_weights=None, want_biases=None):
+    """``(dWs, dbs)``: the gradients of the encoder's weights and biases for ``d_out`` [B, 3 d], the gradient of a loss
+    with respect to the rows ``embed_graphs`` returns for the same arguments (K21, gae_embed_graphs_bwd: the encoder is
+    recomputed per molecule in LDS, only the gradients reach memory).  ``want_weights`` / ``want_biases``: one flag per
+    layer (None: all; a layer without bias never gets one); an entry that is not wanted comes back as None.  Same call,
+    same bits.  Raises GaeHipError for shapes the kernel does not take (``embed_graphs_bwd_usable``)."""
+    head, keep, dev, B, widths, N, code, f_in = _request("embed_graphs_bwd", graph_ptr, indptr, indices, feat, weights,
+                                                          biases, acts, norm, graph_ids, max_graph_nodes)
+    L = len(widths)
+    if L == 0:
+        raise GaeHipError("embed_graphs_bwd: an encoder of at least one layer expected")
+    d = widths[-1]
+    g = _gpu(d_out, "d_out").detach()
+    if g.dtype != torch.float32 or tuple(g.shape) != (B, 3 * d) or g.device != dev:
+        raise GaeHipError(f"embed_graphs_bwd: d_out must be fp32 [{B}, {3 * d}] on {dev}, got {g.dtype} "
+                          f"{tuple(g.shape)} on {g.device}")
+    if g.stride(1) != 1 or (B > 1 and g.stride(0) < 3 * d):
+        g = g.contiguous()
+    ldd = g.stride(0) if B > 1 else max(3 * d, 1)
+    biases = [None] * L if biases is None else list(biases)
+    want_weights = [True] * L if want_weights is None else [bool(w) for w in want_weights]
+    want_biases = [True] * L if want_biases is None else [bool(w) for w in want_biases]
+    ins = [f_in] + widths[:-1]
+    dWs = [torch.empty(widths[l], ins[l], dtype=torch.float32, device=dev) if want_weights[l] else None for l in range(L)]
+    dbs = [torch.empty(widths[l], dtype=torch.float32, device=dev) if want_biases[l] and biases[l] is not None else None
+           for l in range(L)]
+    c_widths = (ctypes.c_int64 * L)(*widths)
+    nbytes = int(_lib.load().gae_embed_graphs_bwd_workspace_bytes(int(f_in), L, c_widths, B))
+    if nbytes < 0:
+        _lib.check(nbytes, "gae_embed_graphs_bwd_workspace_bytes")
+    ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
+    p_dw, p_db, lddw = (ctypes.c_void_p * L)(), (ctypes.c_void_p * L)(), (ctypes.c_int64 * L)()
+    for l in range(L):
+        p_dw[l] = dWs[l].data_ptr() if dWs[l] is not None else None
+        p_db[l] = dbs[l].data_ptr() if dbs[l] is not None else None
+        lddw[l] = max(ins[l], 1)
+    args = head + (_ptr(g), int(ldd), p_dw, lddw, p_db, _ptr(ws), ws.numel())
+    embed_graphs_bwd.last_request = {"n_out": B, "widths": widths, "norm": norm, "dtype": code,
+                                     "want_weights": want_weights, "want_biases": want_biases}
+    with _on_device(dev):
+        def launch():
+            _lib.call("gae_embed_graphs_bwd", *args, _stream())
+        if _ops.profiler is not None:
+            _ops.profiler.wrap(("embed_graphs_bwd", N, B, tuple(widths)), launch)
+        else:
+            launch()
+    del keep
+    return dWs, dbs
+
+
+embed_graphs_bwd.last_request = None
+
+
+class _EmbedGraphs(torch.autograd.Function):
+    """ops.embed_graphs with a backward: one gae_embed_graphs launch forward, one gae_embed_graphs_bwd call backward; the
+    node holds the call's inputs and nothing per node"""
+
+    @staticmethod
+    def forward(ctx, static, L, *params):
+        graph_ptr, indptr, indices, feat, acts, norm, graph_ids, max_graph_nodes = static
+        weights, biases = list(params[:L]), list(params[L:])
+        head, keep, dev, B, widths, N, code, _ = _request("embed_graphs", graph_ptr, indptr, indices, feat, weights,
+                                                          biases, acts, norm, graph_ids, max_graph_nodes)
+        out = _launch_forward(head, dev, B, widths, N, code, norm)
+        ctx.static, ctx.L = static[:7] + (head[4],), L           # (max_graph_nodes as resolved by the forward)
+        ctx.save_for_backward(*[p for p in params if p is not None])
+        ctx.has_bias = [b is not None for b in biases]
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        graph_ptr, indptr, indices, feat, acts, norm, graph_ids, max_graph_nodes = ctx.static
+        L, saved = ctx.L, list(ctx.saved_tensors)
+        weights = saved[:L]
+        it = iter(saved[L:])
+        biases = [next(it) if has else None for has in ctx.has_bias]
+        need = ctx.needs_input_grad[2:]
+        dWs, dbs = embed_graphs_bwd(graph_ptr, indptr, indices, feat, weights, biases, acts, d_out.float(), norm=norm,
+                                    graph_ids=graph_ids, max_graph_nodes=max_graph_nodes,
+                                    want_weights=need[:L], want_biases=need[L:])
+        return (None, None) + tuple(dWs) + tuple(dbs)
+
+
+def embed_graphs(graph_ptr, indptr, indices, feat, weights, biases, acts, norm="none", graph_ids=None,
+                 max_graph_nodes=None):
+    """[B, 3 d] fp32: row k = [mean | sum | max] over the nodes of member graph ``graph_ids[k]`` (None: every graph in
+    order) of the embedding the encoder ``weights`` / ``biases`` / ``acts`` (per layer: [out, in] fp32, [out] or None,
+    ACT_IDENTITY / ACT_RELU) gives on that graph alone.  ``graph_ptr`` int64 [G + 1], ``indptr`` / ``indices`` the int32
+    CSR of the whole set (rows = destination, global column ids), ``feat`` uint8 or fp32 [N, F]: the arrays of a
+    ``DeviceGraphDataset`` as they are.  ``norm``: "none" or "both" (D^-1/2 A D^-1/2 from the row lengths).
+    ``max_graph_nodes``: host-side bound of the selected graphs' node counts (None: computed from ``graph_ptr``, one
+    device read-back).  One launch; a graph's row has the same bits whatever else is embedded with it.
+    With grad mode on and a weight or bias that requires a gradient the result carries one: its backward is one
+    ``embed_graphs_bwd`` call (K21) that gives gradients to exactly the parameters that require them; the forward launch
+    and its values are the same.  No gradient reaches ``feat``.
+    Raises GaeHipError for CPU tensors and for shapes the kernel does not take (``embed_graphs_usable``; with a
+    gradient also ``embed_graphs_bwd_usable``: never a detached result instead); there is no other route behind this
+    function."""
+    weights = list(weights)
+    biases = [None] * len(weights) if biases is None else list(biases)
+    if torch.is_grad_enabled() and any(isinstance(p, torch.Tensor) and p.requires_grad for p in weights + biases):
+        if len(weights) != len(biases):
+            raise GaeHipError("embed_graphs: weights, biases and acts must list the same layers")
+        f_in = int(feat.shape[1]) if isinstance(feat, torch.Tensor) and feat.dim() == 2 else 0
+        widths = [int(W.shape[0]) for W in weights]
+        if not embed_graphs_bwd_usable(f_in, widths, 0):
+            raise GaeHipError(f"embed_graphs: a gradient is asked for, but the backward kernel (gae_embed_graphs_bwd) "
+                              f"does not take the encoder {f_in} -> {widths} (embed_graphs_bwd_usable); run under "
+                              f"no_grad or use the chunked route")
+        static = (graph_ptr, indptr, indices, feat, tuple(int(a) for a in acts), norm, graph_ids, max_graph_nodes)
+        return _EmbedGraphs.apply(static, len(weights), *weights, *biases)
+    head, keep, dev, B, widths, N, code, _ = _request("embed_graphs", graph_ptr, indptr, indices, feat, weights, biases,
+                                                      acts, norm, graph_ids, max_graph_nodes)
+    out = _launch_forward(head, dev, B, widths, N, code, norm)
     del keep
     return out
 

@@ -12,7 +12,7 @@ from ._base import _dtype_code, _f32, _gpu, _on_device, _ptr, _rowmajor, _stream
 
 __all__ = [
     'csr_from_coo', 'degree_norm', 'rows_pack', 'csr_to_dense', 'batch_plan', 'batch_select', 'batch_plan_next',
-    'batch_feature_ld', 'batch_gather', 'batch_gather_next', 'segment_readout',
+    'batch_feature_ld', 'batch_gather', 'batch_gather_next', 'segment_readout', 'segment_readout_bwd',
 ]
 
 
@@ -199,10 +199,7 @@ def batch_gather_next(graph_ptr, ds_indptr, ds_indices, ds_feat, order, cursor, 
     return ptrs[0], ptrs[1]
 
 
-def segment_readout(Z, graph_ptr):
-    """[mean | sum | max] of the rows of Z [N, d] per member graph (README.md:54 of the reference: the 48-d molecule
-    feature); ``graph_ptr`` int64 [G + 1] node offsets on the device.  Returns [G, 3 d] fp32.  Inference-side op:
-    no autograd."""
+def _segment_readout_launch(Z, graph_ptr):
     Z, ldz = _rowmajor(_gpu(Z, "Z").detach(), "Z")
     if Z.dtype != torch.float32:
         raise GaeHipError(f"segment_readout: fp32 embeddings expected, got {Z.dtype}")
@@ -212,4 +209,48 @@ def segment_readout(Z, graph_ptr):
     out = torch.empty(max(G_, 0), 3 * d, dtype=torch.float32, device=Z.device)
     with _on_device(Z.device):
         _lib.call("gae_segment_readout", _ptr(Z), ldz, n, d, _ptr(gp), G_, _ptr(out), max(3 * d, 1), _stream())
-    return out
+    return out, Z, ldz, gp
+
+
+def segment_readout_bwd(Z, graph_ptr, d_out):
+    """the gradient of ``segment_readout`` with respect to Z [N, d] for ``d_out`` [G, 3 d] (gae_segment_readout_bwd):
+    dZ[r] = d_sum + d_mean / n + d_max on the LOWEST row of the graph that attains the column's maximum.  Rows that
+    belong to no graph get zeros."""
+    Z, ldz = _rowmajor(_gpu(Z, "Z").detach(), "Z")
+    if Z.dtype != torch.float32:
+        raise GaeHipError(f"segment_readout_bwd: fp32 embeddings expected, got {Z.dtype}")
+    gp = _gpu(graph_ptr, "graph_ptr").to(torch.int64).contiguous()
+    n, d = Z.shape
+    G_ = gp.numel() - 1
+    g, ldd = _rowmajor(_gpu(d_out, "d_out").detach().float(), "d_out")
+    if tuple(g.shape) != (max(G_, 0), 3 * d) or g.device != Z.device:
+        raise GaeHipError(f"segment_readout_bwd: d_out must be [{max(G_, 0)}, {3 * d}] on {Z.device}, got "
+                          f"{tuple(g.shape)} on {g.device}")
+    dZ = torch.zeros(n, d, dtype=torch.float32, device=Z.device)
+    with _on_device(Z.device):
+        _lib.call("gae_segment_readout_bwd", _ptr(Z), ldz, n, d, _ptr(gp), G_, _ptr(g), max(ldd, 3 * d, 1), _ptr(dZ),
+                  max(d, 1), _stream())
+    return dZ
+
+
+class _SegmentReadout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Z, graph_ptr):
+        out, Zr, _, gp = _segment_readout_launch(Z, graph_ptr)
+        ctx.save_for_backward(Zr, gp)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        Zr, gp = ctx.saved_tensors
+        return segment_readout_bwd(Zr, gp, d_out), None
+
+
+def segment_readout(Z, graph_ptr):
+    """[mean | sum | max] of the rows of Z [N, d] per member graph (README.md:54 of the reference: the 48-d molecule
+    feature); ``graph_ptr`` int64 [G + 1] node offsets on the device.  Returns [G, 3 d] fp32.  The result carries a
+    gradient exactly when Z requires one and grad mode is on (``segment_readout_bwd``); the forward launch and its values
+    are the same either way."""
+    if torch.is_grad_enabled() and isinstance(Z, torch.Tensor) and Z.requires_grad:
+        return _SegmentReadout.apply(Z, graph_ptr)
+    return _segment_readout_launch(Z, graph_ptr)[0]

@@ -415,6 +415,55 @@ int gae_embed_graphs(const int64_t *graph_ptr, int64_t n_graphs, int64_t n_nodes
                      const float *const *biases, const int *acts, int norm, const int64_t *graph_ids,
                      int64_t n_out, float *out, int64_t ldo, void *stream);
 
+/* ---- K21: the backward of K19 (ops.embed_graphs under autograd, GAE.embed_graphs(grad=True)) in ONE launch plus the
+ * reduction of its partials.  Arguments up to n_out: exactly those of the forward entry above (the same arrays, the same
+ * checks, the same robustness rules).  Then:
+ *   d_out        fp32 [n_out, ldd], ldd >= 3 d: the gradient of a loss with respect to the feature rows
+ *   dW, lddw, db HOST arrays of n_layers entries.  dW[l] = device pointer to fp32 [widths[l], input width] with leading
+ *                dimension lddw[l], db[l] = device pointer to fp32 [widths[l]]; an ENTRY may be NULL: that gradient is
+ *                not wanted (layers below the lowest wanted one are not walked).  Written, not accumulated.  No gradient
+ *                with respect to the input features is produced
+ *   workspace    device memory of the size the workspace query returns (a pure host function of the shapes and n_out, > 0
+ *                and growing with n_out): one partial per parameter and wave
+ * Per group of <= 64 rows the encoder runs again in LDS with every layer's aggregated input M_l kept there and the ReLU
+ * pass masks as one 64-bit word per lane; nothing per node is saved between the two calls.  Readout:
+ * dZ[r][c] = d_sum[c] + d_mean[c] / n + (r == r* ? d_max[c] : 0), r* = the LOWEST row of the graph whose value equals
+ * the column's maximum; an empty graph and a refused slot (bad id, bad range, more than 64 rows: the forward's NaN row)
+ * contribute nothing.  Per layer, last to first: dY = dH (.) mask, db += sum_r dY[r], dW += dY^T M_l on
+ * v_mfma_f32_32x32x2_f32 (accumulators in registers across all groups of a wave), dM = dY W_l, dH = A^T dM as a gather
+ * in ascending row order with multiplicities (directed sets, repeated edges, self loops).  No float atomics; the partials
+ * are added in the library's one order for such lists: the same call gives the same bits, run to run, and a layer's
+ * gradient has the same bits whichever other gradients are asked for.
+ * NUMERICAL CONTRACT: fp32 throughout; within the library's 1e-5 of an fp64 evaluation (max |difference| over
+ * max(1, max |reference|)).
+ * SHAPES TAKEN: the forward's, as far as every M_l, two row buffers and the weights in both orientations fit 160 KB of
+ * LDS with one wave and the 32 x 32 accumulator tiles of all layers number at most 8: the usable query below is the
+ * truth (1 = taken; no launch, no GPU).  It takes 39->32->16, 39->16, 39->64->32->16 and 39->32->32->32->8 at 64 nodes
+ * per graph and refuses e.g. four layers of width 64.  Refusals return GAE_E_RANGE with a message naming the quantity.
+ * Argument errors are returned before any launch, as the forward's, plus: NULL dW / lddw / db table (GAE_E_NULL), lddw
+ * below the input width, ldd < 3 d, a workspace that is NULL or too small (GAE_E_SIZE).  n_out = 0: nothing is launched,
+ * the gradients asked for are set to zero (none asked for: no GPU is needed). */
+int gae_embed_graphs_bwd_usable(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes);
+
+int64_t gae_embed_graphs_bwd_workspace_bytes(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t n_out);
+
+int gae_embed_graphs_bwd(const int64_t *graph_ptr, int64_t n_graphs, int64_t n_nodes, int64_t n_edges,
+                         int64_t max_graph_nodes, const int32_t *indptr, const int32_t *indices,
+                         const void *feat, int feat_dtype, int64_t ldf, int64_t f_in, int64_t n_layers,
+                         const int64_t *widths, const float *const *weights, const int64_t *ldw,
+                         const float *const *biases, const int *acts, int norm, const int64_t *graph_ids,
+                         int64_t n_out, const float *d_out, int64_t ldd, float *const *dW, const int64_t *lddw,
+                         float *const *db, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* The gradient of the segment readout of gae_hip.h (mean | sum | max per member graph) for the chunked route
+ * batch -> encode -> readout_nodes: dZ[r][c] = d_sum[c] + d_mean[c] / n + (r == r* ? d_max[c] : 0) for the rows r of
+ * graph g (n of them), d_mean / d_sum / d_max = the three blocks of row g of d_out [n_graphs, ldd >= 3 d]; r* = the
+ * LOWEST row of the graph whose value of Z equals the column's maximum (K21's tie rule).  Every row of dZ [n_nodes, lddz]
+ * that belongs to a graph is written (an empty graph has none).  One wave per graph like the forward, any d (d > 64:
+ * column blocks of 64); HBM-bound; no atomics, deterministic. */
+int gae_segment_readout_bwd(const float *Z, int64_t ldz, int64_t n_nodes, int64_t d, const int64_t *graph_ptr,
+                            int64_t n_graphs, const float *d_out, int64_t ldd, float *dZ, int64_t lddz, void *stream);
+
 /* ---- K20: how well a molecule set is reconstructed, per graph, in ONE launch (GAE.score_graphs, ops.score_graphs)
  * K19's pipeline with a second tail: for every selected member graph the same encoder on the graph's own rows (the Z
  * that is ranked has the bits of the Z gae_embed_graphs reads out), then the inner-product decoder on the graph's own
