@@ -5,30 +5,13 @@
 // The node embeddings never go to HBM: inputs are read from the dataset as it is stored (uint8 or fp32 feature rows,
 // the block-diagonal CSR with global column ids), 12 d bytes are written per graph.
 //
-// Layout.  A wave owns S <= 64 consecutive output slots; lane t loads slot t's graph id and node range ONCE.  The wave
-// then walks its slots in groups: as many consecutive graphs as fit 64 rows (a register prefix scan, no memory), one
-// atom per lane.  Two LDS buffers per wave hold the activations [64 rows][width] of the layer being read and the one
-// being written; the weights of all layers are staged once per block, transposed and zero padded to [f_in][JP]
-// (JP = output width rounded up to 8).
-//   aggregate   lane r walks its CSR row (the first 4 column ids sit in registers, longer rows continue from the CSR)
-//               and adds the LDS rows of its neighbours in CSR order, four features at a time; the sums go to the
-//               lane's own row of the buffer being written
-//   transform   y_j = act(b_j + sum_k m_k W_jk), k ascending over the true input width: JP accumulators per lane, per k
-//               one read of m_k and JP / 4 broadcast reads of row k of W^T (every lane reads the same address).  The
-//               sums are fp32 fmaf chains -- the arithmetic v_mfma_f32_32x32x2_f32 performs, at the same peak rate: on
-//               gfx950 the fp32 MFMA shares the fp32 FMA lanes with the VALU (common.h), so atoms-as-lanes costs no
-//               throughput, needs no operand shuffles between the layers and fills 64 rows instead of 32
+// The walk -- a wave owns S <= 64 output slots, packs consecutive graphs into groups of <= 64 rows, one atom per lane,
+// the encoder of a group in two LDS buffers, the next group's loads in flight -- its aggregate / transform and its
+// safety rules are graphs_walk.h's, shared with K21 (embed_bwd.hip).  K19's own tail:
 //   readout     lane (slot, c) adds feature c of its graphs' rows first to last: an order that depends on the node count
 //               alone
 // Every output element is its own chain over the graph's own rows, so a graph's feature row has the same bits at any
-// position, in any group, in any launch.  No atomics.
-//
-// Loads.  The feature row (3 x 16 bytes for 39 uint8 features) and the row bounds of the NEXT group are issued into
-// registers before the current group's layers run, and written to LDS only when that group's turn comes.
-//
-// Safety.  A graph id outside [0, G), a node range outside [0, N] or above 64 rows gives a row of NaN; a row pointer
-// outside [0, E] reads as an empty row; a column id outside the graph's own rows is skipped: nothing outside the arrays
-// is read or written.
+// position, in any group, in any launch.  No atomics.  A slot the walk refuses gives a row of NaN.
 //
 // Measured (tools/embed_bench.py, profiles/r10_embed_graphs.json; 39 -> 32 -> 16, uint8 features): the 249 455 molecules of
 // the ZINC-sized set in 2.43 ms of kernel time (3.1 ms per call) against 15.5 ms for batch -> encode -> readout in chunks
@@ -36,8 +19,8 @@
 // FMA (DESIGN.md K19 lists the levers).  175 VGPRs, no scratch (uint8 form).
 //
 // K20: how well every selected member graph is reconstructed (GAE.score_graphs, ops.score_graphs).  The same walk and
-// the same encoder -- graphs_body below is the body of both kernels, aggregate / transform are called by both -- with
-// a second tail in place of the readout: the decoder on each graph's own ordered pairs, ranked and scored in LDS.
+// the same encoder -- graphs_body below is the body of both kernels -- with a second tail in place of the readout: the
+// decoder on each graph's own ordered pairs, ranked and scored in LDS.
 //   logits      lane r computes row r of its graph's n x n block: s_rb = the fmaf chain over k ascending, from 0.f, of
 //               z_r[k] z_b[k] (Z rows from LDS, 16 bytes at a time), into the buffer the last layer no longer needs,
 //               rows max_graph_nodes | 1 floats apart (odd: a column walk of a graph's lanes hits distinct banks)
@@ -61,17 +44,14 @@
 // block as K19, 3 blocks = 6 waves per CU = 1.5 per SIMD, unchanged.  max_graph_nodes = 64 needs 64 x 65 floats: 64.6 KB
 // per block for this model, 2 blocks = 1 wave per SIMD.  Registers: 227 VGPRs (uint8 form, 2 waves per SIMD), 270 (fp32
 // form, 1 wave per SIMD, as K19's 261), no scratch.
-#include "common.h"
+#include "graphs_walk.h"
+
+using namespace gae::walk;
+using gae::v4f;
 
 namespace {
 
-using gae::v4f;
-
-constexpr int kMaxLayers = 4;
-constexpr int kMaxWidth = 64;
-constexpr int kRows = 64;         // rows of a group: one atom per lane
 constexpr int kWaves = 2;         // waves per block
-constexpr int kRegNb = 4;         // column ids of a row kept in registers
 
 struct EmbedArgs {
     const int64_t *graph_ptr;
@@ -96,94 +76,6 @@ struct EmbedArgs {
     int wfloats;                  // floats of the staged weights and biases
     int wave_floats;              // floats of one wave's private LDS
 };
-
-// LDS written by one lane of a wave and read by another: LDS operations of a wave complete in order, the fence keeps
-// the compiler from moving them
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-struct Lane {                     // one atom of the current group
-    bool active;
-    int mb, mn;                   // first row and node count of its graph in the group
-    int g0;                       // first global row of its graph
-    int e0, e1;
-    int nb[kRegNb];               // group rows of its first neighbours, -1 = none
-    float sc;
-};
-
-// M = (D^-1/2) A (D^-1/2) H of the lane's row, four features per trip, into its own row of `out`
-__device__ __forceinline__ void aggregate(const EmbedArgs &a, const Lane &ln, int row, int fi, const float *in, int sin,
-                                          float *out, int sout, const float *scale)
-{
-    float s[kRegNb];
-#pragma unroll
-    for (int q = 0; q < kRegNb; ++q) s[q] = (a.norm_both && ln.nb[q] >= 0) ? scale[ln.nb[q]] : 1.f;
-    const bool tail = ln.e1 - ln.e0 > kRegNb;
-    for (int c = 0; c < (fi + 3) / 4; ++c) {
-        v4f m = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < kRegNb; ++q)
-            if (ln.nb[q] >= 0) {
-                const v4f v = *reinterpret_cast<const v4f *>(in + ln.nb[q] * sin + 4 * c);
-                if (a.norm_both) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) m[i] = fmaf(s[q], v[i], m[i]);
-                } else {
-                    m += v;
-                }
-            }
-        if (tail)
-            for (int e = ln.e0 + kRegNb; e < ln.e1; ++e) {      // the rare long row continues from the CSR
-                const int u = a.indices[e] - ln.g0;
-                if (u >= 0 && u < ln.mn) {
-                    const v4f v = *reinterpret_cast<const v4f *>(in + (ln.mb + u) * sin + 4 * c);
-                    if (a.norm_both) {
-                        const float su = scale[ln.mb + u];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) m[i] = fmaf(su, v[i], m[i]);
-                    } else {
-                        m += v;
-                    }
-                }
-            }
-        if (a.norm_both) m *= ln.sc;
-        *reinterpret_cast<v4f *>(out + row * sout + 4 * c) = m;
-    }
-}
-
-// y = act(M W^T + b) of the lane's row: M is read from the lane's own row of `out`, y replaces it
-template <int JP>
-__device__ __forceinline__ void transform(const float *Wt, const float *bl, int fi, bool relu, float *mine)
-{
-    float y[JP];
-#pragma unroll
-    for (int j = 0; j < JP; ++j) y[j] = 0.f;
-#pragma unroll 1
-    for (int k = 0; k < fi; ++k) {
-        const float mk = mine[k];
-        const v4f *w = reinterpret_cast<const v4f *>(Wt + k * JP);
-#pragma unroll
-        for (int q = 0; q < JP / 4; ++q) {
-            const v4f wv = w[q];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) y[4 * q + i] = fmaf(mk, wv[i], y[4 * q + i]);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < JP / 4; ++q) {
-        const v4f b = *reinterpret_cast<const v4f *>(bl + 4 * q);
-        v4f v;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float t = y[4 * q + i] + b[i];
-            v[i] = !relu || t > 0.f || t != t ? t : 0.f;         // ReLU keeps a NaN
-        }
-        *reinterpret_cast<v4f *>(mine + 4 * q) = v;
-    }
-}
 
 // ---- K20: the decoder tail (see the header comment) ------------------------------------------------------------------
 struct ScoreArgs {
@@ -360,20 +252,9 @@ __device__ __forceinline__ void graphs_body(const EmbedArgs &a, const ScoreArgs 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
     // ---- the weights of all layers, once per block: W^T zero padded to [f_in][jp]
-    for (int l = 0; l < a.L; ++l) {
-        const int jp = a.jp[l], fi = a.width[l], fo = a.width[l + 1];
-        const float *W = a.W[l];
-        const int64_t ldw = a.ldw[l];
-        float *dst = lds + a.w_off[l];
-#pragma unroll 4
-        for (int idx = tid; idx < fi * jp; idx += kWaves * 64) {
-            const int k = idx / jp, j = idx - k * jp;
-            const float v = W[j < fo ? j * ldw + k : 0];
-            dst[idx] = j < fo ? v : 0.f;
-        }
-        const float *bias = a.bias[l];
-        for (int j = tid; j < jp; j += kWaves * 64) lds[a.b_off[l] + j] = (bias && j < fo) ? bias[j] : 0.f;
-    }
+    for (int l = 0; l < a.L; ++l)
+        stage_layer(a.W[l], a.ldw[l], a.bias[l], a.width[l], a.width[l + 1], a.jp[l], lds + a.w_off[l],
+                    lds + a.b_off[l], tid, kWaves * 64);
     __syncthreads();
 
     float *bufA = lds + a.wfloats + wave * a.wave_floats;
@@ -396,18 +277,9 @@ __device__ __forceinline__ void graphs_body(const EmbedArgs &a, const ScoreArgs 
     const int f0 = a.width[0];
 
     // ---- this wave's slots: lane t holds slot t (graph id -> node range), loaded once
+    // (K20: the logit block is sized for max_graph_nodes <= 64)
     int sn = 0, sr0 = 0;
-    {
-        const bool sv = lane < avail;
-        const int64_t gid = sv ? (a.graph_ids ? a.graph_ids[k0 + lane] : k0 + lane) : -1;
-        bool ok = sv && gid >= 0 && gid < a.G;
-        int64_t r0 = 0, r1 = 0;
-        if (ok) { r0 = a.graph_ptr[gid]; r1 = a.graph_ptr[gid + 1]; }
-        ok = ok && r0 >= 0 && r1 >= r0 && r1 <= a.N && r1 - r0 <= kRows;
-        if constexpr (SCORE) ok = ok && r1 - r0 <= t.max_nodes;      // the logit block is sized for max_graph_nodes
-        sn = ok ? int(r1 - r0) : kRows + 1;        // a slot that cannot be taken never fits a group
-        sr0 = ok ? int(r0) : 0;
-    }
+    load_slot(a, k0, lane, avail, SCORE ? t.max_nodes : kRows, sn, sr0);
 
     // ---- the group that starts at slot `pos` and the loads issued for it
     constexpr int NX = U8 ? 4 : 16;                // 16-byte vectors of a feature row held in registers
@@ -418,22 +290,7 @@ __device__ __forceinline__ void graphs_body(const EmbedArgs &a, const ScoreArgs 
 
     auto issue = [&](int at) {
         pos = at;
-        int v = (lane >= at && lane < avail) ? sn : 0;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(v, off, 64);
-            if (lane >= off) v += t;
-        }
-        const bool take = lane >= at && lane < avail && v <= kRows;
-        cnt = __builtin_popcountll(__ballot(take));
-        const int rows = cnt ? __shfl(v, at + cnt - 1, 64) : 0;
-        gbase = v - sn;
-        ln.active = lane < rows;
-        ln.mb = 0; ln.mn = 0; ln.g0 = 0; ln.e0 = 0; ln.e1 = 0; ln.sc = 0.f;
-        for (int m = at; m < at + cnt; ++m) {
-            const int b = __shfl(gbase, m, 64), n = __shfl(sn, m, 64), g0 = __shfl(sr0, m, 64);
-            if (lane >= b && lane < b + n) { ln.mb = b; ln.mn = n; ln.g0 = g0; }
-        }
+        pack_group(at, lane, avail, sn, sr0, cnt, gbase, ln);
         if (ln.active) {
             const int64_t gr = int64_t(ln.g0) + (lane - ln.mb);
             ln.e0 = a.indptr[gr];
@@ -465,31 +322,12 @@ __device__ __forceinline__ void graphs_body(const EmbedArgs &a, const ScoreArgs 
         {
             const int mi = lane - cpos;
             if (mi >= 0 && mi < ccnt) { mbase[mi] = gbase; mcount[mi] = sn; }
-            const bool rowok = me.active && me.e0 >= 0 && me.e1 >= me.e0 && int64_t(me.e1) <= a.E;
-            if (!rowok) me.e0 = me.e1 = 0;
-#pragma unroll
-            for (int q = 0; q < kRegNb; ++q) {
-                me.nb[q] = -1;
-                if (me.e0 + q < me.e1) {
-                    const int c = a.indices[me.e0 + q] - me.g0;
-                    if (c >= 0 && c < me.mn) me.nb[q] = me.mb + c;
-                }
-            }
-            const int deg = me.e1 - me.e0;
-            me.sc = deg > 0 ? 1.0f / sqrtf(float(deg)) : 0.f;
+            lane_turn(a.indices, a.E, me);
             scale[lane] = me.sc;
             if (me.active) {
                 v4f *dst = reinterpret_cast<v4f *>(bufA + lane * a.sa);
-                if (U8) {
-#pragma unroll
-                    for (int c = 0; c < 16; ++c)
-                        if (4 * c < f0) {
-                            const unsigned w = __float_as_uint(x[c / 4][c & 3]);
-                            v4f v;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) v[i] = 4 * c + i < f0 ? float((w >> (8 * i)) & 0xffu) : 0.f;
-                            dst[c] = v;
-                        }
+                if constexpr (U8) {
+                    unpack_u8_row(x, f0, dst);
                 } else {
 #pragma unroll
                     for (int c = 0; c < 16; ++c)
@@ -514,15 +352,15 @@ __device__ __forceinline__ void graphs_body(const EmbedArgs &a, const ScoreArgs 
                 const float *Wt = lds + a.w_off[l], *bl = lds + a.b_off[l];
                 const bool relu = a.act[l] == GAE_ACT_RELU;
                 float *mine = out + lane * sout;
-                switch (a.jp[l]) {
-                case 8: transform<8>(Wt, bl, fi, relu, mine); break;
-                case 16: transform<16>(Wt, bl, fi, relu, mine); break;
-                case 24: transform<24>(Wt, bl, fi, relu, mine); break;
-                case 32: transform<32>(Wt, bl, fi, relu, mine); break;
-                case 40: transform<40>(Wt, bl, fi, relu, mine); break;
-                case 48: transform<48>(Wt, bl, fi, relu, mine); break;
-                case 56: transform<56>(Wt, bl, fi, relu, mine); break;
-                default: transform<64>(Wt, bl, fi, relu, mine); break;
+                switch (a.jp[l]) {                    // y replaces M; the pass mask is K21's (its switch: embed_bwd.hip)
+                case 8: transform_keep<8>(Wt, bl, fi, relu, mine, mine); break;
+                case 16: transform_keep<16>(Wt, bl, fi, relu, mine, mine); break;
+                case 24: transform_keep<24>(Wt, bl, fi, relu, mine, mine); break;
+                case 32: transform_keep<32>(Wt, bl, fi, relu, mine, mine); break;
+                case 40: transform_keep<40>(Wt, bl, fi, relu, mine, mine); break;
+                case 48: transform_keep<48>(Wt, bl, fi, relu, mine, mine); break;
+                case 56: transform_keep<56>(Wt, bl, fi, relu, mine, mine); break;
+                default: transform_keep<64>(Wt, bl, fi, relu, mine, mine); break;
                 }
             }
             wave_sync();
@@ -568,102 +406,6 @@ __global__ __launch_bounds__(kWaves * 64) void score_graphs_kernel(const EmbedAr
     graphs_body<U8, true>(a, t);
 }
 
-int round_up(int v, int q) { return (v + q - 1) / q * q; }
-
-// the shapes the kernels take (K20 also the encoder of no layers: the feature rows are Z); `what` (may be NULL)
-// receives the offending quantity
-bool shape_taken(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes, int min_layers,
-                 char *what, size_t cap)
-{
-    if (n_layers < min_layers || n_layers > kMaxLayers) {
-        if (what) snprintf(what, cap, "n_layers = %lld outside %d..%d", (long long)n_layers, min_layers, kMaxLayers);
-        return false;
-    }
-    if (f_in < 1 || f_in > kMaxWidth) {
-        if (what) snprintf(what, cap, "input width f_in = %lld outside 1..%d", (long long)f_in, kMaxWidth);
-        return false;
-    }
-    for (int64_t l = 0; l < n_layers; ++l)
-        if (widths[l] < 1 || widths[l] > kMaxWidth) {
-            if (what)
-                snprintf(what, cap, "width of layer %lld = %lld outside 1..%d", (long long)l, (long long)widths[l],
-                         kMaxWidth);
-            return false;
-        }
-    if (max_graph_nodes > kRows) {
-        if (what)
-            snprintf(what, cap, "max_graph_nodes = %lld above %d nodes per graph", (long long)max_graph_nodes, kRows);
-        return false;
-    }
-    return true;
-}
-
-// what gae_embed_graphs and gae_score_graphs ask of their common arguments, in this order; `fn` names the caller
-struct Request {
-    const int64_t *graph_ptr;
-    int64_t n_graphs, n_nodes, n_edges, max_graph_nodes;
-    const int32_t *indptr, *indices;
-    const void *feat;
-    int feat_dtype;
-    int64_t ldf, f_in, n_layers;
-    const int64_t *widths;
-    const float *const *weights;
-    const int64_t *ldw;
-    const float *const *biases;
-    const int *acts;
-    int norm;
-    const int64_t *graph_ids;
-    int64_t n_out;
-};
-
-int check_layers(const char *fn, const Request &r, int min_layers)
-{
-    GAE_REQUIRE((min_layers == 0 && r.n_layers == 0) || (r.widths && r.weights && r.ldw && r.acts), GAE_E_NULL,
-                "%s: widths / weights / ldw / acts is NULL", fn);
-    GAE_REQUIRE(r.n_graphs >= 0 && r.n_nodes >= 0 && r.n_edges >= 0 && r.n_out >= 0 && r.max_graph_nodes >= 0, GAE_E_SIZE,
-                "%s: negative n_graphs = %lld, n_nodes = %lld, n_edges = %lld, n_out = %lld or "
-                "max_graph_nodes = %lld", fn, (long long)r.n_graphs, (long long)r.n_nodes, (long long)r.n_edges,
-                (long long)r.n_out, (long long)r.max_graph_nodes);
-    GAE_REQUIRE(r.n_nodes < (int64_t(1) << 31) && r.n_edges < (int64_t(1) << 31), GAE_E_SIZE,
-                "%s: n_nodes = %lld or n_edges = %lld beyond the int32 CSR", fn, (long long)r.n_nodes,
-                (long long)r.n_edges);
-    char what[160];
-    GAE_REQUIRE(shape_taken(r.f_in, r.n_layers, r.widths, r.max_graph_nodes, min_layers, what, sizeof what), GAE_E_RANGE,
-                "%s: %s", fn, what);
-    GAE_REQUIRE(r.norm == GAE_EMBED_NORM_NONE || r.norm == GAE_EMBED_NORM_BOTH, GAE_E_RANGE,
-                "%s: unknown norm code %d (0 = none, 1 = both)", fn, r.norm);
-    GAE_REQUIRE(r.feat_dtype == GAE_F32 || r.feat_dtype == GAE_U8, GAE_E_DTYPE,
-                "%s: feature dtype %d (GAE_F32 or GAE_U8)", fn, r.feat_dtype);
-    for (int64_t l = 0; l < r.n_layers; ++l) {
-        GAE_REQUIRE(r.acts[l] == GAE_ACT_IDENTITY || r.acts[l] == GAE_ACT_RELU, GAE_E_DTYPE,
-                    "%s: unknown activation code %d of layer %lld", fn, r.acts[l], (long long)l);
-        GAE_REQUIRE(r.weights[l], GAE_E_NULL, "%s: the weight of layer %lld is NULL", fn, (long long)l);
-        GAE_REQUIRE(r.ldw[l] >= (l ? r.widths[l - 1] : r.f_in), GAE_E_SIZE,
-                    "%s: leading dimension ldw = %lld of layer %lld below its input width", fn,
-                    (long long)r.ldw[l], (long long)l);
-    }
-    return GAE_OK;
-}
-
-int check_feature_rows(const char *fn, const Request &r)
-{
-    const int64_t row_elems = r.feat_dtype == GAE_U8 ? (r.f_in + 15) / 16 * 16 : (r.f_in + 3) / 4 * 4;
-    GAE_REQUIRE(r.ldf >= row_elems, GAE_E_SIZE,
-                "%s: feature rows of ldf = %lld elements, %lld needed (whole 16-byte vectors)", fn,
-                (long long)r.ldf, (long long)row_elems);
-    return GAE_OK;
-}
-
-int check_arrays(const char *fn, const Request &r)
-{
-    GAE_REQUIRE(r.n_nodes == 0 || (r.indptr && r.feat), GAE_E_NULL, "%s: indptr / feat is NULL", fn);
-    GAE_REQUIRE(r.n_edges == 0 || r.indices, GAE_E_NULL, "%s: indices is NULL", fn);
-    const int64_t row_bytes = r.ldf * (r.feat_dtype == GAE_U8 ? 1 : 4);
-    GAE_REQUIRE(r.n_nodes == 0 || (gae::aligned16(r.feat) && row_bytes % 16 == 0), GAE_E_ALIGN,
-                "%s: feature rows must start on 16-byte boundaries (pointer and ldf)", fn);
-    return GAE_OK;
-}
-
 // the kernel arguments of a checked request: staged weights, row strides of the two buffers, slots per wave.  The LDS
 // of a wave (wave_floats) is K19's; gae_score_graphs replaces it.
 int64_t fill_args(const Request &r, EmbedArgs &a)
@@ -702,20 +444,6 @@ int64_t fill_args(const Request &r, EmbedArgs &a)
     return (waves + kWaves - 1) / kWaves;
 }
 
-// a launch of `kernel` with `lds` bytes of dynamic LDS; the attribute is raised once per (kernel, device)
-#define GAE_GRAPHS_LAUNCH(kernel, ...)                                                                                 \
-    do {                                                                                                               \
-        static int configured[16] = {0};   /* per (instantiation, device): raised when a launch needs more LDS */      \
-        int dev_ = 0;                                                                                                  \
-        GAE_HIP(hipGetDevice(&dev_));                                                                                  \
-        if (lds > 48 * 1024 && (dev_ < 0 || dev_ >= 16 || configured[dev_] < int(lds))) {                              \
-            GAE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&kernel),                                       \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));                        \
-            if (dev_ >= 0 && dev_ < 16) configured[dev_] = int(lds);                                                   \
-        }                                                                                                              \
-        hipLaunchKernelGGL(kernel, dim3(unsigned(blocks)), dim3(kWaves * 64), lds, st, __VA_ARGS__);                   \
-    } while (0)
-
 } // namespace
 
 extern "C" int gae_embed_graphs_usable(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes)
@@ -749,8 +477,8 @@ extern "C" int gae_embed_graphs(const int64_t *graph_ptr, int64_t n_graphs, int6
     GAE_REQUIRE(blocks < (int64_t(1) << 31), GAE_E_SIZE, "gae_embed_graphs: n_out = %lld is too large", (long long)n_out);
     const size_t lds = size_t(a.wfloats + kWaves * a.wave_floats) * 4;
     hipStream_t st = gae::as_stream(stream);
-    if (feat_dtype == GAE_U8) GAE_GRAPHS_LAUNCH(embed_graphs_kernel<true>, a);
-    else GAE_GRAPHS_LAUNCH(embed_graphs_kernel<false>, a);
+    if (feat_dtype == GAE_U8) GAE_GRAPHS_LAUNCH(embed_graphs_kernel<true>, blocks, kWaves * 64, a);
+    else GAE_GRAPHS_LAUNCH(embed_graphs_kernel<false>, blocks, kWaves * 64, a);
     GAE_CHECK_LAUNCH("embed_graphs_kernel");
     return GAE_OK;
 }
@@ -801,8 +529,8 @@ extern "C" int gae_score_graphs(const int64_t *graph_ptr, int64_t n_graphs, int6
     a.wave_floats = kRows * s_z + t.block_floats + 3 * kRows;
     const size_t lds = size_t(a.wfloats + kWaves * a.wave_floats) * 4;
     hipStream_t st = gae::as_stream(stream);
-    if (feat_dtype == GAE_U8) GAE_GRAPHS_LAUNCH(score_graphs_kernel<true>, a, t);
-    else GAE_GRAPHS_LAUNCH(score_graphs_kernel<false>, a, t);
+    if (feat_dtype == GAE_U8) GAE_GRAPHS_LAUNCH(score_graphs_kernel<true>, blocks, kWaves * 64, a, t);
+    else GAE_GRAPHS_LAUNCH(score_graphs_kernel<false>, blocks, kWaves * 64, a, t);
     GAE_CHECK_LAUNCH("score_graphs_kernel");
     return GAE_OK;
 }

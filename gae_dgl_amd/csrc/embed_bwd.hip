@@ -4,11 +4,11 @@
 // the weight and bias gradients of every encoder layer behind and nothing else: per group of <= 64 rows it runs the
 // encoder AGAIN in LDS (nothing per node is saved between the forward and the backward call), then walks the layers
 // last to first.  The walk -- a wave owns S consecutive slots, packs consecutive graphs into groups of <= 64 rows, one
-// atom per lane, the next group's row bounds (and uint8 feature rows) in flight while this one computes -- is K19's
-// (embed.hip), restated here so that the forward's translation unit stays as it is.
+// atom per lane, the next group's row bounds (and uint8 feature rows) in flight while this one computes -- is K19's:
+// both kernels call the one copy in graphs_walk.h, which describes its layout, loads and safety rules.
 //
 // Per group.
-//   forward     aggregate / transform exactly as K19 (the same fmaf chains, k ascending); every layer's aggregated input
+//   forward     K19's aggregate / transform_keep (graphs_walk.h: the same fmaf chains, k ascending); every layer's aggregated input
 //               M_l [64][width_l] STAYS in LDS, the activations go through one buffer T; a hidden layer's ReLU pass mask
 //               is one 64-bit word per lane (widths <= 64, a lane holds one atom's row)
 //   readout     lane (slot, c) walks column c of its graphs' rows of Z: the maximum and the LOWEST row attaining it, then
@@ -29,7 +29,7 @@
 // the partials in the library's one order (gae::sum_partials, through gae::launch_partials_reduce) and writes dW / db.
 // Same call, same bits.
 //
-// Safety: K19's rules.  A refused slot (bad id, bad range, more than 64 rows) and an empty graph contribute nothing; a
+// Safety: the walk's rules (graphs_walk.h).  A refused slot (bad id, bad range, more than 64 rows) and an empty graph contribute nothing; a
 // row pointer outside [0, E] reads as an empty row; a column id outside the graph's own rows is skipped.
 //
 // LDS per wave: sum_l 64 x (width_l rounded up to 4, + 4) floats of M_l, two buffers of 64 x (widest layer + 4) floats
@@ -45,17 +45,15 @@
 // gae_embed_graphs_bwd_usable refuses what does not fit one wave or needs more than 8 tiles: four layers of width 64
 // (16 tiles, 219 KB) and 39 -> 64 -> 64 -> 64 (12 tiles) are outside, 39 -> 64 -> 64 (8 tiles, 108.5 KB) is inside.
 // Time: DESIGN.md K21 (tools/embed_bwd_bench.py).
-#include "common.h"
+#include "graphs_walk.h"
+
+using namespace gae::walk;
+using gae::v4f;
 
 namespace {
 
-using gae::v4f;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kMaxLayers = 4;
-constexpr int kMaxWidth = 64;
-constexpr int kRows = 64;         // rows of a group: one atom per lane
-constexpr int kRegNb = 4;         // column ids of a row / out-neighbours of a row kept in registers
 constexpr int kMaxWaves = 4;      // waves per block
 constexpr int kMaxTiles = 8;      // 32 x 32 accumulator tiles of all layers
 constexpr int kLdsCap = 160 * 1024;
@@ -94,100 +92,6 @@ struct BwdArgs {
 // float offsets of a wave's tables
 enum { kTabScale = 0, kTabBase = 64, kTabCount = 128, kTabNb = 192, kTabE0 = 448, kTabE1 = 512, kTabMask = 576,
        kTabFloats = 576 + 2 * kRows * kMaxLayers };
-
-// LDS written by one lane of a wave and read by another: LDS operations of a wave complete in order, the fence keeps
-// the compiler from moving them
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-struct Lane {                     // one atom of the current group
-    bool active;
-    int mb, mn;                   // first row and node count of its graph in the group
-    int g0;                       // first global row of its graph
-    int e0, e1;
-    int nb[kRegNb];               // group rows of its first neighbours, -1 = none
-    float sc;
-};
-
-// K19's aggregate: M = (D^-1/2) A (D^-1/2) H of the lane's row, four features per trip, into its own row of `out`
-__device__ __forceinline__ void aggregate(const BwdArgs &a, const Lane &ln, int row, int fi, const float *in, int sin,
-                                          float *out, int sout, const float *scale)
-{
-    float s[kRegNb];
-#pragma unroll
-    for (int q = 0; q < kRegNb; ++q) s[q] = (a.norm_both && ln.nb[q] >= 0) ? scale[ln.nb[q]] : 1.f;
-    const bool tail = ln.e1 - ln.e0 > kRegNb;
-    for (int c = 0; c < (fi + 3) / 4; ++c) {
-        v4f m = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < kRegNb; ++q)
-            if (ln.nb[q] >= 0) {
-                const v4f v = *reinterpret_cast<const v4f *>(in + ln.nb[q] * sin + 4 * c);
-                if (a.norm_both) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) m[i] = fmaf(s[q], v[i], m[i]);
-                } else {
-                    m += v;
-                }
-            }
-        if (tail)
-            for (int e = ln.e0 + kRegNb; e < ln.e1; ++e) {      // the rare long row continues from the CSR
-                const int u = a.indices[e] - ln.g0;
-                if (u >= 0 && u < ln.mn) {
-                    const v4f v = *reinterpret_cast<const v4f *>(in + (ln.mb + u) * sin + 4 * c);
-                    if (a.norm_both) {
-                        const float su = scale[ln.mb + u];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) m[i] = fmaf(su, v[i], m[i]);
-                    } else {
-                        m += v;
-                    }
-                }
-            }
-        if (a.norm_both) m *= ln.sc;
-        *reinterpret_cast<v4f *>(out + row * sout + 4 * c) = m;
-    }
-}
-
-// K19's transform with M kept: y = act(M W^T + b) of the lane's row, M read from `mrow`, y written to `yrow`; returns
-// the pass mask (bit j: output j went through the activation unchanged)
-template <int JP>
-__device__ __forceinline__ uint64_t transform_keep(const float *Wt, const float *bl, int fi, bool relu, const float *mrow,
-                                                   float *yrow)
-{
-    float y[JP];
-#pragma unroll
-    for (int j = 0; j < JP; ++j) y[j] = 0.f;
-#pragma unroll 1
-    for (int k = 0; k < fi; ++k) {
-        const float mk = mrow[k];
-        const v4f *w = reinterpret_cast<const v4f *>(Wt + k * JP);
-#pragma unroll
-        for (int q = 0; q < JP / 4; ++q) {
-            const v4f wv = w[q];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) y[4 * q + i] = fmaf(mk, wv[i], y[4 * q + i]);
-        }
-    }
-    uint64_t mask = 0;
-#pragma unroll
-    for (int q = 0; q < JP / 4; ++q) {
-        const v4f b = *reinterpret_cast<const v4f *>(bl + 4 * q);
-        v4f v;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float t = y[4 * q + i] + b[i];
-            const bool pass = !relu || t > 0.f || t != t;        // ReLU keeps a NaN
-            v[i] = pass ? t : 0.f;
-            mask |= uint64_t(pass) << (4 * q + i);
-        }
-        *reinterpret_cast<v4f *>(yrow + 4 * q) = v;
-    }
-    return mask;
-}
 
 // dM = dY W of the lane's row: dY (fo values) is read from `mine`, dM (KP values, zero beyond the input width) replaces it
 template <int KP>
@@ -255,12 +159,7 @@ __global__ __launch_bounds__(kMaxWaves * 64) void embed_graphs_bwd_kernel(const 
         const int jp = a.jp[l], kp = a.kp[l], fi = a.width[l], fo = a.width[l + 1];
         const float *W = a.W[l];
         const int64_t ldw = a.ldw[l];
-        float *dst = lds + a.wt_off[l];
-        for (int idx = tid; idx < fi * jp; idx += nthreads) {
-            const int k = idx / jp, j = idx - k * jp;
-            const float v = W[j < fo ? j * ldw + k : 0];
-            dst[idx] = j < fo ? v : 0.f;
-        }
+        stage_layer(W, ldw, a.bias[l], fi, fo, jp, lds + a.wt_off[l], lds + a.b_off[l], tid, nthreads);
         if (l > a.l_stop) {
             float *dk = lds + a.wk_off[l];
             for (int idx = tid; idx < fo * kp; idx += nthreads) {
@@ -269,8 +168,6 @@ __global__ __launch_bounds__(kMaxWaves * 64) void embed_graphs_bwd_kernel(const 
                 dk[idx] = k < fi ? v : 0.f;
             }
         }
-        const float *bias = a.bias[l];
-        for (int j = tid; j < jp; j += nthreads) lds[a.b_off[l] + j] = (bias && j < fo) ? bias[j] : 0.f;
     }
     __syncthreads();
 
@@ -297,16 +194,7 @@ __global__ __launch_bounds__(kMaxWaves * 64) void embed_graphs_bwd_kernel(const 
 
     // ---- this wave's slots: lane t holds slot t (graph id -> node range), loaded once
     int sn = 0, sr0 = 0;
-    {
-        const bool sv = lane < avail;
-        const int64_t gid = sv ? (a.graph_ids ? a.graph_ids[k0 + lane] : k0 + lane) : -1;
-        bool ok = sv && gid >= 0 && gid < a.G;
-        int64_t r0 = 0, r1 = 0;
-        if (ok) { r0 = a.graph_ptr[gid]; r1 = a.graph_ptr[gid + 1]; }
-        ok = ok && r0 >= 0 && r1 >= r0 && r1 <= a.N && r1 - r0 <= kRows;
-        sn = ok ? int(r1 - r0) : kRows + 1;        // a slot that cannot be taken never fits a group
-        sr0 = ok ? int(r0) : 0;
-    }
+    load_slot(a, k0, lane, avail, kRows, sn, sr0);
 
     // ---- the group that starts at slot `pos` and the loads issued for it
     constexpr int NX = 4;                          // 16-byte vectors of a uint8 feature row held in registers
@@ -317,22 +205,7 @@ __global__ __launch_bounds__(kMaxWaves * 64) void embed_graphs_bwd_kernel(const 
 
     auto issue = [&](int at) {
         pos = at;
-        int v = (lane >= at && lane < avail) ? sn : 0;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(v, off, 64);
-            if (lane >= off) v += t;
-        }
-        const bool take = lane >= at && lane < avail && v <= kRows;
-        cnt = __builtin_popcountll(__ballot(take));
-        grows = cnt ? __shfl(v, at + cnt - 1, 64) : 0;
-        gbase = v - sn;
-        ln.active = lane < grows;
-        ln.mb = 0; ln.mn = 0; ln.g0 = 0; ln.e0 = 0; ln.e1 = 0; ln.sc = 0.f;
-        for (int m = at; m < at + cnt; ++m) {
-            const int b = __shfl(gbase, m, 64), n = __shfl(sn, m, 64), g0 = __shfl(sr0, m, 64);
-            if (lane >= b && lane < b + n) { ln.mb = b; ln.mn = n; ln.g0 = g0; }
-        }
+        grows = pack_group(at, lane, avail, sn, sr0, cnt, gbase, ln);
         if (ln.active) {
             const int64_t gr = int64_t(ln.g0) + (lane - ln.mb);
             ln.e0 = a.indptr[gr];
@@ -359,34 +232,16 @@ __global__ __launch_bounds__(kMaxWaves * 64) void embed_graphs_bwd_kernel(const 
         {
             const int mi = lane - cpos;
             if (mi >= 0 && mi < ccnt) { mbase[mi] = gbase; mcount[mi] = sn; }
-            const bool rowok = me.active && me.e0 >= 0 && me.e1 >= me.e0 && int64_t(me.e1) <= a.E;
-            if (!rowok) me.e0 = me.e1 = 0;
+            lane_turn(a.indices, a.E, me);
 #pragma unroll
-            for (int q = 0; q < kRegNb; ++q) {
-                me.nb[q] = -1;
-                if (me.e0 + q < me.e1) {
-                    const int c = a.indices[me.e0 + q] - me.g0;
-                    if (c >= 0 && c < me.mn) me.nb[q] = me.mb + c;
-                }
-                tab[kTabNb + 4 * lane + q] = me.nb[q];
-            }
+            for (int q = 0; q < kRegNb; ++q) tab[kTabNb + 4 * lane + q] = me.nb[q];
             tab[kTabE0 + lane] = me.e0;
             tab[kTabE1 + lane] = me.e1;
-            const int deg = me.e1 - me.e0;
-            me.sc = deg > 0 ? 1.0f / sqrtf(float(deg)) : 0.f;
             scale[lane] = me.sc;
             if (me.active) {
                 v4f *dst = reinterpret_cast<v4f *>(T + lane * st);
                 if constexpr (U8) {
-#pragma unroll
-                    for (int c = 0; c < 16; ++c)
-                        if (4 * c < f0) {
-                            const unsigned w = __float_as_uint(x[c / 4][c & 3]);
-                            v4f v;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) v[i] = 4 * c + i < f0 ? float((w >> (8 * i)) & 0xffu) : 0.f;
-                            dst[c] = v;
-                        }
+                    unpack_u8_row(x, f0, dst);
                 } else {                             // an fp32 row is 16 vectors: loaded here, four at a time
                     const int64_t gr = int64_t(me.g0) + (lane - me.mb);
                     const v4f *row = reinterpret_cast<const v4f *>(static_cast<const char *>(a.feat) + gr * a.ldf * 4);
@@ -441,6 +296,8 @@ __global__ __launch_bounds__(kMaxWaves * 64) void embed_graphs_bwd_kernel(const 
                 const bool relu = a.act[l] == GAE_ACT_RELU;
                 const float *mrow = Ml + lane * sm;
                 float *yrow = T + lane * st;
+                // (the switch is written out here and in embed.hip: behind one shared dispatcher the compiler rescheduled
+                // 760 of this kernel's 10 500 instructions, with nothing to gain)
                 switch (a.jp[l]) {
                 case 8: mask = transform_keep<8>(Wt, bl, fi, relu, mrow, yrow); break;
                 case 16: mask = transform_keep<16>(Wt, bl, fi, relu, mrow, yrow); break;
@@ -575,34 +432,6 @@ __global__ __launch_bounds__(kMaxWaves * 64) void embed_graphs_bwd_kernel(const 
         if (l < a.L && a.want[l] && lane < a.width[l + 1]) part[a.pb_off[l] + lane] = dbacc[l];
 }
 
-int round_up(int v, int q) { return (v + q - 1) / q * q; }
-
-// the shapes the kernel takes; `what` (may be NULL) receives the offending quantity
-bool shape_taken(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes, char *what, size_t cap)
-{
-    if (n_layers < 1 || n_layers > kMaxLayers) {
-        if (what) snprintf(what, cap, "n_layers = %lld outside 1..%d", (long long)n_layers, kMaxLayers);
-        return false;
-    }
-    if (f_in < 1 || f_in > kMaxWidth) {
-        if (what) snprintf(what, cap, "input width f_in = %lld outside 1..%d", (long long)f_in, kMaxWidth);
-        return false;
-    }
-    for (int64_t l = 0; l < n_layers; ++l)
-        if (widths[l] < 1 || widths[l] > kMaxWidth) {
-            if (what)
-                snprintf(what, cap, "width of layer %lld = %lld outside 1..%d", (long long)l, (long long)widths[l],
-                         kMaxWidth);
-            return false;
-        }
-    if (max_graph_nodes > kRows) {
-        if (what)
-            snprintf(what, cap, "max_graph_nodes = %lld above %d nodes per graph", (long long)max_graph_nodes, kRows);
-        return false;
-    }
-    return true;
-}
-
 // the LDS layout, the tiles and the partial's layout of an encoder f_in -> widths (shape_taken holds); returns the
 // waves per block that fit (0: the encoder is refused) and in `what` the reason
 int plan_shapes(int64_t f_in, int64_t n_layers, const int64_t *widths, BwdArgs &a, char *what, size_t cap)
@@ -681,25 +510,12 @@ int64_t partials_bound(int64_t n_out)
     return (small > large ? small : large) + kMaxWaves;
 }
 
-#define GAE_BWD_LAUNCH(kernel, ...)                                                                                    \
-    do {                                                                                                               \
-        static int configured[16] = {0};   /* per (instantiation, device): raised when a launch needs more LDS */      \
-        int dev_ = 0;                                                                                                  \
-        GAE_HIP(hipGetDevice(&dev_));                                                                                  \
-        if (lds > 48 * 1024 && (dev_ < 0 || dev_ >= 16 || configured[dev_] < int(lds))) {                              \
-            GAE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&kernel),                                       \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));                        \
-            if (dev_ >= 0 && dev_ < 16) configured[dev_] = int(lds);                                                   \
-        }                                                                                                              \
-        hipLaunchKernelGGL(kernel, dim3(unsigned(g.blocks)), dim3(g.nw * 64), lds, st, __VA_ARGS__);                   \
-    } while (0)
-
 } // namespace
 
 extern "C" int gae_embed_graphs_bwd_usable(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes)
 {
     if (!widths || max_graph_nodes < 0) return 0;
-    if (!shape_taken(f_in, n_layers, widths, max_graph_nodes, nullptr, 0)) return 0;
+    if (!shape_taken(f_in, n_layers, widths, max_graph_nodes, 1, nullptr, 0)) return 0;
     BwdArgs a;
     return plan_shapes(f_in, n_layers, widths, a, nullptr, 0) > 0 ? 1 : 0;
 }
@@ -710,7 +526,7 @@ extern "C" int64_t gae_embed_graphs_bwd_workspace_bytes(int64_t f_in, int64_t n_
     GAE_REQUIRE(widths, GAE_E_NULL, "gae_embed_graphs_bwd_workspace_bytes: widths is NULL");
     GAE_REQUIRE(n_out >= 0, GAE_E_SIZE, "gae_embed_graphs_bwd_workspace_bytes: negative n_out = %lld", (long long)n_out);
     char what[200];
-    GAE_REQUIRE(shape_taken(f_in, n_layers, widths, 0, what, sizeof what), GAE_E_RANGE,
+    GAE_REQUIRE(shape_taken(f_in, n_layers, widths, 0, 1, what, sizeof what), GAE_E_RANGE,
                 "gae_embed_graphs_bwd_workspace_bytes: %s", what);
     BwdArgs a;
     GAE_REQUIRE(plan_shapes(f_in, n_layers, widths, a, what, sizeof what) > 0, GAE_E_RANGE,
@@ -728,33 +544,18 @@ extern "C" int gae_embed_graphs_bwd(const int64_t *graph_ptr, int64_t n_graphs, 
                                     void *stream)
 {
     static const char fn[] = "gae_embed_graphs_bwd";
-    GAE_REQUIRE(widths && weights && ldw && acts, GAE_E_NULL, "%s: widths / weights / ldw / acts is NULL", fn);
+    const Request r = {graph_ptr, n_graphs, n_nodes, n_edges, max_graph_nodes, indptr, indices, feat, feat_dtype, ldf,
+                       f_in, n_layers, widths, weights, ldw, biases, acts, norm, graph_ids, n_out};
+    if (const int rc = check_layers(fn, r, 1)) return rc;
     GAE_REQUIRE(dW && lddw && db, GAE_E_NULL, "%s: the table dW / lddw / db is NULL (an ENTRY may be NULL: not wanted)",
                 fn);
-    GAE_REQUIRE(n_graphs >= 0 && n_nodes >= 0 && n_edges >= 0 && n_out >= 0 && max_graph_nodes >= 0, GAE_E_SIZE,
-                "%s: negative n_graphs = %lld, n_nodes = %lld, n_edges = %lld, n_out = %lld or max_graph_nodes = %lld",
-                fn, (long long)n_graphs, (long long)n_nodes, (long long)n_edges, (long long)n_out,
-                (long long)max_graph_nodes);
-    GAE_REQUIRE(n_nodes < (int64_t(1) << 31) && n_edges < (int64_t(1) << 31), GAE_E_SIZE,
-                "%s: n_nodes = %lld or n_edges = %lld beyond the int32 CSR", fn, (long long)n_nodes, (long long)n_edges);
     char what[200];
-    GAE_REQUIRE(shape_taken(f_in, n_layers, widths, max_graph_nodes, what, sizeof what), GAE_E_RANGE, "%s: %s", fn, what);
     BwdArgs a;
     const int nw_max = plan_shapes(f_in, n_layers, widths, a, what, sizeof what);
     GAE_REQUIRE(nw_max > 0, GAE_E_RANGE, "%s: %s", fn, what);
-    GAE_REQUIRE(norm == GAE_EMBED_NORM_NONE || norm == GAE_EMBED_NORM_BOTH, GAE_E_RANGE,
-                "%s: unknown norm code %d (0 = none, 1 = both)", fn, norm);
-    GAE_REQUIRE(feat_dtype == GAE_F32 || feat_dtype == GAE_U8, GAE_E_DTYPE, "%s: feature dtype %d (GAE_F32 or GAE_U8)",
-                fn, feat_dtype);
     bool any = false;
     for (int64_t l = 0; l < n_layers; ++l) {
-        const int64_t fi = l ? widths[l - 1] : f_in;
-        GAE_REQUIRE(acts[l] == GAE_ACT_IDENTITY || acts[l] == GAE_ACT_RELU, GAE_E_DTYPE,
-                    "%s: unknown activation code %d of layer %lld", fn, acts[l], (long long)l);
-        GAE_REQUIRE(weights[l], GAE_E_NULL, "%s: the weight of layer %lld is NULL", fn, (long long)l);
-        GAE_REQUIRE(ldw[l] >= fi, GAE_E_SIZE, "%s: leading dimension ldw = %lld of layer %lld below its input width", fn,
-                    (long long)ldw[l], (long long)l);
-        GAE_REQUIRE(!dW[l] || lddw[l] >= fi, GAE_E_SIZE,
+        GAE_REQUIRE(!dW[l] || lddw[l] >= (l ? widths[l - 1] : f_in), GAE_E_SIZE,
                     "%s: leading dimension lddw = %lld of layer %lld below its input width", fn, (long long)lddw[l],
                     (long long)l);
         any = any || dW[l] || db[l];
@@ -762,9 +563,7 @@ extern "C" int gae_embed_graphs_bwd(const int64_t *graph_ptr, int64_t n_graphs, 
     const int64_t d = widths[n_layers - 1];
     GAE_REQUIRE(ldd >= 3 * d, GAE_E_SIZE, "%s: leading dimension too small (ldd %lld < 3 d = %lld)", fn, (long long)ldd,
                 (long long)(3 * d));
-    const int64_t row_elems = feat_dtype == GAE_U8 ? (f_in + 15) / 16 * 16 : (f_in + 3) / 4 * 4;
-    GAE_REQUIRE(ldf >= row_elems, GAE_E_SIZE, "%s: feature rows of ldf = %lld elements, %lld needed (whole 16-byte vectors)",
-                fn, (long long)ldf, (long long)row_elems);
+    if (const int rc = check_feature_rows(fn, r)) return rc;
     const int64_t need = partials_bound(n_out) * a.P * 4;
     GAE_REQUIRE(n_out == 0 || !any || (workspace && workspace_bytes >= need), GAE_E_SIZE,
                 "%s: workspace of %lld bytes, %lld needed (gae_embed_graphs_bwd_workspace_bytes)", fn,
@@ -780,11 +579,7 @@ extern "C" int gae_embed_graphs_bwd(const int64_t *graph_ptr, int64_t n_graphs, 
         return GAE_OK;
     }
     GAE_REQUIRE(graph_ptr && d_out, GAE_E_NULL, "%s: graph_ptr / d_out is NULL", fn);
-    GAE_REQUIRE(n_nodes == 0 || (indptr && feat), GAE_E_NULL, "%s: indptr / feat is NULL", fn);
-    GAE_REQUIRE(n_edges == 0 || indices, GAE_E_NULL, "%s: indices is NULL", fn);
-    const int64_t row_bytes = ldf * (feat_dtype == GAE_U8 ? 1 : 4);
-    GAE_REQUIRE(n_nodes == 0 || (gae::aligned16(feat) && row_bytes % 16 == 0), GAE_E_ALIGN,
-                "%s: feature rows must start on 16-byte boundaries (pointer and ldf)", fn);
+    if (const int rc = check_arrays(fn, r)) return rc;
 
     a.graph_ptr = graph_ptr; a.indptr = indptr; a.indices = indices; a.feat = feat; a.ldf = ldf;
     a.G = n_graphs; a.N = n_nodes; a.E = n_edges; a.B = n_out;
@@ -801,8 +596,8 @@ extern "C" int gae_embed_graphs_bwd(const int64_t *graph_ptr, int64_t n_graphs, 
     a.S = g.S;
     GAE_REQUIRE(g.blocks < (int64_t(1) << 31), GAE_E_SIZE, "%s: n_out = %lld is too large", fn, (long long)n_out);
     const size_t lds = size_t(a.wfloats + g.nw * a.wave_floats) * 4;
-    if (feat_dtype == GAE_U8) GAE_BWD_LAUNCH(embed_graphs_bwd_kernel<true>, a);
-    else GAE_BWD_LAUNCH(embed_graphs_bwd_kernel<false>, a);
+    if (feat_dtype == GAE_U8) GAE_GRAPHS_LAUNCH(embed_graphs_bwd_kernel<true>, g.blocks, g.nw * 64, a);
+    else GAE_GRAPHS_LAUNCH(embed_graphs_bwd_kernel<false>, g.blocks, g.nw * 64, a);
     GAE_CHECK_LAUNCH("embed_graphs_bwd_kernel");
     // ---- second stage: the partials of every wave, added in the library's one order
     for (int l = 0; l < a.L; ++l) {
