@@ -2,14 +2,10 @@
 //
 // For query q = (i, j) = (src[q], dst[q]) and t = s_ij = z_i . z_j: how many candidates c of row i, the target left out,
 // score above t and how many score exactly t -- the rank of j among all candidates of i (MRR, Hits@K, mean rank, the
-// exact all-negatives AUC; metrics.rank_metrics).  The candidate rule is K16's (include/gae_hip.h): a column window,
-// c != i, c not in CSR row i, s_ic neither NaN nor -inf.
+// exact all-negatives AUC; metrics.rank_metrics).  Who is a candidate, how the columns are split over waves and which
+// bits s_ic has: decoder_pairs.h, shared with K16 -- s_ic is the number gae_decoder_topk lists for that pair.
 //
-// Products.  K16's, operand for operand: one wave per 32-query panel and column split; panel row r holds z_{src[q0 + r]}
-// (gathered) as the B operand of v_mfma_f32_32x32x2_f32, 32-column tiles of Z are the A operand, lane half h feeds
-// features [h DH, h DH + DH) of each 2 DH-wide chunk, same d -> DH / chunk dispatch.  The accumulator of lane l holds
-// query q0 + (l & 31) against the 16 columns c0 + (r & 3) + 8 (r >> 2) + 4 (l >> 5).  s_ic is therefore the number
-// gae_decoder_topk computes for that pair: a function of the bits of z_i and z_c only.
+// Products.  Panel row r holds z_{src[q0 + r]} (gathered); the tiles of Z are the other operand.
 // The threshold t comes out of the same instruction: one extra tile whose A operand is the gathered dst rows; the lane
 // that owns the diagonal element (row r against column r) hands it to the other half of its row.  No score is computed
 // by a second route, so "s_ic == t" is an equality of bits of one and the same chain.
@@ -35,43 +31,19 @@
 // gae_decoder_topk(k = 10) on the same Z.  What buys that: operand loads without branches (row and feature clamped, two
 // 16-byte loads per tile at d = 16) and the next tile's loads issued before the current tile is counted.  118 VGPRs at
 // d <= 16 (4 waves per SIMD), accumulators in VGPRs (-amdgpu-mfma-vgpr-form, _build.py): the epilogue reads each one.
-#include "common.h"
+#include "decoder_pairs.h"
 
 namespace {
 
-constexpr int kRows = 32;         // queries per wave
-constexpr int kTile = 32;         // columns per tile
-constexpr int kMaxSplits = 16;
+using namespace gae::pairs;
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-struct RankArgs {
-    const float *Z;
-    int64_t ldz;
-    int n, d, m, nch, S;
+struct RankArgs : Common {
+    int m;
     const int64_t *src, *dst;
-    const int64_t *node_ptr;      // NULL = scope batch
-    int64_t G;
-    const int32_t *indptr, *indices;
-    int excl_self;
     float *score_out;
     int64_t *greater_out, *equal_out, *cand_out;
     int32_t *part;                // [S][m][3] (S > 1): above, at-or-above, valid
 };
-
-// the member window [w0, w1) of row i (empty when i lies outside every member): K16's rule
-__device__ void member_window(const RankArgs &a, int i, int &w0, int &w1)
-{
-    if (!a.node_ptr) { w0 = 0; w1 = a.n; return; }
-    w0 = 0; w1 = 0;
-    if (a.G <= 0 || a.node_ptr[0] > i) return;
-    int64_t l = 0, h = a.G;                       // last member g < G with node_ptr[g] <= i
-    while (h - l > 1) { const int64_t m = (l + h) >> 1; if (a.node_ptr[m] <= i) l = m; else h = m; }
-    int64_t p0 = a.node_ptr[l], p1 = a.node_ptr[l + 1];
-    p0 = p0 < 0 ? 0 : p0;                         // clipped to [0, n): a bad node_ptr never reads outside Z
-    p1 = p1 > a.n ? a.n : p1;
-    if (i >= p0 && i < p1) { w0 = int(p0); w1 = int(p1); }
-}
 
 __device__ __forceinline__ void write_result(const RankArgs &a, int64_t q, bool ok, float t, int gt, int ge, int valid)
 {
@@ -108,34 +80,20 @@ __global__ __launch_bounds__(64) void rank_kernel(const RankArgs a)
     if (ok) member_window(a, i, w0, w1);
     int e0 = 0, e1 = 0;
     if (ok && a.indptr) { e0 = a.indptr[i]; e1 = a.indptr[i + 1]; }
-    // ---- the wave's column range: the union of its rows' windows, cut into S tile-aligned parts
-    int cb = w0 < w1 ? w0 : INT32_MAX, ce = w0 < w1 ? w1 : INT32_MIN;
-    for (int off = 32; off > 0; off >>= 1) {
-        const int ob = __shfl_xor(cb, off, 64), oe = __shfl_xor(ce, off, 64);
-        cb = ob < cb ? ob : cb;
-        ce = oe > ce ? oe : ce;
-    }
-    int pb = 0, pe = 0;
-    if (cb < ce) {
-        const int64_t span = int64_t(ce) - cb;
-        const int64_t L = ((span + a.S - 1) / a.S + kTile - 1) / kTile * kTile;
-        const int64_t b = cb + L * split, e = b + L;
-        pb = int(b < ce ? b : ce);
-        pe = int(e < ce ? e : ce);
-    }
+    // ---- the wave's column part and this lane's columns in it
+    int pb, pe, lo, hi;
+    wave_part(w0, w1, a.S, split, pb, pe, lo, hi);
     pb = __builtin_amdgcn_readfirstlane(pb);       // the same in every lane: scalar loop control
     pe = __builtin_amdgcn_readfirstlane(pe);
-    // this lane's columns: its row's window inside this part
-    const int lo = w0 > pb ? w0 : pb, hi = w1 < pe ? w1 : pe;
 
-    // ---- operand loads: DH features f = ch 2 DH + h DH + s of one row of Z per lane.  The caller clamps the row into
+    // ---- operand loads: the DH features feat0 + s of one row of Z per lane.  The caller clamps the row into
     // [0, n) (the host launches nothing when n = 0) and the feature index is clamped here, so no load carries a branch.
     // A feature past d is zeroed: it would enter every product.  A clamped ROW is not: row c of the A operand reaches
     // only the scores of column c, row r of the B operand only those of query r, and neither is counted.
     const bool full = a.d == a.nch * 2 * DH;       // no feature tail: the common d = 16, 32, 64, 128, 256
     auto load_feats = [&](float (&z)[DH], int64_t row, int ch) {
         const float *p = a.Z + row * a.ldz;
-        const int f0 = ch * 2 * DH + h * DH;
+        const int f0 = feat0<DH>(ch, h);
         if (full) {
 #pragma unroll
             for (int s = 0; s < DH; ++s) z[s] = p[f0 + s];
@@ -148,38 +106,30 @@ __global__ __launch_bounds__(64) void rank_kernel(const RankArgs a)
             }
         }
     };
-    auto mma = [&](v16f acc, const float (&za)[DH], const float (&zb)[DH]) {
-#pragma unroll
-        for (int s = 0; s < DH; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(za[s], zb[s], acc, 0, 0, 0);
-        return acc;
-    };
     // the panel rows (B operand) stay in registers when one chunk holds all of d
     float zr[DH];
     if constexpr (ONE) load_feats(zr, i, 0);
     // one tile: rows of Z picked by `row` (in [0, n)) against the panel
     auto tile = [&](int64_t row) {
-        v16f acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        v16f acc = zero_acc();
         for (int ch = 0; ch < (ONE ? 1 : a.nch); ++ch) {
             if constexpr (!ONE) load_feats(zr, i, ch);
             float za[DH];
             load_feats(za, row, ch);
-            acc = mma(acc, za, zr);
+            acc = mma<DH>(acc, za, zr);
         }
         return acc;
     };
 
-    // ---- the threshold: the diagonal of (gathered dst rows) x (panel); column `col` of this tile sits in lane half
-    // (col >> 2) & 1, register (col & 3) + 4 (col >> 3)
+    // ---- the threshold: the diagonal of (gathered dst rows) x (panel), row `col` against column `col` of this tile
     float t;
     {
         const v16f acc = tile(j);
-        const int dr = (col & 3) + 4 * (col >> 3);
+        int owner, dr;
+        tile_owner(col, col, owner, dr);
         float dv = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) dv = r == dr ? acc[r] : dv;
-        const int owner = col + 32 * ((col >> 2) & 1);
         t = __shfl(dv, owner, 64);
     }
 
@@ -206,7 +156,7 @@ __global__ __launch_bounds__(64) void rank_kernel(const RankArgs a)
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int c = tile_col(0, r, h);
                 const bool cand = c >= lo_r && c < hi_r && c != j_r && c != x_r && acc[r] > -INFINITY;
                 gt += (cand && acc[r] > t) ? 1 : 0;
                 ge += (cand && acc[r] >= t) ? 1 : 0;
@@ -220,10 +170,7 @@ __global__ __launch_bounds__(64) void rank_kernel(const RankArgs a)
         const int64_t last = int64_t(pe) - 1;      // a column past the part is clamped into it
         if (pb < pe) load_feats(za, int64_t(pb) + col < last ? int64_t(pb) + col : last, 0);
         for (int64_t c0 = pb; c0 < pe; c0 += kTile) {
-            v16f acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            acc = mma(acc, za, zr);
+            const v16f acc = mma<DH>(zero_acc(), za, zr);
             const int64_t jn = c0 + kTile + col;
             if (c0 + kTile < pe) load_feats(za, jn < last ? jn : last, 0);
             count(acc, int(c0));
@@ -273,19 +220,7 @@ __global__ __launch_bounds__(64) void rank_kernel(const RankArgs a)
                 const int b = s_e0[l];
                 const int e = b + int(p - s_pref[l]);
                 const int v = a.indices[e];
-                bool first;
-                if (s_sorted[l]) {
-                    first = e == b || a.indices[e - 1] != v;
-                } else {
-                    first = true;
-                    for (int x = b; x < e && first; x += 4) {      // four independent loads per round trip
-                        const int32_t v0 = a.indices[x];
-                        const int32_t v1 = a.indices[x + 1 < e ? x + 1 : e - 1];
-                        const int32_t v2 = a.indices[x + 2 < e ? x + 2 : e - 1];
-                        const int32_t v3 = a.indices[x + 3 < e ? x + 3 : e - 1];
-                        first = !(v0 == v || v1 == v || v2 == v || v3 == v);
-                    }
-                }
+                const bool first = s_sorted[l] ? e == b || a.indices[e - 1] != v : !row_holds(a.indices, b, e, v);
                 if (first && v >= 0 && v < a.n) c = v;             // a bad CSR entry never reads outside Z
             }
             __syncthreads();                       // the previous tile's readers are done with s_col
@@ -295,7 +230,7 @@ __global__ __launch_bounds__(64) void rank_kernel(const RankArgs a)
             const int64_t base = tix * kTile;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int s = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int s = tile_col(0, r, h);
                 const int64_t ps = base + s;
                 const int cs = s_col[s];
                 // mine, and counted by the sweep: inside the row's whole window, neither the target nor self, valid
@@ -339,20 +274,6 @@ __global__ __launch_bounds__(256) void rank_combine_kernel(const RankArgs a)
     write_result(a, q, ok, ok ? a.score_out[q] : 0.f, gt, ge, valid);
 }
 
-int splits_for(int64_t n, int64_t m, const int64_t *node_ptr, int64_t max_graph_nodes)
-{
-    if (n <= 0 || m <= 0) return 1;
-    const int64_t panels = (m + kRows - 1) / kRows;
-    int64_t S = gae::g_rank_splits;
-    if (S <= 0) {
-        const int64_t span = node_ptr ? (max_graph_nodes < n ? max_graph_nodes : n) : n;
-        S = (4096 + panels - 1) / panels;                  // ~4096 waves: several per SIMD
-        const int64_t by_span = (span + 255) / 256;        // parts of >= 256 columns
-        S = S < by_span ? S : by_span;
-    }
-    return int(S < 1 ? 1 : (S > kMaxSplits ? kMaxSplits : S));
-}
-
 int64_t need_bytes(int64_t m, int S) { return S > 1 ? int64_t(S) * m * 12 + 256 : 256; }
 
 } // namespace
@@ -367,44 +288,28 @@ extern "C" int gae_decoder_rank(const float *Z, int64_t ldz, int64_t n, int64_t 
                                 float *score_out, int64_t *greater_out, int64_t *equal_out, int64_t *candidates_out,
                                 void *workspace, int64_t *workspace_bytes, void *stream)
 {
-    GAE_REQUIRE(d >= 1 && d <= 256, GAE_E_RANGE, "gae_decoder_rank: d = %lld outside 1..256", (long long)d);
-    GAE_REQUIRE(n >= 0 && m >= 0, GAE_E_SIZE, "gae_decoder_rank: negative n = %lld or m = %lld", (long long)n,
-                (long long)m);
-    GAE_REQUIRE(n < (int64_t(1) << 31), GAE_E_SIZE, "gae_decoder_rank: n = %lld beyond the int32 CSR", (long long)n);
-    GAE_REQUIRE(m < (int64_t(1) << 31), GAE_E_SIZE, "gae_decoder_rank: m = %lld queries, 2^31 - 1 at most",
-                (long long)m);
-    GAE_REQUIRE(ldz >= d, GAE_E_SIZE, "gae_decoder_rank: leading dimension too small (ldz %lld < d)", (long long)ldz);
-    GAE_REQUIRE((flags & ~(GAE_TOPK_EXCLUDE_SELF | GAE_TOPK_EXCLUDE_EDGES)) == 0, GAE_E_RANGE,
-                "gae_decoder_rank: unknown flags 0x%x", flags);
-    GAE_REQUIRE(!node_ptr || (n_graphs >= 0 && max_graph_nodes >= 0), GAE_E_SIZE,
-                "gae_decoder_rank: negative n_graphs / max_graph_nodes");
-    GAE_REQUIRE(workspace_bytes, GAE_E_NULL, "gae_decoder_rank: workspace_bytes is NULL");
-    const int S = splits_for(n, m, node_ptr, max_graph_nodes);
+    const char *fn = "gae_decoder_rank";
+    const Request r{Z, ldz, n, d, node_ptr, n_graphs, max_graph_nodes, indptr, indices, flags, workspace_bytes};
+    GAE_REQUIRE(n >= 0 && m >= 0, GAE_E_SIZE, "%s: negative n = %lld or m = %lld", fn, (long long)n, (long long)m);
+    GAE_REQUIRE(m < (int64_t(1) << 31), GAE_E_SIZE, "%s: m = %lld queries, 2^31 - 1 at most", fn, (long long)m);
+    if (const int rc = check_sizes(fn, r)) return rc;
+    const int64_t panels = (m + kRows - 1) / kRows;
+    const int S = splits(panels, n, node_ptr, max_graph_nodes, gae::g_rank_splits);
     const int64_t need = need_bytes(m, S);
     if (!workspace) {                               // size query: no device work
         *workspace_bytes = need;
         return GAE_OK;
     }
-    GAE_REQUIRE(n == 0 || Z, GAE_E_NULL, "gae_decoder_rank: Z is NULL");
-    GAE_REQUIRE(m == 0 || (src && dst), GAE_E_NULL, "gae_decoder_rank: src / dst is NULL");
+    GAE_REQUIRE(m == 0 || (src && dst), GAE_E_NULL, "%s: src / dst is NULL", fn);
     GAE_REQUIRE(m == 0 || (score_out && greater_out && equal_out && candidates_out), GAE_E_NULL,
-                "gae_decoder_rank: score_out / greater_out / equal_out / candidates_out is NULL");
-    GAE_REQUIRE(!(flags & GAE_TOPK_EXCLUDE_EDGES) || (indptr && indices), GAE_E_NULL,
-                "gae_decoder_rank: GAE_TOPK_EXCLUDE_EDGES without a CSR");
-    GAE_REQUIRE(*workspace_bytes >= need, GAE_E_WORKSPACE, "gae_decoder_rank: workspace of %lld bytes, %lld needed",
-                (long long)*workspace_bytes, (long long)need);
+                "%s: score_out / greater_out / equal_out / candidates_out is NULL", fn);
+    if (const int rc = check_arrays(fn, r, need)) return rc;
     if (m == 0) return GAE_OK;
     RankArgs a;
-    a.Z = Z; a.ldz = ldz; a.n = int(n); a.d = int(d); a.m = int(m); a.S = S;
-    a.src = src; a.dst = dst;
-    a.node_ptr = node_ptr; a.G = n_graphs;
-    const bool edges = (flags & GAE_TOPK_EXCLUDE_EDGES) != 0;
-    a.indptr = edges ? indptr : nullptr; a.indices = edges ? indices : nullptr;
-    a.excl_self = (flags & GAE_TOPK_EXCLUDE_SELF) ? 1 : 0;
+    fill(a, r, S);
+    a.m = int(m); a.src = src; a.dst = dst;
     a.score_out = score_out; a.greater_out = greater_out; a.equal_out = equal_out; a.cand_out = candidates_out;
     a.part = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + 256);
-    const int64_t panels = (m + kRows - 1) / kRows;
-    const dim3 grid(unsigned(panels * S));
     hipStream_t st = gae::as_stream(stream);
     if (n == 0) {
         a.S = 0;
@@ -412,19 +317,7 @@ extern "C" int gae_decoder_rank(const float *Z, int64_t ldz, int64_t n, int64_t 
         GAE_CHECK_LAUNCH("rank_combine_kernel");
         return GAE_OK;
     }
-    if (d <= 16) {
-        a.nch = 1;
-        hipLaunchKernelGGL((rank_kernel<8, true>), grid, dim3(64), 0, st, a);
-    } else if (d <= 32) {
-        a.nch = 1;
-        hipLaunchKernelGGL((rank_kernel<16, true>), grid, dim3(64), 0, st, a);
-    } else if (d <= 64) {
-        a.nch = 1;
-        hipLaunchKernelGGL((rank_kernel<32, true>), grid, dim3(64), 0, st, a);
-    } else {
-        a.nch = int((d + 63) / 64);
-        hipLaunchKernelGGL((rank_kernel<32, false>), grid, dim3(64), 0, st, a);
-    }
+    GAE_PAIRS_LAUNCH(rank_kernel, d, dim3(unsigned(panels * S)), dim3(64), 0, st, a);
     GAE_CHECK_LAUNCH("rank_kernel");
     if (S > 1) {
         hipLaunchKernelGGL(rank_combine_kernel, dim3(unsigned((m + 255) / 256)), dim3(256), 0, st, a);

@@ -1,16 +1,12 @@
 // K16: top-k link prediction without the N x N matrix (GAE.predict_links, ops.decoder_topk).
 //
 // For every row i the k candidates j with the largest logit s_ij = z_i . z_j (gae_dgl/gae.py:69-72 without dropout and
-// before the sigmoid), under the candidate rule of include/gae_hip.h: a column window (all n, or i's own member graph),
-// j != i, j not in CSR row i, s_ij neither NaN nor -inf.  Rows are sorted by (score descending, j ascending).
+// before the sigmoid).  Rows are sorted by (score descending, j ascending).  Who is a candidate, how the columns are
+// split over waves and which bits s_ij has: decoder_pairs.h, shared with K18.
 //
-// Products.  One wave per 32-row panel and column split.  The panel's rows are the B operand of
-// v_mfma_f32_32x32x2_f32 and stay in registers; 32-column tiles of Z are the A operand, loaded straight from global
-// memory (L2-resident at every size measured).  With A = candidates and B = panel rows the accumulator of lane l holds
-// row i = r0 + (l & 31) against the 16 columns c0 + (r & 3) + 8 (r >> 2) + 4 (l >> 5): every lane's scores belong to ONE
-// row, so the threshold test needs no cross-lane traffic.  The f32 MFMA is bitwise a k-ordered fmaf chain; the feature
-// order is fixed (lane half h feeds features [h DH, h DH + DH) of each 2 DH-wide chunk), so s_ij depends only on the
-// bits of z_i and z_j, never on where j falls in a tile: equal rows give bit-equal scores and the tie rule is exact.
+// Products.  The panel's rows stay in registers; the tiles of Z are loaded straight from global memory (L2-resident at
+// every size measured), each feature behind its own bounds test.  Every lane's 16 scores belong to ONE row, so the
+// threshold test needs no cross-lane traffic.
 //
 // Selection.  Each lane keeps a running top-k of its (row, lane half) in LDS as a heap with the worst entry at the root.  Per tile the
 // fast path is the max of the lane's 16 scores against the lane's k-th score (about 0.5 VALU op per pair); only lanes
@@ -26,26 +22,16 @@
 #include <float.h>
 #include <string.h>
 
-#include "common.h"
+#include "decoder_pairs.h"
 
 namespace {
 
-constexpr int kRows = 32;         // panel rows per wave
-constexpr int kTile = 32;         // columns per tile
+using namespace gae::pairs;
+
 constexpr int kMaxK = 64;
-constexpr int kMaxSplits = 16;
 
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-struct TopkArgs {
-    const float *Z;
-    int64_t ldz;
-    int n, d, k, nch, S;
-    const int64_t *node_ptr;      // NULL = scope batch
-    int64_t G;
-    const int32_t *indptr, *indices;
-    int excl_self;
+struct TopkArgs : Common {
+    int k;
     float *score_out;
     int64_t *index_out;
     int64_t ldo;
@@ -57,20 +43,6 @@ struct TopkArgs {
 __device__ __forceinline__ bool better(float s, int j, float t, int q) { return s > t || (s == t && j < q); }
 
 __device__ __forceinline__ unsigned hash6(int j) { return (unsigned(j) * 0x9E3779B1u) >> 26; }
-
-// the member window [w0, w1) of row i (empty when i lies outside every member)
-__device__ void member_window(const TopkArgs &a, int i, int &w0, int &w1)
-{
-    if (!a.node_ptr) { w0 = 0; w1 = a.n; return; }
-    w0 = 0; w1 = 0;
-    if (a.G <= 0 || a.node_ptr[0] > i) return;
-    int64_t l = 0, h = a.G;                       // last member g < G with node_ptr[g] <= i
-    while (h - l > 1) { const int64_t m = (l + h) >> 1; if (a.node_ptr[m] <= i) l = m; else h = m; }
-    int64_t p0 = a.node_ptr[l], p1 = a.node_ptr[l + 1];
-    p0 = p0 < 0 ? 0 : p0;                         // clipped to [0, n): a bad node_ptr never reads outside Z
-    p1 = p1 > a.n ? a.n : p1;
-    if (i >= p0 && i < p1) { w0 = int(p0); w1 = int(p1); }
-}
 
 // Each lane's running top-k is a binary heap in LDS (entry p of lane l at [p * 64 + l]) with the WORST entry at the
 // root: the threshold is the root, and an insert costs log2 k dependent LDS round trips instead of the k / 2 of a
@@ -136,30 +108,16 @@ __global__ __launch_bounds__(64) void topk_kernel(const TopkArgs a)
         e0 = a.indptr[i]; e1 = a.indptr[i + 1];
         for (int e = e0; e < e1; ++e) hmask |= 1ull << hash6(a.indices[e]);
     }
-    // ---- the wave's column range: the union of its rows' windows, cut into S tile-aligned parts
-    int cb = w0 < w1 ? w0 : INT32_MAX, ce = w0 < w1 ? w1 : INT32_MIN;
-    for (int off = 32; off > 0; off >>= 1) {
-        const int ob = __shfl_xor(cb, off, 64), oe = __shfl_xor(ce, off, 64);
-        cb = ob < cb ? ob : cb;
-        ce = oe > ce ? oe : ce;
-    }
-    int pb = 0, pe = 0;
-    if (cb < ce) {
-        const int64_t span = int64_t(ce) - cb;
-        const int64_t L = ((span + a.S - 1) / a.S + kTile - 1) / kTile * kTile;
-        const int64_t b = cb + L * split, e = b + L;
-        pb = int(b < ce ? b : ce);
-        pe = int(e < ce ? e : ce);
-    }
-    // this lane's candidates: its row's window inside this part
-    const int lo = w0 > pb ? w0 : pb, hi = w1 < pe ? w1 : pe;
+    // ---- the wave's column part and this lane's candidates in it
+    int pb, pe, lo, hi;
+    wave_part(w0, w1, a.S, split, pb, pe, lo, hi);
 
-    // ---- the panel rows (B operand): features q 2 DH + h DH + s
+    // ---- the panel rows (B operand)
     float zr[DH];
     auto load_row = [&](int q) {
 #pragma unroll
         for (int s = 0; s < DH; ++s) {
-            const int f = q * 2 * DH + h * DH + s;
+            const int f = feat0<DH>(q, h) + s;
             zr[s] = (row_ok && f < a.d) ? a.Z[int64_t(i) * a.ldz + f] : 0.f;
         }
     };
@@ -170,9 +128,7 @@ __global__ __launch_bounds__(64) void topk_kernel(const TopkArgs a)
     int thr_j = INT32_MAX;
     for (int64_t c0_ = pb; c0_ < pe; c0_ += kTile) {
         const int c0 = int(c0_);
-        v16f acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        v16f acc = zero_acc();
         const int64_t jc = int64_t(c0) + col;      // this lane's A-operand column (int64: n may reach 2^31 - 1)
         const bool col_ok = jc < pe;
         for (int q = 0; q < (ONE ? 1 : a.nch); ++q) {
@@ -180,11 +136,10 @@ __global__ __launch_bounds__(64) void topk_kernel(const TopkArgs a)
             float za[DH];
 #pragma unroll
             for (int s = 0; s < DH; ++s) {
-                const int f = q * 2 * DH + h * DH + s;
+                const int f = feat0<DH>(q, h) + s;
                 za[s] = (col_ok && f < a.d) ? a.Z[jc * a.ldz + f] : 0.f;
             }
-#pragma unroll
-            for (int s = 0; s < DH; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(za[s], zr[s], acc, 0, 0, 0);
+            acc = mma<DH>(acc, za, zr);
         }
         // ---- fast path: one max per score, one compare per tile
         float m = acc[0];
@@ -201,23 +156,12 @@ __global__ __launch_bounds__(64) void topk_kernel(const TopkArgs a)
                 const int r = __builtin_ctz(pass);
                 pass &= pass - 1;
                 const float s = scr[r * 64 + lane];
-                const int64_t jj = int64_t(c0) + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int64_t jj = tile_col(int64_t(c0), r, h);
                 if (jj < lo || jj >= hi) continue;
                 const int j = int(jj);
                 if (a.excl_self && j == i) continue;
                 if (cnt == k && !better(s, j, thr, thr_j)) continue;
-                if ((hmask >> hash6(j)) & 1ull) {
-                    // a hash hit: scan the CSR row, four independent loads per round trip (clamped inside the row)
-                    bool edge = false;
-                    for (int e = e0; e < e1 && !edge; e += 4) {
-                        const int32_t v0 = a.indices[e];
-                        const int32_t v1 = a.indices[e + 1 < e1 ? e + 1 : e1 - 1];
-                        const int32_t v2 = a.indices[e + 2 < e1 ? e + 2 : e1 - 1];
-                        const int32_t v3 = a.indices[e + 3 < e1 ? e + 3 : e1 - 1];
-                        edge = v0 == j || v1 == j || v2 == j || v3 == j;
-                    }
-                    if (edge) continue;
-                }
+                if (((hmask >> hash6(j)) & 1ull) && row_holds(a.indices, e0, e1, j)) continue;     // scanned on a hash hit
                 if (cnt < k) {
                     heap_push(ls, lj, lane, cnt, s, j);
                     ++cnt;
@@ -314,20 +258,6 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const TopkArgs a)
     }
 }
 
-int splits_for(int64_t n, const int64_t *node_ptr, int64_t max_graph_nodes)
-{
-    if (n <= 0) return 1;
-    const int64_t panels = (n + kRows - 1) / kRows;
-    int64_t S = gae::g_topk_splits;
-    if (S <= 0) {
-        const int64_t span = node_ptr ? (max_graph_nodes < n ? max_graph_nodes : n) : n;
-        S = (4096 + panels - 1) / panels;                  // ~4096 waves: several per SIMD
-        const int64_t by_span = (span + 255) / 256;        // parts of >= 256 columns
-        S = S < by_span ? S : by_span;
-    }
-    return int(S < 1 ? 1 : (S > kMaxSplits ? kMaxSplits : S));
-}
-
 int64_t need_bytes(int64_t n, int64_t k, int S) { return S > 1 ? int64_t(S) * n * k * 8 + 256 : 256; }
 
 } // namespace
@@ -341,56 +271,31 @@ extern "C" int gae_decoder_topk(const float *Z, int64_t ldz, int64_t n, int64_t 
                                 const int32_t *indices, int flags, float *score_out, int64_t *index_out, int64_t ldo,
                                 void *workspace, int64_t *workspace_bytes, void *stream)
 {
-    GAE_REQUIRE(k >= 1 && k <= kMaxK, GAE_E_RANGE, "gae_decoder_topk: k = %lld outside 1..64", (long long)k);
-    GAE_REQUIRE(d >= 1 && d <= 256, GAE_E_RANGE, "gae_decoder_topk: d = %lld outside 1..256", (long long)d);
-    GAE_REQUIRE(n >= 0, GAE_E_SIZE, "gae_decoder_topk: negative n = %lld", (long long)n);
-    GAE_REQUIRE(n < (int64_t(1) << 31), GAE_E_SIZE, "gae_decoder_topk: n = %lld beyond the int32 CSR", (long long)n);
-    GAE_REQUIRE(ldz >= d && ldo >= k, GAE_E_SIZE, "gae_decoder_topk: leading dimension too small (ldz %lld < d or "
-                "ldo %lld < k)", (long long)ldz, (long long)ldo);
-    GAE_REQUIRE((flags & ~(GAE_TOPK_EXCLUDE_SELF | GAE_TOPK_EXCLUDE_EDGES)) == 0, GAE_E_RANGE,
-                "gae_decoder_topk: unknown flags 0x%x", flags);
-    GAE_REQUIRE(!node_ptr || (n_graphs >= 0 && max_graph_nodes >= 0), GAE_E_SIZE,
-                "gae_decoder_topk: negative n_graphs / max_graph_nodes");
-    GAE_REQUIRE(workspace_bytes, GAE_E_NULL, "gae_decoder_topk: workspace_bytes is NULL");
-    const int S = splits_for(n, node_ptr, max_graph_nodes);
+    const char *fn = "gae_decoder_topk";
+    const Request r{Z, ldz, n, d, node_ptr, n_graphs, max_graph_nodes, indptr, indices, flags, workspace_bytes};
+    GAE_REQUIRE(k >= 1 && k <= kMaxK, GAE_E_RANGE, "%s: k = %lld outside 1..64", fn, (long long)k);
+    // both leading dimensions in one message, ahead of the common ldz check: the text callers have seen since K16
+    GAE_REQUIRE(ldz >= d && ldo >= k, GAE_E_SIZE, "%s: leading dimension too small (ldz %lld < d or ldo %lld < k)", fn,
+                (long long)ldz, (long long)ldo);
+    if (const int rc = check_sizes(fn, r)) return rc;
+    const int64_t panels = (n + kRows - 1) / kRows;
+    const int S = splits(panels, n, node_ptr, max_graph_nodes, gae::g_topk_splits);
     const int64_t need = need_bytes(n, k, S);
     if (!workspace) {                               // size query: no device work
         *workspace_bytes = need;
         return GAE_OK;
     }
-    GAE_REQUIRE(n == 0 || Z, GAE_E_NULL, "gae_decoder_topk: Z is NULL");
-    GAE_REQUIRE(n == 0 || (score_out && index_out), GAE_E_NULL, "gae_decoder_topk: score_out / index_out is NULL");
-    GAE_REQUIRE(!(flags & GAE_TOPK_EXCLUDE_EDGES) || (indptr && indices), GAE_E_NULL,
-                "gae_decoder_topk: GAE_TOPK_EXCLUDE_EDGES without a CSR");
-    GAE_REQUIRE(*workspace_bytes >= need, GAE_E_WORKSPACE, "gae_decoder_topk: workspace of %lld bytes, %lld needed",
-                (long long)*workspace_bytes, (long long)need);
+    GAE_REQUIRE(n == 0 || (score_out && index_out), GAE_E_NULL, "%s: score_out / index_out is NULL", fn);
+    if (const int rc = check_arrays(fn, r, need)) return rc;
     if (n == 0) return GAE_OK;
     TopkArgs a;
-    a.Z = Z; a.ldz = ldz; a.n = int(n); a.d = int(d); a.k = int(k); a.S = S;
-    a.node_ptr = node_ptr; a.G = n_graphs;
-    const bool edges = (flags & GAE_TOPK_EXCLUDE_EDGES) != 0;
-    a.indptr = edges ? indptr : nullptr; a.indices = edges ? indices : nullptr;
-    a.excl_self = (flags & GAE_TOPK_EXCLUDE_SELF) ? 1 : 0;
-    a.score_out = score_out; a.index_out = index_out; a.ldo = ldo;
+    fill(a, r, S);
+    a.k = int(k); a.score_out = score_out; a.index_out = index_out; a.ldo = ldo;
     a.part_s = reinterpret_cast<float *>(static_cast<char *>(workspace) + 256);
     a.part_j = reinterpret_cast<int32_t *>(a.part_s + (S > 1 ? int64_t(S) * n * k : 0));
-    const int64_t panels = (n + kRows - 1) / kRows;
-    const dim3 grid(unsigned(panels * S));
     const size_t lds = size_t(2 * k + 16) * 64 * 4;
     hipStream_t st = gae::as_stream(stream);
-    if (d <= 16) {
-        a.nch = 1;
-        hipLaunchKernelGGL((topk_kernel<8, true>), grid, dim3(64), lds, st, a);
-    } else if (d <= 32) {
-        a.nch = 1;
-        hipLaunchKernelGGL((topk_kernel<16, true>), grid, dim3(64), lds, st, a);
-    } else if (d <= 64) {
-        a.nch = 1;
-        hipLaunchKernelGGL((topk_kernel<32, true>), grid, dim3(64), lds, st, a);
-    } else {
-        a.nch = int((d + 63) / 64);
-        hipLaunchKernelGGL((topk_kernel<32, false>), grid, dim3(64), lds, st, a);
-    }
+    GAE_PAIRS_LAUNCH(topk_kernel, d, dim3(unsigned(panels * S)), dim3(64), lds, st, a);
     GAE_CHECK_LAUNCH("topk_kernel");
     if (S > 1) {
         const int64_t threads = n * S * k;

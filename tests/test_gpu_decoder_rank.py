@@ -209,6 +209,86 @@ def test_scores_and_ranks_agree_with_topk(dev):
     assert bool((res.candidates >= n - 2 - deg).all())
 
 
+def _fma32(a, b, c):
+    """fp32 fma(a, b, c) exactly: the product of two fp32 is exact in fp64, and the fp64 sum is rounded to odd (TwoSum
+    tells whether it was exact), so that the rounding to fp32 afterwards is the only one that counts"""
+    p, c = a.astype(np.float64) * b.astype(np.float64), c.astype(np.float64)
+    s = p + c
+    t = s - p
+    err = (p - (s - t)) + (c - t)
+    even = (s.view(np.int64) & 1) == 0
+    s = np.where((err != 0) & even, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def _chain_scores(Z):
+    """Z Z^T as csrc/decoder_pairs.h defines it: per pair ONE fp32 fma chain from 0 over the features in the order the
+    two lane halves feed them -- of every 2 DH-wide chunk feature s of the lower half, then of the upper, s ascending;
+    DH = 8, 16, 32 for d <= 16, 32, above.  fp32 [n, n], the bits both kernels must return"""
+    n, d = Z.shape
+    DH = 8 if d <= 16 else 16 if d <= 32 else 32
+    S = np.zeros((n, n), dtype=np.float32)
+    for c0 in range(0, d, 2 * DH):
+        for s in range(DH):
+            for f in (c0 + s, c0 + DH + s):
+                if f < d:                                 # a feature past d is a zero operand: the sum stays
+                    S = _fma32(Z[:, f:f + 1], Z[None, :, f], S)
+    return S
+
+
+@pytest.mark.parametrize("d", [3, 16, 17, 33, 64, 65, 130, 256])
+def test_topk_and_rank_share_scores_small(d, dev, tuning):
+    """the seam of csrc/decoder_pairs.h in every dispatch form (all four <DH, ONE> forms, with and without a feature
+    tail), on ragged members whose windows start and end off the tile boundaries, in both scopes and with 1 and 3
+    column splits of either kernel: the rank query of every top-k entry returns the list's score bit for bit and a
+    rank interval that holds its position, and both kernels equal their CPU references (oracle_topk, rank_ref) read
+    off the fp32 chain of _chain_scores: exact indices, counts and score bits"""
+    from gae_dgl_amd import ops
+    from test_gpu_decoder_topk import allowed_mask, oracle_topk
+    sizes = [1, 2, 31, 32, 33, 70, 5]
+    gp = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    n, k = int(gp[-1]), 8
+    member = np.searchsorted(gp, np.arange(n), side="right") - 1
+    windows = np.stack([gp[member], gp[member + 1]], 1)
+    rng = np.random.default_rng(d)
+    torch.manual_seed(d)
+    Zc = torch.randn(n, d)
+    Zc[120], Zc[160] = Zc[101], Zc[140]                   # bitwise copies inside the 70-node member [99, 169): ties
+    rows = []
+    for i in range(n):                                    # block diagonal, about three in-edges, unsorted, empty rows
+        r = rng.integers(windows[i, 0], windows[i, 1], rng.integers(0, 7))
+        if r.size > 1 and rng.random() < 0.3:
+            r[-1] = r[0]                                  # a repeated entry
+        rows.append(r)
+    assert any(r.size == 0 for r in rows) and any(r.size > np.unique(r).size for r in rows)
+    csr = (np.concatenate([[0], np.cumsum([r.size for r in rows])]).astype(np.int64),
+           np.concatenate(rows).astype(np.int64))
+    Z, dcsr, node_ptr = Zc.to(dev), dev_csr(csr, dev), torch.as_tensor(gp, device=dev)
+    S = _chain_scores(Zc.numpy()).astype(np.float64)
+    extra = rng.integers(0, n, (2, 64))                   # random queries: targets outside the window, self pairs
+    for scope, wins in ((node_ptr, windows), (None, None)):
+        sc, idx = oracle_topk(S, allowed_mask(n, wins, csr), k)
+        ok = idx >= 0
+        src = np.concatenate([np.nonzero(ok)[0], extra[0]])
+        dst = np.concatenate([idx[ok], extra[1]])
+        pos = torch.as_tensor(np.nonzero(ok)[1], device=dev)
+        ref = rank_ref(Zc.numpy(), src, dst, wins, csr, True, scores=S)
+        src_t, dst_t = torch.as_tensor(src, device=dev), torch.as_tensor(dst, device=dev)
+        for ts in (1, 3):
+            tuning("topk_splits", ts)
+            score, index = ops.decoder_topk_raw(Z, k, scope, max(sizes), dcsr)
+            assert np.array_equal(as_np(index), idx), (scope is None, ts)
+            assert np.array_equal(as_np(score), sc.astype(np.float32)), (scope is None, ts)
+            for rs in (1, 3):
+                tuning("rank_splits", rs)
+                res = ops.decoder_rank_raw(Z, src_t, dst_t, scope, max(sizes), dcsr)
+                m = int(ok.sum())
+                listed = score[torch.as_tensor(ok, device=dev)]
+                assert torch.equal(res.score[:m].view(torch.int32), listed.view(torch.int32))
+                assert bool((res.greater[:m] <= pos).all()) and bool((pos <= res.greater[:m] + res.equal[:m]).all())
+                assert_equal_ref(res, ref, (scope is None, ts, rs))
+
+
 def test_bitwise_copies_tie(dev):
     from gae_dgl_amd import ops
     torch.manual_seed(6)

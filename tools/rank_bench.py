@@ -3,8 +3,8 @@
 embeddings, d = 16, self and the edges of a random 5-regular graph excluded: m = n queries (src = arange(n), random
 dst) at n = 2 708, 19 717 and 200 000, and the evaluation-shaped case n = 200 000 with m = 2e5 random sources.
 Beside each, in the same process and alternating with it call by call, the yardstick: ops.decoder_topk(Z, 10, g) on the
-same Z and graph (gae_decoder_topk sweeps the same n x n products with the same MFMA chain; its source is untouched by
-K18, so the library's own kernel is the parent's).  The spread of both series is recorded: the machines are shared.
+same Z and graph (gae_decoder_topk sweeps the same n x n products with the same MFMA chain, csrc/decoder_pairs.h).  The
+spread of both series is recorded: the machines are shared.
 Where it fits (n <= 19 717) the torch route (Z[src] @ Z.T, compare, sum) is timed for scale only; it is never on the
 product path.  Prints one JSON object (and writes it with --out).  Kernel stats: run once more under
 `rocprofv3 --kernel-trace --stats`.
@@ -110,8 +110,7 @@ def main():
     result = {"what": "ops.decoder_rank (gae_decoder_rank) against ops.decoder_topk(k = 10) on the same random fp32 Z "
                       "(d = 16) and 5-regular graph, self and known edges excluded; device-event timings after "
                       "warm-up, the two series alternating call by call in one process; ms = median",
-              "yardstick": "gae_decoder_topk of this library: csrc/decoder_topk.hip is byte-identical to the parent "
-                           "commit's (K18 shares no code with it)",
+              "yardstick": "gae_decoder_topk of this library, on the same products (csrc/decoder_pairs.h)",
               "reps": a.reps, "rows": rows}
     text = json.dumps(result)
     print(text)
