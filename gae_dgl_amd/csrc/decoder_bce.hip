@@ -316,10 +316,24 @@ __device__ __forceinline__ s16x4 third_piece(const f32x4 &v, const s16x4 &hi, co
 
 // ---- fp16 pieces (round 4).  v = hi + lo with hi = fp16(v), lo = fp16(v - hi): 22 mantissa bits in TWO pieces (bf16
 // needs three for 24), so all four partial products of S cost two K = 32 MFMAs instead of three, and the split is one
-// v_cvt_pkrtz per pair and piece plus a mixed-precision subtract.  The price is fp16's range: the pieces are exact to
-// 2^-22 |v| only while 2^-14 <= |v| <= 65504 (below: absolute error <= 2^-25, harmless; above: overflow).  The kernels
-// that use them therefore report embeddings beyond kF16Max, and the three-piece bf16 form then recomputes the call's
-// outputs (the range guard of bce_dense_sym_kernel).
+// v_cvt_pkrtz per pair and piece plus a mixed-precision subtract.  The price is fp16's range, at both ends:
+//   |v - hi - lo| <= max(2^-22 |v|, 2^-25)   for |v| <= 65504   (above: overflow).
+// The 22 bits hold only while the SECOND piece is a normal fp16 number, |v| >= 2^-3; below that v - hi is an fp16
+// subnormal (spacing 2^-24) and the error an ABSOLUTE 2^-25, i.e. 2^-25 / |v| relative; below 2^-25 both pieces are 0.
+// Contract at the high end: the kernels that use the pieces report embeddings beyond kF16Max, and the three-piece bf16
+// form then recomputes the call's outputs (the range guard of bce_dense_sym_kernel).
+// Contract at the low end: no guard is needed, because of WHERE the pieces are used.  They enter S = Zt Zt^T and P V with
+// P = sigmoid(S) - 1/2 (P is split the same way); the 1/2 colsum(Zt) and the edge terms of the gradient -- all of it
+// when the embeddings are small -- come from the fp32 values (fp64 column sums, the fp32 edge walk).  A value's piece
+// error reaches dZ multiplied by a P that is itself <= |x| / 4, and a small P's own piece error (2^-25 absolute below
+// 2^-3) multiplied by V.  What this leaves, against the suite's bounds (1e-5 of the loss, 5e-5 of max |dZ|), measured
+// on an MI355X against the fp64 oracle (tests/test_gpu_loss_range.py; CPU model of the rounding:
+// tests/loss_pieces_ref.py; MEASUREMENTS.md):
+//   * one scale per call, Z = randn * s: gradient error <= 2.4e-7 for every s from 1 down to 1e-8 (where all pieces
+//     are zero) -- the same as the three-piece bf16 form;
+//   * dynamic range within one call: rows of scale 1e-5 next to rows of scale 100 give 4.0e-6 (bf16: 2.2e-6) -- the
+//     split of P ~ 1e-3 between them, times the large V; the model puts 1e-6 next to 3000 at 1.2e-5.  Wider ranges
+//     than that are not covered by a test.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
@@ -349,7 +363,7 @@ __device__ __forceinline__ float minus_f16_hi(float v, unsigned hh)
     return r;
 }
 // hi = fp16(v) and lo = fp16(v - hi), both round-to-nearest-even (v_cvt_pk_f16_f32); v - hi is exact in fp32:
-// |v - hi - lo| <= 2^-22 |v| for 2^-14 <= |v| <= 65504.  4 VALU instructions per pair of values.
+// |v - hi - lo| <= max(2^-22 |v|, 2^-25) for |v| <= 65504 (see above).  4 VALU instructions per pair of values.
 // (v_fma_mixlo / mixhi_f16 would round v - hi straight into the fp16 halves, one instruction less per pair: measured
 //  SLOWER -- ZINC-95 k step 2.92 -> 3.01 ms -- and not the same bits; not used.)
 __device__ __forceinline__ void split_f16x4(const f32x4 &v, s16x4 &hi, s16x4 &lo)
@@ -930,8 +944,10 @@ __global__ __launch_bounds__(256, (RI == 2 && FORM != SymForm::kBf16x3Fallback) 
     unsigned *__restrict__ range_flag, int flag_mode, unsigned ticket, unsigned n_chunks, int bal_tpb,
     const SymWalkArgs wk)
 {
-    // Range guard of the fp16 pieces.  flag_mode 1 (the F16 launch): a thread that meets |Zt| > kF16Max (or a NaN)
-    // writes this call's ticket to *range_flag; the launch's results are then meaningless.  flag_mode 2 (the
+    // Range guard of the fp16 pieces.  flag_mode 1 (the F16 launch): a thread that meets |Zt| > kF16Max (+-inf included)
+    // writes this call's ticket to *range_flag; the launch's results are then meaningless.  A NaN does NOT fire it
+    // (fmaxf returns its other operand, so a NaN among four values is dropped): it propagates through the fp16 pieces
+    // as it does through the bf16 ones -- a NaN loss and NaN gradient rows in either form.  flag_mode 2 (the
     // three-piece bf16 launch that follows it): does nothing unless *range_flag holds the ticket, else recomputes every
     // output of the first launch.  The flag lives in the caller's workspace, which nobody initialises: the ticket (a
     // process-wide counter, scrambled) tells this call's report from whatever the memory held, and the edge kernel
