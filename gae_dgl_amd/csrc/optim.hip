@@ -156,6 +156,10 @@ extern "C" int gae_x_adam_step_tail(const gae_adam_tensor *tensors, int32_t n_te
         GAE_REQUIRE(t.n_partials >= 0 && (t.n_partials == 0 || (t.partials && t.row_len > 0 && t.partial_stride >= 0)),
                     GAE_E_SIZE, "gae_adam_step: tensor %d has a malformed partial-sum list", k);
         a.t[k] = t;
+        // an empty tensor takes the plain branch, which tests e < n BEFORE it touches a pointer: the deferred branches
+        // request param[0] / the moments / the clamped partial first, and when every tensor of the call is empty the one
+        // block of the launch ends its walk on the last of them (whose pointers may be NULL)
+        if (t.n == 0) a.t[k].n_partials = 0;
         a.first_block[k] = int32_t(blocks);
         GAE_REQUIRE(t.n < (int64_t(1) << 31) && t.row_len < (int64_t(1) << 31), GAE_E_SIZE,
                     "gae_adam_step: tensor %d too large", k);

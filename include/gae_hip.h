@@ -613,6 +613,8 @@ int gae_segment_readout(const float *Z, int64_t ldz, int64_t n_nodes, int64_t d,
  * state_dev: GAE_ADAM_STATE_WORDS (6) x uint64 on the device, zeroed by the caller once: [0] = steps taken so far
  * (advanced by the call, stream-ordered, so a replayed HIP graph counts its own steps; may be preset to resume),
  * [1] = scratch ticket, [2..5] = the library's cache of beta1, beta1^steps, beta2, beta2^steps (doubles).
+ * A caller who presets word 0 must zero words 2..5 with it: a cache that holds the call's betas is trusted, so a
+ * preset counter next to a stale cache gets the stale beta^t (zeroed words hold no beta > 0: the call recomputes beta^steps with pow).
  * `tensors` is a HOST array (copied into the kernel arguments). */
 #define GAE_ADAM_MAX_TENSORS 16
 #define GAE_ADAM_STATE_WORDS 6
@@ -624,7 +626,10 @@ typedef struct gae_adam_tensor {
     int64_t n;
     /* Deferred reduction (n_partials > 0): the gradient has not been added up yet -- it is the list of partial sums
      * gae_x_xw_wgrad_partials / gae_x_linear_bwd_partials left in their workspace,
-     *     grad[e] = sum over q < n_partials, in order, of partials[q * partial_stride + (e / row_len) * row_pitch + e % row_len].
+     *     grad[e] = sum over q < n_partials of partials[q * partial_stride + (e / row_len) * row_pitch + e % row_len],
+     * added in fp32 in the library's one order for such lists: up to 32 partials q = 0, 1, 2, ... in
+     * order, starting from +0; longer lists as 64 lane sums (lane l adds partials l, l + 64, ... in order), then
+     * lane[i] += lane[i + off] for off = 32, 16, ..., 1, and lane 0 is the sum.
      * The kernel adds the list (deterministic order), WRITES the sum to grad[e] and applies the update: the separate
      * reduction launch of every weight gradient disappears from a training step (two kernel nodes of ~5 us each).
      * n_partials = 0: grad holds the gradient. */
