@@ -52,6 +52,7 @@ const KnobEntry kKnobs[] = {
     {"bce_sym_ri", &gae::g_bce_sym_ri, 0, 4, V(0) | V(2) | V(4), true},
     {"bce_sym_bal", &gae::g_bce_sym_bal, 0, 2, 0, true},
     {"bce_last_kind", &gae::g_bce_last_kind, 0, 3, 0, false},
+    {"dense_last_kind", &gae::g_dense_last_kind, 0, 11, 0, false},
     {"topk_splits", &gae::g_topk_splits, 0, 16, 0, true},
     {"rank_splits", &gae::g_rank_splits, 0, 16, 0, true},
 };

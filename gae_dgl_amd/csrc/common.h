@@ -23,7 +23,7 @@ struct Knob {
 
 // the knobs, defined next to the code that reads them; names, defaults and allowed values: the table in api.hip
 extern Knob g_spmm_variant, g_spmm_rpg, g_spmm_tile_vecs, g_spmm_ell, g_spmm_ell_rpg, g_spmm_hot, g_spmm_desc, g_spmm_light;
-extern Knob g_gemm_rows, g_linear_wlds, g_atb_bf16, g_ell_side;
+extern Knob g_gemm_rows, g_linear_wlds, g_atb_bf16, g_ell_side, g_dense_last_kind;
 extern Knob g_xw_rows, g_xw_parts, g_xw_glds, g_xw_p3;
 extern Knob g_bce_s_bf16, g_bce_pv_bf16, g_bce_sym, g_bce_sym_ri, g_bce_sym_bal, g_bce_last_kind;
 extern Knob g_topk_splits, g_rank_splits;

@@ -29,12 +29,18 @@ Knob g_gemm_rows{1};    // "gemm_rows": 0 = never use gemm_rows_kernel, 1 = oper
 Knob g_linear_wlds{1};  // "linear_wlds": 0 = never use linear_fwd_wlds_kernel, 1 = where measured faster, 2 = wherever it applies
 Knob g_atb_bf16{1};     // "atb_bf16", weight-gradient products (dW kernel where the layout allows; gae_gcn2_bwd_dense): 0 = exact fp32
                         // MFMAs, 1 = three bf16 pieces per operand, six pairs (fp32-grade; default), 2 = two pieces, three pairs (16 bits)
+Knob g_dense_last_kind{0}; // "dense_last_kind" (telemetry, read-only through gae_tuning_get): the last GEMM-family kernel a launcher of
+                        // this file started, one of the DENSE_KIND_* values below (a host-side store next to the launch)
 } // namespace gae
 
 namespace {
 using gae::g_gemm_rows;
 using gae::g_linear_wlds;
 using gae::g_atb_bf16;
+using gae::g_dense_last_kind;
+enum { DENSE_KIND_ROWS = 1, DENSE_KIND_PIECES = 2, DENSE_KIND_WLDS = 3, DENSE_KIND_STREAM = 4, DENSE_KIND_STREAM_SPLIT = 5,
+       DENSE_KIND_TILED = 6, DENSE_KIND_XW = 7, DENSE_KIND_ATB_BF16 = 8, DENSE_KIND_ATB_NARROW = 9, DENSE_KIND_ATB_VEC = 10,
+       DENSE_KIND_ATB_SCALAR = 11 };
 
 // ---------------------------------------------------------------------------
 // out[n, J] = epi( proA(A)[n, K] * proB(B) )      B given as [J, K] (BT) or [K, J]
@@ -190,6 +196,7 @@ int launch_gemm(const float *A, int64_t lda, const float *Amask, int64_t ldam, c
         hipLaunchKernelGGL((gemm_kernel<NT, BT, PRO_A, MASK_B, false>), grid, dim3(256), 0, s, A, lda, Amask, ldam,
                            B, ldb, Bmask, ldbm, bias, act, out, ldo, n, K, J);
     GAE_CHECK_LAUNCH("gemm_kernel");
+    g_dense_last_kind = DENSE_KIND_TILED;
     return GAE_OK;
 }
 
@@ -781,6 +788,7 @@ int launch_gemm_stream(const float *A, int64_t lda, const float *Amask, int64_t 
         else { if (av) GAE_GR(8, true); else GAE_GR(8, false); }
 #undef GAE_GR
         GAE_CHECK_LAUNCH("gemm_rows_kernel");
+        g_dense_last_kind = DENSE_KIND_ROWS;
         return GAE_OK;
     }
     int splits = split_ws ? gemm_stream_splits(n, K) : 1;
@@ -801,6 +809,7 @@ int launch_gemm_stream(const float *A, int64_t lda, const float *Amask, int64_t 
         if (wvec) GAE_LB(true); else GAE_LB(false);
 #undef GAE_LB
         GAE_CHECK_LAUNCH("linear_fwd_pieces_kernel");
+        g_dense_last_kind = DENSE_KIND_PIECES;
         if (splits > 1) {
             const int64_t ne = n * J;
             hipLaunchKernelGGL(split_reduce_kernel, dim3(unsigned((ne + 255) / 256)), dim3(256), 0, s, split_ws, splits,
@@ -827,6 +836,7 @@ int launch_gemm_stream(const float *A, int64_t lda, const float *Amask, int64_t 
         else GAE_WL(false, false);
 #undef GAE_WL
         GAE_CHECK_LAUNCH("linear_fwd_wlds_kernel");
+        g_dense_last_kind = DENSE_KIND_WLDS;
         if (splits > 1) {
             const int64_t ne = n * J;
             hipLaunchKernelGGL(split_reduce_kernel, dim3(unsigned((ne + 255) / 256)), dim3(256), 0, s, split_ws, splits,
@@ -849,6 +859,7 @@ int launch_gemm_stream(const float *A, int64_t lda, const float *Amask, int64_t 
     else GAE_GS(false, false);
 #undef GAE_GS
     GAE_CHECK_LAUNCH("gemm_stream_kernel");
+    g_dense_last_kind = splits > 1 ? DENSE_KIND_STREAM_SPLIT : DENSE_KIND_STREAM;
     if (splits > 1) {
         const int64_t ne = n * J;
         hipLaunchKernelGGL(split_reduce_kernel, dim3(unsigned((ne + 255) / 256)), dim3(256), 0, s, split_ws, splits, ne,
@@ -1302,6 +1313,7 @@ int launch_atb(const float *P, int64_t ldp, const float *Pmask, int64_t ldpm, co
             hipLaunchKernelGGL((atb_bf16_kernel<PRO_P, true>), grid, dim3(512), 0, s, P, ldp, Pmask, ldpm, Q, ldq, n, O, I,
                                pl.rows_per_slot, partial, pl.slot_stride, colsum ? int64_t(O) * I : int64_t(-1));
         GAE_CHECK_LAUNCH("atb_bf16_kernel");
+        g_dense_last_kind = DENSE_KIND_ATB_BF16;
         return GAE_OK;
     }
     const int cols_per_block = narrow ? 32 : 128;
@@ -1320,6 +1332,7 @@ int launch_atb(const float *P, int64_t ldp, const float *Pmask, int64_t ldpm, co
     else GAE_ATB(4, false);
 #undef GAE_ATB
     GAE_CHECK_LAUNCH("atb_partial_kernel");
+    g_dense_last_kind = narrow ? DENSE_KIND_ATB_NARROW : qvec ? DENSE_KIND_ATB_VEC : DENSE_KIND_ATB_SCALAR;
     return GAE_OK;
 }
 
@@ -1590,9 +1603,11 @@ extern "C" int gae_linear_fwd(const float *M, int64_t ldm, int64_t n, int64_t f_
     // wide input, narrow output (layer 1 in the reference's order, (A X) W^T): the stream family of xw.hip
     if (gae::xw_usable(M, ldm, n, f_in, f_out, 4) &&
         (gae::xw_fwd_workspace_bytes(n, f_in, f_out, 4) == 0 ||
-         (workspace && workspace_bytes >= gae::xw_fwd_workspace_bytes(n, f_in, f_out, 4))))
+         (workspace && workspace_bytes >= gae::xw_fwd_workspace_bytes(n, f_in, f_out, 4)))) {
+        g_dense_last_kind = DENSE_KIND_XW;
         return gae::xw_fwd_launch(M, ldm, n, int(f_in), 4, W, f_in, b, int(f_out), act, Y, ldy, workspace, workspace_bytes,
                                   gae::as_stream(stream), false);
+    }
     return dispatch_gemm<true, PRO_NONE, false>(M, ldm, nullptr, 0, W, f_in, nullptr, 0, b, act, Y, ldy, n, int(f_in),
                                                 f_out, gae::as_stream(stream), static_cast<float *>(workspace),
                                                 workspace ? workspace_bytes / 4 : 0);
@@ -1652,7 +1667,7 @@ extern "C" int gae_linear_bwd(const float *dY, int64_t lddy, const float *Y, int
     if (dW || db) {
         GAE_REQUIRE(!dW || (ldm >= f_in && (n == 0 || M)), GAE_E_NULL, "gae_linear_bwd: dW needs M");
         const AtbPlan pl = atb_plan(n, f_out, f_in);
-        const int64_t need = align256(pl.n_slots * pl.slot_stride * 4);
+        const int64_t need = align256(pl.n_slots * pl.slot_stride * 4) + 256;      // gae_linear_bwd_workspace_bytes
         GAE_REQUIRE(workspace && workspace_bytes >= need, GAE_E_WORKSPACE,
                     "gae_linear_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
         GAE_REQUIRE(gae::aligned16(workspace), GAE_E_ALIGN, "gae_linear_bwd: workspace not 16-byte aligned");

@@ -103,7 +103,10 @@ int gae_device_info_get(int device, gae_device_info *out_host);
  *    = 1 {0, 1}, "xw_p3" = 1 {0, 1} and "atb_bf16" = 1 {0, 1, 2} (1 = bf16 x 3 split products; 0 = exact fp32
  *    MFMA; atb_bf16 = 2: two pieces, 16 bits).
  * Read-only (gae_tuning_get): "bce_last_kind", the dense kernel of the last loss call (0 none yet, 1 full square,
- * 2 / 3 symmetric with 128- / 256-row panels). */
+ * 2 / 3 symmetric with 128- / 256-row panels); "dense_last_kind", the last product kernel of the node-apply family
+ * (gae_linear_fwd / gae_linear_bwd, gae_decoder_dense(_bwd)) started in this process: 0 none yet, 1 rows, 2 pieces,
+ * 3 wlds, 4 stream, 5 stream + split-K, 6 tiled (gemm_kernel), 7 xw (gae_xw_fwd's kernel), and for the weight gradient
+ * 8 atb_bf16, 9 / 10 / 11 atb_partial narrow / vec / scalar. */
 int gae_tuning_set(const char *name, int64_t value);
 int gae_tuning_get(const char *name, int64_t *value_out);
 

@@ -207,7 +207,7 @@ RETIRED_KNOBS = ["xw", "xw_dbg", "xw_depth", "xw_tc", "xw_stamps", "xw_stamps_hi
 
 def test_tuning_knobs_match_the_header_and_check_their_values():
     """every knob the header lists reads back its stated default and takes exactly its stated values; retired
-    knobs are unknown; the telemetry value bce_last_kind is read-only"""
+    knobs are unknown; the telemetry values bce_last_kind and dense_last_kind are read-only"""
     import ctypes
     from gae_dgl_amd import _lib
     lib = _lib.load()
@@ -239,6 +239,10 @@ def test_tuning_knobs_match_the_header_and_check_their_values():
 
     assert get("bce_last_kind") in (0, 1, 2, 3)
     assert lib.gae_tuning_set(b"bce_last_kind", 1) == GAE_E_RANGE and b"read-only" in lib.gae_last_error()
+    assert get("dense_last_kind") in range(12)          # 0 in a fresh process; a host-side store next to each launch
+    assert "dense_last_kind" in open(HEADER).read()
+    for v in (0, 4, 11):
+        assert lib.gae_tuning_set(b"dense_last_kind", v) == GAE_E_RANGE and b"read-only" in lib.gae_last_error()
     for name in RETIRED_KNOBS:
         assert lib.gae_tuning_set(name.encode(), 0) == GAE_E_RANGE and b"unknown knob" in lib.gae_last_error(), name
         assert lib.gae_tuning_get(name.encode(), ctypes.byref(ctypes.c_int64())) == GAE_E_RANGE, name
