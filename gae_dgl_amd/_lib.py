@@ -168,6 +168,9 @@ SIGNATURES = {
     "gae_decoder_topk": (_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _int, _p, _p, _i64, _p, _p, _p]),
     "gae_decoder_rank": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _p, _i64, _i64, _p, _p, _int, _p, _p, _p, _p, _p, _p,
                                 _p]),
+    "gae_decoder_threshold_count": (_int, [_p, _i64, _i64, _i64, _f, _p, _i64, _i64, _p, _p, _int, _i64, _p, _p, _p, _p]),
+    "gae_decoder_threshold_fill": (_int, [_p, _i64, _i64, _i64, _f, _p, _i64, _i64, _p, _p, _int, _i64, _p, _p, _p, _i64,
+                                          _p, _p, _p]),
     "gae_decoder_bce": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _f, _f, _u64, _u64, _p, _p, _p, _i64, _p,
                                _i64, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),

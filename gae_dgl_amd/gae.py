@@ -160,6 +160,31 @@ class GCN(nn.Module):
         return g.ndata.pop('h')
 
 
+_UNSET = object()
+
+
+def reconstruct_threshold(prob=_UNSET, threshold=None):
+    """the logit threshold of ``reconstruct(prob=..., threshold=...)``: exactly one of the two may be given (neither:
+    prob = 0.5); ``prob`` in (0, 1) becomes log(p / (1 - p)), computed in fp64 and rounded to fp32 (0.5 -> exactly 0.0)"""
+    if threshold is not None:
+        if prob is not _UNSET and prob is not None:
+            raise ValueError("reconstruct: give prob or threshold, not both")
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("reconstruct: threshold is NaN")
+        return threshold
+    return ops.threshold_of_prob(0.5 if prob is _UNSET or prob is None else prob)
+
+
+def reconstruct_embedding(z, g, threshold, scope, exclude_self, exclude_edges, max_pairs):
+    """ops.decoder_threshold on a given embedding: what GAE.reconstruct does with Z and VGAE.reconstruct with mu"""
+    z = z.detach()
+    if z.dtype != torch.float32:
+        z = z.float()
+    return ops.decoder_threshold(z, threshold, g, scope=scope, exclude_self=exclude_self, exclude_edges=exclude_edges,
+                                 max_pairs=max_pairs)
+
+
 def _empty_scores(B, dev):
     f64 = lambda: torch.empty(B, dtype=torch.float64, device=dev)       # noqa: E731
     i64 = lambda: torch.empty(B, dtype=torch.int64, device=dev)         # noqa: E731
@@ -262,6 +287,25 @@ class GAE(nn.Module):
             z = self.encode(g)
         return ops.decoder_rank(z, pairs, g, filter_graph=filter_graph, scope=scope, exclude_self=exclude_self,
                                 exclude_edges=exclude_edges)
+
+    def reconstruct(self, g, *, prob=_UNSET, threshold=None, scope="batch", exclude_self=True, exclude_edges=False,
+                    max_pairs=2 ** 27):
+        """``ops.DecodedLinks(indptr, index, score)``: the reconstructed graph A_hat = 1[sigmoid(z_i . z_j) >= prob]
+        of the decoder (gae.py:69-72, no dropout) as a CSR -- row i lists, columns ascending, the nodes j whose logit
+        z_i . z_j reaches the threshold, with the logits -- from the fused HIP launches of ops.decoder_threshold that
+        never form the N x N matrix.  Give ``prob`` in (0, 1) (default 0.5) or the logit ``threshold`` itself, not both.
+        ``scope="graph"``: every member of a batched ``g`` is decoded inside its own window.  ``exclude_edges`` lists
+        only pairs that are not edges of ``g`` (new links); ``max_pairs`` bounds the output (GaeHipError beyond it).
+        ``metrics.reconstruction_metrics`` compares the result with the graph.  Runs encode(g) under no_grad;
+        ``g.ndata['h']`` is restored on exit."""
+        t = reconstruct_threshold(prob, threshold)
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                z = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return reconstruct_embedding(z, g, t, scope, exclude_self, exclude_edges, max_pairs)
 
     def embed_graphs(self, data, *, fused="auto", batch_size=4096, grad=False):
         """fp32 [n_graphs, 3 d]: the molecule feature of the reference's chemistry table (README.md:54: mean | sum |

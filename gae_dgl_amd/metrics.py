@@ -128,6 +128,59 @@ def rank_metrics(greater, equal, candidates, ks=(1, 10, 50, 100)):
     return out
 
 
+def _csr_keys(indptr, indices, n, exclude_self):
+    """the distinct keys i n + j of the entries (i, j) of a CSR with n rows, sorted: entries outside [0, n) ignored,
+    the diagonal dropped under ``exclude_self``"""
+    indptr = indptr.reshape(-1).long()
+    rows = torch.repeat_interleave(torch.arange(n, device=indptr.device), indptr[1:] - indptr[:-1])
+    cols = indices.reshape(-1).long()[int(indptr[0]):int(indptr[-1])] if n else indices.reshape(-1).long()[:0]
+    keep = (cols >= 0) & (cols < n)
+    if exclude_self:
+        keep &= cols != rows
+    return torch.unique(rows[keep] * n + cols[keep])
+
+
+def reconstruction_metrics(pred_indptr, pred_index, true_indptr, true_indices, node_ptr=None, exclude_self=True):
+    """How well a decoded graph (``GAE.reconstruct`` / ``ops.decoder_threshold``: CSR ``pred_indptr`` [n + 1],
+    ``pred_index``) reproduces the graph it was decoded from (CSR ``true_indptr`` [n + 1], ``true_indices``), over the
+    ordered pairs (i, j): plain torch ops on the device of ``pred_indptr``.  On either side the pairs are the distinct
+    entries of the CSR -- a repeated entry counts once, entries outside [0, n) are ignored, the diagonal is dropped
+    under ``exclude_self``.  Returns a dict: ``tp`` / ``fp`` / ``fn`` (ints), ``n_pred`` = tp + fp, ``precision`` =
+    tp / n_pred, ``recall`` = tp / (tp + fn), ``f1`` = 2 tp / (2 tp + fp + fn); an empty denominator gives NaN.
+    With ``node_ptr`` (int [G + 1] member offsets of a batched graph) also ``exact``, bool [G]: the predicted pairs of
+    the member's rows are exactly its true pairs (an empty member is exact), and ``exact_fraction``, its mean (NaN when
+    G = 0) -- the share of molecules whose bond graph is reproduced."""
+    pred_indptr = torch.as_tensor(pred_indptr)
+    dev = pred_indptr.device
+    pred_index, true_indptr, true_indices = (torch.as_tensor(t, device=dev) for t in (pred_index, true_indptr, true_indices))
+    n = pred_indptr.numel() - 1
+    if n < 0 or true_indptr.numel() != n + 1:
+        raise ValueError(f"reconstruction_metrics: row pointers of {pred_indptr.numel()} and {true_indptr.numel()} "
+                         "entries: both must be [n + 1]")
+    pred = _csr_keys(pred_indptr, pred_index, n, exclude_self)
+    true = _csr_keys(true_indptr, true_indices, n, exclude_self)
+    hit = torch.isin(pred, true, assume_unique=True)
+    tp = int(hit.sum())
+    n_pred, n_true = int(pred.numel()), int(true.numel())
+    fp, fn = n_pred - tp, n_true - tp
+    nan = float("nan")
+    out = {"tp": tp, "fp": fp, "fn": fn, "n_pred": n_pred,
+           "precision": tp / n_pred if n_pred else nan, "recall": tp / n_true if n_true else nan,
+           "f1": 2 * tp / (n_pred + n_true) if n_pred + n_true else nan}
+    if node_ptr is not None:
+        node_ptr = torch.as_tensor(node_ptr, device=dev).reshape(-1).long()
+        G = node_ptr.numel() - 1
+        if G < 0:
+            raise ValueError("reconstruction_metrics: node_ptr must be [G + 1]")
+        wrong = torch.cat([pred[~hit], true[~torch.isin(true, pred, assume_unique=True)]])
+        rows = torch.div(wrong, max(n, 1), rounding_mode="floor")
+        member = torch.searchsorted(node_ptr, rows, right=True) - 1
+        inside = (member >= 0) & (member < G)
+        out["exact"] = torch.bincount(member[inside], minlength=max(G, 0))[:max(G, 0)] == 0
+        out["exact_fraction"] = float(out["exact"].double().mean()) if G > 0 else nan
+    return out
+
+
 def graph_scores_dense(z_g, csr_g, exclude_self=True):
     """The per-graph scores of ``GAE.score_graphs`` / ``ops.score_graphs`` for ONE graph of any size, by the definitions
     taken literally with torch ops on the device of ``z_g`` [n, d]: the route of graphs above the fused kernel's 64

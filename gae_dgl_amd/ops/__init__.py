@@ -5,7 +5,7 @@ hand-written HIP kernels from libgae_hip.so on PyTorch's current HIP stream.
 There is no CPU / eager fallback -- a CPU tensor raises.
 
 A package since round 6 (one 2 355-line module before): `_base` (plumbing, step context), `structure`, `aggregate`, `dense`,
-`vgae_heads`, `loss`, `graph_loss`, `topk`, `rank`, `sampled`, `embed`, `score`, `layers`, `wide`.  Every name of the former module is re-exported here; the submodules resolve each
+`vgae_heads`, `loss`, `graph_loss`, `topk`, `rank`, `threshold`, `sampled`, `embed`, `score`, `layers`, `wide`.  Every name of the former module is re-exported here; the submodules resolve each
 other through THIS namespace at call time, so `ops.FLAG = ...` and patched functions behave as they did."""
 from .. import _lib
 from .._lib import ACT_IDENTITY, ACT_RELU, BF16, F32, GaeHipError
@@ -18,6 +18,7 @@ from .loss import *  # noqa: F401,F403
 from .graph_loss import *  # noqa: F401,F403
 from .topk import *  # noqa: F401,F403
 from .rank import *  # noqa: F401,F403
+from .threshold import *  # noqa: F401,F403
 from .sampled import *  # noqa: F401,F403
 from .embed import *  # noqa: F401,F403
 from .score import *  # noqa: F401,F403

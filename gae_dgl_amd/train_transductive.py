@@ -5,7 +5,7 @@ epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
 59-60) -- on the HIP kernels.
 
   python -m gae_dgl_amd.train_transductive --dataset cora [--norm both] [--eval [--rank]] [--topk 10 [--topk_out top.npz]]
-      [--loss_samples M]
+      [--loss_samples M] [--decode_out graph.npz [--decode_prob P] [--decode_max_pairs M]]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -59,6 +59,14 @@ def build_parser():
     ap.add_argument("--loss_samples", type=int, default=None, metavar="M",
                     help="train on the unbiased sampled loss (GAE.reconstruction_loss(g, samples=M)): the edge term "
                          "exactly, the all-pairs term from M random partners per node, O((E + N M) d) per step")
+    ap.add_argument("--decode_out", default=None, metavar="PATH",
+                    help="after training, decode the training graph (GAE.reconstruct: the pairs with sigmoid(z_i . z_j) "
+                         ">= P, no N x N matrix), print its precision / recall / F1 against the graph and write the CSR "
+                         "to PATH (.npz with 'indptr' int64 [n + 1], 'index' int32 [nnz], 'score' fp32 [nnz])")
+    ap.add_argument("--decode_prob", type=float, default=None, metavar="P",
+                    help="with --decode_out: the probability cut-off, inside (0, 1) (default 0.5)")
+    ap.add_argument("--decode_max_pairs", type=int, default=None, metavar="M",
+                    help="with --decode_out: refuse to write more than M pairs (default 2^27, 12 bytes each)")
     return ap
 
 
@@ -77,6 +85,14 @@ def parse_args(argv=None):
         ap.error("--rank needs --eval (it ranks the held-out test edges)")
     if args.loss_samples is not None and args.loss_samples < 1:
         ap.error(f"--loss_samples {args.loss_samples}: M must be at least 1")
+    if args.decode_out is None:
+        if args.decode_prob is not None or args.decode_max_pairs is not None:
+            ap.error("--decode_prob / --decode_max_pairs need --decode_out PATH")
+    else:
+        if args.decode_prob is not None and not 0.0 < args.decode_prob < 1.0:
+            ap.error(f"--decode_prob {args.decode_prob}: P must lie inside (0, 1)")
+        if args.decode_max_pairs is not None and args.decode_max_pairs < 1:
+            ap.error(f"--decode_max_pairs {args.decode_max_pairs}: M must be at least 1")
     return args
 
 
@@ -171,6 +187,17 @@ def main(argv=None):
         if args.topk_out is not None:
             import numpy as np
             np.savez(args.topk_out, index=index.cpu().numpy(), score=score.cpu().numpy())
+    if args.decode_out is not None:
+        import numpy as np
+        g.ndata['h'] = features
+        links = model.reconstruct(g, prob=0.5 if args.decode_prob is None else args.decode_prob,
+                                  max_pairs=2 ** 27 if args.decode_max_pairs is None else args.decode_max_pairs)
+        rm = metrics.reconstruction_metrics(links.indptr, links.index, *g.csr())
+        print(f"reconstruction precision: {rm['precision']:.4f} | recall: {rm['recall']:.4f} | F1: {rm['f1']:.4f} | "
+              f"predicted pairs: {rm['n_pred']}")
+        main.last_decode = rm
+        np.savez(args.decode_out, indptr=links.indptr.cpu().numpy(), index=links.index.cpu().numpy(),
+                 score=links.score.cpu().numpy())
     return [float(l) for l in losses]
 
 

@@ -12,7 +12,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .gae import GCN, InnerProductDecoder, identity, score_embedding
+from .gae import (_UNSET, GCN, InnerProductDecoder, identity, reconstruct_embedding, reconstruct_threshold,
+                  score_embedding)
 
 
 # mu and log sigma heads as ONE fused launch on the shared aggregate (gae_x_gcn_layer_fused2) and one packed gradient
@@ -120,6 +121,19 @@ class VGAE(nn.Module):
             mu, _ = self.encode(g)
         return ops.decoder_rank(mu, pairs, g, filter_graph=filter_graph, scope=scope, exclude_self=exclude_self,
                                 exclude_edges=exclude_edges)
+
+    def reconstruct(self, g, *, prob=_UNSET, threshold=None, scope="batch", exclude_self=True, exclude_edges=False,
+                    max_pairs=2 ** 27):
+        """GAE.reconstruct on the mean embedding mu (no noise): ``ops.DecodedLinks`` of the pairs with
+        sigmoid(mu_i . mu_j) >= prob (ops.decoder_threshold); ``g.ndata['h']`` is restored on exit"""
+        t = reconstruct_threshold(prob, threshold)
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                mu, _ = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return reconstruct_embedding(mu, g, t, scope, exclude_self, exclude_edges, max_pairs)
 
     def score_graphs(self, g, *, exclude_self=True):
         """GAE.score_graphs on the mean embedding mu (no noise) of a batched graph ``g``: ``ops.GraphScores`` per member

@@ -365,6 +365,50 @@ int gae_decoder_rank(const float *Z, int64_t ldz, int64_t n, int64_t d,
                      float *score_out, int64_t *greater_out, int64_t *equal_out, int64_t *candidates_out,
                      void *workspace, int64_t *workspace_bytes, void *stream);
 
+/* ---- K22: the decoded graph without the N x N matrix (GAE.reconstruct, ops.decoder_threshold)
+ * The reconstruction A_hat = 1[sigmoid(z_i . z_j) >= p] of gae.py:69-72 as a CSR: row i lists, in ascending column
+ * order, every candidate c of row i with s_ic >= threshold (threshold = log(p / (1 - p)); fp32 compare, a score equal
+ * to the threshold is listed), and its score.  s_ic is the SAME fp32 number gae_decoder_topk and gae_decoder_rank
+ * compute for that pair and that d (csrc/decoder_pairs.h).
+ * Candidates C(i): exactly K16's -- c in i's column window (all n, or i's member [node_ptr[g], node_ptr[g + 1])),
+ *   c != i                                 when flags & GAE_TOPK_EXCLUDE_SELF,
+ *   c not in CSR row i (indices in any order, repeats allowed)   when flags & GAE_TOPK_EXCLUDE_EDGES,
+ *   s_ic neither NaN nor -inf.             Same flags values as gae_decoder_topk.
+ * threshold = -inf lists every candidate, +inf only the scores that are +inf; NaN is an argument error.
+ * Two calls with the SAME selection arguments (Z .. splits):
+ *   gae_decoder_threshold_count  counts the listed pairs of every row and writes row_ptr_out, int64 [n + 1] on the
+ *       device: row i's pairs are entries [row_ptr_out[i], row_ptr_out[i + 1]), row_ptr_out[n] is the total (it may
+ *       exceed 2^31).  The caller reads the total and allocates.
+ *   gae_decoder_threshold_fill   writes index_out int32 [capacity] (the columns) and score_out fp32 [capacity].  It
+ *       takes the workspace gae_decoder_threshold_count left behind, UNTOUCHED: that workspace holds the offsets of
+ *       every (row, column split), finer than row_ptr, and is what places a pair; row_ptr (as written by _count) is the
+ *       array the caller indexes the output by.  Every store is guarded by its position < capacity: too small a
+ *       buffer loses the tail of the list and nothing is written outside it.
+ * The layout is a function of the scores alone -- no atomic decides a position, no block waits on another --, so every
+ * run, schedule and value of `splits` gives the same bytes.
+ *   splits       column splits per panel of 32 rows: 0 = auto, else 1 .. 16.  An argument, not a tuning knob; both calls
+ *                must be given the same value
+ *   node_ptr, max_graph_nodes, indptr / indices : as gae_decoder_topk.  A bad node_ptr never reads outside Z
+ *   workspace    : NULL = size query (either call; the same number): *workspace_bytes receives the bytes needed and
+ *                  nothing else happens (no device work; works without a GPU).  Otherwise *workspace_bytes is the
+ *                  capacity given.  O(n splits) bytes, never O(n^2) and never O(output).  No logit below the
+ *                  threshold is written to memory.
+ * 1 <= d <= 256, n < 2^31; n = 0 is valid (row_ptr_out[0] = 0).
+ * Argument errors are returned before any launch: NaN threshold, splits outside 0..16, d outside 1..256 (GAE_E_RANGE),
+ * negative n, n >= 2^31, ldz < d, negative capacity (GAE_E_SIZE), unknown flag bits, NULL Z (n > 0), NULL row_ptr_out /
+ * row_ptr, NULL index_out / score_out (capacity > 0), GAE_TOPK_EXCLUDE_EDGES without a CSR, a short workspace.
+ * _count: the sweep, then three launches of the prefix sum.  _fill: one launch. */
+int gae_decoder_threshold_count(const float *Z, int64_t ldz, int64_t n, int64_t d, float threshold,
+                                const int64_t *node_ptr, int64_t n_graphs, int64_t max_graph_nodes,
+                                const int32_t *indptr, const int32_t *indices, int flags, int64_t splits,
+                                int64_t *row_ptr_out, void *workspace, int64_t *workspace_bytes, void *stream);
+
+int gae_decoder_threshold_fill(const float *Z, int64_t ldz, int64_t n, int64_t d, float threshold,
+                               const int64_t *node_ptr, int64_t n_graphs, int64_t max_graph_nodes,
+                               const int32_t *indptr, const int32_t *indices, int flags, int64_t splits,
+                               const int64_t *row_ptr, int32_t *index_out, float *score_out, int64_t capacity,
+                               void *workspace, int64_t *workspace_bytes, void *stream);
+
 /* (from gae_hip.h: graph-level readout) */
 /* ---- K19: the molecule feature of a whole resident set in ONE launch (GAE.embed_graphs, ops.embed_graphs)
  * For every selected member graph: the complete GCN encoder of gae.py:26-31,36-45 on that graph's own rows -- per layer
