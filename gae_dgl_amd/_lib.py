@@ -173,6 +173,10 @@ SIGNATURES = {
                                           _p, _p, _p]),
     "gae_decoder_bce": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _f, _f, _u64, _u64, _p, _p, _p, _i64, _p,
                                _i64, _p]),
+    "gae_kmeans_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "gae_kmeans_assign": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
+    "gae_kmeans_step": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, ctypes.c_double, _int, _p, _i64, _p]),
+    "gae_kmeans_init_pp": (_int, [_p, _i64, _i64, _i64, _i64, _u64, _p, _p, _p, _i64, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

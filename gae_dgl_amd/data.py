@@ -2,7 +2,7 @@
 (gae_dgl/train_transductive.py:6,19,37-38,45): citation datasets.
 
 Real data is used when present under ``--data_root``: either ``<root>/<name>.npz``
-(``src``, ``dst``, ``features`` [, ``n``]) or the Planetoid files themselves
+(``src``, ``dst``, ``features`` [, ``n``] [, ``labels``]) or the Planetoid files themselves
 (``<root>/ind.<name>.{x,tx,allx,graph,test.index}``, also looked for in
 ``<root>/<name>/``: the format DGL's citation loader and Kipf's gcn read --
 load_planetoid); otherwise a seeded synthetic graph with the dataset's N / E / F
@@ -30,8 +30,11 @@ class EdgeListGraph:
 
 
 class CitationData:
-    def __init__(self, name, features, graph, synthetic):
+    """``labels``: int64 [n] class of every node (-1 = unlabelled) where the dataset carries them, else None"""
+
+    def __init__(self, name, features, graph, synthetic, labels=None):
         self.name, self.features, self.graph, self.synthetic = name, features, graph, synthetic
+        self.labels = None if labels is None else np.asarray(labels, dtype=np.int64).reshape(-1)
 
 
 def register_data_args(parser):
@@ -104,6 +107,38 @@ def load_planetoid(root, name):
     return n, src, dst, np.asarray(feats.todense(), dtype=np.float32)
 
 
+def load_planetoid_labels(root, name, n):
+    """int64 [n] class labels from ``ind.<name>.ally`` / ``.ty`` (one-hot rows next to ``allx`` / ``tx``), or None
+    unless BOTH files exist: a one-hot row maps to its argmax, an all-zero row (Citeseer's isolated test nodes, and every
+    id the files do not cover) to -1; the rows of ``ty`` go back to their ids through ``test.index`` exactly as the
+    feature rows of ``tx`` do.  ``n``: the node count ``load_planetoid`` returned."""
+    import pickle
+    import scipy.sparse as sp
+    paths = [os.path.join(root, f"ind.{name}.{ext}") for ext in ("ally", "ty")]
+    if not all(os.path.exists(p) for p in paths):
+        return None
+
+    def read(path):
+        with open(path, "rb") as f:
+            m = pickle.load(f, encoding="latin1")
+        m = np.asarray(m.todense() if sp.issparse(m) else m)
+        return m.reshape(m.shape[0], -1)
+    ally, ty = read(paths[0]), read(paths[1])
+    with open(os.path.join(root, f"ind.{name}.test.index")) as f:
+        reorder = np.asarray([int(line.strip()) for line in f if line.strip()], dtype=np.int64)
+    if reorder.size != ty.shape[0]:
+        raise ValueError(f"ind.{name}.test.index lists {reorder.size} nodes, ind.{name}.ty has {ty.shape[0]} rows")
+
+    def classes(m):
+        return np.where(m.any(1), m.argmax(1), -1).astype(np.int64) if m.size else np.full(m.shape[0], -1, np.int64)
+    if ally.shape[0] > n or (reorder.size and (reorder.min() < ally.shape[0] or reorder.max() >= n)):
+        raise ValueError(f"ind.{name}.ally / .ty do not fit the {n} nodes of the graph")
+    labels = np.full(n, -1, dtype=np.int64)
+    labels[:ally.shape[0]] = classes(ally)
+    labels[reorder] = classes(ty)
+    return labels
+
+
 def load_data(args):
     name = args.dataset.lower()
     root = getattr(args, "data_root", "data")
@@ -112,12 +147,13 @@ def load_data(args):
         z = np.load(path)
         feats = z["features"].astype(np.float32)
         n = int(z["n"]) if "n" in z.files else feats.shape[0]
-        return CitationData(name, feats, EdgeListGraph(n, z["src"], z["dst"]), False)
+        labels = z["labels"] if "labels" in z.files else None
+        return CitationData(name, feats, EdgeListGraph(n, z["src"], z["dst"]), False, labels)
     pdir = planetoid_dir(root, name)
     if pdir is not None:
         n, src, dst, feats = load_planetoid(pdir, name)
         print(f"[gae_dgl_amd] {name}: Planetoid files under {pdir}: {n} nodes, {src.size} edges, {feats.shape[1]} features")
-        return CitationData(name, feats, EdgeListGraph(n, src, dst), False)
+        return CitationData(name, feats, EdgeListGraph(n, src, dst), False, load_planetoid_labels(pdir, name, n))
     from . import workloads
     if name not in workloads.CITATION:
         raise ValueError(f"unknown dataset {name!r}")

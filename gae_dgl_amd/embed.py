@@ -10,7 +10,9 @@ writes.  The whole set is embedded by ``GAE.embed_graphs``: one fused launch whe
 (``--fused auto|on``), the chunked batch -> encode -> readout route otherwise (``--fused off``).  Writes fp32
 [G, 3 d] as .npy and prints the graph count, the route taken and the time of the embedding call.
 ``--scores PATH`` also writes how well each molecule is reconstructed (``GAE.score_graphs``): fp64 [G, 5] .npy with the
-columns loss, auc, ap, n_pos, n_neg; the feature output is the same with and without it."""
+columns loss, auc, ap, n_pos, n_neg; the feature output is the same with and without it.
+``--clusters K`` clusters the molecule features just computed with k-means on the device (``ops.kmeans``): chemical-space
+clusters of the resident set; ``--clusters_out PATH`` writes 'labels' int32 [G] and 'centers' fp32 [K, 3 d] as .npz."""
 import argparse
 import os
 import time
@@ -35,6 +37,11 @@ def build_parser():
     ap.add_argument("--scores", type=str, default=None, metavar="PATH",
                     help="also write the per-molecule reconstruction scores (.npy, [G, 5] fp64: loss, auc, ap, n_pos, "
                          "n_neg)")
+    ap.add_argument("--clusters", type=int, default=None, metavar="K",
+                    help="also cluster the features with k-means (K in 1..256, on the device; 3 d <= 64) and print the "
+                         "inertia, the iterations and the cluster sizes")
+    ap.add_argument("--clusters_out", type=str, default=None, metavar="PATH",
+                    help="with --clusters: write the labels and centres (.npz: 'labels' int32 [G], 'centers' fp32 [K, 3 d])")
     ap.add_argument("--norm", choices=["none", "both"], default="none",
                     help="none = the reference's plain in-edge sums; both = D^-1/2 A D^-1/2")
     ap.add_argument("--fused", choices=["auto", "on", "off"], default="auto",
@@ -63,6 +70,12 @@ def parse_args(argv=None):
     if args.fused == "on" and not ops.embed_graphs_usable(args.in_dim, args.hidden_dims, 0):
         parser.error(f"--fused on: the kernel takes 1..{ops.EMBED_MAX_LAYERS} layers of widths <= {ops.EMBED_MAX_WIDTH}, "
                      f"not {args.in_dim} -> {args.hidden_dims}; use --fused auto or off")
+    if args.clusters is None:
+        if args.clusters_out:
+            parser.error("--clusters_out needs --clusters K")
+    elif not 1 <= args.clusters <= 256 or 3 * args.hidden_dims[-1] > 64:
+        parser.error(f"--clusters {args.clusters}: K must lie in 1..256 and the feature width 3 d = "
+                     f"{3 * args.hidden_dims[-1]} must not exceed 64")
     return args
 
 
@@ -110,6 +123,14 @@ def main(argv=None):
         print(f"Scored {table.shape[0]} molecules | AUC {summary['auc']:.4f} | AP {summary['ap']:.4f} | "
               f"loss (no dropout) {summary['loss']:.4f} | {summary['left_out']} without both classes | wrote {args.scores}")
         main.scores = sc
+    main.clusters = None
+    if args.clusters is not None:
+        res = ops.kmeans(feats, args.clusters, seed=args.seed or 0)
+        print(f"Clustered {out.shape[0]} molecules into {args.clusters} | inertia {res.inertia:.6g} | iterations: "
+              f"{res.n_iter}{'' if res.converged else ' (not converged)'} | sizes: {res.counts.tolist()}")
+        if args.clusters_out:
+            np.savez(args.clusters_out, labels=res.labels.cpu().numpy(), centers=res.centers.cpu().numpy())
+        main.clusters = res
     return out
 
 

@@ -307,6 +307,19 @@ class GAE(nn.Module):
                 g.ndata['h'] = feat
         return reconstruct_embedding(z, g, t, scope, exclude_self, exclude_edges, max_pairs)
 
+    def cluster_nodes(self, g, k, **kw):
+        """``ops.KMeansResult``: node clustering, the second downstream task of a graph auto-encoder -- k-means with
+        ``k`` clusters on the embedding encode(g), on the device (ops.kmeans; its keyword arguments pass through:
+        init, n_init, max_iter, tol, seed, check_every).  ``metrics.clustering_metrics`` scores the labels against
+        classes.  Runs encode(g) under no_grad; ``g.ndata['h']`` is restored on exit."""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                z = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return ops.kmeans(z, k, **kw)
+
     def embed_graphs(self, data, *, fused="auto", batch_size=4096, grad=False):
         """fp32 [n_graphs, 3 d]: the molecule feature of the reference's chemistry table (README.md:54: mean | sum |
         max of the hidden vectors, 48 numbers for ``--hidden_dims 32 16``) of every graph of ``data`` -- a

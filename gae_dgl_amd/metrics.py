@@ -266,3 +266,42 @@ def graph_score_summary(scores):
     pairs = float((n_pos[both].double() * n_neg[both].double()).sum())
     out["micro_auc"] = (float(wins[both].double().sum()) + float(ties[both].double().sum()) / 2) / pairs
     return out
+
+
+def clustering_metrics(pred, true):
+    """How well cluster labels ``pred`` [n] agree with classes ``true`` [n] (rows with ``true < 0`` are ignored): a
+    dict with ``nmi`` (mutual information over the ARITHMETIC mean of the two entropies, natural logarithms), ``ari``
+    (adjusted Rand index from the contingency table), ``acc`` (the best one-to-one matching of clusters to classes,
+    scipy.optimize.linear_sum_assignment) and ``n`` (rows counted).  Host code on the small contingency table.  Two
+    single-cluster labellings agree perfectly (1 / 1 / 1); no row gives NaN."""
+    pred, true = np.asarray(pred).reshape(-1), np.asarray(true).reshape(-1)
+    if pred.shape != true.shape:
+        raise ValueError(f"clustering_metrics: {pred.size} predictions for {true.size} labels")
+    keep = true >= 0
+    pred, true = pred[keep], true[keep]
+    n = int(pred.size)
+    nan = float("nan")
+    if n == 0:
+        return {"nmi": nan, "ari": nan, "acc": nan, "n": 0}
+    _, pi = np.unique(pred, return_inverse=True)
+    _, ti = np.unique(true, return_inverse=True)
+    table = np.zeros((int(pi.max()) + 1, int(ti.max()) + 1), dtype=np.int64)
+    np.add.at(table, (pi, ti), 1)
+    a, b = table.sum(1).astype(np.float64), table.sum(0).astype(np.float64)
+    # NMI
+    nz = table > 0
+    p = table[nz] / n
+    mi = float((p * np.log(p / (np.outer(a, b)[nz] / (float(n) * n)))).sum())
+    ha = float(-(a / n * np.log(a / n)).sum())
+    hb = float(-(b / n * np.log(b / n)).sum())
+    nmi = 1.0 if ha + hb == 0 else max(mi, 0.0) / ((ha + hb) / 2)
+    # ARI
+    comb = lambda x: x * (x - 1) / 2.0
+    sum_ij, sum_a, sum_b = float(comb(table.astype(np.float64)).sum()), float(comb(a).sum()), float(comb(b).sum())
+    expected = sum_a * sum_b / comb(float(n)) if n > 1 else 0.0
+    upper = (sum_a + sum_b) / 2
+    ari = 1.0 if upper == expected else (sum_ij - expected) / (upper - expected)
+    # accuracy under the best one-to-one matching
+    from scipy.optimize import linear_sum_assignment
+    rows, cols = linear_sum_assignment(-table)
+    return {"nmi": float(nmi), "ari": float(ari), "acc": float(table[rows, cols].sum()) / n, "n": n}

@@ -6,6 +6,7 @@ epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
 
   python -m gae_dgl_amd.train_transductive --dataset cora [--norm both] [--eval [--rank]] [--topk 10 [--topk_out top.npz]]
       [--loss_samples M] [--decode_out graph.npz [--decode_prob P] [--decode_max_pairs M]]
+      [--cluster K [--cluster_seed S] [--cluster_out clusters.npz]]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -67,6 +68,14 @@ def build_parser():
                     help="with --decode_out: the probability cut-off, inside (0, 1) (default 0.5)")
     ap.add_argument("--decode_max_pairs", type=int, default=None, metavar="M",
                     help="with --decode_out: refuse to write more than M pairs (default 2^27, 12 bytes each)")
+    ap.add_argument("--cluster", type=int, default=None, metavar="K",
+                    help="after training, k-means with K (1..256) clusters on the node embedding (GAE.cluster_nodes, on "
+                         "the device): prints the inertia, the iterations and the cluster sizes, and NMI | ARI | ACC "
+                         "where the dataset carries class labels")
+    ap.add_argument("--cluster_seed", type=int, default=None, metavar="S",
+                    help="with --cluster: the seed of the k-means++ seeding (default 0)")
+    ap.add_argument("--cluster_out", default=None, metavar="PATH",
+                    help="with --cluster: write PATH (.npz with 'labels' int32 [n] and 'centers' fp32 [K, d])")
     return ap
 
 
@@ -93,6 +102,11 @@ def parse_args(argv=None):
             ap.error(f"--decode_prob {args.decode_prob}: P must lie inside (0, 1)")
         if args.decode_max_pairs is not None and args.decode_max_pairs < 1:
             ap.error(f"--decode_max_pairs {args.decode_max_pairs}: M must be at least 1")
+    if args.cluster is None:
+        if args.cluster_seed is not None or args.cluster_out is not None:
+            ap.error("--cluster_seed / --cluster_out need --cluster K")
+    elif not 1 <= args.cluster <= 256:
+        ap.error(f"--cluster {args.cluster}: K must lie in 1..256")
     return args
 
 
@@ -198,6 +212,19 @@ def main(argv=None):
         main.last_decode = rm
         np.savez(args.decode_out, indptr=links.indptr.cpu().numpy(), index=links.index.cpu().numpy(),
                  score=links.score.cpu().numpy())
+    if args.cluster is not None:
+        import numpy as np
+        g.ndata['h'] = features
+        res = model.cluster_nodes(g, args.cluster, seed=args.cluster_seed or 0)
+        print(f"k-means K = {args.cluster}: inertia {res.inertia:.6g} | iterations: {res.n_iter}"
+              f"{'' if res.converged else ' (not converged)'} | sizes: {res.counts.tolist()}")
+        main.last_cluster = {"result": res}
+        if data.labels is not None:
+            cm = metrics.clustering_metrics(res.labels.cpu().numpy(), data.labels)
+            print(f"NMI: {cm['nmi']:.4f} | ARI: {cm['ari']:.4f} | ACC: {cm['acc']:.4f}")
+            main.last_cluster.update(cm)
+        if args.cluster_out is not None:
+            np.savez(args.cluster_out, labels=res.labels.cpu().numpy(), centers=res.centers.cpu().numpy())
     return [float(l) for l in losses]
 
 

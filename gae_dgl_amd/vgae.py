@@ -135,6 +135,17 @@ class VGAE(nn.Module):
                 g.ndata['h'] = feat
         return reconstruct_embedding(mu, g, t, scope, exclude_self, exclude_edges, max_pairs)
 
+    def cluster_nodes(self, g, k, **kw):
+        """GAE.cluster_nodes on the mean embedding mu (no noise): ``ops.KMeansResult`` of ops.kmeans; mu is read in
+        place where the two heads are packed in one buffer; ``g.ndata['h']`` is restored on exit"""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                mu, _ = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return ops.kmeans(mu, k, **kw)
+
     def score_graphs(self, g, *, exclude_self=True):
         """GAE.score_graphs on the mean embedding mu (no noise) of a batched graph ``g``: ``ops.GraphScores`` per member
         graph, mu scored through the no-layer mode of ops.score_graphs (gae.score_embedding)"""

@@ -10,7 +10,8 @@
  *   gae_linear2_*, gae_gcn2_*   the dense halves of a two-layer encoder on millions of rows (row-sharded RMAT path)
  * and gae_decoder_bce_sampled, an unbiased stochastic estimate of gae_decoder_bce's loss for graphs beyond the N^2 sum,
  * and gae_decoder_rank, the filtered rank of given pairs among all candidates of gae_decoder_topk's rule,
- * and gae_score_graphs, the per-molecule reconstruction scores (AUC counts, average precision, loss) of a resident set.
+ * and gae_score_graphs, the per-molecule reconstruction scores (AUC counts, average precision, loss) of a resident set,
+ * and gae_kmeans_*, node clustering on the device: k-means++ seeding, Lloyd iterations and assignment over an embedding.
  * Same conventions as gae_hip.h: caller-owned buffers, 0 / negative / hipError_t return codes, asynchronous launches on
  * the stream passed last.  These signatures may change between versions without a GAE_VERSION major bump. */
 #ifndef GAE_HIP_EXPERIMENTAL_H
@@ -547,6 +548,68 @@ int gae_score_graphs(const int64_t *graph_ptr, int64_t n_graphs, int64_t n_nodes
                      const float *const *biases, const int *acts, int norm, const int64_t *graph_ids,
                      int64_t n_out, int exclude_self, int64_t *counts_out, double *ap_out, float *loss_out,
                      void *stream);
+
+/* ---- K23: k-means over the rows of an embedding, on the device (ops.kmeans, ops.kmeans_assign, GAE.cluster_nodes)
+ * Node clustering, the second downstream task of a graph auto-encoder: Lloyd iterations and k-means++ seeding without
+ * the n x k distance matrix, without float atomics and without a host round trip per iteration.
+ *   X            fp32 [n, d], rows ldx >= d floats apart (any ldx: no alignment is asked for)
+ *   C            fp32 [k, d], dense
+ *   1 <= d <= 64, 1 <= k <= 256 (else GAE_E_RANGE); 0 <= n < 2^31, k <= n (else GAE_E_SIZE).  No fallback for other shapes.
+ *   workspace    device memory of at least the workspace query's bytes: a pure host function of (n, d, k), positive,
+ *                non-decreasing in n; a negative error code for the argument errors above.  A step keeps nothing in it
+ *                between calls; the seeding and the steps may share one.
+ * ASSIGNMENT (gae_kmeans_assign; the first launch of a step): row i goes to argmin_c |x_i - c_c|^2, evaluated in fp32 as
+ * h_c - x_i . c_c with h_c = |c_c|^2 / 2 (an ascending-f fmaf chain, halved), the products on v_mfma_f32_32x32x2_f32 in the
+ * fixed feature order of csrc/decoder_pairs.h.  Ties -- equal computed fp32 values, duplicate centres -- go to the LOWER
+ * centre index.  dist2 of the chosen centre a is taken directly: the fmaf chain over f = 0 .. d - 1 ascending, from 0.f,
+ * of (x_if - c_af)^2 -- no cancellation of the expanded form.  labels_out int32 [n]; dist2_out fp32 [n] or NULL.
+ * STEP (gae_kmeans_step): one Lloyd iteration in four launches -- assign (labels in/out: the rows whose label differs
+ * from the one found on entry are counted, -1 on entry counts as changed), cluster sums, fold, finish:
+ *   sums         blocks own fixed contiguous row ranges, every accumulator has one writer that adds its rows in
+ *                ascending order, the block partials are added in the library's one order for partial lists (common.h
+ *                sum_partials), counts as int64.  The grid is a function of n alone.  The same bits run to run and for
+ *                any ldx; no float atomics
+ *   update       new centre = sum / count (fp32), written to C in place; a cluster without rows KEEPS its centre
+ *   status       a 48-byte device block, zeroed by the caller before the first step:
+ *                  done        set by the step when changed == 0 or shift2 <= tol_abs
+ *                  iterations  += 1 per step that ran
+ *                  changed     labels that differ from the ones on entry
+ *                  empty       clusters without rows in this step
+ *                  inertia     sum_i dist2_i of the labels against the centres they were chosen with (the C on entry):
+ *                              fp64; per block of rows thread t adds rows t, t + 256, ... then a halving tree, the blocks
+ *                              in sum_partials' 64-lane order
+ *                  shift2      sum_c |c_new - c_old|^2: fp64, per centre in ascending f, the centres in ascending c
+ *                Every kernel of a LATER step on a status whose done is set returns at once and touches neither C nor
+ *                labels nor status: iterations may be enqueued in groups and the block read once per group, and the
+ *                result has the same bits whatever the group size.
+ *   tol_abs      double; negative: stop on changed == 0 only; NaN is GAE_E_RANGE.  flags: 0 (other bits GAE_E_RANGE)
+ * SEEDING (gae_kmeans_init_pp): k-means++ as an exponential race, all k rounds enqueued by one call, one launch each.
+ * key = seed ^ 0x9E3779B97F4A7C15.  Round 0 picks row philox4x32_10(ctr = 0, draw = 0, key)[0] mod n.  Round r >= 1:
+ * mind2_i = min(mind2_i, |x_i - x_prev|^2) (direct, ascending-f fmaf chain), m_i = philox4x32_10(ctr = i, draw = r, key)[0]
+ * >> 8, u_i = (m_i + 0.5) 2^-24, pick = argmax_i mind2_i / (-log u_i) in fp32 (-log u as -logf(u) for m_i < 2^23, else
+ * -log1pf(-(2^24 - 1 - m_i + 0.5) 2^-24): both arguments exact), the LOWEST i among equal keys -- sampling with
+ * probability proportional to D^2.  The pick does not depend on the grid.  chosen_out int32 [k]: the rows, distinct
+ * unless X has fewer than k distinct rows (all keys 0: the lowest index wins; duplicate centres are legal input to a
+ * step); C_out fp32 [k, d]: their rows, bit for bit.
+ * Argument errors are returned before any launch: the shape errors above, ldx < d (GAE_E_SIZE), NULL X / C / labels /
+ * status / outputs / workspace (GAE_E_NULL), a short workspace (GAE_E_WORKSPACE).  Non-finite X is the caller's
+ * business (ops.kmeans checks): nothing outside the arrays is read or written, the labels stay inside [0, k). */
+typedef struct gae_kmeans_status {
+    int64_t done, iterations, changed, empty;
+    double inertia, shift2;
+} gae_kmeans_status;
+
+int64_t gae_kmeans_workspace_bytes(int64_t n, int64_t d, int64_t k);
+
+int gae_kmeans_assign(const float *X, int64_t ldx, int64_t n, int64_t d, const float *C, int64_t k,
+                      int32_t *labels_out, float *dist2_out, void *workspace, int64_t workspace_bytes, void *stream);
+
+int gae_kmeans_step(const float *X, int64_t ldx, int64_t n, int64_t d, float *C, int64_t k, int32_t *labels,
+                    gae_kmeans_status *status, double tol_abs, int flags, void *workspace, int64_t workspace_bytes,
+                    void *stream);
+
+int gae_kmeans_init_pp(const float *X, int64_t ldx, int64_t n, int64_t d, int64_t k, uint64_t seed, float *C_out,
+                       int32_t *chosen_out, void *workspace, int64_t workspace_bytes, void *stream);
 
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
