@@ -19,6 +19,8 @@ SPMM_ELL_WIDTH = 16
 ACT_IDENTITY, ACT_RELU = 0, 1
 TOPK_EXCLUDE_SELF, TOPK_EXCLUDE_EDGES = 1, 2
 EMBED_NORM_NONE, EMBED_NORM_BOTH = 0, 1
+KNN_L2, KNN_DOT = 0, 1
+KNN_EXCLUDE_SAME_INDEX = 1
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _p, _f, _int = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
@@ -177,6 +179,8 @@ SIGNATURES = {
     "gae_kmeans_assign": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
     "gae_kmeans_step": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, ctypes.c_double, _int, _p, _i64, _p]),
     "gae_kmeans_init_pp": (_int, [_p, _i64, _i64, _i64, _i64, _u64, _p, _p, _p, _i64, _p]),
+    "gae_knn_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _int]),
+    "gae_knn": (_int, [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _int, _int, _int, _p, _p, _i64, _p, _i64, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

@@ -1,0 +1,420 @@
+// K24: exact k-nearest-neighbour search of one row set against another (ops.knn, GAE.nearest_nodes, GAE.nearest_graphs).
+//
+// Queries Q fp32 [m, d] (ldq), database X fp32 [n, d] (ldx); 1 <= d <= 256, 1 <= k <= 64, m, n < 2^31.  The contract --
+// candidates, keys, reported values, order, padding -- is the comment of gae_knn in include/gae_hip_experimental.h.
+//
+// Launches (ordinary ones, no float atomics):
+//   half    L2 only: h_j = (fmaf chain of x_jf^2, f ascending from 0.f) / 2 for every database row, into the workspace.
+//   sweep   one block per (group of NW panels of 32 queries, column split), one wave per panel.  The products are the
+//           tile of decoder_pairs.h: the panel is the B operand (in registers for d <= 64), a tile of 32 database rows
+//           the A operand, the same DH, chunk order and mma<DH> as K16 -- with Q = X the product has K16's bits.  Unlike
+//           K16's Z the database is not cache-resident at the molecule shape (48 MB at n = 249 455, d = 48), so the block
+//           stages every (tile, chunk) ONCE in LDS for its NW waves, h beside it: two buffers, the global loads of the
+//           next one issued before the products of the current one, one barrier per (tile, chunk).  key = p - h_j (DOT:
+//           h = 0, the product itself).  Every lane's 16 keys belong to one query: the lane keeps its top k in an LDS
+//           heap with the worst entry at the root (topk_heap.h, K16's), one max and one compare per tile on the fast
+//           path.  NaN, -inf and +inf never enter.  The two lane halves of a query merge their sorted lists; with one
+//           split that is the query's list, else it goes to the workspace.
+//   merge   S > 1: the S sorted lists of each query are merged by rank (K16's scheme): the order is total, so the
+//           result does not depend on S.
+//   finish  L2 only: per query the direct distance sum_f (q_f - x_jf)^2 of the k chosen rows (fmaf chain, f ascending
+//           from 0.f) replaces the key, and the row is re-sorted by (distance ascending, j ascending) with a rank count
+//           inside a lane group; padding (j = -1) gets +inf.
+//
+// LDS of the sweep: NW (2 k + 16) 256 bytes of heaps and tile scratch, 2 . 32 (2 DH + 4) 4 bytes of tile, 256 bytes of
+// h.  NW = 4 whenever that fits 160 KB (every shape but d > 32 with k = 64), else 2.  Accumulators in VGPRs
+// (-amdgpu-mfma-vgpr-form, _build.py): every one is compared.
+#include <float.h>
+
+#include "decoder_pairs.h"
+#include "topk_heap.h"
+
+namespace {
+
+using namespace gae::pairs;
+using namespace gae::topk;
+
+constexpr int kMaxK = 64, kMaxD = 256;
+constexpr int64_t kLdsLimit = 160 * 1024;
+constexpr int kTargetBlocks = 1024;        // auto split: about four blocks per CU
+
+struct KnnArgs {
+    const float *Q, *X;
+    int64_t ldq, ldx, ldo;
+    int m, n, d, k, nch, S;
+    int l2, excl_same;
+    const float *half;                     // [n] (L2)
+    float *value_out;
+    int32_t *index_out;
+    float *part_s;                         // [S][m][k] (S > 1)
+    int32_t *part_j;
+};
+
+inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int dh_of(int64_t d) { return d <= 16 ? 8 : d <= 32 ? 16 : 32; }
+
+inline int64_t sweep_lds(int nw, int64_t d, int64_t k)
+{
+    return int64_t(nw) * (2 * k + 16) * 256 + 2 * kTile * (2 * dh_of(d) + 4) * 4 + 2 * kTile * 4;
+}
+inline int waves_of(int64_t d, int64_t k) { return sweep_lds(4, d, k) <= kLdsLimit ? 4 : 2; }
+
+// column splits per block: the caller's, or (0 = auto) enough for ~kTargetBlocks blocks with parts of >= 256 rows
+inline int splits_of(int64_t m, int64_t n, int64_t d, int64_t k, int splits)
+{
+    if (splits > 0) return splits;
+    if (m <= 0 || n <= 0) return 1;
+    const int64_t blocks = cdiv(m, int64_t(kRows) * waves_of(d, k));
+    int64_t S = cdiv(kTargetBlocks, blocks);
+    const int64_t by_span = cdiv(n, 256);
+    S = S < by_span ? S : by_span;
+    return int(S < 1 ? 1 : (S > kMaxSplits ? kMaxSplits : S));
+}
+
+// entries of the partial lists the workspace holds: a bound of S m that never shrinks as m, n or splits grow
+// (auto: S <= kTargetBlocks / blocks + 1 and m <= 128 blocks, S <= 16, S <= ceil(n / 256))
+inline int64_t part_rows(int64_t m, int64_t n, int splits)
+{
+    if (splits > 0) return int64_t(splits) * m;
+    int64_t b = int64_t(kMaxSplits) * m;
+    const int64_t by_blocks = int64_t(kTargetBlocks) * kRows * 4 + m, by_span = cdiv(n, 256) * m;
+    b = b < by_blocks ? b : by_blocks;
+    return b < by_span ? b : by_span;
+}
+
+struct Plan { int64_t half_at, part_at, need; };
+
+int plan(const char *fn, int64_t m, int64_t n, int64_t d, int64_t k, int splits, Plan &p)
+{
+    GAE_REQUIRE(d >= 1 && d <= kMaxD, GAE_E_RANGE, "%s: d = %lld outside 1..256", fn, (long long)d);
+    GAE_REQUIRE(k >= 1 && k <= kMaxK, GAE_E_RANGE, "%s: k = %lld outside 1..64", fn, (long long)k);
+    GAE_REQUIRE(m >= 0 && n >= 0, GAE_E_SIZE, "%s: negative m = %lld or n = %lld", fn, (long long)m, (long long)n);
+    GAE_REQUIRE(m < (int64_t(1) << 31) && n < (int64_t(1) << 31), GAE_E_SIZE, "%s: m = %lld or n = %lld beyond int32 indices",
+                fn, (long long)m, (long long)n);
+    GAE_REQUIRE(splits >= 0 && splits <= kMaxSplits, GAE_E_RANGE, "%s: splits = %d outside 0..16", fn, splits);
+    p.half_at = 0;
+    p.part_at = up256(4 * n);
+    p.need = up256(p.part_at + part_rows(m, n, splits) * k * 8) + 256;
+    return GAE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------ half
+__global__ __launch_bounds__(256) void knn_half_kernel(const float *X, int64_t ldx, int n, int d, float *half)
+{
+    const int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (j >= n) return;
+    const float *xp = X + j * ldx;
+    float s = 0.f;
+    for (int f = 0; f < d; ++f) s = fmaf(xp[f], xp[f], s);
+    half[j] = 0.5f * s;
+}
+
+// ------------------------------------------------------------------------------------------------------ sweep
+template <int DH, bool ONE, int NW>
+__global__ __launch_bounds__(64 * NW) void knn_kernel(const KnnArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int W = 2 * DH, pitch = W + 4, T = 64 * NW;
+    constexpr int PF = kTile * W / T;                  // staged floats per thread and (tile, chunk)
+    static_assert(PF * T == kTile * W, "the tile is a whole number of block passes");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
+    const int k = a.k;
+    float *tile = lds;                                 // [2][kTile][pitch]: the A operand's image of a (tile, chunk)
+    float *hs = tile + 2 * kTile * pitch;              // [2][kTile]: h of a tile's rows
+    float *wl = hs + 2 * kTile + wave * (2 * k + 16) * 64;
+    float *ls = wl;                                    // [k][64] keys of each lane's list
+    int *lj = reinterpret_cast<int *>(wl + k * 64);    // [k][64] indices
+    float *scr = wl + 2 * k * 64;                      // [16][64] keys of a tile that has a passing lane
+    const int64_t blockp = blockIdx.x / a.S;
+    const int split = blockIdx.x % a.S;
+    const int64_t i64 = (blockp * NW + wave) * kRows + col;
+    const bool row_ok = i64 < a.m;
+    const int i = row_ok ? int(i64) : -1;
+
+    // ---- the block's column part [pb, pe): S parts of whole tiles
+    const int64_t L = ((int64_t(a.n) + a.S - 1) / a.S + kTile - 1) / kTile * kTile;
+    const int64_t pb = L * split < a.n ? L * split : a.n;
+    const int64_t pe = pb + L < a.n ? pb + L : a.n;
+    const int ntile = int((pe - pb + kTile - 1) / kTile);
+    const int nit = ntile * a.nch;                     // (tile, chunk) steps, chunks inside a tile
+
+    // ---- the panel rows (B operand)
+    float zr[DH];
+    auto load_row = [&](int q) {
+#pragma unroll
+        for (int s = 0; s < DH; ++s) {
+            const int f = feat0<DH>(q, h) + s;
+            zr[s] = (row_ok && f < a.d) ? a.Q[i64 * a.ldq + f] : 0.f;
+        }
+    };
+    if constexpr (ONE) load_row(0);
+
+    // ---- staging: element e = tid + u T of a (tile, chunk) is row e / W, feature e % W of the chunk
+    float pf[PF];
+    float pfh = 0.f;
+    auto fetch = [&](int it) {
+        const int t = it / a.nch, q = it - t * a.nch;
+        const int64_t c0 = pb + int64_t(t) * kTile;
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const int e = tid + u * T, r = e / W, f = q * W + e % W;
+            pf[u] = (c0 + r < pe && f < a.d) ? a.X[(c0 + r) * a.ldx + f] : 0.f;
+        }
+        if (q == 0 && tid < kTile) pfh = (a.l2 && c0 + tid < pe) ? a.half[c0 + tid] : 0.f;
+    };
+    auto stash = [&](int it) {
+        const int t = it / a.nch, q = it - t * a.nch;
+        float *dst = tile + (it & 1) * kTile * pitch;
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const int e = tid + u * T;
+            dst[(e / W) * pitch + e % W] = pf[u];
+        }
+        if (q == 0 && tid < kTile) hs[(t & 1) * kTile + tid] = pfh;
+    };
+    if (nit > 0) { fetch(0); stash(0); }
+    __syncthreads();
+
+    int cnt = 0;
+    float thr = -FLT_MAX;                              // key of the k-th entry once the list is full
+    int thr_j = INT32_MAX;
+    v16f acc = zero_acc();
+    for (int it = 0; it < nit; ++it) {
+        const int t = it / a.nch, q = it - t * a.nch;
+        if (it + 1 < nit) fetch(it + 1);               // in flight during this step's products
+        if constexpr (!ONE) load_row(q);
+        float za[DH];
+        const float *cp = tile + (it & 1) * kTile * pitch + col * pitch + h * DH;
+#pragma unroll
+        for (int s = 0; s < DH; ++s) za[s] = cp[s];
+        if (q == 0) acc = zero_acc();
+        acc = mma<DH>(acc, za, zr);
+        if (q == a.nch - 1) {
+            const int64_t c0 = pb + int64_t(t) * kTile;
+            const float *hp = hs + (t & 1) * kTile;
+            float key[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) key[r] = acc[r] - hp[tile_col(0, r, h)];
+            // ---- fast path: one max per key, one compare per tile
+            float mx = key[0];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, key[r]);
+            if (mx >= thr && row_ok) {
+                unsigned pass = 0;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    scr[r * 64 + lane] = key[r];
+                    pass |= (key[r] >= thr ? 1u : 0u) << r;
+                }
+                while (pass) {
+                    const int r = __builtin_ctz(pass);
+                    pass &= pass - 1;
+                    const float s = scr[r * 64 + lane];
+                    const int64_t jj = tile_col(c0, r, h);
+                    if (jj >= pe || !(s <= FLT_MAX)) continue;         // past the part; +inf is no candidate
+                    const int j = int(jj);
+                    if (a.excl_same && j == i) continue;
+                    if (cnt == k && !better(s, j, thr, thr_j)) continue;
+                    if (cnt < k) {
+                        heap_push(ls, lj, lane, cnt, s, j);
+                        ++cnt;
+                    } else {
+                        heap_replace_root(ls, lj, lane, k, s, j);
+                    }
+                    if (cnt == k) {
+                        thr = ls[lane];
+                        thr_j = lj[lane];
+                    }
+                }
+            }
+        }
+        if (it + 1 < nit) stash(it + 1);               // the buffer step it - 1 read; every wave is past that barrier
+        __syncthreads();
+    }
+    heap_sort(ls, lj, lane, cnt);
+    // ---- merge the two lane halves of each query; lane h = 0 writes the list
+    __syncthreads();
+    const int pcnt = __shfl_down(cnt, 32, 64);
+    if (h == 0 && row_ok) {
+        const bool direct = a.S == 1;
+        float *os = direct ? a.value_out + i64 * a.ldo : a.part_s + (int64_t(split) * a.m + i64) * k;
+        int32_t *oj = direct ? a.index_out + i64 * a.ldo : a.part_j + (int64_t(split) * a.m + i64) * k;
+        int p0 = 0, p1 = 0;
+        for (int t = 0; t < k; ++t) {
+            float s = -INFINITY;
+            int j = -1;
+            const bool h0 = p0 < cnt, h1 = p1 < pcnt;
+            if (h0 || h1) {
+                const float s0 = h0 ? ls[p0 * 64 + lane] : 0.f, s1 = h1 ? ls[p1 * 64 + lane + 32] : 0.f;
+                const int j0 = h0 ? lj[p0 * 64 + lane] : 0, j1 = h1 ? lj[p1 * 64 + lane + 32] : 0;
+                if (h0 && (!h1 || better(s0, j0, s1, j1))) { s = s0; j = j0; ++p0; }
+                else { s = s1; j = j1; ++p1; }
+            }
+            os[t] = s;
+            oj[t] = j;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ merge
+// one thread per (query, split, position): the entry's rank among the S lists of its query is its output slot
+__global__ __launch_bounds__(256) void knn_merge_kernel(const KnnArgs a)
+{
+    const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    const int k = a.k, S = a.S;
+    if (t >= int64_t(a.m) * S * k) return;
+    const int q = int(t % k);
+    const int s = int((t / k) % S);
+    const int64_t i = t / (int64_t(k) * S);
+    const int64_t stride = int64_t(a.m) * k;
+    const float *ps = a.part_s + i * k;
+    const int32_t *pj = a.part_j + i * k;
+    float *os = a.value_out + i * a.ldo;
+    int32_t *oj = a.index_out + i * a.ldo;
+    const int j = pj[s * stride + q];
+    if (j >= 0) {
+        const float v = ps[s * stride + q];
+        int rank = q;
+        for (int u = 0; u < S; ++u)
+            if (u != s) rank += rank_in(ps + u * stride, pj + u * stride, k, v, j);
+        if (rank < k) { os[rank] = v; oj[rank] = j; }
+    }
+    if (s == 0) {
+        int total = 0;
+        for (int u = 0; u < S; ++u) total += valid_in(pj + u * stride, k);
+        if (q >= total) { os[q] = -INFINITY; oj[q] = -1; }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ finish
+// L2: a group of G = 2^ceil(log2 k) lanes per query; lane e holds entry e of the query's list.
+// The row is rewritten IN PLACE: that is safe only because G <= 64 divides the wave, so a group never leaves one wave,
+// every lane's load of oj[e] comes before the shuffles and every store after them in the wave's one instruction stream.
+// A block size that is no multiple of 64, or loads moved behind the shuffles, would break it.
+__global__ __launch_bounds__(256) void knn_finish_kernel(const KnnArgs a, int G)
+{
+    const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    const int64_t row = t / G;
+    const int e = int(t % G);
+    const bool mine = row < a.m && e < a.k;
+    float *os = a.value_out + (mine ? row : 0) * a.ldo;
+    int32_t *oj = a.index_out + (mine ? row : 0) * a.ldo;
+    const int j = mine ? oj[e] : -1;
+    float dist = INFINITY;
+    if (j >= 0) {
+        const float *qp = a.Q + row * a.ldq, *xp = a.X + int64_t(j) * a.ldx;
+        dist = 0.f;
+        for (int f = 0; f < a.d; ++f) {
+            const float df = qp[f] - xp[f];
+            dist = fmaf(df, df, dist);
+        }
+    }
+    int rank = 0;
+    for (int u = 0; u < G; ++u) {                      // every lane of the wave takes part in the shuffles
+        const int ju = __shfl(j, u, G);
+        const float du = __shfl(dist, u, G);
+        if (ju >= 0 && (du < dist || (du == dist && ju < j))) ++rank;
+    }
+    if (mine) {
+        const int slot = j >= 0 ? rank : e;            // padding stays where it is, behind the valid entries
+        os[slot] = dist;
+        oj[slot] = j;
+    }
+}
+
+template <auto Kernel>
+int launch_sweep(int64_t blocks, int threads, size_t lds, hipStream_t st, const KnnArgs &a)
+{
+    static int configured[16] = {0};
+    int dev = 0;
+    GAE_HIP(hipGetDevice(&dev));
+    if (lds > 48 * 1024 && (dev < 0 || dev >= 16 || configured[dev] < int(lds))) {
+        GAE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    int(lds)));
+        if (dev >= 0 && dev < 16) configured[dev] = int(lds);
+    }
+    hipLaunchKernelGGL(Kernel, dim3(unsigned(blocks)), dim3(threads), lds, st, a);
+    GAE_CHECK_LAUNCH("knn_kernel");
+    return GAE_OK;
+}
+
+template <int NW>
+int launch_sweep_nw(int64_t blocks, size_t lds, hipStream_t st, const KnnArgs &a)
+{
+    // the same DH and chunk choice per d as GAE_PAIRS_LAUNCH
+    if (a.d <= 16) return launch_sweep<&knn_kernel<8, true, NW>>(blocks, 64 * NW, lds, st, a);
+    if (a.d <= 32) return launch_sweep<&knn_kernel<16, true, NW>>(blocks, 64 * NW, lds, st, a);
+    if (a.d <= 64) return launch_sweep<&knn_kernel<32, true, NW>>(blocks, 64 * NW, lds, st, a);
+    return launch_sweep<&knn_kernel<32, false, NW>>(blocks, 64 * NW, lds, st, a);
+}
+
+} // namespace
+
+extern "C" int64_t gae_knn_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int splits)
+{
+    Plan p;
+    if (const int rc = plan("gae_knn_workspace_bytes", m, n, d, k, splits, p)) return rc;
+    return p.need;
+}
+
+extern "C" int gae_knn(const float *Q, int64_t ldq, int64_t m, const float *X, int64_t ldx, int64_t n, int64_t d, int64_t k,
+                       int metric, int flags, int splits, int32_t *index_out, float *value_out, int64_t ldo,
+                       void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const char *fn = "gae_knn";
+    Plan p;
+    if (const int rc = plan(fn, m, n, d, k, splits, p)) return rc;
+    GAE_REQUIRE(metric == GAE_KNN_L2 || metric == GAE_KNN_DOT, GAE_E_RANGE, "%s: unknown metric %d", fn, metric);
+    GAE_REQUIRE((flags & ~GAE_KNN_EXCLUDE_SAME_INDEX) == 0, GAE_E_RANGE, "%s: unknown flags 0x%x", fn, flags);
+    GAE_REQUIRE(ldq >= d && ldx >= d && ldo >= k, GAE_E_SIZE,
+                "%s: leading dimension too small (ldq %lld < d, ldx %lld < d or ldo %lld < k)", fn, (long long)ldq,
+                (long long)ldx, (long long)ldo);
+    GAE_REQUIRE(m == 0 || (index_out && value_out), GAE_E_NULL, "%s: index_out / value_out is NULL", fn);
+    GAE_REQUIRE(m == 0 || Q, GAE_E_NULL, "%s: Q is NULL", fn);
+    GAE_REQUIRE(m == 0 || n == 0 || X, GAE_E_NULL, "%s: X is NULL", fn);
+    GAE_REQUIRE(workspace, GAE_E_NULL, "%s: workspace is NULL", fn);
+    GAE_REQUIRE(workspace_bytes >= p.need, GAE_E_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn,
+                (long long)workspace_bytes, (long long)p.need);
+    if (m == 0) return GAE_OK;
+
+    const int S = splits_of(m, n, d, k, splits);
+    const int nw = waves_of(d, k);
+    char *ws = static_cast<char *>(workspace);
+    KnnArgs a;
+    a.Q = Q; a.X = X; a.ldq = ldq; a.ldx = ldx; a.ldo = ldo;
+    a.m = int(m); a.n = int(n); a.d = int(d); a.k = int(k); a.S = S;
+    a.nch = d <= 64 ? 1 : int((d + 63) / 64);
+    a.l2 = metric == GAE_KNN_L2 ? 1 : 0;
+    a.excl_same = (flags & GAE_KNN_EXCLUDE_SAME_INDEX) ? 1 : 0;
+    a.half = reinterpret_cast<const float *>(ws + p.half_at);
+    a.value_out = value_out; a.index_out = index_out;
+    a.part_s = reinterpret_cast<float *>(ws + p.part_at);
+    a.part_j = reinterpret_cast<int32_t *>(a.part_s + (S > 1 ? int64_t(S) * m * k : 0));
+    hipStream_t st = gae::as_stream(stream);
+
+    // every grid of the call, before the first launch
+    int G = 1;
+    while (G < k) G *= 2;
+    const int64_t blocks = cdiv(m, int64_t(kRows) * nw) * S;
+    const int64_t merge_blocks = cdiv(m * S * k, 256), finish_blocks = cdiv(m * G, 256);
+    GAE_REQUIRE(blocks < (int64_t(1) << 31) && merge_blocks < (int64_t(1) << 31) && finish_blocks < (int64_t(1) << 31),
+                GAE_E_SIZE, "%s: a grid of %lld / %lld / %lld blocks", fn, (long long)blocks, (long long)merge_blocks,
+                (long long)finish_blocks);
+    if (a.l2 && n > 0) {
+        hipLaunchKernelGGL(knn_half_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, st, X, ldx, int(n), int(d),
+                           reinterpret_cast<float *>(ws + p.half_at));
+        GAE_CHECK_LAUNCH("knn_half_kernel");
+    }
+    const size_t lds = size_t(sweep_lds(nw, d, k));
+    if (const int rc = nw == 4 ? launch_sweep_nw<4>(blocks, lds, st, a) : launch_sweep_nw<2>(blocks, lds, st, a)) return rc;
+    if (S > 1) {
+        hipLaunchKernelGGL(knn_merge_kernel, dim3(unsigned(merge_blocks)), dim3(256), 0, st, a);
+        GAE_CHECK_LAUNCH("knn_merge_kernel");
+    }
+    if (a.l2) {
+        hipLaunchKernelGGL(knn_finish_kernel, dim3(unsigned(finish_blocks)), dim3(256), 0, st, a, G);
+        GAE_CHECK_LAUNCH("knn_finish_kernel");
+    }
+    return GAE_OK;
+}

@@ -12,7 +12,11 @@ writes.  The whole set is embedded by ``GAE.embed_graphs``: one fused launch whe
 ``--scores PATH`` also writes how well each molecule is reconstructed (``GAE.score_graphs``): fp64 [G, 5] .npy with the
 columns loss, auc, ap, n_pos, n_neg; the feature output is the same with and without it.
 ``--clusters K`` clusters the molecule features just computed with k-means on the device (``ops.kmeans``): chemical-space
-clusters of the resident set; ``--clusters_out PATH`` writes 'labels' int32 [G] and 'centers' fp32 [K, 3 d] as .npz."""
+clusters of the resident set; ``--clusters_out PATH`` writes 'labels' int32 [G] and 'centers' fp32 [K, 3 d] as .npz.
+``--neighbours K`` searches the features just computed against themselves (``ops.knn``: the exact K nearest other
+molecules of every molecule, ``--metric l2|dot|cosine``) and prints the time of that one call, first-use set-up included; ``--neighbours_out PATH``
+writes 'index' int32 [G, K] and 'value' fp32 [G, K] as .npz; ``--targets y.npy`` (one property per molecule) prints the
+leave-one-out RMSE | MAE | R2 of the kNN regressor on the frozen features."""
 import argparse
 import os
 import time
@@ -42,6 +46,17 @@ def build_parser():
                          "inertia, the iterations and the cluster sizes")
     ap.add_argument("--clusters_out", type=str, default=None, metavar="PATH",
                     help="with --clusters: write the labels and centres (.npz: 'labels' int32 [G], 'centers' fp32 [K, 3 d])")
+    ap.add_argument("--neighbours", type=int, default=None, metavar="K",
+                    help="also search the features against themselves: the K (1..64) nearest other molecules of every "
+                         "molecule, exact, on the device (3 d <= 256); prints the time of the one call made (its "
+                         "first-use set-up included: tools/knn_bench.py times warm calls)")
+    ap.add_argument("--metric", choices=["l2", "dot", "cosine"], default=None,
+                    help="with --neighbours: squared Euclidean distance (default), inner product or cosine similarity")
+    ap.add_argument("--neighbours_out", type=str, default=None, metavar="PATH",
+                    help="with --neighbours: write the lists (.npz: 'index' int32 [G, K], 'value' fp32 [G, K])")
+    ap.add_argument("--targets", type=str, default=None, metavar="PATH",
+                    help="with --neighbours: a .npy of one property per molecule; prints the leave-one-out RMSE | MAE | "
+                         "R2 of the kNN regressor (mean of the K neighbours' targets)")
     ap.add_argument("--norm", choices=["none", "both"], default="none",
                     help="none = the reference's plain in-edge sums; both = D^-1/2 A D^-1/2")
     ap.add_argument("--fused", choices=["auto", "on", "off"], default="auto",
@@ -76,6 +91,15 @@ def parse_args(argv=None):
     elif not 1 <= args.clusters <= 256 or 3 * args.hidden_dims[-1] > 64:
         parser.error(f"--clusters {args.clusters}: K must lie in 1..256 and the feature width 3 d = "
                      f"{3 * args.hidden_dims[-1]} must not exceed 64")
+    if args.neighbours is None:
+        if args.metric is not None or args.neighbours_out or args.targets:
+            parser.error("--metric / --neighbours_out / --targets need --neighbours K")
+    else:
+        if not 1 <= args.neighbours <= ops.KNN_MAX_K or 3 * args.hidden_dims[-1] > ops.KNN_MAX_D:
+            parser.error(f"--neighbours {args.neighbours}: K must lie in 1..{ops.KNN_MAX_K} and the feature width 3 d = "
+                         f"{3 * args.hidden_dims[-1]} must not exceed {ops.KNN_MAX_D}")
+        if args.targets and not os.path.exists(args.targets):
+            parser.error(f"--targets {args.targets}: no such file")
     return args
 
 
@@ -131,6 +155,28 @@ def main(argv=None):
         if args.clusters_out:
             np.savez(args.clusters_out, labels=res.labels.cpu().numpy(), centers=res.centers.cpu().numpy())
         main.clusters = res
+    main.neighbours = None
+    if args.neighbours is not None:
+        from gae_dgl_amd import metrics
+        metric = args.metric or "l2"
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        nn = ops.knn(feats, k=args.neighbours, metric=metric)
+        torch.cuda.synchronize(device)
+        print(f"Searched {out.shape[0]} molecules for their {args.neighbours} nearest ({metric}) | "
+              f"{(time.perf_counter() - t0) * 1e3:.3f} ms (one call, set-up included)")
+        main.neighbours = nn
+        if args.neighbours_out:
+            np.savez(args.neighbours_out, index=nn.index.cpu().numpy(), value=nn.value.cpu().numpy())
+        if args.targets:
+            y = np.load(args.targets).reshape(-1)
+            if y.shape[0] != out.shape[0]:
+                raise ValueError(f"--targets holds {y.shape[0]} values for {out.shape[0]} molecules")
+            y = torch.from_numpy(y.astype(np.float64)).to(device)
+            rm = metrics.regression_metrics(metrics.knn_predict(nn.index, nn.value, y), y)
+            print(f"kNN ({args.neighbours}, leave-one-out) RMSE: {rm['rmse']:.6f} | MAE: {rm['mae']:.6f} | "
+                  f"R2: {rm['r2']:.6f}")
+            main.knn_scores = rm
     return out
 
 

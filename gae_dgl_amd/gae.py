@@ -320,6 +320,34 @@ class GAE(nn.Module):
                 g.ndata['h'] = feat
         return ops.kmeans(z, k, **kw)
 
+    def nearest_nodes(self, g, k, *, metric="l2"):
+        """``ops.KNNResult(index, value)``: the ``k`` nearest nodes of every node in the embedding encode(g), the node
+        itself left out -- exact, on the device (ops.knn), without the N x N distance matrix.  ``metric``: "l2"
+        (squared distance, ascending), "dot" or "cosine" (descending).  ``metrics.knn_predict`` turns the lists and
+        class labels into the leave-one-out kNN accuracy of the embedding.  Runs encode(g) under no_grad;
+        ``g.ndata['h']`` is restored on exit."""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                z = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return ops.knn(z, k=k, metric=metric)
+
+    def nearest_graphs(self, data, k, *, queries=None, metric="l2", **embed_kw):
+        """``ops.KNNResult(index, value)``: similarity search over the molecule features of ``embed_graphs`` (its
+        keyword arguments pass through: fused, batch_size).  ``queries=None``: the kNN graph of ``data`` -- for every
+        graph its ``k`` nearest other graphs.  Otherwise the graphs of ``queries`` (a set, a ``subset()`` view or a
+        batched graph) are searched against ``data``; a graph that is in both is its own nearest neighbour.  The
+        indices are rows of ``data`` in the order ``embed_graphs(data)`` returns them.  Runs under no_grad."""
+        if "grad" in embed_kw:
+            raise ValueError("nearest_graphs runs under no_grad: the neighbour lists carry no gradient")
+        with torch.no_grad():
+            X = self.embed_graphs(data, **embed_kw)
+            if queries is None:
+                return ops.knn(X, k=k, metric=metric)
+            return ops.knn(self.embed_graphs(queries, **embed_kw), X, k=k, metric=metric)
+
     def embed_graphs(self, data, *, fused="auto", batch_size=4096, grad=False):
         """fp32 [n_graphs, 3 d]: the molecule feature of the reference's chemistry table (README.md:54: mean | sum |
         max of the hidden vectors, 48 numbers for ``--hidden_dims 32 16``) of every graph of ``data`` -- a

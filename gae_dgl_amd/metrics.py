@@ -305,3 +305,85 @@ def clustering_metrics(pred, true):
     from scipy.optimize import linear_sum_assignment
     rows, cols = linear_sum_assignment(-table)
     return {"nmi": float(nmi), "ari": float(ari), "acc": float(table[rows, cols].sum()) / n, "n": n}
+
+
+KNN_DISTANCE_EPS = 1e-12
+
+
+def knn_predict(index, value, y, *, task="regression", weights="uniform", n_classes=None):
+    """The kNN regressor / classifier over neighbour lists: ``index`` [m, k] (rows of the database, -1 = padding) and
+    ``value`` [m, k] as ``ops.knn`` returns them, ``y`` [n] the targets of the database rows.  Torch on the device of
+    ``index``; no m x n matrix.
+    ``task="regression"``: fp64 [m], the mean of the neighbours' targets, or under ``weights="distance"`` their mean
+    weighted by 1 / (sqrt(value) + 1e-12) (``value`` = the squared distances of metric "l2"); a NaN target does not
+    vote; a row with no voter is NaN.
+    ``task="classification"``: int64 [m], the class with the most (or, weighted, the heaviest) votes among the
+    neighbours' labels in [0, n_classes) (default: max label + 1), ties to the LOWER class; a neighbour whose label is
+    -1 (unlabelled) does not vote; a row with no voter is -1.
+    With the lists of a self-search (``ops.knn(Z, k=k)``: every row left out of its own list) this is the
+    leave-one-out prediction."""
+    if task not in ("regression", "classification"):
+        raise ValueError(f"task: 'regression' or 'classification', not {task!r}")
+    if weights not in ("uniform", "distance"):
+        raise ValueError(f"weights: 'uniform' or 'distance', not {weights!r}")
+    index = torch.as_tensor(index)
+    dev = index.device
+    value = torch.as_tensor(value).to(dev)
+    y = torch.as_tensor(y).to(dev).reshape(-1)
+    if index.dim() != 2 or value.shape != index.shape:
+        raise ValueError(f"knn_predict: index {tuple(index.shape)} and value {tuple(value.shape)} must be equal [m, k]")
+    idx = index.long()
+    if idx.numel() and int(idx.max()) >= y.numel():
+        raise ValueError(f"knn_predict: a neighbour index {int(idx.max())} beyond the {y.numel()} targets")
+    votes = idx >= 0
+    if y.numel() == 0:
+        y = torch.zeros(1, dtype=y.dtype, device=dev)          # every entry is padding: nothing is gathered for real
+    got = y[idx.clamp(min=0)]
+    if weights == "distance":
+        w = 1.0 / (value.double().clamp(min=0.0).sqrt() + KNN_DISTANCE_EPS)
+    else:
+        w = torch.ones(idx.shape, dtype=torch.float64, device=dev)
+    if task == "regression":
+        got = got.double()
+        votes = votes & ~torch.isnan(got)
+        w = torch.where(votes, w, torch.zeros_like(w))
+        total = w.sum(1)
+        pred = (w * torch.where(votes, got, torch.zeros_like(got))).sum(1) / total
+        return torch.where(total > 0, pred, torch.full_like(pred, float("nan")))
+    if got.is_floating_point():
+        raise ValueError("knn_predict: classification takes integer labels")
+    got = got.long()
+    votes = votes & (got >= 0)
+    C = int(n_classes) if n_classes is not None else (int(y.max()) + 1 if y.numel() else 0)
+    C = max(C, 1)
+    if bool((got[votes] >= C).any()):
+        raise ValueError(f"knn_predict: a label beyond n_classes = {C}")
+    w = torch.where(votes, w, torch.zeros_like(w))
+    score = torch.zeros(idx.shape[0], C, dtype=torch.float64, device=dev)
+    score.scatter_add_(1, torch.where(votes, got, torch.zeros_like(got)), w)
+    best = score.max(1, keepdim=True).values
+    classes = torch.arange(C, device=dev).expand_as(score)
+    pred = torch.where(score == best, classes, torch.full_like(classes, C)).min(1).values     # ties: the lower class
+    return torch.where(votes.any(1), pred, torch.full_like(pred, -1))
+
+
+def regression_metrics(pred, y):
+    """``rmse``, ``mae``, ``r2`` (1 - SSE / SST about the mean of the scored targets; NaN when they are constant) and ``n``
+    of predictions ``pred`` [m] against targets ``y`` [m], as the reference's chemistry table reports them (README.md:
+    "GAE + Ridge / MLP / Random Forest").  Rows whose prediction or target is NaN (``knn_predict``: no voter) are left
+    out and counted in ``left_out``.  Torch on the device of ``pred``, fp64; Python numbers out."""
+    pred = torch.as_tensor(pred).double().reshape(-1)
+    y = torch.as_tensor(y).to(pred.device).double().reshape(-1)
+    if pred.shape != y.shape:
+        raise ValueError(f"regression_metrics: {pred.numel()} predictions for {y.numel()} targets")
+    keep = ~(torch.isnan(pred) | torch.isnan(y))
+    n = int(keep.sum())
+    nan = float("nan")
+    if n == 0:
+        return {"rmse": nan, "mae": nan, "r2": nan, "n": 0, "left_out": int(pred.numel())}
+    p, t = pred[keep], y[keep]
+    err = p - t
+    sse = float((err * err).sum())
+    sst = float(((t - t.mean()) ** 2).sum())
+    return {"rmse": (sse / n) ** 0.5, "mae": float(err.abs().mean()), "r2": 1.0 - sse / sst if sst > 0 else nan, "n": n,
+            "left_out": int(pred.numel()) - n}

@@ -6,7 +6,7 @@ epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
 
   python -m gae_dgl_amd.train_transductive --dataset cora [--norm both] [--eval [--rank]] [--topk 10 [--topk_out top.npz]]
       [--loss_samples M] [--decode_out graph.npz [--decode_prob P] [--decode_max_pairs M]]
-      [--cluster K [--cluster_seed S] [--cluster_out clusters.npz]]
+      [--cluster K [--cluster_seed S] [--cluster_out clusters.npz]] [--knn K [--knn_metric l2|dot|cosine]]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -76,6 +76,12 @@ def build_parser():
                     help="with --cluster: the seed of the k-means++ seeding (default 0)")
     ap.add_argument("--cluster_out", default=None, metavar="PATH",
                     help="with --cluster: write PATH (.npz with 'labels' int32 [n] and 'centers' fp32 [K, d])")
+    ap.add_argument("--knn", type=int, default=None, metavar="K",
+                    help="after training, the leave-one-out kNN accuracy of the node embedding against the class labels: "
+                         "every labelled node takes the plurality class of its K (1..64) nearest "
+                         "neighbours (GAE.nearest_nodes, on the device); unlabelled nodes neither vote nor are scored")
+    ap.add_argument("--knn_metric", choices=["l2", "dot", "cosine"], default=None,
+                    help="with --knn: squared Euclidean distance (default), inner product or cosine similarity")
     return ap
 
 
@@ -107,6 +113,11 @@ def parse_args(argv=None):
             ap.error("--cluster_seed / --cluster_out need --cluster K")
     elif not 1 <= args.cluster <= 256:
         ap.error(f"--cluster {args.cluster}: K must lie in 1..256")
+    if args.knn is None:
+        if args.knn_metric is not None:
+            ap.error("--knn_metric needs --knn K")
+    elif not 1 <= args.knn <= 64:
+        ap.error(f"--knn {args.knn}: K must lie in 1..64")
     return args
 
 
@@ -225,6 +236,21 @@ def main(argv=None):
             main.last_cluster.update(cm)
         if args.cluster_out is not None:
             np.savez(args.cluster_out, labels=res.labels.cpu().numpy(), centers=res.centers.cpu().numpy())
+    if args.knn is not None:
+        main.last_knn = None
+        if data.labels is None:
+            print(f"kNN K = {args.knn}: the dataset carries no class labels, nothing to score")
+        else:
+            g.ndata['h'] = features
+            nn = model.nearest_nodes(g, args.knn, metric=args.knn_metric or "l2")
+            labels = torch.as_tensor(data.labels, dtype=torch.int64, device=device)
+            pred = metrics.knn_predict(nn.index, nn.value, labels, task="classification")
+            scored = (labels >= 0) & (pred >= 0)
+            acc = float((pred[scored] == labels[scored]).double().mean()) if bool(scored.any()) else float("nan")
+            print(f"kNN K = {args.knn} ({args.knn_metric or 'l2'}, leave-one-out) accuracy: {acc:.4f} | "
+                  f"nodes scored: {int(scored.sum())} of {n_nodes}")
+            main.last_knn = {"acc": acc, "n": int(scored.sum()), "result": nn, "pred": pred, "model": model, "graph": g,
+                             "features": features}
     return [float(l) for l in losses]
 
 

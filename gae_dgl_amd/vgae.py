@@ -146,6 +146,17 @@ class VGAE(nn.Module):
                 g.ndata['h'] = feat
         return ops.kmeans(mu, k, **kw)
 
+    def nearest_nodes(self, g, k, *, metric="l2"):
+        """GAE.nearest_nodes on the mean embedding mu (no noise): ``ops.KNNResult`` of ops.knn, the node itself left
+        out; mu is read in place where the two heads are packed in one buffer; ``g.ndata['h']`` is restored on exit"""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                mu, _ = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return ops.knn(mu, k=k, metric=metric)
+
     def score_graphs(self, g, *, exclude_self=True):
         """GAE.score_graphs on the mean embedding mu (no noise) of a batched graph ``g``: ``ops.GraphScores`` per member
         graph, mu scored through the no-layer mode of ops.score_graphs (gae.score_embedding)"""

@@ -11,7 +11,8 @@
  * and gae_decoder_bce_sampled, an unbiased stochastic estimate of gae_decoder_bce's loss for graphs beyond the N^2 sum,
  * and gae_decoder_rank, the filtered rank of given pairs among all candidates of gae_decoder_topk's rule,
  * and gae_score_graphs, the per-molecule reconstruction scores (AUC counts, average precision, loss) of a resident set,
- * and gae_kmeans_*, node clustering on the device: k-means++ seeding, Lloyd iterations and assignment over an embedding.
+ * and gae_kmeans_*, node clustering on the device: k-means++ seeding, Lloyd iterations and assignment over an embedding,
+ * and gae_knn, the exact k nearest rows of one embedding for every row of another.
  * Same conventions as gae_hip.h: caller-owned buffers, 0 / negative / hipError_t return codes, asynchronous launches on
  * the stream passed last.  These signatures may change between versions without a GAE_VERSION major bump. */
 #ifndef GAE_HIP_EXPERIMENTAL_H
@@ -610,6 +611,48 @@ int gae_kmeans_step(const float *X, int64_t ldx, int64_t n, int64_t d, float *C,
 
 int gae_kmeans_init_pp(const float *X, int64_t ldx, int64_t n, int64_t d, int64_t k, uint64_t seed, float *C_out,
                        int32_t *chosen_out, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- K24: exact k-nearest-neighbour search over embeddings (ops.knn, GAE.nearest_nodes, GAE.nearest_graphs)
+ * For every query row q_i of Q fp32 [m, d] (rows ldq floats apart) the k rows x_j of the database X fp32 [n, d] (ldx)
+ * that are nearest to it, without the m x n matrix.  No alignment is asked of ldq / ldx / ldo.
+ * METRICS  GAE_KNN_L2: squared Euclidean distance, smallest first.  GAE_KNN_DOT: inner product, largest first.  Cosine is
+ *   not a kernel metric: the caller divides the rows by their norms and asks for GAE_KNN_DOT (ops.knn does).
+ * CANDIDATES of query i: every database row j in [0, n) whose key (below) is neither NaN nor +-inf, minus j = i under
+ *   GAE_KNN_EXCLUDE_SAME_INDEX (for Q = X: a row is not its own neighbour).
+ * PRODUCTS  p_ij = q_i . x_j is the fp32 chain of csrc/decoder_pairs.h: v_mfma_f32_32x32x2_f32 (bitwise a k-ordered fmaf
+ *   chain from 0.f) in K16's fixed feature order, the same lane width and chunk choice per d, chunks ascending.  With
+ *   Q = X = Z it has the bits of gae_decoder_topk's s_ij.  It does not depend on tile position, split or schedule.
+ * SELECTION KEY  DOT: key = p_ij.  L2: key = p_ij - h_j, h_j = (fmaf chain of x_jf^2, f ascending from 0.f) / 2, computed
+ *   once per call into the workspace by a small first launch (|q - x|^2 / 2 = |q|^2 / 2 - key: the same order for one
+ *   query).  The k candidates with the LARGEST key are chosen; equal keys go to the lower j.
+ * REPORTED VALUE  DOT: the key.  L2: sum_f (q_if - x_jf)^2 taken directly -- an fmaf chain in ascending f from 0.f, as
+ *   gae_kmeans_assign's dist2: no cancellation of the expanded form reaches the output.
+ * ORDER OF A ROW  DOT: (value descending, j ascending).  L2: (reported value ascending, j ascending): the k chosen
+ *   entries are re-sorted by the direct distance, so the distances of a row are monotone.  Fewer than k candidates pad
+ *   the row's tail with index -1 and value +inf (L2) or -inf (DOT).
+ * DETERMINISM  No float atomics, ordinary launches only.  The result is a function of the values of Q and X and of
+ *   (m, n, d, k, metric, flags) alone: the same bits run to run, for any ldq / ldx / ldo and any `splits`.
+ *   index_out    int32 [m, ldo >= k]: database rows;  value_out fp32 [m, ldo >= k]
+ *   splits       column splits per group of query panels: 0 = auto, else 1 .. 16.  An argument, not a tuning knob
+ *   workspace    device memory of at least gae_knn_workspace_bytes(m, n, d, k, splits) bytes: a pure host function,
+ *                positive, non-decreasing in m, n, k and splits (1 .. 16); a negative error code for a shape error.
+ *                O(n + m k splits) bytes, never O(m n)
+ *   stream       a hipStream_t, passed as void * like everywhere in this library
+ * 1 <= d <= 256, 1 <= k <= 64 (else GAE_E_RANGE); 0 <= m, n < 2^31 (else GAE_E_SIZE).  m = 0 and n = 0 are valid: with
+ * n = 0 every row is padding.  There is no fallback for other shapes.
+ * Argument errors are returned before anything is dereferenced or launched (no GPU is needed to see them): the shape
+ * errors above, splits outside 0..16, an unknown metric or flag bit (GAE_E_RANGE), ldq < d, ldx < d, ldo < k
+ * (GAE_E_SIZE), NULL index_out / value_out / Q (m > 0), NULL X (m, n > 0), NULL workspace (GAE_E_NULL), a short
+ * workspace (GAE_E_WORKSPACE).
+ * Launches: h (L2), the sweep, the merge of the splits' lists (splits > 1), the direct distances and re-sort (L2). */
+enum { GAE_KNN_L2 = 0, GAE_KNN_DOT = 1 };
+enum { GAE_KNN_EXCLUDE_SAME_INDEX = 1 };
+
+int64_t gae_knn_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int splits);
+
+int gae_knn(const float *Q, int64_t ldq, int64_t m, const float *X, int64_t ldx, int64_t n, int64_t d, int64_t k,
+            int metric, int flags, int splits, int32_t *index_out, float *value_out, int64_t ldo,
+            void *workspace, int64_t workspace_bytes, void *stream);
 
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
