@@ -62,6 +62,27 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
         }                                                                            \
     } while (0)
 
+inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// a launch of Kernel(args...) with `lds` bytes of dynamic LDS, reported as `what`; above the 48 KB every kernel may have,
+// the attribute is raised once per (kernel instantiation, device), and again when a launch needs more
+template <auto Kernel, class... Args>
+int launch_lds(const char *what, int64_t blocks, int threads, size_t lds, hipStream_t st, const Args &...args)
+{
+    static int configured[16] = {0};
+    int dev = 0;
+    GAE_HIP(hipGetDevice(&dev));
+    if (lds > 48 * 1024 && (dev < 0 || dev >= 16 || configured[dev] < int(lds))) {
+        GAE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    int(lds)));
+        if (dev >= 0 && dev < 16) configured[dev] = int(lds);
+    }
+    hipLaunchKernelGGL(Kernel, dim3(unsigned(blocks)), dim3(threads), lds, st, args...);
+    GAE_CHECK_LAUNCH(what);
+    return GAE_OK;
+}
+
 constexpr int kWave = 64;  // gfx950 wavefront
 constexpr int kNumXcd = 8; // MI355X: 8 XCDs, private L2 each; block b runs on XCD b % 8
 

@@ -13,7 +13,8 @@
 // Counting.  Each lane keeps three int32 counts of its (query, lane half): scores above t, scores at or above t, valid
 // scores.  A tile that lies inside the lane's window, holds neither i (when self is excluded) nor j, and whose 16
 // scores add up to something above -inf (no NaN, no -inf among them) takes the fast path: two compares and two adds
-// per score plus the sum.  Every other tile takes the masked path (window, self, target, validity per column).
+// per score plus the sum.  Every other tile takes the masked path (window, self, target, validity per column).  The
+// rule is LaneTile of decoder_pairs.h, shared with K22.
 //
 // Known edges.  The sweep counts them like any column; a second sweep takes them out again.  The CSR rows of the
 // panel's 32 sources are laid end to end, 32 entries per tile: the A operand gathers those columns, the same MFMA
@@ -29,7 +30,8 @@
 // Measured (tools/rank_bench.py, profiles/r09_decoder_rank.json; d = 16, m = n, a 5-regular graph excluded): 0.25 ms at
 // n = 19 717 and 19.2 ms at n = 200 000 (66 Tflop/s of fp32 MFMA, 42 % of peak) -- 0.27 x and 0.52 x the time of
 // gae_decoder_topk(k = 10) on the same Z.  What buys that: operand loads without branches (row and feature clamped, two
-// 16-byte loads per tile at d = 16) and the next tile's loads issued before the current tile is counted.  118 VGPRs at
+// 16-byte loads per tile at d = 16) and the next tile's loads issued before the current tile is counted (load_feats and
+// sweep_tiles of decoder_pairs.h, shared with K22).  118 VGPRs at
 // d <= 16 (4 waves per SIMD), accumulators in VGPRs (-amdgpu-mfma-vgpr-form, _build.py): the epilogue reads each one.
 #include "decoder_pairs.h"
 
@@ -86,40 +88,12 @@ __global__ __launch_bounds__(64) void rank_kernel(const RankArgs a)
     pb = __builtin_amdgcn_readfirstlane(pb);       // the same in every lane: scalar loop control
     pe = __builtin_amdgcn_readfirstlane(pe);
 
-    // ---- operand loads: the DH features feat0 + s of one row of Z per lane.  The caller clamps the row into
-    // [0, n) (the host launches nothing when n = 0) and the feature index is clamped here, so no load carries a branch.
-    // A feature past d is zeroed: it would enter every product.  A clamped ROW is not: row c of the A operand reaches
-    // only the scores of column c, row r of the B operand only those of query r, and neither is counted.
-    const bool full = a.d == a.nch * 2 * DH;       // no feature tail: the common d = 16, 32, 64, 128, 256
-    auto load_feats = [&](float (&z)[DH], int64_t row, int ch) {
-        const float *p = a.Z + row * a.ldz;
-        const int f0 = feat0<DH>(ch, h);
-        if (full) {
-#pragma unroll
-            for (int s = 0; s < DH; ++s) z[s] = p[f0 + s];
-        } else {
-#pragma unroll
-            for (int s = 0; s < DH; ++s) {
-                const int f = f0 + s;
-                const float v = p[f < a.d ? f : a.d - 1];
-                z[s] = f < a.d ? v : 0.f;
-            }
-        }
-    };
-    // the panel rows (B operand) stay in registers when one chunk holds all of d
+    // ---- operands (decoder_pairs.h): the panel rows (B operand) stay in registers when one chunk holds all of d
+    const bool full = no_tail<DH>(a);
     float zr[DH];
-    if constexpr (ONE) load_feats(zr, i, 0);
+    if constexpr (ONE) load_feats(zr, a.Z, a.ldz, i, 0, h, a.d, full);
     // one tile: rows of Z picked by `row` (in [0, n)) against the panel
-    auto tile = [&](int64_t row) {
-        v16f acc = zero_acc();
-        for (int ch = 0; ch < (ONE ? 1 : a.nch); ++ch) {
-            if constexpr (!ONE) load_feats(zr, i, ch);
-            float za[DH];
-            load_feats(za, row, ch);
-            acc = mma<DH>(acc, za, zr);
-        }
-        return acc;
-    };
+    auto tile = [&](int64_t row) { return tile_product<DH, ONE>(a, zr, i, row, h, full); };
 
     // ---- the threshold: the diagonal of (gathered dst rows) x (panel), row `col` against column `col` of this tile
     float t;
@@ -135,18 +109,12 @@ __global__ __launch_bounds__(64) void rank_kernel(const RankArgs a)
 
     int gt = 0, ge = 0, valid = 0;
     const int xs = a.excl_self ? i : -1;           // the column left out as "self" (-1: none)
-    // counts of one tile at c0; everything relative to c0, so no column index leaves int32 (n may reach 2^31 - 1)
-    auto count = [&](const v16f &acc, int c0) {
-        const int lo_r = lo > c0 ? lo - c0 : 0, hi_r = hi - c0 < kTile ? hi - c0 : kTile;
-        if (lo_r >= hi_r) return;                  // nothing of this lane's window in the tile
-        const int j_r = j >= c0 ? j - c0 : -1, x_r = xs >= c0 ? xs - c0 : -1;     // >= 32: not in the tile
-        float sum = acc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) sum += acc[r];
-        const bool clean = lo_r == 0 && hi_r == kTile && unsigned(j_r) >= unsigned(kTile) &&
-                           unsigned(x_r) >= unsigned(kTile);
-        if (clean && sum > -INFINITY) {
-            // ---- fast path: 16 valid scores of candidates (a NaN or a -inf among them makes the sum NaN or -inf)
+    // counts of one tile at c0: the target is left out like self (LaneTile, decoder_pairs.h)
+    sweep_tiles<DH, ONE>(a, zr, i, col, h, full, pb, pe, [&](const v16f &acc, int c0) {
+        const LaneTile w(lo, hi, c0);
+        if (w.empty()) return;
+        const int j_r = tile_rel(j, c0), x_r = tile_rel(xs, c0);
+        if (w.all_candidates(acc, j_r, x_r)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 gt += acc[r] > t ? 1 : 0;
@@ -156,32 +124,13 @@ __global__ __launch_bounds__(64) void rank_kernel(const RankArgs a)
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = tile_col(0, r, h);
-                const bool cand = c >= lo_r && c < hi_r && c != j_r && c != x_r && acc[r] > -INFINITY;
+                const bool cand = w.candidate(tile_col(0, r, h), acc[r], j_r, x_r);
                 gt += (cand && acc[r] > t) ? 1 : 0;
                 ge += (cand && acc[r] >= t) ? 1 : 0;
                 valid += cand ? 1 : 0;
             }
         }
-    };
-    if constexpr (ONE) {
-        // the next tile's A operand is in flight while this tile is multiplied and counted
-        float za[DH];
-        const int64_t last = int64_t(pe) - 1;      // a column past the part is clamped into it
-        if (pb < pe) load_feats(za, int64_t(pb) + col < last ? int64_t(pb) + col : last, 0);
-        for (int64_t c0 = pb; c0 < pe; c0 += kTile) {
-            const v16f acc = mma<DH>(zero_acc(), za, zr);
-            const int64_t jn = c0 + kTile + col;
-            if (c0 + kTile < pe) load_feats(za, jn < last ? jn : last, 0);
-            count(acc, int(c0));
-        }
-    } else {
-        for (int64_t c0 = pb; c0 < pe; c0 += kTile) {
-            const int64_t jc = c0 + col;           // this lane's A-operand column
-            const v16f acc = tile(jc < pe ? jc : int64_t(pe) - 1);
-            count(acc, int(c0));
-        }
-    }
+    });
 
     // ---- known edges: take the distinct neighbours the sweep counted out again
     if (a.indptr) {
@@ -317,7 +266,9 @@ extern "C" int gae_decoder_rank(const float *Z, int64_t ldz, int64_t n, int64_t 
         GAE_CHECK_LAUNCH("rank_combine_kernel");
         return GAE_OK;
     }
-    GAE_PAIRS_LAUNCH(rank_kernel, d, dim3(unsigned(panels * S)), dim3(64), 0, st, a);
+    dispatch(d, [&](auto dh, auto one) {
+        hipLaunchKernelGGL((rank_kernel<dh, one>), dim3(unsigned(panels * S)), dim3(64), 0, st, a);
+    });
     GAE_CHECK_LAUNCH("rank_kernel");
     if (S > 1) {
         hipLaunchKernelGGL(rank_combine_kernel, dim3(unsigned((m + 255) / 256)), dim3(256), 0, st, a);

@@ -20,12 +20,12 @@
 //
 // passing().  A tile that lies inside the lane's window, does not hold the row itself (when self is excluded) and whose
 // 16 scores add up to something above -inf (no NaN, no -inf among them) takes one compare per score; every other tile
-// the masked form.  Only the columns that passed are looked up in the CSR row (row_holds), so a sparse decode pays
-// almost nothing for GAE_TOPK_EXCLUDE_EDGES.
+// the masked form (LaneTile of decoder_pairs.h, K18's rule with one excluded column).  Only the columns that passed are
+// looked up in the CSR row (row_holds), so a sparse decode pays almost nothing for GAE_TOPK_EXCLUDE_EDGES.
 //
-// Operand loads as in decoder_rank.hip: row and feature clamped, tail features zeroed, the next tile's loads in flight
-// while the current tile is multiplied and compacted.  Accumulators in VGPRs (-amdgpu-mfma-vgpr-form, _build.py): the
-// epilogue reads each one.
+// Operand loads and the sweep are K18's (load_feats and sweep_tiles of decoder_pairs.h): row and feature clamped, tail
+// features zeroed, the next tile's loads in flight while the current tile is multiplied and compacted.  Accumulators in
+// VGPRs (-amdgpu-mfma-vgpr-form, _build.py): the epilogue reads each one.
 //
 // Measured (tools/decode_bench.py, profiles/r12_decoder_threshold.json; d = 16, one pair in a thousand listed, the whole
 // call with its host sync): 0.51 ms at n = 19 717 (count 0.20, fill 0.27) and 43.4 ms at n = 200 000 for 4.2e7 pairs
@@ -73,49 +73,27 @@ __device__ __forceinline__ void sweep(const ThresholdArgs &a)
     pb = __builtin_amdgcn_readfirstlane(pb);       // the same in every lane: scalar loop control
     pe = __builtin_amdgcn_readfirstlane(pe);
 
-    // ---- operand loads (decoder_rank.hip): the DH features feat0 + s of one row of Z per lane, the row clamped into
-    // [0, n) by the caller, the feature index here; a feature past d is zeroed, a clamped row reaches no listed score
-    const bool full = a.d == a.nch * 2 * DH;       // no feature tail
-    auto load_feats = [&](float (&z)[DH], int64_t r, int ch) {
-        const float *p = a.Z + r * a.ldz;
-        const int f0 = feat0<DH>(ch, h);
-        if (full) {
-#pragma unroll
-            for (int s = 0; s < DH; ++s) z[s] = p[f0 + s];
-        } else {
-#pragma unroll
-            for (int s = 0; s < DH; ++s) {
-                const int f = f0 + s;
-                const float v = p[f < a.d ? f : a.d - 1];
-                z[s] = f < a.d ? v : 0.f;
-            }
-        }
-    };
-    float zr[DH];                                  // the panel rows (B operand) stay in registers with one chunk
-    if constexpr (ONE) load_feats(zr, i, 0);
+    // ---- operands (decoder_pairs.h): the panel rows (B operand) stay in registers with one chunk
+    const bool full = no_tail<DH>(a);
+    float zr[DH];
+    if constexpr (ONE) load_feats(zr, a.Z, a.ldz, i, 0, h, a.d, full);
 
     const float thr = a.threshold;
     const int xs = a.excl_self && row_in ? i : -1; // the column left out as "self" (-1: none)
-    // the bits of the tile's columns (bit c: column c0 + c) among this lane's 16 that are listed; relative to c0, so no
-    // column index leaves int32
+    // the bits of the tile's columns (bit c: column c0 + c) among this lane's 16 that are listed (LaneTile,
+    // decoder_pairs.h)
     auto passing = [&](const v16f &acc, int c0) -> unsigned {
-        const int lo_r = lo > c0 ? lo - c0 : 0, hi_r = hi - c0 < kTile ? hi - c0 : kTile;
-        if (lo_r >= hi_r) return 0u;               // nothing of this lane's window in the tile
-        const int x_r = xs >= c0 ? xs - c0 : -1;   // >= 32: not in the tile
-        float sum = acc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) sum += acc[r];
-        const bool clean = lo_r == 0 && hi_r == kTile && unsigned(x_r) >= unsigned(kTile);
+        const LaneTile w(lo, hi, c0);
+        if (w.empty()) return 0u;
+        const int x_r = tile_rel(xs, c0);
         unsigned m = 0;                            // bits of lane half 0's columns; moved to this half's below
-        if (clean && sum > -INFINITY) {
-            // ---- fast path: 16 valid scores of candidates (a NaN or a -inf among them makes the sum NaN or -inf)
+        if (w.all_candidates(acc, x_r)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) m |= acc[r] >= thr ? 1u << tile_col(0, r, 0) : 0u;
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = tile_col(0, r, h);
-                const bool ok = c >= lo_r && c < hi_r && c != x_r && acc[r] > -INFINITY && acc[r] >= thr;
+                const bool ok = w.candidate(tile_col(0, r, h), acc[r], x_r) && acc[r] >= thr;
                 m |= ok ? 1u << tile_col(0, r, 0) : 0u;
             }
         }
@@ -132,7 +110,7 @@ __device__ __forceinline__ void sweep(const ThresholdArgs &a)
     int count = 0;
     int64_t base = 0;                              // fill: where the row's next listed pair of this part goes
     if constexpr (FILL) base = row_in ? a.offset[row * a.S + split] : 0;
-    auto emit = [&](const v16f &acc, int c0) {
+    sweep_tiles<DH, ONE>(a, zr, i, col, h, full, pb, pe, [&](const v16f &acc, int c0) {
         const unsigned m = passing(acc, c0);
         if constexpr (FILL) {
             const unsigned both = m | unsigned(__shfl_xor(int(m), 32, 64));      // the row's 32 columns of the tile
@@ -151,33 +129,7 @@ __device__ __forceinline__ void sweep(const ThresholdArgs &a)
         } else {
             count += __popc(m);
         }
-    };
-
-    if constexpr (ONE) {
-        // the next tile's A operand is in flight while this tile is multiplied and compacted
-        float za[DH];
-        const int64_t last = int64_t(pe) - 1;      // a column past the part is clamped into it
-        if (pb < pe) load_feats(za, int64_t(pb) + col < last ? int64_t(pb) + col : last, 0);
-        for (int64_t c0 = pb; c0 < pe; c0 += kTile) {
-            const v16f acc = mma<DH>(zero_acc(), za, zr);
-            const int64_t jn = c0 + kTile + col;
-            if (c0 + kTile < pe) load_feats(za, jn < last ? jn : last, 0);
-            emit(acc, int(c0));
-        }
-    } else {
-        for (int64_t c0 = pb; c0 < pe; c0 += kTile) {
-            const int64_t jc = c0 + col;           // this lane's A-operand column
-            const int64_t ja = jc < pe ? jc : int64_t(pe) - 1;
-            v16f acc = zero_acc();
-            for (int ch = 0; ch < a.nch; ++ch) {
-                float za[DH];
-                load_feats(zr, i, ch);
-                load_feats(za, ja, ch);
-                acc = mma<DH>(acc, za, zr);
-            }
-            emit(acc, int(c0));
-        }
-    }
+    });
 
     if constexpr (!FILL) {
         count += __shfl_down(count, 32, 64);       // the two lane halves of each row; lane half 0 writes
@@ -330,7 +282,9 @@ extern "C" int gae_decoder_threshold_count(const float *Z, int64_t ldz, int64_t 
     a.row_ptr_out = row_ptr_out;
     hipStream_t st = gae::as_stream(stream);
     if (n > 0) {
-        GAE_PAIRS_LAUNCH(threshold_count_kernel, d, dim3(unsigned(L.panels * L.S)), dim3(64), 0, st, a);
+        dispatch(d, [&](auto dh, auto one) {
+            hipLaunchKernelGGL((threshold_count_kernel<dh, one>), dim3(unsigned(L.panels * L.S)), dim3(64), 0, st, a);
+        });
         GAE_CHECK_LAUNCH("threshold_count_kernel");
         hipLaunchKernelGGL(threshold_scan_blocks_kernel, dim3(unsigned(L.nb)), dim3(kScanThreads), 0, st, a);
         GAE_CHECK_LAUNCH("threshold_scan_blocks_kernel");
@@ -364,7 +318,10 @@ extern "C" int gae_decoder_threshold_fill(const float *Z, int64_t ldz, int64_t n
     ThresholdArgs a;
     fill_args(a, r, L, threshold, workspace);
     a.index_out = index_out; a.score_out = score_out; a.capacity = capacity;
-    GAE_PAIRS_LAUNCH(threshold_fill_kernel, d, dim3(unsigned(L.panels * L.S)), dim3(64), 0, gae::as_stream(stream), a);
+    hipStream_t st = gae::as_stream(stream);
+    dispatch(d, [&](auto dh, auto one) {
+        hipLaunchKernelGGL((threshold_fill_kernel<dh, one>), dim3(unsigned(L.panels * L.S)), dim3(64), 0, st, a);
+    });
     GAE_CHECK_LAUNCH("threshold_fill_kernel");
     return GAE_OK;
 }

@@ -2,14 +2,15 @@
 //
 // For every row i the k candidates j with the largest logit s_ij = z_i . z_j (gae_dgl/gae.py:69-72 without dropout and
 // before the sigmoid).  Rows are sorted by (score descending, j ascending).  Who is a candidate, how the columns are
-// split over waves and which bits s_ij has: decoder_pairs.h, shared with K18.
+// split over waves and which bits s_ij has: decoder_pairs.h, shared with K18, K22, K23 and K24.
 //
 // Products.  The panel's rows stay in registers; the tiles of Z are loaded straight from global memory (L2-resident at
 // every size measured), each feature behind its own bounds test.  Every lane's 16 scores belong to ONE row, so the
 // threshold test needs no cross-lane traffic.
 //
-// Selection.  Each lane keeps a running top-k of its (row, lane half) in LDS as a heap with the worst entry at the root.  Per tile the
-// fast path is the max of the lane's 16 scores against the lane's k-th score (about 0.5 VALU op per pair); only lanes
+// Selection (topk_heap.h, shared with K24: offer_tile, merge_halves, merge_kernel).  Each lane keeps a running top-k of
+// its (row, lane half) in LDS as a heap with the worst entry at the root.  Per tile the fast path is the max of the
+// lane's 16 scores against the lane's k-th score (about 0.5 VALU op per pair); only lanes
 // with a passing score store the tile to an LDS scratch row and walk the passing columns: window, self, a 64-bit hash
 // of the CSR row (the row's indices are scanned only on a hash hit; any order, repeats allowed) and the heap insert.
 // One heapsort at the end turns each heap into a list sorted best first.
@@ -98,39 +99,16 @@ __global__ __launch_bounds__(64) void topk_kernel(const TopkArgs a)
             }
             acc = mma<DH>(acc, za, zr);
         }
-        // ---- fast path: one max per score, one compare per tile
-        float m = acc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) m = fmaxf(m, acc[r]);
-        if (m >= thr && lo < hi) {
-            unsigned pass = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                scr[r * 64 + lane] = acc[r];
-                pass |= (acc[r] >= thr ? 1u : 0u) << r;
-            }
-            while (pass) {
-                const int r = __builtin_ctz(pass);
-                pass &= pass - 1;
-                const float s = scr[r * 64 + lane];
+        // ---- selection (offer_tile, topk_heap.h): window and self before the threshold, the CSR row -- scanned on a
+        // hash hit only -- after it
+        offer_tile(
+            acc, lo < hi, scr, ls, lj, lane, k, cnt, thr, thr_j,
+            [&](int r, float) {
                 const int64_t jj = tile_col(int64_t(c0), r, h);
-                if (jj < lo || jj >= hi) continue;
-                const int j = int(jj);
-                if (a.excl_self && j == i) continue;
-                if (cnt == k && !better(s, j, thr, thr_j)) continue;
-                if (((hmask >> hash6(j)) & 1ull) && row_holds(a.indices, e0, e1, j)) continue;     // scanned on a hash hit
-                if (cnt < k) {
-                    heap_push(ls, lj, lane, cnt, s, j);
-                    ++cnt;
-                } else {
-                    heap_replace_root(ls, lj, lane, k, s, j);
-                }
-                if (cnt == k) {
-                    thr = ls[lane];
-                    thr_j = lj[lane];
-                }
-            }
-        }
+                if (jj < lo || jj >= hi) return -1;
+                return a.excl_self && int(jj) == i ? -1 : int(jj);
+            },
+            [&](int j) { return !(((hmask >> hash6(j)) & 1ull) && row_holds(a.indices, e0, e1, j)); });
     }
     // ---- the heap into a list sorted best first: the worst entry goes to the end, k log k steps once
     heap_sort(ls, lj, lane, cnt);
@@ -142,49 +120,10 @@ __global__ __launch_bounds__(64) void topk_kernel(const TopkArgs a)
         float *os = direct ? a.score_out + int64_t(i) * a.ldo : a.part_s + (int64_t(split) * a.n + i) * k;
         int64_t *oj64 = a.index_out + int64_t(i) * a.ldo;
         int32_t *oj32 = a.part_j + (int64_t(split) * a.n + i) * k;
-        int p0 = 0, p1 = 0;
-        for (int t = 0; t < k; ++t) {
-            float s = -INFINITY;
-            int j = -1;
-            const bool h0 = p0 < cnt, h1 = p1 < pcnt;
-            if (h0 || h1) {
-                const float s0 = h0 ? ls[p0 * 64 + lane] : 0.f, s1 = h1 ? ls[p1 * 64 + lane + 32] : 0.f;
-                const int j0 = h0 ? lj[p0 * 64 + lane] : 0, j1 = h1 ? lj[p1 * 64 + lane + 32] : 0;
-                if (h0 && (!h1 || better(s0, j0, s1, j1))) { s = s0; j = j0; ++p0; }
-                else { s = s1; j = j1; ++p1; }
-            }
+        merge_halves(ls, lj, lane, k, cnt, pcnt, [&](int t, float s, int j) {
             os[t] = s;
             if (direct) oj64[t] = j; else oj32[t] = j;
-        }
-    }
-}
-
-// one thread per (row, split, position): the entry's rank among the S lists of its row is its output slot
-__global__ __launch_bounds__(256) void topk_merge_kernel(const TopkArgs a)
-{
-    const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    const int k = a.k, S = a.S;
-    if (t >= int64_t(a.n) * S * k) return;
-    const int q = int(t % k);
-    const int s = int((t / k) % S);
-    const int64_t i = t / (int64_t(k) * S);
-    const int64_t stride = int64_t(a.n) * k;
-    const float *ps = a.part_s + i * k;
-    const int32_t *pj = a.part_j + i * k;
-    float *os = a.score_out + i * a.ldo;
-    int64_t *oj = a.index_out + i * a.ldo;
-    const int j = pj[s * stride + q];
-    if (j >= 0) {
-        const float v = ps[s * stride + q];
-        int rank = q;
-        for (int u = 0; u < S; ++u)
-            if (u != s) rank += rank_in(ps + u * stride, pj + u * stride, k, v, j);
-        if (rank < k) { os[rank] = v; oj[rank] = j; }
-    }
-    if (s == 0) {
-        int total = 0;
-        for (int u = 0; u < S; ++u) total += valid_in(pj + u * stride, k);
-        if (q >= total) { os[q] = -INFINITY; oj[q] = -1; }
+        });
     }
 }
 
@@ -225,11 +164,14 @@ extern "C" int gae_decoder_topk(const float *Z, int64_t ldz, int64_t n, int64_t 
     a.part_j = reinterpret_cast<int32_t *>(a.part_s + (S > 1 ? int64_t(S) * n * k : 0));
     const size_t lds = size_t(2 * k + 16) * 64 * 4;
     hipStream_t st = gae::as_stream(stream);
-    GAE_PAIRS_LAUNCH(topk_kernel, d, dim3(unsigned(panels * S)), dim3(64), lds, st, a);
+    dispatch(d, [&](auto dh, auto one) {
+        hipLaunchKernelGGL((topk_kernel<dh, one>), dim3(unsigned(panels * S)), dim3(64), lds, st, a);
+    });
     GAE_CHECK_LAUNCH("topk_kernel");
     if (S > 1) {
         const int64_t threads = n * S * k;
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(unsigned((threads + 255) / 256)), dim3(256), 0, st, a);
+        const MergeArgs<int64_t> ma{a.part_s, a.part_j, n, a.k, S, score_out, index_out, ldo};
+        hipLaunchKernelGGL(merge_kernel<int64_t>, dim3(unsigned((threads + 255) / 256)), dim3(256), 0, st, ma);
         GAE_CHECK_LAUNCH("topk_merge_kernel");
     }
     return GAE_OK;

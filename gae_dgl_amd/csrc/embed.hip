@@ -477,10 +477,9 @@ extern "C" int gae_embed_graphs(const int64_t *graph_ptr, int64_t n_graphs, int6
     GAE_REQUIRE(blocks < (int64_t(1) << 31), GAE_E_SIZE, "gae_embed_graphs: n_out = %lld is too large", (long long)n_out);
     const size_t lds = size_t(a.wfloats + kWaves * a.wave_floats) * 4;
     hipStream_t st = gae::as_stream(stream);
-    if (feat_dtype == GAE_U8) GAE_GRAPHS_LAUNCH(embed_graphs_kernel<true>, blocks, kWaves * 64, a);
-    else GAE_GRAPHS_LAUNCH(embed_graphs_kernel<false>, blocks, kWaves * 64, a);
-    GAE_CHECK_LAUNCH("embed_graphs_kernel");
-    return GAE_OK;
+    const char *what = "embed_graphs_kernel";
+    if (feat_dtype == GAE_U8) return gae::launch_lds<&embed_graphs_kernel<true>>(what, blocks, kWaves * 64, lds, st, a);
+    return gae::launch_lds<&embed_graphs_kernel<false>>(what, blocks, kWaves * 64, lds, st, a);
 }
 
 extern "C" int gae_score_graphs_usable(int64_t f_in, int64_t n_layers, const int64_t *widths, int64_t max_graph_nodes)
@@ -529,8 +528,7 @@ extern "C" int gae_score_graphs(const int64_t *graph_ptr, int64_t n_graphs, int6
     a.wave_floats = kRows * s_z + t.block_floats + 3 * kRows;
     const size_t lds = size_t(a.wfloats + kWaves * a.wave_floats) * 4;
     hipStream_t st = gae::as_stream(stream);
-    if (feat_dtype == GAE_U8) GAE_GRAPHS_LAUNCH(score_graphs_kernel<true>, blocks, kWaves * 64, a, t);
-    else GAE_GRAPHS_LAUNCH(score_graphs_kernel<false>, blocks, kWaves * 64, a, t);
-    GAE_CHECK_LAUNCH("score_graphs_kernel");
-    return GAE_OK;
+    const char *what = "score_graphs_kernel";
+    if (feat_dtype == GAE_U8) return gae::launch_lds<&score_graphs_kernel<true>>(what, blocks, kWaves * 64, lds, st, a, t);
+    return gae::launch_lds<&score_graphs_kernel<false>>(what, blocks, kWaves * 64, lds, st, a, t);
 }

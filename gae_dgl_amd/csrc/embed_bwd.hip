@@ -596,9 +596,11 @@ extern "C" int gae_embed_graphs_bwd(const int64_t *graph_ptr, int64_t n_graphs, 
     a.S = g.S;
     GAE_REQUIRE(g.blocks < (int64_t(1) << 31), GAE_E_SIZE, "%s: n_out = %lld is too large", fn, (long long)n_out);
     const size_t lds = size_t(a.wfloats + g.nw * a.wave_floats) * 4;
-    if (feat_dtype == GAE_U8) GAE_GRAPHS_LAUNCH(embed_graphs_bwd_kernel<true>, g.blocks, g.nw * 64, a);
-    else GAE_GRAPHS_LAUNCH(embed_graphs_bwd_kernel<false>, g.blocks, g.nw * 64, a);
-    GAE_CHECK_LAUNCH("embed_graphs_bwd_kernel");
+    const char *kn = "embed_graphs_bwd_kernel";
+    if (const int rc = feat_dtype == GAE_U8
+                           ? gae::launch_lds<&embed_graphs_bwd_kernel<true>>(kn, g.blocks, g.nw * 64, lds, st, a)
+                           : gae::launch_lds<&embed_graphs_bwd_kernel<false>>(kn, g.blocks, g.nw * 64, lds, st, a))
+        return rc;
     // ---- second stage: the partials of every wave, added in the library's one order
     for (int l = 0; l < a.L; ++l) {
         if (!a.want[l]) continue;

@@ -320,20 +320,5 @@ inline int check_arrays(const char *fn, const Request &r)
     return GAE_OK;
 }
 
-// a launch of `kernel` on `blocks` blocks of `threads` threads with `lds` bytes of dynamic LDS on the stream `st` (both
-// names of the caller); the attribute is raised once per (kernel, device)
-#define GAE_GRAPHS_LAUNCH(kernel, blocks, threads, ...)                                                                \
-    do {                                                                                                               \
-        static int configured[16] = {0};   /* per (instantiation, device): raised when a launch needs more LDS */      \
-        int dev_ = 0;                                                                                                  \
-        GAE_HIP(hipGetDevice(&dev_));                                                                                  \
-        if (lds > 48 * 1024 && (dev_ < 0 || dev_ >= 16 || configured[dev_] < int(lds))) {                              \
-            GAE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&kernel),                                       \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));                        \
-            if (dev_ >= 0 && dev_ < 16) configured[dev_] = int(lds);                                                   \
-        }                                                                                                              \
-        hipLaunchKernelGGL(kernel, dim3(unsigned(blocks)), dim3(threads), lds, st, __VA_ARGS__);                       \
-    } while (0)
-
 } // namespace walk
 } // namespace gae

@@ -63,8 +63,9 @@ struct Plan {
     int64_t dist2_at, changed_at, psum_at, pcount_at, pinertia_at, shift_at, empty_at, cand_at, need;
 };
 
-inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+using gae::cdiv;
+using gae::launch_lds;
+using gae::up256;
 
 int plan(const char *fn, int64_t n, int64_t d, int64_t k, Plan &p)
 {
@@ -73,7 +74,7 @@ int plan(const char *fn, int64_t n, int64_t d, int64_t k, Plan &p)
     GAE_REQUIRE(n >= 0, GAE_E_SIZE, "%s: negative n = %lld", fn, (long long)n);
     GAE_REQUIRE(n < (int64_t(1) << 31), GAE_E_SIZE, "%s: n = %lld beyond int32 labels", fn, (long long)n);
     GAE_REQUIRE(k <= n, GAE_E_SIZE, "%s: k = %lld centres for n = %lld rows", fn, (long long)k, (long long)n);
-    p.DH = d <= 16 ? 8 : d <= 32 ? 16 : 32;
+    p.DH = dh_of(d);
     p.ktiles = int(cdiv(k, kTile));
     p.panels = cdiv(n, kRows);
     const int64_t ab = cdiv(p.panels, kWaves);
@@ -99,23 +100,6 @@ int plan(const char *fn, int64_t n, int64_t d, int64_t k, Plan &p)
     p.empty_at = up256(p.shift_at + 8 * k);
     p.cand_at = up256(p.empty_at + 4 * k);
     p.need = up256(p.cand_at + 2 * int64_t(sizeof(Cand)) * smax);
-    return GAE_OK;
-}
-
-// a launch with `lds` bytes of dynamic LDS; the attribute is raised once per (kernel, device)
-template <auto Kernel, class Args>
-int launch_lds(const char *what, int64_t blocks, int threads, size_t lds, hipStream_t st, const Args &a)
-{
-    static int configured[16] = {0};
-    int dev = 0;
-    GAE_HIP(hipGetDevice(&dev));
-    if (lds > 48 * 1024 && (dev < 0 || dev >= 16 || configured[dev] < int(lds))) {
-        GAE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    int(lds)));
-        if (dev >= 0 && dev < 16) configured[dev] = int(lds);
-    }
-    hipLaunchKernelGGL(Kernel, dim3(unsigned(blocks)), dim3(threads), lds, st, a);
-    GAE_CHECK_LAUNCH(what);
     return GAE_OK;
 }
 
@@ -209,9 +193,10 @@ __global__ __launch_bounds__(kThreads) void kmeans_assign_kernel(const AssignArg
 
 int launch_assign(const Plan &p, const AssignArgs &a, hipStream_t st)
 {
-    if (p.DH == 8) return launch_lds<&kmeans_assign_kernel<8>>("kmeans_assign_kernel", p.assign_blocks, kThreads, p.assign_lds, st, a);
-    if (p.DH == 16) return launch_lds<&kmeans_assign_kernel<16>>("kmeans_assign_kernel", p.assign_blocks, kThreads, p.assign_lds, st, a);
-    return launch_lds<&kmeans_assign_kernel<32>>("kmeans_assign_kernel", p.assign_blocks, kThreads, p.assign_lds, st, a);
+    return dispatch(a.d, [&](auto dh, auto) {          // d <= 64: always one chunk
+        return launch_lds<&kmeans_assign_kernel<dh>>("kmeans_assign_kernel", p.assign_blocks, kThreads, p.assign_lds, st,
+                                                     a);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------- sums

@@ -12,11 +12,11 @@
 //           stages every (tile, chunk) ONCE in LDS for its NW waves, h beside it: two buffers, the global loads of the
 //           next one issued before the products of the current one, one barrier per (tile, chunk).  key = p - h_j (DOT:
 //           h = 0, the product itself).  Every lane's 16 keys belong to one query: the lane keeps its top k in an LDS
-//           heap with the worst entry at the root (topk_heap.h, K16's), one max and one compare per tile on the fast
-//           path.  NaN, -inf and +inf never enter.  The two lane halves of a query merge their sorted lists; with one
-//           split that is the query's list, else it goes to the workspace.
-//   merge   S > 1: the S sorted lists of each query are merged by rank (K16's scheme): the order is total, so the
-//           result does not depend on S.
+//           heap with the worst entry at the root (offer_tile of topk_heap.h, K16's), one max and one compare per tile
+//           on the fast path.  NaN, -inf and +inf never enter.  The two lane halves of a query merge their sorted lists
+//           (merge_halves); with one split that is the query's list, else it goes to the workspace.
+//   merge   S > 1: the S sorted lists of each query are merged by rank (merge_kernel of topk_heap.h, K16's): the order
+//           is total, so the result does not depend on S.
 //   finish  L2 only: per query the direct distance sum_f (q_f - x_jf)^2 of the k chosen rows (fmaf chain, f ascending
 //           from 0.f) replaces the key, and the row is re-sorted by (distance ascending, j ascending) with a rank count
 //           inside a lane group; padding (j = -1) gets +inf.
@@ -50,9 +50,8 @@ struct KnnArgs {
     int32_t *part_j;
 };
 
-inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline int dh_of(int64_t d) { return d <= 16 ? 8 : d <= 32 ? 16 : 32; }
+using gae::cdiv;
+using gae::up256;
 
 inline int64_t sweep_lds(int nw, int64_t d, int64_t k)
 {
@@ -196,38 +195,12 @@ __global__ __launch_bounds__(64 * NW) void knn_kernel(const KnnArgs a)
             float key[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) key[r] = acc[r] - hp[tile_col(0, r, h)];
-            // ---- fast path: one max per key, one compare per tile
-            float mx = key[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, key[r]);
-            if (mx >= thr && row_ok) {
-                unsigned pass = 0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    scr[r * 64 + lane] = key[r];
-                    pass |= (key[r] >= thr ? 1u : 0u) << r;
-                }
-                while (pass) {
-                    const int r = __builtin_ctz(pass);
-                    pass &= pass - 1;
-                    const float s = scr[r * 64 + lane];
-                    const int64_t jj = tile_col(c0, r, h);
-                    if (jj >= pe || !(s <= FLT_MAX)) continue;         // past the part; +inf is no candidate
-                    const int j = int(jj);
-                    if (a.excl_same && j == i) continue;
-                    if (cnt == k && !better(s, j, thr, thr_j)) continue;
-                    if (cnt < k) {
-                        heap_push(ls, lj, lane, cnt, s, j);
-                        ++cnt;
-                    } else {
-                        heap_replace_root(ls, lj, lane, k, s, j);
-                    }
-                    if (cnt == k) {
-                        thr = ls[lane];
-                        thr_j = lj[lane];
-                    }
-                }
-            }
+            // ---- selection (offer_tile, topk_heap.h): past the part, +inf (no candidate) and the same index
+            offer_tile(key, row_ok, scr, ls, lj, lane, k, cnt, thr, thr_j, [&](int r, float s) {
+                const int64_t jj = tile_col(c0, r, h);
+                if (jj >= pe || !(s <= FLT_MAX)) return -1;
+                return a.excl_same && int(jj) == i ? -1 : int(jj);
+            });
         }
         if (it + 1 < nit) stash(it + 1);               // the buffer step it - 1 read; every wave is past that barrier
         __syncthreads();
@@ -240,50 +213,7 @@ __global__ __launch_bounds__(64 * NW) void knn_kernel(const KnnArgs a)
         const bool direct = a.S == 1;
         float *os = direct ? a.value_out + i64 * a.ldo : a.part_s + (int64_t(split) * a.m + i64) * k;
         int32_t *oj = direct ? a.index_out + i64 * a.ldo : a.part_j + (int64_t(split) * a.m + i64) * k;
-        int p0 = 0, p1 = 0;
-        for (int t = 0; t < k; ++t) {
-            float s = -INFINITY;
-            int j = -1;
-            const bool h0 = p0 < cnt, h1 = p1 < pcnt;
-            if (h0 || h1) {
-                const float s0 = h0 ? ls[p0 * 64 + lane] : 0.f, s1 = h1 ? ls[p1 * 64 + lane + 32] : 0.f;
-                const int j0 = h0 ? lj[p0 * 64 + lane] : 0, j1 = h1 ? lj[p1 * 64 + lane + 32] : 0;
-                if (h0 && (!h1 || better(s0, j0, s1, j1))) { s = s0; j = j0; ++p0; }
-                else { s = s1; j = j1; ++p1; }
-            }
-            os[t] = s;
-            oj[t] = j;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------ merge
-// one thread per (query, split, position): the entry's rank among the S lists of its query is its output slot
-__global__ __launch_bounds__(256) void knn_merge_kernel(const KnnArgs a)
-{
-    const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    const int k = a.k, S = a.S;
-    if (t >= int64_t(a.m) * S * k) return;
-    const int q = int(t % k);
-    const int s = int((t / k) % S);
-    const int64_t i = t / (int64_t(k) * S);
-    const int64_t stride = int64_t(a.m) * k;
-    const float *ps = a.part_s + i * k;
-    const int32_t *pj = a.part_j + i * k;
-    float *os = a.value_out + i * a.ldo;
-    int32_t *oj = a.index_out + i * a.ldo;
-    const int j = pj[s * stride + q];
-    if (j >= 0) {
-        const float v = ps[s * stride + q];
-        int rank = q;
-        for (int u = 0; u < S; ++u)
-            if (u != s) rank += rank_in(ps + u * stride, pj + u * stride, k, v, j);
-        if (rank < k) { os[rank] = v; oj[rank] = j; }
-    }
-    if (s == 0) {
-        int total = 0;
-        for (int u = 0; u < S; ++u) total += valid_in(pj + u * stride, k);
-        if (q >= total) { os[q] = -INFINITY; oj[q] = -1; }
+        merge_halves(ls, lj, lane, k, cnt, pcnt, [&](int t, float s, int j) { os[t] = s; oj[t] = j; });
     }
 }
 
@@ -323,30 +253,12 @@ __global__ __launch_bounds__(256) void knn_finish_kernel(const KnnArgs a, int G)
     }
 }
 
-template <auto Kernel>
-int launch_sweep(int64_t blocks, int threads, size_t lds, hipStream_t st, const KnnArgs &a)
-{
-    static int configured[16] = {0};
-    int dev = 0;
-    GAE_HIP(hipGetDevice(&dev));
-    if (lds > 48 * 1024 && (dev < 0 || dev >= 16 || configured[dev] < int(lds))) {
-        GAE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    int(lds)));
-        if (dev >= 0 && dev < 16) configured[dev] = int(lds);
-    }
-    hipLaunchKernelGGL(Kernel, dim3(unsigned(blocks)), dim3(threads), lds, st, a);
-    GAE_CHECK_LAUNCH("knn_kernel");
-    return GAE_OK;
-}
-
 template <int NW>
-int launch_sweep_nw(int64_t blocks, size_t lds, hipStream_t st, const KnnArgs &a)
+int launch_sweep(int64_t blocks, size_t lds, hipStream_t st, const KnnArgs &a)
 {
-    // the same DH and chunk choice per d as GAE_PAIRS_LAUNCH
-    if (a.d <= 16) return launch_sweep<&knn_kernel<8, true, NW>>(blocks, 64 * NW, lds, st, a);
-    if (a.d <= 32) return launch_sweep<&knn_kernel<16, true, NW>>(blocks, 64 * NW, lds, st, a);
-    if (a.d <= 64) return launch_sweep<&knn_kernel<32, true, NW>>(blocks, 64 * NW, lds, st, a);
-    return launch_sweep<&knn_kernel<32, false, NW>>(blocks, 64 * NW, lds, st, a);
+    return dispatch(a.d, [&](auto dh, auto one) {
+        return gae::launch_lds<&knn_kernel<dh, one, NW>>("knn_kernel", blocks, 64 * NW, lds, st, a);
+    });
 }
 
 } // namespace
@@ -384,7 +296,7 @@ extern "C" int gae_knn(const float *Q, int64_t ldq, int64_t m, const float *X, i
     KnnArgs a;
     a.Q = Q; a.X = X; a.ldq = ldq; a.ldx = ldx; a.ldo = ldo;
     a.m = int(m); a.n = int(n); a.d = int(d); a.k = int(k); a.S = S;
-    a.nch = d <= 64 ? 1 : int((d + 63) / 64);
+    a.nch = chunks_of(d);
     a.l2 = metric == GAE_KNN_L2 ? 1 : 0;
     a.excl_same = (flags & GAE_KNN_EXCLUDE_SAME_INDEX) ? 1 : 0;
     a.half = reinterpret_cast<const float *>(ws + p.half_at);
@@ -407,9 +319,10 @@ extern "C" int gae_knn(const float *Q, int64_t ldq, int64_t m, const float *X, i
         GAE_CHECK_LAUNCH("knn_half_kernel");
     }
     const size_t lds = size_t(sweep_lds(nw, d, k));
-    if (const int rc = nw == 4 ? launch_sweep_nw<4>(blocks, lds, st, a) : launch_sweep_nw<2>(blocks, lds, st, a)) return rc;
+    if (const int rc = nw == 4 ? launch_sweep<4>(blocks, lds, st, a) : launch_sweep<2>(blocks, lds, st, a)) return rc;
     if (S > 1) {
-        hipLaunchKernelGGL(knn_merge_kernel, dim3(unsigned(merge_blocks)), dim3(256), 0, st, a);
+        const MergeArgs<int32_t> ma{a.part_s, a.part_j, m, a.k, S, value_out, index_out, ldo};
+        hipLaunchKernelGGL(merge_kernel<int32_t>, dim3(unsigned(merge_blocks)), dim3(256), 0, st, ma);
         GAE_CHECK_LAUNCH("knn_merge_kernel");
     }
     if (a.l2) {

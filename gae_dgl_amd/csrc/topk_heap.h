@@ -1,6 +1,8 @@
-// The selection helpers of the k-best kernels: K16 gae_decoder_topk (decoder_topk.hip) and K24 gae_knn (knn.hip).
-// One total order (larger value first, then the lower index), a per-lane heap in LDS with the WORST entry at the root,
-// and the rank of an entry in a sorted partial list, by which the lists of the column splits are merged.
+// The k-best tail of K16 gae_decoder_topk (decoder_topk.hip) and K24 gae_knn (knn.hip), from a lane's 16 keys of a
+// tile to the output row: one total order (larger value first, then the lower index); a per-lane heap in LDS with the
+// WORST entry at the root; offer_tile, the walk that feeds it the keys of a tile that pass the running threshold, with
+// the kernel's own candidate tests as hooks; merge_halves, the merge of the two lane halves of a row; and merge_kernel,
+// the second launch that merges the sorted partial lists of the column splits by rank.
 #pragma once
 #include <stdint.h>
 
@@ -68,6 +70,73 @@ __device__ __forceinline__ void heap_sort(float *ls, int *lj, int lane, int cnt)
     }
 }
 
+// what offer_tile's second hook is when a kernel has none
+struct EveryIndex {
+    __device__ __forceinline__ bool operator()(int) const { return true; }
+};
+
+// The 16 keys of a lane's tile against its running top k: the heap (ls, lj) of cnt entries, (thr, thr_j) its k-th
+// entry once it is full (before that thr = -FLT_MAX: NaN and -inf never pass).  The fast path is one max per key and
+// one compare per tile; only a `live` lane with a passing key spills the tile to its column of the scratch rows scr
+// ([16][64]) and walks the passing keys in register order.  index_of(r, key) gives the candidate's index, or a negative
+// number when register r holds none; it runs BEFORE the test against the threshold, keep(j) (a dearer test, such as a
+// CSR lookup) only after it
+template <class Keys, class IndexOf, class Keep = EveryIndex>
+__device__ __forceinline__ void offer_tile(const Keys &key, bool live, float *scr, float *ls, int *lj, int lane, int k,
+                                           int &cnt, float &thr, int &thr_j, IndexOf &&index_of, Keep &&keep = Keep())
+{
+    float m = key[0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) m = fmaxf(m, key[r]);
+    if (!(m >= thr && live)) return;
+    unsigned pass = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        scr[r * 64 + lane] = key[r];
+        pass |= (key[r] >= thr ? 1u : 0u) << r;
+    }
+    while (pass) {
+        const int r = __builtin_ctz(pass);
+        pass &= pass - 1;
+        const float s = scr[r * 64 + lane];
+        const int j = index_of(r, s);
+        if (j < 0) continue;
+        if (cnt == k && !better(s, j, thr, thr_j)) continue;
+        if (!keep(j)) continue;
+        if (cnt < k) {
+            heap_push(ls, lj, lane, cnt, s, j);
+            ++cnt;
+        } else {
+            heap_replace_root(ls, lj, lane, k, s, j);
+        }
+        if (cnt == k) {
+            thr = ls[lane];
+            thr_j = lj[lane];
+        }
+    }
+}
+
+// the two sorted lists of a row -- cnt entries of `lane` (lane half 0, the caller) and pcnt of lane + 32 -- merged into
+// k entries best first, padding (-inf, -1) at the end: store(t, s, j) for t = 0 .. k - 1
+template <class Store>
+__device__ __forceinline__ void merge_halves(const float *ls, const int *lj, int lane, int k, int cnt, int pcnt,
+                                             Store &&store)
+{
+    int p0 = 0, p1 = 0;
+    for (int t = 0; t < k; ++t) {
+        float s = -INFINITY;
+        int j = -1;
+        const bool h0 = p0 < cnt, h1 = p1 < pcnt;
+        if (h0 || h1) {
+            const float s0 = h0 ? ls[p0 * 64 + lane] : 0.f, s1 = h1 ? ls[p1 * 64 + lane + 32] : 0.f;
+            const int j0 = h0 ? lj[p0 * 64 + lane] : 0, j1 = h1 ? lj[p1 * 64 + lane + 32] : 0;
+            if (h0 && (!h1 || better(s0, j0, s1, j1))) { s = s0; j = j0; ++p0; }
+            else { s = s1; j = j1; ++p1; }
+        }
+        store(t, s, j);
+    }
+}
+
 // entries of a sorted partial list (length k, padding j = -1 at the end) better than (s, j)
 __device__ __forceinline__ int rank_in(const float *ps, const int32_t *pj, int k, float s, int j)
 {
@@ -85,6 +154,49 @@ __device__ __forceinline__ int valid_in(const int32_t *pj, int k)
     int l = 0, h = k;
     while (l < h) { const int m = (l + h) >> 1; if (pj[m] >= 0) l = m + 1; else h = m; }
     return l;
+}
+
+// ---- the second launch of a call with S > 1 column splits
+template <class Index>
+struct MergeArgs {
+    const float *part_s;          // [S][rows][k]: the sorted partial lists
+    const int32_t *part_j;
+    int64_t rows;
+    int k, S;
+    float *score_out;             // [rows][ldo]
+    Index *index_out;
+    int64_t ldo;
+};
+
+// one thread per (row, split, position): the entry's rank among the S lists of its row is its output slot.  The order
+// is total and strict, so the result is unique: no atomics, and every schedule and every S give the same bits
+template <class Index>
+__global__ __launch_bounds__(256) void merge_kernel(const MergeArgs<Index> a)
+{
+    const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    const int k = a.k, S = a.S;
+    if (t >= a.rows * S * k) return;
+    const int q = int(t % k);
+    const int s = int((t / k) % S);
+    const int64_t i = t / (int64_t(k) * S);
+    const int64_t stride = a.rows * k;
+    const float *ps = a.part_s + i * k;
+    const int32_t *pj = a.part_j + i * k;
+    float *os = a.score_out + i * a.ldo;
+    Index *oj = a.index_out + i * a.ldo;
+    const int j = pj[s * stride + q];
+    if (j >= 0) {
+        const float v = ps[s * stride + q];
+        int rank = q;
+        for (int u = 0; u < S; ++u)
+            if (u != s) rank += rank_in(ps + u * stride, pj + u * stride, k, v, j);
+        if (rank < k) { os[rank] = v; oj[rank] = j; }
+    }
+    if (s == 0) {
+        int total = 0;
+        for (int u = 0; u < S; ++u) total += valid_in(pj + u * stride, k);
+        if (q >= total) { os[q] = -INFINITY; oj[q] = -1; }
+    }
 }
 
 } // namespace topk

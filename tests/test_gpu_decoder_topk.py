@@ -273,6 +273,31 @@ def test_graph_scope_windows(dev, tuning):
             assert np.array_equal(score[rows], sc.astype(np.float32)), (splits, g)
 
 
+def test_short_lists_merge_the_same_for_any_split(dev, tuning):
+    """the merge of the lane halves and of the column splits (topk_heap.h) on lists shorter than k: members of 1, 5 and
+    64 nodes give rows of 0, 4 and 63 candidates at k = 64; n = 70 is two full tiles and a tail of 6.  Integer scores,
+    so every split count must give the oracle's bits, padding included"""
+    from gae_dgl_amd import ops
+    sizes = [1, 5, 64]
+    gp = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    n, d, k = int(gp[-1]), 3, 64
+    member = np.searchsorted(gp, np.arange(n), side="right") - 1
+    windows = np.stack([gp[member], gp[member + 1]], 1)
+    Zi = np.random.default_rng(70).integers(-2, 3, (n, d)).astype(np.float32)
+    Z64 = Zi.astype(np.float64)
+    sc, idx = oracle_topk(Z64 @ Z64.T, allowed_mask(n, windows), k)
+    # the oracle alone: 0, 4 and 63 candidates per row, then -1 / -inf
+    n_cand = np.repeat(np.array(sizes) - 1, sizes)
+    filled = np.arange(k)[None, :] < n_cand[:, None]
+    assert ((idx >= 0) == filled).all() and (idx[~filled] == -1).all() and (sc[~filled] == -np.inf).all()
+    Z, node_ptr = torch.from_numpy(Zi).to(dev), torch.as_tensor(gp, device=dev)
+    for splits in (1, 3, 16):
+        tuning("topk_splits", splits)
+        score, index = ops.decoder_topk_raw(Z, k, node_ptr, max(sizes), None)
+        assert np.array_equal(as_np(index), idx), splits
+        assert np.array_equal(as_np(score), sc.astype(np.float32)), splits
+
+
 def test_single_member_graph_scope_equals_batch_scope(dev):
     import gae_dgl_amd as G
     g = load_golden("sym200")

@@ -186,6 +186,25 @@ def test_same_bits_for_any_split_stride_and_run(dev):
         assert torch.equal(r.index, self0.index) and torch.equal(r.value, self0.value)
 
 
+def test_short_lists_merge_the_same_for_any_split(dev):
+    """the merge of the lane halves and of the column splits (topk_heap.h) on lists shorter than k: 60 of the 70 database
+    rows are finite at k = 64; n = 70 is two full tiles and a tail of 6, m = 33 a panel and a tail of 1.  On the exact
+    grid every split count must give the reference's bits, padding included"""
+    rng = np.random.default_rng(70)
+    m, n, d, k = 33, 70, 3, 64
+    Q, X = grid(rng, m, d), grid(rng, n, d)
+    X[[0, 5, 31, 32, 33, 40, 63, 64, 66, 69]] = NAN
+    Qd, Xd = strided(Q, 5, dev), strided(X, 2, dev)
+    for metric, pad in (("l2", INF), ("dot", -INF)):
+        want_i, want_v = R.knn(Q, X, k, metric)
+        # the reference alone: 60 neighbours per query, then -1 / +inf (l2), -1 / -inf (dot)
+        assert (want_i[:, :60] >= 0).all() and (want_i[:, 60:] == -1).all() and (want_v[:, 60:] == pad).all()
+        for splits in (1, 3, 16):
+            got_i, got_v = raw_knn(Qd, Xd, k, metric, splits=splits)
+            assert np.array_equal(got_i, want_i), (metric, splits)
+            assert np.array_equal(got_v.astype(np.float64), want_v), (metric, splits)
+
+
 # ------------------------------------------------------------------ 6. non-finite values
 @pytest.mark.parametrize("metric", ["l2", "dot"])
 def test_non_finite_rows_are_never_returned(dev, metric):
