@@ -21,6 +21,9 @@ TOPK_EXCLUDE_SELF, TOPK_EXCLUDE_EDGES = 1, 2
 EMBED_NORM_NONE, EMBED_NORM_BOTH = 0, 1
 KNN_L2, KNN_DOT = 0, 1
 KNN_EXCLUDE_SAME_INDEX = 1
+RIDGE_CHUNK_ROWS = 256            # GAE_RIDGE_CHUNK_ROWS
+RIDGE_NO_INTERCEPT = 1
+RIDGE_ERR_FOLD_PTR, RIDGE_ERR_ROW_ID, RIDGE_ERR_LAMBDA = 1, 2, 4
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _p, _f, _int = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
@@ -181,6 +184,9 @@ SIGNATURES = {
     "gae_kmeans_init_pp": (_int, [_p, _i64, _i64, _i64, _i64, _u64, _p, _p, _p, _i64, _p]),
     "gae_knn_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _int]),
     "gae_knn": (_int, [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _int, _int, _int, _p, _p, _i64, _p, _i64, _p]),
+    "gae_ridge_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "gae_ridge_stats": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
+    "gae_ridge_solve": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _int, _p, _p, _p, _p, _p, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

@@ -16,7 +16,12 @@ clusters of the resident set; ``--clusters_out PATH`` writes 'labels' int32 [G] 
 ``--neighbours K`` searches the features just computed against themselves (``ops.knn``: the exact K nearest other
 molecules of every molecule, ``--metric l2|dot|cosine``) and prints the time of that one call, first-use set-up included; ``--neighbours_out PATH``
 writes 'index' int32 [G, K] and 'value' fp32 [G, K] as .npz; ``--targets y.npy`` (one property per molecule) prints the
-leave-one-out RMSE | MAE | R2 of the kNN regressor on the frozen features."""
+leave-one-out RMSE | MAE | R2 of the kNN regressor on the frozen features.
+``--ridge [LAMBDA ...]`` fits the reference table's "GAE + Ridge" head on the features just computed (``ops.ridge``: per-fold
+fp64 moments in one pass over the features, lambda chosen by ``--ridge_folds F``-fold CV on the device; no values = the
+default grid 10^-3 .. 10^3); needs ``--targets`` ([G] or [G, t]); prints the time of the call and the cross-validated
+RMSE | R2 at the chosen lambda, one pair per target; ``--ridge_out PATH`` writes 'coef', 'intercept', 'lam', 'lambdas',
+'cv_rmse' and 'cv_r2' as .npz."""
 import argparse
 import os
 import time
@@ -56,7 +61,16 @@ def build_parser():
                     help="with --neighbours: write the lists (.npz: 'index' int32 [G, K], 'value' fp32 [G, K])")
     ap.add_argument("--targets", type=str, default=None, metavar="PATH",
                     help="with --neighbours: a .npy of one property per molecule; prints the leave-one-out RMSE | MAE | "
-                         "R2 of the kNN regressor (mean of the K neighbours' targets)")
+                         "R2 of the kNN regressor (mean of the K neighbours' targets).  With --ridge: [G] or [G, t], the "
+                         "targets of the ridge head")
+    ap.add_argument("--ridge", type=float, nargs="*", default=None, metavar="LAMBDA",
+                    help="also fit a ridge regression head on the features (needs --targets; 3 d <= 128): the penalty "
+                         "is chosen among the given values (none given: 10^-3 .. 10^3, 13 values) by k-fold CV on the "
+                         "device; prints the cross-validated RMSE | R2")
+    ap.add_argument("--ridge_folds", type=int, default=None, metavar="F", help="with --ridge: CV folds, 2..32 (default 5)")
+    ap.add_argument("--ridge_out", type=str, default=None, metavar="PATH",
+                    help="with --ridge: write the model (.npz: 'coef' [t, 3 d], 'intercept' [t], 'lam', 'lambdas', "
+                         "'cv_rmse' [L, t], 'cv_r2' [L, t])")
     ap.add_argument("--norm", choices=["none", "both"], default="none",
                     help="none = the reference's plain in-edge sums; both = D^-1/2 A D^-1/2")
     ap.add_argument("--fused", choices=["auto", "on", "off"], default="auto",
@@ -91,9 +105,23 @@ def parse_args(argv=None):
     elif not 1 <= args.clusters <= 256 or 3 * args.hidden_dims[-1] > 64:
         parser.error(f"--clusters {args.clusters}: K must lie in 1..256 and the feature width 3 d = "
                      f"{3 * args.hidden_dims[-1]} must not exceed 64")
+    if args.ridge is None:
+        if args.ridge_out or args.ridge_folds is not None:
+            parser.error("--ridge_out / --ridge_folds need --ridge")
+    else:
+        if not args.targets:
+            parser.error("--ridge needs --targets PATH: the property (or properties) to regress on")
+        if 3 * args.hidden_dims[-1] > ops.RIDGE_MAX_D:
+            parser.error(f"--ridge: the feature width 3 d = {3 * args.hidden_dims[-1]} must not exceed {ops.RIDGE_MAX_D}")
+        if args.ridge_folds is not None and not 2 <= args.ridge_folds <= ops.RIDGE_MAX_FOLDS:
+            parser.error(f"--ridge_folds {args.ridge_folds}: F must lie in 2..{ops.RIDGE_MAX_FOLDS}")
+        if len(args.ridge) > ops.RIDGE_MAX_LAMBDAS or not all(v >= 0.0 and v < float("inf") for v in args.ridge):
+            parser.error(f"--ridge: at most {ops.RIDGE_MAX_LAMBDAS} finite values >= 0")
+        if not os.path.exists(args.targets):
+            parser.error(f"--targets {args.targets}: no such file")
     if args.neighbours is None:
-        if args.metric is not None or args.neighbours_out or args.targets:
-            parser.error("--metric / --neighbours_out / --targets need --neighbours K")
+        if args.metric is not None or args.neighbours_out or (args.targets and args.ridge is None):
+            parser.error("--metric / --neighbours_out / --targets need --neighbours K (--targets: or --ridge)")
     else:
         if not 1 <= args.neighbours <= ops.KNN_MAX_K or 3 * args.hidden_dims[-1] > ops.KNN_MAX_D:
             parser.error(f"--neighbours {args.neighbours}: K must lie in 1..{ops.KNN_MAX_K} and the feature width 3 d = "
@@ -169,14 +197,37 @@ def main(argv=None):
         if args.neighbours_out:
             np.savez(args.neighbours_out, index=nn.index.cpu().numpy(), value=nn.value.cpu().numpy())
         if args.targets:
-            y = np.load(args.targets).reshape(-1)
-            if y.shape[0] != out.shape[0]:
-                raise ValueError(f"--targets holds {y.shape[0]} values for {out.shape[0]} molecules")
-            y = torch.from_numpy(y.astype(np.float64)).to(device)
+            y = np.load(args.targets)
+            if y.shape[0] != out.shape[0] or (y.ndim > 1 and int(np.prod(y.shape[1:])) != 1):
+                raise ValueError(f"--targets of shape {y.shape} for the kNN regressor on {out.shape[0]} molecules: one "
+                                 f"property per molecule")
+            y = torch.from_numpy(y.reshape(-1).astype(np.float64)).to(device)
             rm = metrics.regression_metrics(metrics.knn_predict(nn.index, nn.value, y), y)
             print(f"kNN ({args.neighbours}, leave-one-out) RMSE: {rm['rmse']:.6f} | MAE: {rm['mae']:.6f} | "
                   f"R2: {rm['r2']:.6f}")
             main.knn_scores = rm
+    main.ridge = None
+    if args.ridge is not None:
+        y = np.load(args.targets)
+        if y.ndim not in (1, 2) or y.shape[0] != out.shape[0]:
+            raise ValueError(f"--targets of shape {y.shape} for {out.shape[0]} molecules: [G] or [G, t]")
+        y = torch.from_numpy(y.astype(np.float32)).to(device)
+        n_folds = args.ridge_folds or 5
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        res = ops.ridge(feats, y, args.ridge or None, folds=n_folds, seed=args.seed or 0)
+        torch.cuda.synchronize(device)
+        print(f"Fitted ridge on {res.n_used} molecules, {len(res.lambdas)} lambdas x {n_folds} folds | "
+              f"{(time.perf_counter() - t0) * 1e3:.3f} ms (one call, set-up included)")
+        chosen = res.lambdas.tolist().index(res.lam)
+        pairs = " | ".join(f"RMSE: {r:.6f} | R2: {q:.6f}"
+                           for r, q in zip(res.cv_rmse[chosen].tolist(), res.cv_r2[chosen].tolist()))
+        print(f"Ridge ({n_folds}-fold CV, lambda = {res.lam:g}) {pairs}")
+        if args.ridge_out:
+            np.savez(args.ridge_out, coef=res.coef.cpu().numpy(), intercept=res.intercept.cpu().numpy(),
+                     lam=np.float64(res.lam), lambdas=res.lambdas.cpu().numpy(), cv_rmse=res.cv_rmse.cpu().numpy(),
+                     cv_r2=res.cv_r2.cpu().numpy())
+        main.ridge = res
     return out
 
 

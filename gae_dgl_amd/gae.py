@@ -348,6 +348,18 @@ class GAE(nn.Module):
                 return ops.knn(X, k=k, metric=metric)
             return ops.knn(self.embed_graphs(queries, **embed_kw), X, k=k, metric=metric)
 
+    def ridge_graphs(self, data, y, **kw):
+        """``ops.RidgeResult``: ridge regression of the per-molecule targets ``y`` ([G] or [G, t]) on the molecule
+        features of ``embed_graphs`` -- the reference's "GAE + Ridge" head, lambda chosen by k-fold CV on the device
+        (``ops.ridge``; its keyword arguments pass through: lambdas, folds, fold, seed, fit_intercept, pivot).  ``fused``
+        and ``batch_size`` go to the embedding.  Rows are in the order ``embed_graphs(data)`` returns them.  Runs under
+        no_grad."""
+        if "grad" in kw:
+            raise ValueError("ridge_graphs runs under no_grad: the closed-form fit carries no gradient")
+        embed_kw = {k: kw.pop(k) for k in ("fused", "batch_size") if k in kw}
+        with torch.no_grad():
+            return ops.ridge(self.embed_graphs(data, **embed_kw), y, **kw)
+
     def embed_graphs(self, data, *, fused="auto", batch_size=4096, grad=False):
         """fp32 [n_graphs, 3 d]: the molecule feature of the reference's chemistry table (README.md:54: mean | sum |
         max of the hidden vectors, 48 numbers for ``--hidden_dims 32 16``) of every graph of ``data`` -- a

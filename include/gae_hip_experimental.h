@@ -12,7 +12,8 @@
  * and gae_decoder_rank, the filtered rank of given pairs among all candidates of gae_decoder_topk's rule,
  * and gae_score_graphs, the per-molecule reconstruction scores (AUC counts, average precision, loss) of a resident set,
  * and gae_kmeans_*, node clustering on the device: k-means++ seeding, Lloyd iterations and assignment over an embedding,
- * and gae_knn, the exact k nearest rows of one embedding for every row of another.
+ * and gae_knn, the exact k nearest rows of one embedding for every row of another,
+ * and gae_ridge_*, ridge regression on a frozen feature: per-fold fp64 moments in one pass, the k-fold CV lambda path.
  * Same conventions as gae_hip.h: caller-owned buffers, 0 / negative / hipError_t return codes, asynchronous launches on
  * the stream passed last.  These signatures may change between versions without a GAE_VERSION major bump. */
 #ifndef GAE_HIP_EXPERIMENTAL_H
@@ -653,6 +654,73 @@ int64_t gae_knn_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int 
 int gae_knn(const float *Q, int64_t ldq, int64_t m, const float *X, int64_t ldx, int64_t n, int64_t d, int64_t k,
             int metric, int flags, int splits, int32_t *index_out, float *value_out, int64_t ldo,
             void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- K25: ridge regression on a frozen feature with a k-fold CV lambda path (ops.ridge, GAE.ridge_graphs)
+ * The first row of the reference's chemistry table ("GAE + Ridge" on the [mean | sum | max] molecule feature): closed
+ * form, deterministic, lambda chosen by cross-validation from ONE pass over X -- every fold's fit and every fold's
+ * held-out error follow from per-fold second moments.
+ *   X            fp32 [n, d], rows ldx >= d floats apart;  Y fp32 [n, t], rows ldy >= t apart (no alignment asked)
+ *   pivot        fp32 [d + t] (p_x, then p_y) or NULL = zeros.  v_i = [1, x_i - p_x, y_i - p_y], width W = 1 + d + t; the
+ *                subtraction is done in fp64 after widening (exact for fp32 values of comparable exponent).  The fitted
+ *                model does not depend on the pivot mathematically; a pivot near the column means keeps the moments small
+ *   1 <= d <= 128, 1 <= t <= 8, 1 <= folds <= 32, 1 <= n_lambdas <= 64 (else GAE_E_RANGE); 0 <= n, n_rows < 2^31 (else
+ *   GAE_E_SIZE).  There is no fallback for other shapes.
+ * MOMENTS (gae_ridge_stats): for every fold f, M_f = sum_{i in fold f} v_i v_i^T in fp64, as a packed upper triangle:
+ *   stats[f][i W - i (i - 1) / 2 + (j - i)] = M_f[i][j], 0 <= i <= j < W (fp64 [folds][W (W + 1) / 2]).
+ *   rows         int32 [n_rows]: row ids of X / Y, ascending inside each fold; fold f owns rows[fold_ptr[f] ..
+ *                fold_ptr[f + 1]).  fold_ptr is DEVICE int32 [folds + 1], 0 <= fold_ptr[0] <= ... <= fold_ptr[folds] ==
+ *                n_rows.  rows = NULL means rows 0 .. n - 1, all in fold 0 (then n_rows == n and folds == 1, fold_ptr is
+ *                ignored).  Rows that are not listed are never read.
+ *   products     on v_mfma_f64_16x16x4_f64, the upper-triangle tiles of M split over the waves of a block.
+ *   determinism  each fold's list is cut into chunks of GAE_RIDGE_CHUNK_ROWS rows (a constant, not a function of the
+ *                device); a chunk never straddles folds; one block per chunk adds its rows in ascending list order,
+ *                four per product; the chunk partials go to the workspace and a second launch adds each fold's partials
+ *                in ascending chunk order, in THE order of partial lists (csrc/common.h sum_partials, here in fp64: <= 32
+ *                partials one lane in order; more: 64 lanes, lane l adds l, l + 64, ..., then the shuffle-down tree).
+ *                No float atomics.  stats is a function of the listed values and the fold lists alone: the same bits
+ *                run to run, for any ldx / ldy and any stream.  A fold without rows gives an all-zero block.
+ *   status       a 32-byte device block the caller zeroes; the launches only add to it:
+ *                  nonfinite_rows  listed rows that hold a NaN or an infinity in X or Y (integer atomics)
+ *                  errors          GAE_RIDGE_ERR_FOLD_PTR: fold_ptr is not monotone from >= 0 to n_rows -- nothing is read
+ *                                  through it and stats is filled with NaN;  GAE_RIDGE_ERR_ROW_ID: a row id outside [0, n)
+ *                                  -- the row is skipped;  GAE_RIDGE_ERR_LAMBDA (gae_ridge_solve): a lambda that is
+ *                                  negative or not finite
+ *   workspace    device memory of at least gae_ridge_workspace_bytes(n_rows, d, t, folds) bytes: a pure host function,
+ *                positive, non-decreasing in n_rows; a negative error code for a shape error.
+ * MODELS (gae_ridge_solve): one launch, one block per (model m in 0 .. folds, lambda index l).  Model m < folds trains on
+ * every fold but m, model `folds` on all listed rows.
+ *   1. S = sum of M_f over the training folds, f ascending;  c = S[0][0], mu = S[0][1:] / c;  C = S[1:, 1:] - c mu mu^T
+ *   2. A = C_xx + lambda I: the intercept is not penalised.  GAE_RIDGE_NO_INTERCEPT: no centring; the moments are moved
+ *      back from the pivot to the origin first, so the model is y = x^T w for any pivot
+ *   3. fp64 Cholesky of the packed triangle in LDS;  4. forward and back substitution for the t right-hand sides
+ *   5. intercept b = p_y + mu_y - mu_x^T w - p_x^T w
+ *   The held-out squared error of fold m comes from the moments too: with b' = b - p_y + p_x^T w and u = [-b', -w, e_j],
+ *   cv_sse[m][l][j] = u^T M_m u.  X is not read again.
+ *   coef fp64 [folds + 1][L][t][d];  intercept fp64 [folds + 1][L][t];  cv_sse fp64 [folds][L][t];
+ *   info int32 [folds + 1][L], LAPACK style: 0, or the 1-based index of the first pivot that is <= 0 or not finite; -1:
+ *   the model's training set is empty (c = 0); -2: its lambda is negative or not finite.  Where info != 0 the cell's
+ *   coefficients, intercept and SSE are NaN.  lambdas: DEVICE fp64 [L].  pivot: the one the moments were taken with.
+ * Argument errors are returned before anything is dereferenced or launched (no GPU is needed to see them): the shape
+ * errors above, ldx < d, ldy < t, rows = NULL with n_rows != n or folds != 1 (GAE_E_SIZE), unknown flag bits (GAE_E_RANGE),
+ * NULL X / Y (n_rows > 0), fold_ptr (rows given), stats, status, workspace, lambdas or an output (GAE_E_NULL), a short
+ * workspace (GAE_E_WORKSPACE). */
+enum { GAE_RIDGE_CHUNK_ROWS = 256 };
+enum { GAE_RIDGE_NO_INTERCEPT = 1 };
+enum { GAE_RIDGE_ERR_FOLD_PTR = 1, GAE_RIDGE_ERR_ROW_ID = 2, GAE_RIDGE_ERR_LAMBDA = 4 };
+
+typedef struct gae_ridge_status {
+    int64_t nonfinite_rows, errors, reserved[2];
+} gae_ridge_status;
+
+int64_t gae_ridge_workspace_bytes(int64_t n_rows, int64_t d, int64_t t, int64_t folds);
+
+int gae_ridge_stats(const float *X, int64_t ldx, const float *Y, int64_t ldy, int64_t n, int64_t d, int64_t t,
+                    const float *pivot, const int32_t *rows, int64_t n_rows, const int32_t *fold_ptr, int64_t folds,
+                    double *stats, gae_ridge_status *status, void *workspace, int64_t workspace_bytes, void *stream);
+
+int gae_ridge_solve(const double *stats, int64_t d, int64_t t, int64_t folds, const float *pivot, const double *lambdas,
+                    int64_t n_lambdas, int flags, double *coef, double *intercept, double *cv_sse, int32_t *info,
+                    gae_ridge_status *status, void *stream);
 
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
