@@ -24,6 +24,10 @@ KNN_EXCLUDE_SAME_INDEX = 1
 RIDGE_CHUNK_ROWS = 256            # GAE_RIDGE_CHUNK_ROWS
 RIDGE_NO_INTERCEPT = 1
 RIDGE_ERR_FOLD_PTR, RIDGE_ERR_ROW_ID, RIDGE_ERR_LAMBDA = 1, 2, 4
+FOREST_SPLIT_ROWS = 8192          # GAE_FOREST_SPLIT_ROWS
+FOREST_BOOTSTRAP = 1
+FOREST_ERR_ROW_ID, FOREST_ERR_NODE, FOREST_ERR_CODE = 1, 2, 4
+FOREST_KEY_XOR = 0xA0761D6478BD642F
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _p, _f, _int = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
@@ -187,6 +191,11 @@ SIGNATURES = {
     "gae_ridge_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "gae_ridge_stats": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
     "gae_ridge_solve": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _int, _p, _p, _p, _p, _p, _p]),
+    "gae_forest_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64, _i64, _i64]),
+    "gae_forest_bin": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p]),
+    "gae_forest_fit": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64,
+                              _int, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _p]),
+    "gae_forest_predict": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

@@ -21,7 +21,12 @@ leave-one-out RMSE | MAE | R2 of the kNN regressor on the frozen features.
 fp64 moments in one pass over the features, lambda chosen by ``--ridge_folds F``-fold CV on the device; no values = the
 default grid 10^-3 .. 10^3); needs ``--targets`` ([G] or [G, t]); prints the time of the call and the cross-validated
 RMSE | R2 at the chosen lambda, one pair per target; ``--ridge_out PATH`` writes 'coef', 'intercept', 'lam', 'lambdas',
-'cv_rmse' and 'cv_r2' as .npz."""
+'cv_rmse' and 'cv_r2' as .npz.
+``--forest [N_TREES]`` grows the table's "GAE + Random Forest" head on the features just computed (``ops.forest``: histogram
+trees on the device, default 100 trees; ``--forest_depth D`` (default 12), ``--forest_features M`` features per split
+(default all)); needs ``--targets`` ([G] or [G, t]); prints the time of the call and the out-of-bag RMSE | R2, one pair
+per target; ``--forest_out PATH`` writes the node tables, 'edges', 'n_edges', 'oob_prediction', 'oob_rmse', 'oob_r2' and
+'importances' as .npz.  Combines with ``--ridge`` and ``--neighbours``."""
 import argparse
 import os
 import time
@@ -71,6 +76,16 @@ def build_parser():
     ap.add_argument("--ridge_out", type=str, default=None, metavar="PATH",
                     help="with --ridge: write the model (.npz: 'coef' [t, 3 d], 'intercept' [t], 'lam', 'lambdas', "
                          "'cv_rmse' [L, t], 'cv_r2' [L, t])")
+    ap.add_argument("--forest", type=int, nargs="?", const=100, default=None, metavar="N_TREES",
+                    help="also grow a random forest regression head on the features (needs --targets; 3 d <= 256): "
+                         "N_TREES histogram trees (default 100) on the device; prints the out-of-bag RMSE | R2")
+    ap.add_argument("--forest_depth", type=int, default=None, metavar="D", help="with --forest: depth limit, 1..16 (default 12)")
+    ap.add_argument("--forest_features", type=int, default=None, metavar="M",
+                    help="with --forest: features looked at per split, 1..3 d (default all)")
+    ap.add_argument("--forest_out", type=str, default=None, metavar="PATH",
+                    help="with --forest: write the model (.npz: the node tables 'feature', 'threshold_bin', 'threshold', "
+                         "'left', 'count', 'value', 'gain', 'n_nodes', and 'edges', 'n_edges', 'oob_prediction', "
+                         "'oob_rmse', 'oob_r2', 'importances')")
     ap.add_argument("--norm", choices=["none", "both"], default="none",
                     help="none = the reference's plain in-edge sums; both = D^-1/2 A D^-1/2")
     ap.add_argument("--fused", choices=["auto", "on", "off"], default="auto",
@@ -119,9 +134,24 @@ def parse_args(argv=None):
             parser.error(f"--ridge: at most {ops.RIDGE_MAX_LAMBDAS} finite values >= 0")
         if not os.path.exists(args.targets):
             parser.error(f"--targets {args.targets}: no such file")
+    if args.forest is None:
+        if args.forest_out or args.forest_depth is not None or args.forest_features is not None:
+            parser.error("--forest_out / --forest_depth / --forest_features need --forest")
+    else:
+        if not args.targets:
+            parser.error("--forest needs --targets PATH: the property (or properties) to regress on")
+        if not 1 <= args.forest <= ops.FOREST_MAX_TREES or 3 * args.hidden_dims[-1] > ops.FOREST_MAX_D:
+            parser.error(f"--forest {args.forest}: N_TREES must lie in 1..{ops.FOREST_MAX_TREES} and the feature width 3 d = "
+                         f"{3 * args.hidden_dims[-1]} must not exceed {ops.FOREST_MAX_D}")
+        if args.forest_depth is not None and not 1 <= args.forest_depth <= ops.FOREST_MAX_DEPTH:
+            parser.error(f"--forest_depth {args.forest_depth}: D must lie in 1..{ops.FOREST_MAX_DEPTH}")
+        if args.forest_features is not None and not 1 <= args.forest_features <= 3 * args.hidden_dims[-1]:
+            parser.error(f"--forest_features {args.forest_features}: M must lie in 1..{3 * args.hidden_dims[-1]}")
+        if not os.path.exists(args.targets):
+            parser.error(f"--targets {args.targets}: no such file")
     if args.neighbours is None:
-        if args.metric is not None or args.neighbours_out or (args.targets and args.ridge is None):
-            parser.error("--metric / --neighbours_out / --targets need --neighbours K (--targets: or --ridge)")
+        if args.metric is not None or args.neighbours_out or (args.targets and args.ridge is None and args.forest is None):
+            parser.error("--metric / --neighbours_out / --targets need --neighbours K (--targets: or --ridge / --forest)")
     else:
         if not 1 <= args.neighbours <= ops.KNN_MAX_K or 3 * args.hidden_dims[-1] > ops.KNN_MAX_D:
             parser.error(f"--neighbours {args.neighbours}: K must lie in 1..{ops.KNN_MAX_K} and the feature width 3 d = "
@@ -228,6 +258,27 @@ def main(argv=None):
                      lam=np.float64(res.lam), lambdas=res.lambdas.cpu().numpy(), cv_rmse=res.cv_rmse.cpu().numpy(),
                      cv_r2=res.cv_r2.cpu().numpy())
         main.ridge = res
+    main.forest = None
+    if args.forest is not None:
+        y = np.load(args.targets)
+        if y.ndim not in (1, 2) or y.shape[0] != out.shape[0]:
+            raise ValueError(f"--targets of shape {y.shape} for {out.shape[0]} molecules: [G] or [G, t]")
+        y = torch.from_numpy(y.astype(np.float32)).to(device)
+        depth = args.forest_depth or 12
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        res = ops.forest(feats, y, args.forest, max_depth=depth, max_features=args.forest_features or 1.0,
+                         seed=args.seed or 0)
+        torch.cuda.synchronize(device)
+        print(f"Grew a forest on {res.n_used} molecules, {args.forest} trees of {int(res.n_nodes.sum())} nodes | "
+              f"{(time.perf_counter() - t0) * 1e3:.3f} ms (one call, set-up included)")
+        pairs = " | ".join(f"RMSE: {r:.6f} | R2: {q:.6f}" for r, q in zip(res.oob_rmse.tolist(), res.oob_r2.tolist()))
+        print(f"Random Forest ({args.forest} trees, depth {depth}, out-of-bag) {pairs}")
+        if args.forest_out:
+            np.savez(args.forest_out, **{k: getattr(res, k).cpu().numpy() for k in (
+                "feature", "threshold_bin", "threshold", "left", "count", "value", "gain", "n_nodes", "edges", "n_edges",
+                "oob_prediction", "oob_rmse", "oob_r2", "importances")})
+        main.forest = res
     return out
 
 

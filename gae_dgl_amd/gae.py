@@ -360,6 +360,18 @@ class GAE(nn.Module):
         with torch.no_grad():
             return ops.ridge(self.embed_graphs(data, **embed_kw), y, **kw)
 
+    def forest_graphs(self, data, y, **kw):
+        """``ops.ForestResult``: a random forest regression of the per-molecule targets ``y`` ([G] or [G, t]) on the
+        molecule features of ``embed_graphs`` -- the reference's "GAE + Random Forest" head, grown on the device with its
+        out-of-bag scores (``ops.forest``; its keyword arguments pass through: n_trees, max_depth, max_features,
+        min_samples_leaf, max_bins, bootstrap, max_samples, rows, seed).  ``fused`` and ``batch_size`` go to the embedding.
+        Rows are in the order ``embed_graphs(data)`` returns them.  Runs under no_grad."""
+        if "grad" in kw:
+            raise ValueError("forest_graphs runs under no_grad: a forest carries no gradient")
+        embed_kw = {k: kw.pop(k) for k in ("fused", "batch_size") if k in kw}
+        with torch.no_grad():
+            return ops.forest(self.embed_graphs(data, **embed_kw), y, **kw)
+
     def embed_graphs(self, data, *, fused="auto", batch_size=4096, grad=False):
         """fp32 [n_graphs, 3 d]: the molecule feature of the reference's chemistry table (README.md:54: mean | sum |
         max of the hidden vectors, 48 numbers for ``--hidden_dims 32 16``) of every graph of ``data`` -- a

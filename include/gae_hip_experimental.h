@@ -722,6 +722,97 @@ int gae_ridge_solve(const double *stats, int64_t d, int64_t t, int64_t folds, co
                     int64_t n_lambdas, int flags, double *coef, double *intercept, double *cv_sse, int32_t *info,
                     gae_ridge_status *status, void *stream);
 
+/* ---- K26: a histogram-based regression forest on a frozen feature (ops.forest, GAE.forest_graphs, embed --forest)
+ * The third row of the reference's chemistry table ("GAE + Random Forest").  EVERY ACCUMULATED QUANTITY IS AN INTEGER:
+ * features become bin codes, targets fixed-point int64, histogram cells integer counts and integer sums.  Integer atomics
+ * in LDS and in global memory are exact and free of order: no float atomics, the same bits run to run, for any row
+ * stride, stream or launch split, and a numpy restatement (tests/forest_ref.py) reproduces every tree node for node.
+ * Regression only; classification and gradient boosting are not built.
+ *   1 <= d <= 256, 1 <= t <= 8, 1 <= n_trees <= 1024, 1 <= max_depth <= 16, 2 <= max_bins <= 256 (else GAE_E_RANGE);
+ *   1 <= n_used, n_boot < 2^31, 0 <= n, m < 2^31 (else GAE_E_SIZE).  There is no fallback for other shapes.
+ * BINNING (gae_forest_bin): per feature f an ascending fp32 edge list edges[f][0 .. n_edges[f]), n_edges[f] <= max_bins - 1
+ *   (edges: DEVICE fp32 [d][max_bins - 1], entries past n_edges[f] are not read; n_edges: DEVICE int32 [d]).
+ *   code(x) = #{e in edges[f] : e < x}, a uint8: a binary search over the edge lists held in LDS.  codes_out is uint8
+ *   [n_rows][d], row-major by LISTED row: row i of it belongs to X's row rows[i] (rows = NULL: rows 0 .. n - 1, then
+ *   n_rows == n).  The histogram launch gathers d contiguous bytes per sample from it.  Rows that are not listed are
+ *   never read.  A feature without edges is constant and can never split.  ops.forest computes the edges with torch
+ *   from a column sort of the listed rows: at most max_bins distinct values -> the midpoints of consecutive distinct
+ *   values a < b, (double(a) + double(b)) / 2 rounded to fp32, and a itself where that rounds up to b, so a <= edge < b
+ *   and the binning is lossless; more -> the order statistics v[(k n_used) / max_bins], k = 1 .. max_bins - 1 (integer
+ *   division) of the sorted column v, de-duplicated.  An edge of -0 is stored as +0 (they compare equal).
+ * TARGETS: Y fp32 [n][t] (ldy).  Per target j a pivot c_j (fp32) and an integer exponent e_j, HOST arrays of t values;
+ *   the device forms y_q = rint((double(y) - double(c_j)) 2^e_j) as int64 (ties to even).  ops.forest takes c_j = the fp64
+ *   mean of the listed rows rounded to fp32 and e_j = 30 - E_j with frexp(max_i |double(y_ij) - double(c_j)|) = (m, E_j),
+ *   0.5 <= m < 1 (e_j = 0 when that max is 0): |y_q| <= 2^30, a sum over up to 2^31 samples fits an int64, and the
+ *   quantisation step is 2^-31 of the target's range.  -200 <= e_j <= 200.
+ * BOOTSTRAP (GAE_FOREST_BOOTSTRAP): tree T trains on n_boot samples; sample j is listed row (w n_used) >> 32 (64-bit
+ *   product) with w = word j & 3 of philox4x32_10(ctr = j >> 2, draw = T, key = seed ^ GAE_FOREST_KEY_XOR) (csrc/common.h).
+ *   Without the flag sample j is listed row j and n_boot == n_used.  inbag (uint8 [n_trees][n_used] or NULL) is zeroed
+ *   and then holds 1 where tree T drew listed row i (integer stores).
+ * GROWTH, level by level, all trees at once.  The root is node 0.  A node at depth < max_depth with count >= 2
+ *   min_samples_leaf is offered a split.  Candidate (f, b), 0 <= b < n_edges[f], sends a sample left iff code_f <= b; both
+ *   children need count >= min_samples_leaf.  With S_Lj, S_Rj the children's exact integer sums of y_q for target j:
+ *     score = sum_j ((double(S_Lj) double(S_Lj)) / double(n_L) + (double(S_Rj) double(S_Rj)) / double(n_R)) 4^(-e_j)
+ *   in fp64: convert, square, divide, add the two sides, scale, then add over j ascending from 0.0 -- without contraction
+ *   (csrc/forest.hip is built with -ffp-contract=off).  The parent's score is sum_j ((double(S_j) double(S_j)) /
+ *   double(n)) 4^(-e_j), computed the same way.  The best candidate has the largest score; ties go to the lower f, then
+ *   the lower b.  The node splits iff best > parent (strictly); gain = best - parent.  So a pure node is a leaf.
+ *   max_features = m < d: the candidates of node v of tree T are the m features with the smallest (r_f, f), r_f = word 0
+ *   of philox4x32_10(ctr = (v << 8) | f, draw = 2^32 + T, key).
+ * NODE NUMBERING: with `base` the tree's node count before a level is split, the k-th splitting node of the level in
+ *   ascending id (k from 0) gets the children base + 2 k (left) and base + 2 k + 1: independent of scheduling.
+ * NODE TABLES, [n_trees][node_capacity], node_capacity == min(2^(max_depth + 1) - 1, 2 n_boot - 1):
+ *   feature int32 (-1: a leaf), threshold_bin int32 (b; -1), threshold fp32 (edges[f][b]; 0), left int32 (the right child
+ *   is left + 1; -1), count int32, value fp64 [..][t] = double(c_j) + (double(S_j) / double(count)) 2^(-e_j) for EVERY
+ *   node, gain fp64 (0 for a leaf); n_nodes int32 [n_trees].  Slots past n_nodes hold the leaf defaults with count 0 and
+ *   value 0: gae_forest_fit writes every slot.
+ * HOT PATH: each tree's sample list stays partitioned by node; a block owns (node chunk, feature tile), builds the
+ *   tile's cells in LDS with integer atomics, scans the bins and emits the tile's best candidate only.  A node longer
+ *   than GAE_FOREST_SPLIT_ROWS samples is cut across blocks whose cells are merged by integer atomics before the scan:
+ *   the result cannot depend on the cut.  The host reads one 32-byte level status per level (gae_forest_fit
+ *   synchronises the stream max_depth - 1 times at most).
+ * PREDICTION (gae_forest_predict): X fp32 [m][d] (ldx).  Each row walks every tree on the raw floats, left iff x_f <=
+ *   threshold -- the partition code_f <= b of the fit, a value exactly on an edge included.  out fp64 [m][t] = (sum of
+ *   the reached nodes' values, trees ascending) / (trees added).  skip (uint8 [n_trees][m] or NULL): a non-zero entry
+ *   omits the tree for the row (inbag of the fit gives the out-of-bag prediction); a row every tree skips gets NaN.  A
+ *   row holding a non-finite feature is counted in status.nonfinite and gets NaN.  A walk that leaves the table (child
+ *   ids outside 1 .. node_capacity - 1, feature >= d, more than 64 steps) stops: GAE_FOREST_ERR_NODE, NaN for the row.
+ * STATUS: a 32-byte device block the caller zeroes; launches only add to it.  nonfinite: non-finite values of listed rows
+ *   (gae_forest_bin: X; gae_forest_fit: Y), rows (gae_forest_predict).  errors: GAE_FOREST_ERR_ROW_ID a row id outside
+ *   [0, n) (skipped), GAE_FOREST_ERR_NODE a broken node table, GAE_FOREST_ERR_CODE a code >= max_bins (skipped).
+ * workspace: device memory of gae_forest_workspace_bytes(...) bytes at least: a pure host function, positive; a negative
+ *   error code for a shape error.  Argument errors are returned before anything is dereferenced or launched (no GPU is
+ *   needed to see them): the shape errors above, max_features outside 1 .. d, min_samples_leaf < 1, unknown flags
+ *   (GAE_E_RANGE), ldx < d, ldy < t, rows = NULL with n_rows != n, n_boot != n_used without the bootstrap, another
+ *   node_capacity (GAE_E_SIZE), a NULL array (GAE_E_NULL), a short workspace (GAE_E_WORKSPACE). */
+enum { GAE_FOREST_SPLIT_ROWS = 8192 };
+enum { GAE_FOREST_BOOTSTRAP = 1 };
+enum { GAE_FOREST_ERR_ROW_ID = 1, GAE_FOREST_ERR_NODE = 2, GAE_FOREST_ERR_CODE = 4 };
+#define GAE_FOREST_KEY_XOR 0xA0761D6478BD642FULL
+
+typedef struct gae_forest_status {
+    int64_t nonfinite, errors, reserved[2];
+} gae_forest_status;
+
+int64_t gae_forest_workspace_bytes(int64_t n_used, int64_t d, int64_t t, int64_t n_trees, int64_t n_boot, int64_t max_depth,
+                                   int64_t max_bins);
+
+int gae_forest_bin(const float *X, int64_t ldx, int64_t n, int64_t d, const int32_t *rows, int64_t n_rows,
+                   const float *edges, const int32_t *n_edges, int64_t max_bins, uint8_t *codes_out,
+                   gae_forest_status *status, void *stream);
+
+int gae_forest_fit(const uint8_t *codes, const int32_t *n_edges, const float *edges, int64_t n_used, int64_t d,
+                   int64_t max_bins, const float *Y, int64_t ldy, int64_t n, int64_t t, const int32_t *rows,
+                   const float *pivot, const int32_t *exponent, int64_t n_trees, int64_t n_boot, int64_t max_depth,
+                   int64_t max_features, int64_t min_samples_leaf, int flags, uint64_t seed, int32_t *feature,
+                   int32_t *threshold_bin, float *threshold, int32_t *left, int32_t *count, double *value, double *gain,
+                   int32_t *n_nodes, int64_t node_capacity, uint8_t *inbag, gae_forest_status *status, void *workspace,
+                   int64_t workspace_bytes, void *stream);
+
+int gae_forest_predict(const float *X, int64_t ldx, int64_t m, int64_t d, int64_t t, int64_t n_trees, int64_t node_capacity,
+                       const int32_t *feature, const float *threshold, const int32_t *left, const double *value,
+                       const uint8_t *skip, double *out, gae_forest_status *status, void *stream);
+
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
 int gae_x_decoder_bce_finalize(const gae_bce_tail *tail, void *stream);
