@@ -65,6 +65,25 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
 inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// One walk over a caller's workspace.  Every family states its regions ONCE, in a function that takes a Carver: run on
+// the caller's buffer it hands out the pointers, run on a null base it only counts (every pointer null) and bytes() is
+// what the size query reports.  take<T>(count) advances by up256(count * sizeof(T)); raw<T>(bytes) by exactly `bytes`
+// (the layouts that are not in 256-byte steps); round() closes a run of raw regions at the next multiple of 256.
+struct Carver {
+    char *base;
+    int64_t off = 0;
+    explicit Carver(void *ws) : base(static_cast<char *>(ws)) {}
+    template <class T> T *raw(int64_t bytes)
+    {
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += bytes;
+        return p;
+    }
+    template <class T> T *take(int64_t count) { return raw<T>(up256(count * int64_t(sizeof(T)))); }
+    void round() { off = up256(off); }
+    int64_t bytes() const { return off; }
+};
+
 // a launch of Kernel(args...) with `lds` bytes of dynamic LDS, reported as `what`; above the 48 KB every kernel may have,
 // the attribute is raised once per (kernel instantiation, device), and again when a launch needs more
 template <auto Kernel, class... Args>

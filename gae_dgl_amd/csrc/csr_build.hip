@@ -21,8 +21,6 @@ __host__ __device__ inline int bits_for(int64_t n)
     return b;
 }
 
-inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
 // key = row << col_bits | col ; out-of-range ids are clamped and flagged
 __global__ __launch_bounds__(256) void pack_keys_kernel(const int64_t *__restrict__ row,
                                                         const int64_t *__restrict__ col, int64_t n_edges,
@@ -417,15 +415,22 @@ size_t sort_temp_bytes(int64_t n_edges, int end_bit)
     return bytes;
 }
 
+// THE workspace layout: two key arrays, then rocprim's sort scratch (its size depends, weakly, on the bit range: the
+// size query asks with the widest one, rounds it up and adds 256)
+struct SortWs { uint64_t *keys_a, *keys_b; void *temp; int64_t bytes; };
+SortWs sort_ws(gae::Carver c, int64_t n_edges, size_t temp_bytes)
+{
+    uint64_t *a = c.take<uint64_t>(n_edges), *b = c.take<uint64_t>(n_edges);
+    void *t = c.raw<char>(int64_t(temp_bytes));
+    return {a, b, t, c.bytes()};
+}
+
 } // namespace
 
 extern "C" int64_t gae_csr_from_coo_workspace_bytes(int64_t n_edges, int64_t n_rows)
 {
     if (n_edges < 0 || n_rows < 0) return GAE_E_SIZE;
-    (void)n_rows;
-    const int64_t keys = align_up(n_edges * 8, 256);
-    // temp size depends (weakly) on the bit range; query with the widest one
-    return 2 * keys + align_up(int64_t(sort_temp_bytes(n_edges > 0 ? n_edges : 1, 64)), 256) + 256;
+    return gae::up256(sort_ws(gae::Carver(nullptr), n_edges, sort_temp_bytes(n_edges > 0 ? n_edges : 1, 64)).bytes) + 256;
 }
 
 extern "C" int gae_csr_from_coo(const int64_t *row, const int64_t *col, int64_t n_edges, int64_t n_rows,
@@ -449,21 +454,16 @@ extern "C" int gae_csr_from_coo(const int64_t *row, const int64_t *col, int64_t 
     }
     const int col_bits = bits_for(n_cols);
     const int end_bit = col_bits + bits_for(n_rows);
-    const int64_t keys_bytes = align_up(n_edges * 8, 256);
     size_t temp_bytes = sort_temp_bytes(n_edges, end_bit);
-    GAE_REQUIRE(workspace_bytes >= 2 * keys_bytes + int64_t(temp_bytes), GAE_E_WORKSPACE,
-                "gae_csr_from_coo: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                (long long)(2 * keys_bytes + int64_t(temp_bytes)));
+    const SortWs w = sort_ws(gae::Carver(workspace), n_edges, temp_bytes);
+    GAE_REQUIRE(workspace_bytes >= w.bytes, GAE_E_WORKSPACE, "gae_csr_from_coo: workspace %lld < %lld bytes",
+                (long long)workspace_bytes, (long long)w.bytes);
     GAE_REQUIRE(gae::aligned16(workspace), GAE_E_ALIGN, "gae_csr_from_coo: workspace not 16-byte aligned");
-    char *ws = static_cast<char *>(workspace);
-    uint64_t *keys_a = reinterpret_cast<uint64_t *>(ws);
-    uint64_t *keys_b = reinterpret_cast<uint64_t *>(ws + keys_bytes);
-    void *temp = ws + 2 * keys_bytes;
     hipLaunchKernelGGL(pack_keys_kernel, dim3(grid_for(n_edges)), dim3(256), 0, s, row, col, n_edges, n_rows,
-                       n_cols, col_bits, keys_a, status_dev);
+                       n_cols, col_bits, w.keys_a, status_dev);
     GAE_CHECK_LAUNCH("pack_keys_kernel");
-    GAE_HIP(rocprim::radix_sort_keys(temp, temp_bytes, keys_a, keys_b, size_t(n_edges), 0u, unsigned(end_bit), s));
-    hipLaunchKernelGGL(unpack_fill_kernel, dim3(grid_for(n_edges)), dim3(256), 0, s, keys_b, n_edges, n_rows,
+    GAE_HIP(rocprim::radix_sort_keys(w.temp, temp_bytes, w.keys_a, w.keys_b, size_t(n_edges), 0u, unsigned(end_bit), s));
+    hipLaunchKernelGGL(unpack_fill_kernel, dim3(grid_for(n_edges)), dim3(256), 0, s, w.keys_b, n_edges, n_rows,
                        col_bits, indptr, indices);
     GAE_CHECK_LAUNCH("unpack_fill_kernel");
     return GAE_OK;

@@ -1534,22 +1534,28 @@ __global__ __launch_bounds__(1024) void bce_finalize_kernel(const gae_bce_tail t
     gae::bce_finalize_block<1024>(t, red);
 }
 
+struct BceWs {                    // the workspace regions of one call
+    float *O, *Zt, *S_all_f, *Wmir, *Omir;
+    float *s_walk;                // balanced schedule: the [n][16] sparse rows of its walk blocks (with the gradient)
+    unsigned short *Zhi, *Zlo;
+    double *cs, *S, *lp, *scal;   // scal: the padded batch's three scalars
+    unsigned *range_flag;         // the 4th scalar slot
+};
 struct BcePlan {
     int64_t row_blocks, n_splits, cols_per_split, edge_blocks, prep_blocks;
     int KS, DP, LPR;
-    int64_t o_bytes, zt_bytes, zh_bytes, cs_bytes, s_bytes, n_dense, total_bytes;
+    int64_t cs_bytes, n_dense, total_bytes;   // cs_bytes: the column-sum partials a producer may write (a size, read as one)
     double pad_terms;
     bool sym;                     // symmetric dense kernel (full square, d <= 16, bf16x3 products)
     int sym_pr;                   // its panel height (rows)
     int bal_tpb;                  // balanced schedule: column tiles per block (0 = the 2-D grid)
     int64_t bal_blocks;           // ... and the blocks that have tiles
-    int64_t wmir_bytes, omir_bytes;
-    int64_t sw_bytes;             // balanced schedule: the [n][16] sparse rows of its walk blocks (with the gradient)
+    int64_t wmir_floats;          // symmetric form: the mirror strips
+    BceWs w;                      // the regions in the workspace the plan was made for (NULL: all null)
 };
 
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
-
-bool bce_plan(int64_t n, int64_t n_local, int64_t d, BcePlan &p)
+// the launch shapes and THE workspace layout: the regions carved from `ws` for every entry point; NULL: only total_bytes
+bool bce_plan(int64_t n, int64_t n_local, int64_t d, void *ws, BcePlan &p)
 {
     const int64_t ROWS_PER_BLOCK = 64 * kBceRi;
     if (d > 64) return false;
@@ -1581,8 +1587,7 @@ bool bce_plan(int64_t n, int64_t n_local, int64_t d, BcePlan &p)
     p.sym_pr = 128;
     p.bal_tpb = 0;
     p.bal_blocks = 0;
-    p.wmir_bytes = p.omir_bytes = 0;
-    p.sw_bytes = 0;
+    p.wmir_floats = 0;
     // balanced schedule (round 6): every block the same number of column tiles, one resident round.  It removes the
     // quantisation of the 2-D grid into rounds of blocks, which is what kept 256-row panels from paying below ~32 k rows:
     // with it they win from ~5 k rows on (whole loss sequence, 2-D grid + 128-row panels -> balanced + 256-row panels:
@@ -1629,8 +1634,7 @@ bool bce_plan(int64_t n, int64_t n_local, int64_t d, BcePlan &p)
             p.cols_per_split = cpc;
             p.n_splits = (n + cpc - 1) / cpc;
             p.pad_terms = 0.0;                         // padded columns are corrected inside the kernel
-            p.wmir_bytes = align256(wfloats * 4);
-            p.omir_bytes = align256(n * 16 * 4);
+            p.wmir_floats = wfloats;
             if (bal) {
                 // balanced schedule (see the kernel): one sequence of W column tiles, tpb of them per block, all blocks
                 // resident at once; n_splits = the most partials any panel gets (the edge kernel derives a row's count
@@ -1647,20 +1651,29 @@ bool bce_plan(int64_t n, int64_t n_local, int64_t d, BcePlan &p)
                 p.bal_tpb = int(tpb);
                 p.bal_blocks = (W + tpb - 1) / tpb;
                 p.n_splits = most;
-                // the launch also walks the edges (blocks of 64 rows: edge_blocks, LPR = 4 at d <= 16) and leaves
-                // acc_in + acc_out of every row here for the combine
-                p.sw_bytes = align256(n * 16 * 4);
+                // the launch also walks the edges (blocks of 64 rows: edge_blocks, LPR = 4 at d <= 16): acc_in + acc_out to s_walk
             }
         }
     }
-    p.o_bytes = align256(p.n_splits * n_local * p.DP * 4);
-    p.zt_bytes = align256(n * p.DP * 4);
-    p.zh_bytes = align256(n * p.DP * 2);
-    p.cs_bytes = align256(((n + 15) / 16 + 1) * 2 * p.DP * 8);    // up to one partial per 16 rows (a producer kernel's blocks: gae_x_gcn_layer_fused_prep)
-    p.s_bytes = align256(2 * p.DP * 8 + p.DP * 4 + 4 * 8);       // column sums (double x 2, float) + 3 scalars
+    p.cs_bytes = gae::up256(((n + 15) / 16 + 1) * 2 * p.DP * 8);    // up to one partial per 16 rows (a producer kernel's blocks: gae_x_gcn_layer_fused_prep)
     p.n_dense = p.bal_tpb ? p.bal_blocks : p.row_blocks * p.n_splits;
-    p.total_bytes = p.o_bytes + p.zt_bytes + 2 * p.zh_bytes + p.cs_bytes + p.s_bytes +
-                    align256((2 * p.n_dense + p.edge_blocks) * 8) + p.wmir_bytes + p.omir_bytes + p.sw_bytes;
+    gae::Carver c(ws);
+    BceWs &w = p.w;
+    w.O = c.take<float>(p.n_splits * n_local * p.DP);
+    w.Zt = c.take<float>(n * p.DP);
+    w.Zhi = c.take<unsigned short>(n * p.DP);
+    w.Zlo = c.take<unsigned short>(n * p.DP);
+    w.cs = c.raw<double>(p.cs_bytes);
+    w.S = c.raw<double>(2 * p.DP * 8);                        // column sums (double x 2, float) + 4 scalar slots
+    w.S_all_f = c.raw<float>((p.DP * 4 + 7) & ~7);
+    w.scal = c.raw<double>(3 * 8);
+    w.range_flag = c.raw<unsigned>(8);
+    c.round();
+    w.lp = c.take<double>(2 * p.n_dense + p.edge_blocks);
+    w.Wmir = c.take<float>(p.wmir_floats);
+    w.Omir = c.take<float>(p.sym ? n * 16 : 0);
+    w.s_walk = c.take<float>(p.bal_tpb ? n * 16 : 0);
+    p.total_bytes = c.bytes();
     return true;
 }
 
@@ -1733,7 +1746,7 @@ extern "C" int64_t gae_decoder_bce_workspace_bytes(int64_t n, int64_t n_local, i
 {
     if (n < 0 || d < 0 || n_local < 0 || n_local > n) return GAE_E_SIZE;
     BcePlan p;
-    if (!bce_plan(n, n_local, d, p)) return GAE_E_RANGE;
+    if (!bce_plan(n, n_local, d, nullptr, p)) return GAE_E_RANGE;
     return p.total_bytes + 256;
 }
 
@@ -1770,7 +1783,7 @@ int decoder_bce_impl(const float *Z, float *mask, int64_t ldz, int64_t n, int64_
     GAE_REQUIRE((Z || prepared) && loss_out && workspace && (n_local == 0 || indptr), GAE_E_NULL, "gae_decoder_bce: NULL pointer");
     GAE_REQUIRE(!dZ || n_local == 0 || t_indptr, GAE_E_NULL, "gae_decoder_bce: the gradient needs the CSR of A^T");
     BcePlan p;
-    bce_plan(n, n_local, d, p);
+    bce_plan(n, n_local, d, workspace, p);
     GAE_REQUIRE(workspace_bytes >= p.total_bytes, GAE_E_WORKSPACE, "gae_decoder_bce: workspace %lld < %lld bytes",
                 (long long)workspace_bytes, (long long)p.total_bytes);
     if (prepared) {
@@ -1780,21 +1793,11 @@ int decoder_bce_impl(const float *Z, float *mask, int64_t ldz, int64_t n, int64_
     }
     GAE_REQUIRE(gae::aligned16(workspace), GAE_E_ALIGN, "gae_decoder_bce: workspace not 16-byte aligned");
     hipStream_t s = gae::as_stream(stream);
-    char *w = static_cast<char *>(workspace);
-    float *O = reinterpret_cast<float *>(w); w += p.o_bytes;
-    float *Zt = reinterpret_cast<float *>(w); w += p.zt_bytes;
-    unsigned short *Zhi = reinterpret_cast<unsigned short *>(w); w += p.zh_bytes;
-    unsigned short *Zlo = reinterpret_cast<unsigned short *>(w); w += p.zh_bytes;
-    double *cs = reinterpret_cast<double *>(w); w += p.cs_bytes;
-    double *S = reinterpret_cast<double *>(w);
-    float *S_all_f = reinterpret_cast<float *>(w + 2 * p.DP * 8);
-    double *scal = counts ? reinterpret_cast<double *>(w + 2 * p.DP * 8 + ((p.DP * 4 + 7) & ~7)) : nullptr;
-    unsigned *range_flag = reinterpret_cast<unsigned *>(w + 2 * p.DP * 8 + ((p.DP * 4 + 7) & ~7) + 3 * 8);   // the 4th scalar slot
-    w += p.s_bytes;
-    double *lp = reinterpret_cast<double *>(w); w += align256((2 * p.n_dense + p.edge_blocks) * 8);
-    float *Wmir = reinterpret_cast<float *>(w); w += p.wmir_bytes;
-    float *Omir = reinterpret_cast<float *>(w); w += p.omir_bytes;
-    float *s_walk = reinterpret_cast<float *>(w);
+    const BceWs &w = p.w;
+    float *O = w.O, *Zt = w.Zt, *S_all_f = w.S_all_f, *Wmir = w.Wmir, *Omir = w.Omir, *s_walk = w.s_walk;
+    unsigned short *Zhi = w.Zhi, *Zlo = w.Zlo;
+    double *cs = w.cs, *S = w.S, *scal = counts ? w.scal : nullptr, *lp = w.lp;
+    unsigned *range_flag = w.range_flag;
     const double inv_n2 = 1.0 / (double(n) * double(n));
     if (n_local == 0) {
         GAE_HIP(hipMemsetAsync(loss_out, 0, sizeof(float), s));
@@ -1932,16 +1935,11 @@ extern "C" int gae_x_decoder_bce_prep_layout(int64_t n, int64_t d, void *workspa
     GAE_REQUIRE(out && workspace, GAE_E_NULL, "gae_x_decoder_bce_prep_layout: NULL pointer");
     GAE_REQUIRE(n > 0 && d > 0 && d <= 64, GAE_E_RANGE, "gae_x_decoder_bce_prep_layout: n, d out of range");
     BcePlan p;
-    bce_plan(n, n, d, p);
+    bce_plan(n, n, d, workspace, p);
     GAE_REQUIRE(workspace_bytes >= p.total_bytes && gae::aligned16(workspace), GAE_E_WORKSPACE,
                 "gae_x_decoder_bce_prep_layout: workspace %lld < %lld bytes (or not 16-byte aligned)",
                 (long long)workspace_bytes, (long long)p.total_bytes);
-    char *w = static_cast<char *>(workspace) + p.o_bytes;
-    out->Zt = reinterpret_cast<float *>(w); w += p.zt_bytes;
-    out->Zhi = reinterpret_cast<uint16_t *>(w); w += p.zh_bytes;
-    out->Zlo = reinterpret_cast<uint16_t *>(w); w += p.zh_bytes;
-    out->colsum_partial = reinterpret_cast<double *>(w); w += p.cs_bytes;
-    out->scal = reinterpret_cast<double *>(w + 2 * p.DP * 8 + ((p.DP * 4 + 7) & ~7));
+    out->Zt = p.w.Zt; out->Zhi = p.w.Zhi; out->Zlo = p.w.Zlo; out->colsum_partial = p.w.cs; out->scal = p.w.scal;
     out->all_pairs = bce_all_pairs(p, n, n);
     out->max_blocks = p.cs_bytes / (2 * p.DP * 8);
     out->DP = p.DP;

@@ -515,31 +515,25 @@ __global__ void sampled_empty_kernel(float *loss_out, uint64_t *draw_dev)
     if (draw_dev) *draw_dev += 1;
 }
 
-int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
-
-struct SLayout {
-    int DP, n_tiles, n_b3;
-    int64_t cap, zt, tile_cnt, tile_base, hdr, block_loss, heavy, chunk_slot, cpart, closs, hloss, total;
-};
-
-void sampled_layout(int64_t n, int64_t n_local, int64_t d, SLayout &l)
+// THE workspace layout: the launch shapes and regions of `a`, carved from `c`; the bytes walked are the size (no slack).
+// hdr is a fixed 256 bytes.
+int64_t sampled_layout(int64_t n, int64_t n_local, int64_t d, gae::Carver c, SArgs &a)
 {
-    l.DP = int((d + 3) / 4 * 4);
-    l.n_tiles = int((n_local + kTileRows - 1) / kTileRows);
-    l.n_b3 = int((n_local + kBlockRows - 1) / kBlockRows);
-    l.cap = n_local / 16 + 1024;
-    int64_t o = 0;
-    l.zt = o; o += align256(n * l.DP * 4);
-    l.tile_cnt = o; o += align256(int64_t(l.n_tiles) * 2 * kLevels * 4);
-    l.tile_base = o; o += align256(int64_t(l.n_tiles) * 2 * 8);
-    l.hdr = o; o += 256;
-    l.block_loss = o; o += align256(int64_t(l.n_b3) * 8);
-    l.heavy = o; o += align256(l.cap * 3 * 8);
-    l.chunk_slot = o; o += align256(l.cap * 4);
-    l.cpart = o; o += align256(l.cap * l.DP * 4);
-    l.closs = o; o += align256(l.cap * 8);
-    l.hloss = o; o += align256(l.cap * 8);
-    l.total = o;
+    a.DP = int((d + 3) / 4 * 4);
+    a.n_tiles = int((n_local + kTileRows - 1) / kTileRows);
+    a.n_b3 = int((n_local + kBlockRows - 1) / kBlockRows);
+    a.cap = n_local / 16 + 1024;
+    a.Zt = c.take<float>(n * a.DP);
+    a.tile_cnt = c.take<int32_t>(int64_t(a.n_tiles) * 2 * kLevels);
+    a.tile_base = c.take<int64_t>(int64_t(a.n_tiles) * 2);
+    a.hdr = c.raw<int64_t>(256);
+    a.block_loss = c.take<double>(a.n_b3);
+    a.heavy = c.take<int64_t>(a.cap * 3);
+    a.chunk_slot = c.take<int32_t>(a.cap);
+    a.cpart = c.take<float>(a.cap * a.DP);
+    a.closs = c.take<double>(a.cap);
+    a.hloss = c.take<double>(a.cap);
+    return c.bytes();
 }
 
 template <int G>
@@ -578,16 +572,16 @@ extern "C" int gae_decoder_bce_sampled(const float *Z, float *mask, int64_t ldz,
     GAE_REQUIRE(!dZ || n_local == 0 || t_indptr, GAE_E_NULL,
                 "gae_decoder_bce_sampled: the gradient needs the CSR of A^T");
     GAE_REQUIRE(workspace_bytes, GAE_E_NULL, "gae_decoder_bce_sampled: workspace_bytes is NULL");
-    SLayout l;
-    sampled_layout(n, n_local, d, l);
+    SArgs a;
+    const int64_t total = sampled_layout(n, n_local, d, gae::Carver(workspace), a);
     if (!workspace) {                               // size query: no device work
-        *workspace_bytes = l.total;
+        *workspace_bytes = total;
         return GAE_OK;
     }
     GAE_REQUIRE(dropout_p == 0.f || mask, GAE_E_NULL, "gae_decoder_bce_sampled: dropout_p > 0 needs the mask output buffer");
     GAE_REQUIRE(Z && loss_out && (n_local == 0 || indptr), GAE_E_NULL, "gae_decoder_bce_sampled: NULL pointer");
-    GAE_REQUIRE(*workspace_bytes >= l.total, GAE_E_WORKSPACE, "gae_decoder_bce_sampled: workspace of %lld bytes, %lld needed",
-                (long long)*workspace_bytes, (long long)l.total);
+    GAE_REQUIRE(*workspace_bytes >= total, GAE_E_WORKSPACE, "gae_decoder_bce_sampled: workspace of %lld bytes, %lld needed",
+                (long long)*workspace_bytes, (long long)total);
     GAE_REQUIRE(gae::aligned16(workspace), GAE_E_ALIGN, "gae_decoder_bce_sampled: workspace not 16-byte aligned");
     hipStream_t s = gae::as_stream(stream);
     if (n_local == 0) {
@@ -595,38 +589,25 @@ extern "C" int gae_decoder_bce_sampled(const float *Z, float *mask, int64_t ldz,
         GAE_CHECK_LAUNCH("sampled_empty_kernel");
         return GAE_OK;
     }
-    char *w = static_cast<char *>(workspace);
-    SArgs a;
-    a.Z = Z; a.mask = mask; a.ldz = ldz; a.n = int(n); a.d = int(d); a.DP = l.DP; a.m = int(m);
+    a.Z = Z; a.mask = mask; a.ldz = ldz; a.n = int(n); a.d = int(d); a.m = int(m);
     a.row_begin = row_begin; a.n_local = int(n_local);
     a.indptr = indptr; a.indices = indices; a.t_indptr = t_indptr; a.t_indices = t_indices;
     a.pw = pos_weight; a.drop_p = dropout_p; a.drop_scale = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.f;
     a.inv_n2 = 1.0 / (double(n) * double(n)); a.inv_n2f = float(a.inv_n2);
     a.seed = seed; a.offset = offset; a.draw_dev = draw_dev;
     a.loss_out = loss_out; a.dZ = dZ; a.lddz = lddz; a.partners_out = partners_out; a.grad = dZ != nullptr;
-    a.Zt = reinterpret_cast<float *>(w + l.zt);
-    a.tile_cnt = reinterpret_cast<int32_t *>(w + l.tile_cnt);
-    a.tile_base = reinterpret_cast<int64_t *>(w + l.tile_base);
-    a.hdr = reinterpret_cast<int64_t *>(w + l.hdr);
-    a.block_loss = reinterpret_cast<double *>(w + l.block_loss);
-    a.heavy = reinterpret_cast<int64_t *>(w + l.heavy);
-    a.chunk_slot = reinterpret_cast<int32_t *>(w + l.chunk_slot);
-    a.cpart = reinterpret_cast<float *>(w + l.cpart);
-    a.closs = reinterpret_cast<double *>(w + l.closs);
-    a.hloss = reinterpret_cast<double *>(w + l.hloss);
-    a.cap = l.cap; a.n_tiles = l.n_tiles; a.n_b3 = l.n_b3;
-    const int64_t prep_blocks = (n * l.DP + kPrepElems - 1) / kPrepElems;
-    const int64_t g1 = prep_blocks > l.n_tiles ? prep_blocks : l.n_tiles;
+    const int64_t prep_blocks = (n * a.DP + kPrepElems - 1) / kPrepElems;
+    const int64_t g1 = prep_blocks > a.n_tiles ? prep_blocks : a.n_tiles;
     GAE_REQUIRE(g1 < (int64_t(1) << 31), GAE_E_SIZE, "gae_decoder_bce_sampled: grid too large");
     hipLaunchKernelGGL(sampled_prep_count_kernel, dim3(unsigned(g1)), dim3(256), 0, s, a, int(prep_blocks));
     GAE_CHECK_LAUNCH("sampled_prep_count_kernel");
     hipLaunchKernelGGL(sampled_scan_kernel, dim3(1), dim3(1024), 0, s, a);
     GAE_CHECK_LAUNCH("sampled_scan_kernel");
-    hipLaunchKernelGGL(sampled_place_kernel, dim3(unsigned(l.n_tiles)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(sampled_place_kernel, dim3(unsigned(a.n_tiles)), dim3(256), 0, s, a);
     GAE_CHECK_LAUNCH("sampled_place_kernel");
-    const int64_t waves_cap = (l.cap + 3) / 4;
+    const int64_t waves_cap = (a.cap + 3) / 4;
     const int grid4 = int(waves_cap < 4096 ? waves_cap : 4096), grid5 = int(waves_cap < 1024 ? waves_cap : 1024);
-    const int G = l.DP <= 4 ? 1 : l.DP <= 8 ? 2 : l.DP <= 16 ? 4 : l.DP <= 32 ? 8 : 16;
+    const int G = a.DP <= 4 ? 1 : a.DP <= 8 ? 2 : a.DP <= 16 ? 4 : a.DP <= 32 ? 8 : 16;
     int rc;
     switch (G) {
     case 1: rc = launch_pairs<1>(a, s, grid4, grid5); break;

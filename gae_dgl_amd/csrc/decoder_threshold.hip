@@ -227,10 +227,10 @@ __global__ __launch_bounds__(kScanThreads) void threshold_scan_add_kernel(const 
 struct Layout {
     int S;
     int64_t panels, M, nb, need;
-    int64_t offset_at, sums_at, count_at;          // bytes into the workspace
+    int64_t *offset, *block_sum; int32_t *count;   // the workspace regions (NULL for the size query)
 };
 
-int plan(const char *fn, const Request &r, float threshold, int64_t splits_arg, Layout &L)
+int plan(const char *fn, const Request &r, float threshold, int64_t splits_arg, void *ws, Layout &L)
 {
     GAE_REQUIRE(threshold == threshold, GAE_E_RANGE, "%s: threshold is NaN", fn);
     GAE_REQUIRE(splits_arg >= 0 && splits_arg <= kMaxSplits, GAE_E_RANGE, "%s: splits = %lld outside 0..16", fn,
@@ -240,21 +240,21 @@ int plan(const char *fn, const Request &r, float threshold, int64_t splits_arg, 
     L.S = splits(L.panels, r.n, r.node_ptr, r.max_graph_nodes, int(splits_arg));
     L.M = r.n * L.S;
     L.nb = (L.M + kScanBlock - 1) / kScanBlock;
-    L.offset_at = 256;
-    L.sums_at = L.offset_at + 8 * L.M;
-    L.count_at = L.sums_at + 8 * (L.nb + 1);
-    L.need = (L.count_at + 4 * L.M + 255) / 256 * 256;
+    gae::Carver c(ws);                             // THE layout: behind 256 bytes, three regions packed at 8-byte steps
+    c.raw<char>(256);
+    L.offset = c.raw<int64_t>(8 * L.M);
+    L.block_sum = c.raw<int64_t>(8 * (L.nb + 1));
+    L.count = c.raw<int32_t>(4 * L.M);
+    c.round();
+    L.need = c.bytes();
     return GAE_OK;
 }
 
-void fill_args(ThresholdArgs &a, const Request &r, const Layout &L, float threshold, void *workspace)
+void fill_args(ThresholdArgs &a, const Request &r, const Layout &L, float threshold)
 {
     fill(a, r, L.S);
-    char *ws = static_cast<char *>(workspace);
     a.threshold = threshold;
-    a.offset = reinterpret_cast<int64_t *>(ws + L.offset_at);
-    a.block_sum = reinterpret_cast<int64_t *>(ws + L.sums_at);
-    a.count = reinterpret_cast<int32_t *>(ws + L.count_at);
+    a.offset = L.offset; a.block_sum = L.block_sum; a.count = L.count;
     a.M = L.M; a.nb = L.nb;
     a.row_ptr_out = nullptr; a.index_out = nullptr; a.score_out = nullptr; a.capacity = 0;
 }
@@ -270,7 +270,7 @@ extern "C" int gae_decoder_threshold_count(const float *Z, int64_t ldz, int64_t 
     const char *fn = "gae_decoder_threshold_count";
     const Request r{Z, ldz, n, d, node_ptr, n_graphs, max_graph_nodes, indptr, indices, flags, workspace_bytes};
     Layout L;
-    if (const int rc = plan(fn, r, threshold, splits, L)) return rc;
+    if (const int rc = plan(fn, r, threshold, splits, workspace, L)) return rc;
     if (!workspace) {                               // size query: no device work
         *workspace_bytes = L.need;
         return GAE_OK;
@@ -278,7 +278,7 @@ extern "C" int gae_decoder_threshold_count(const float *Z, int64_t ldz, int64_t 
     GAE_REQUIRE(row_ptr_out, GAE_E_NULL, "%s: row_ptr_out is NULL", fn);
     if (const int rc = check_arrays(fn, r, L.need)) return rc;
     ThresholdArgs a;
-    fill_args(a, r, L, threshold, workspace);
+    fill_args(a, r, L, threshold);
     a.row_ptr_out = row_ptr_out;
     hipStream_t st = gae::as_stream(stream);
     if (n > 0) {
@@ -305,7 +305,7 @@ extern "C" int gae_decoder_threshold_fill(const float *Z, int64_t ldz, int64_t n
     const char *fn = "gae_decoder_threshold_fill";
     const Request r{Z, ldz, n, d, node_ptr, n_graphs, max_graph_nodes, indptr, indices, flags, workspace_bytes};
     Layout L;
-    if (const int rc = plan(fn, r, threshold, splits, L)) return rc;
+    if (const int rc = plan(fn, r, threshold, splits, workspace, L)) return rc;
     if (!workspace) {                               // size query: no device work
         *workspace_bytes = L.need;
         return GAE_OK;
@@ -316,7 +316,7 @@ extern "C" int gae_decoder_threshold_fill(const float *Z, int64_t ldz, int64_t n
     if (const int rc = check_arrays(fn, r, L.need)) return rc;
     if (n == 0 || capacity == 0) return GAE_OK;
     ThresholdArgs a;
-    fill_args(a, r, L, threshold, workspace);
+    fill_args(a, r, L, threshold);
     a.index_out = index_out; a.score_out = score_out; a.capacity = capacity;
     hipStream_t st = gae::as_stream(stream);
     dispatch(d, [&](auto dh, auto one) {

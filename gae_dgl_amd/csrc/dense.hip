@@ -1584,7 +1584,7 @@ extern "C" int64_t gae_linear_fwd_workspace_bytes(int64_t n, int64_t f_in, int64
 {
     if (n < 0 || f_in < 0 || f_out < 0 || f_in >= (1 << 24)) return GAE_E_SIZE;
     const int sp = f_out <= 128 ? gemm_stream_splits(n, int(f_in)) : 1;
-    const int64_t old = sp > 1 ? (int64_t(sp) * n * f_out * 4 + 255) / 256 * 256 : 0;
+    const int64_t old = sp > 1 ? gae::up256(int64_t(sp) * n * f_out * 4) : 0;
     const int64_t xw = (f_out >= 1 && f_out <= 32 && f_in >= 64 && n > 0) ? gae::xw_fwd_workspace_bytes(n, f_in, f_out, 4) : 0;
     return old > xw ? old : xw;
 }
@@ -1613,13 +1613,13 @@ extern "C" int gae_linear_fwd(const float *M, int64_t ldm, int64_t n, int64_t f_
                                                 workspace ? workspace_bytes / 4 : 0);
 }
 
-static int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
+static int64_t atb_partial_bytes(const AtbPlan &pl) { return gae::up256(pl.n_slots * pl.slot_stride * 4); }   // an A^T B launch's partial slots
 
 extern "C" int64_t gae_linear_bwd_workspace_bytes(int64_t n, int64_t f_in, int64_t f_out)
 {
     if (n < 0 || f_in < 0 || f_out < 0) return GAE_E_SIZE;
     const AtbPlan pl = atb_plan(n, f_out, f_in);
-    return align256(pl.n_slots * pl.slot_stride * 4) + 256;
+    return atb_partial_bytes(pl) + 256;
 }
 
 extern "C" int gae_x_linear_bwd_partials(const float *dY, int64_t lddy, const float *Y, int64_t ldy, int act, const float *M,
@@ -1633,7 +1633,7 @@ extern "C" int gae_x_linear_bwd_partials(const float *dY, int64_t lddy, const fl
     GAE_REQUIRE(act != GAE_ACT_RELU || (Y && ldy >= f_out), GAE_E_NULL, "gae_x_linear_bwd_partials: RELU needs Y");
     GAE_REQUIRE(!want_dW || (M && ldm >= f_in && f_in > 0), GAE_E_NULL, "gae_x_linear_bwd_partials: dW needs M");
     const AtbPlan pl = atb_plan(n, f_out, f_in);
-    const int64_t need = align256(pl.n_slots * pl.slot_stride * 4);
+    const int64_t need = atb_partial_bytes(pl);
     GAE_REQUIRE(workspace && workspace_bytes >= need && gae::aligned16(workspace), GAE_E_WORKSPACE,
                 "gae_x_linear_bwd_partials: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
     const bool relu = act == GAE_ACT_RELU;
@@ -1667,7 +1667,7 @@ extern "C" int gae_linear_bwd(const float *dY, int64_t lddy, const float *Y, int
     if (dW || db) {
         GAE_REQUIRE(!dW || (ldm >= f_in && (n == 0 || M)), GAE_E_NULL, "gae_linear_bwd: dW needs M");
         const AtbPlan pl = atb_plan(n, f_out, f_in);
-        const int64_t need = align256(pl.n_slots * pl.slot_stride * 4) + 256;      // gae_linear_bwd_workspace_bytes
+        const int64_t need = atb_partial_bytes(pl) + 256;
         GAE_REQUIRE(workspace && workspace_bytes >= need, GAE_E_WORKSPACE,
                     "gae_linear_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
         GAE_REQUIRE(gae::aligned16(workspace), GAE_E_ALIGN, "gae_linear_bwd: workspace not 16-byte aligned");
@@ -1736,7 +1736,7 @@ extern "C" int64_t gae_decoder_dense_bwd_workspace_bytes(int64_t n, int64_t d)
 {
     if (n < 0 || d < 0) return GAE_E_SIZE;
     const AtbPlan pl = atb_plan(n, d, n);
-    return align256(pl.n_slots * pl.slot_stride * 4) + 256;
+    return atb_partial_bytes(pl) + 256;
 }
 
 extern "C" int gae_decoder_dense_bwd(const float *G, int64_t ldg, const float *Z, const float *mask, int64_t ldz,
@@ -1750,7 +1750,7 @@ extern "C" int gae_decoder_dense_bwd(const float *G, int64_t ldg, const float *Z
     GAE_REQUIRE(G && Z && dZ, GAE_E_NULL, "gae_decoder_dense_bwd: NULL pointer");
     hipStream_t s = gae::as_stream(stream);
     const AtbPlan pl = atb_plan(n, d, n);
-    const int64_t need = align256(pl.n_slots * pl.slot_stride * 4);
+    const int64_t need = atb_partial_bytes(pl);
     GAE_REQUIRE(workspace && workspace_bytes >= need, GAE_E_WORKSPACE,
                 "gae_decoder_dense_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
     int rc;

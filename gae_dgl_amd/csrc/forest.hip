@@ -650,9 +650,17 @@ __global__ __launch_bounds__(kThreads) void forest_predict_kernel(const PredictA
 // ------------------------------------------------------------------------------------------------------ host
 struct Plan {
     int64_t M, max_items, max_chunks, max_long, ft, nft, need;
-    int64_t o_yq, o_sum, o_pos, o_seg, o_items, o_chunks, o_split, o_curs, o_score, o_fb, o_nl, o_sl, o_gcnt, o_gsum, o_info,
-        o_lvl;
+    int32_t *pos[2], *split[2];                             // the ping-pong halves of the level lists, each pair one region
+    Item *items[2];
+    Chunk *chunks[2];
 };
+
+template <class T>
+void take_halves(gae::Carver &c, T *(&two)[2], int64_t half)
+{
+    two[0] = c.take<T>(2 * half);
+    two[1] = two[0] ? two[0] + half : nullptr;
+}
 
 int64_t node_capacity(int64_t n_boot, int64_t max_depth)
 {
@@ -660,8 +668,10 @@ int64_t node_capacity(int64_t n_boot, int64_t max_depth)
     return by_depth < by_rows ? by_depth : by_rows;
 }
 
+// the checks, the sizes and THE workspace layout: on ws = NULL the regions are only counted (p.need), on the caller's buffer
+// they are bound into `a` and the halves of `p`
 int plan(const char *fn, int64_t n_used, int64_t d, int64_t t, int64_t T, int64_t n_boot, int64_t max_depth, int64_t bins,
-         Plan &p)
+         void *ws, Plan &p, FitArgs &a)
 {
     GAE_REQUIRE(d >= 1 && d <= kMaxD, GAE_E_RANGE, "%s: d = %lld outside 1..256", fn, (long long)d);
     GAE_REQUIRE(t >= 1 && t <= kMaxT, GAE_E_RANGE, "%s: t = %lld outside 1..8", fn, (long long)t);
@@ -684,25 +694,24 @@ int plan(const char *fn, int64_t n_used, int64_t d, int64_t t, int64_t T, int64_
     GAE_REQUIRE(p.max_chunks * p.nft < (int64_t(1) << 31), GAE_E_SIZE,
                 "%s: %lld trees of %lld samples in %lld feature tiles are beyond a grid of 2^31 blocks", fn, (long long)T,
                 (long long)n_boot, (long long)p.nft);
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = o; o += up256(bytes); return at; };
-    p.o_yq = take(n_used * t * 8);
-    p.o_sum = take(T * p.M * t * 8);
-    p.o_pos = take(2 * T * n_boot * 4);
-    p.o_seg = take(T * p.M * 4);
-    p.o_items = take(2 * p.max_items * 16);
-    p.o_chunks = take(2 * p.max_chunks * 8);
-    p.o_split = take(2 * p.max_long * 4);
-    p.o_curs = take(p.max_items * 8);
-    p.o_score = take(p.max_items * p.nft * 8);
-    p.o_fb = take(p.max_items * p.nft * 8);
-    p.o_nl = take(p.max_items * p.nft * 4);
-    p.o_sl = take(p.max_items * p.nft * t * 8);
-    p.o_gcnt = take(p.max_long * d * bins * 4);
-    p.o_gsum = take(p.max_long * d * bins * t * 8);
-    p.o_info = take(T * int64_t(sizeof(TreeInfo)));
-    p.o_lvl = take(sizeof(Level));
-    p.need = o + 256;
+    gae::Carver c(ws);
+    a.yq = c.take<i64>(n_used * t);
+    a.node_sum = c.take<i64>(T * p.M * t);
+    take_halves(c, p.pos, T * n_boot);
+    a.seg_start = c.take<int32_t>(T * p.M);
+    take_halves(c, p.items, p.max_items);
+    take_halves(c, p.chunks, p.max_chunks);
+    take_halves(c, p.split, p.max_long);
+    a.curs = c.take<int2>(p.max_items);
+    a.cand_score = c.take<double>(p.max_items * p.nft);
+    a.cand_fb = c.take<int2>(p.max_items * p.nft);
+    a.cand_nl = c.take<int32_t>(p.max_items * p.nft);
+    a.cand_sl = c.take<i64>(p.max_items * p.nft * t);
+    a.gcnt = c.take<unsigned>(p.max_long * d * bins);
+    a.gsum = c.take<i64>(p.max_long * d * bins * t);
+    a.info = c.take<TreeInfo>(T);
+    a.lvl = c.take<Level>(1);
+    p.need = c.bytes() + 256;
     return GAE_OK;
 }
 
@@ -712,7 +721,9 @@ extern "C" int64_t gae_forest_workspace_bytes(int64_t n_used, int64_t d, int64_t
                                               int64_t max_depth, int64_t max_bins)
 {
     Plan p;
-    if (const int rc = plan("gae_forest_workspace_bytes", n_used, d, t, n_trees, n_boot, max_depth, max_bins, p)) return rc;
+    FitArgs a;
+    if (const int rc = plan("gae_forest_workspace_bytes", n_used, d, t, n_trees, n_boot, max_depth, max_bins, nullptr, p, a))
+        return rc;
     return p.need;
 }
 
@@ -753,7 +764,8 @@ extern "C" int gae_forest_fit(const uint8_t *codes, const int32_t *n_edges, cons
 {
     const char *fn = "gae_forest_fit";
     Plan p;
-    if (const int rc = plan(fn, n_used, d, t, n_trees, n_boot, max_depth, max_bins, p)) return rc;
+    FitArgs a;
+    if (const int rc = plan(fn, n_used, d, t, n_trees, n_boot, max_depth, max_bins, workspace, p, a)) return rc;
     GAE_REQUIRE(max_features >= 1 && max_features <= d, GAE_E_RANGE, "%s: max_features = %lld outside 1..d = %lld", fn,
                 (long long)max_features, (long long)d);
     GAE_REQUIRE(min_samples_leaf >= 1 && min_samples_leaf < (int64_t(1) << 30), GAE_E_RANGE,
@@ -778,8 +790,6 @@ extern "C" int gae_forest_fit(const uint8_t *codes, const int32_t *n_edges, cons
         GAE_REQUIRE(exponent[j] >= -200 && exponent[j] <= 200 && fabsf(pivot[j]) <= FLT_MAX, GAE_E_RANGE,
                     "%s: exponent[%d] = %d outside -200..200 or a non-finite pivot", fn, j, exponent[j]);
 
-    char *ws = static_cast<char *>(workspace);
-    FitArgs a;
     a.codes = codes; a.n_edges = n_edges; a.edges = edges; a.Y = Y; a.rows = rows; a.ldy = ldy;
     a.n = int(n); a.n_used = int(n_used); a.d = int(d); a.t = int(t); a.bins = int(max_bins); a.T = int(n_trees);
     a.n_boot = int(n_boot); a.max_depth = int(max_depth); a.m_feat = int(max_features); a.msl = int(min_samples_leaf);
@@ -792,27 +802,11 @@ extern "C" int gae_forest_fit(const uint8_t *codes, const int32_t *n_edges, cons
     }
     a.feature = feature; a.bin = threshold_bin; a.left = left; a.count = count; a.n_nodes = n_nodes;
     a.threshold = threshold; a.value = value; a.gain = gain; a.inbag = inbag; a.status = status;
-    a.yq = reinterpret_cast<i64 *>(ws + p.o_yq);
-    a.node_sum = reinterpret_cast<i64 *>(ws + p.o_sum);
-    int32_t *pos[2] = {reinterpret_cast<int32_t *>(ws + p.o_pos), reinterpret_cast<int32_t *>(ws + p.o_pos) + n_trees * n_boot};
-    a.seg_start = reinterpret_cast<int32_t *>(ws + p.o_seg);
-    Item *items[2] = {reinterpret_cast<Item *>(ws + p.o_items), reinterpret_cast<Item *>(ws + p.o_items) + p.max_items};
-    Chunk *chunks[2] = {reinterpret_cast<Chunk *>(ws + p.o_chunks), reinterpret_cast<Chunk *>(ws + p.o_chunks) + p.max_chunks};
-    int32_t *split[2] = {reinterpret_cast<int32_t *>(ws + p.o_split), reinterpret_cast<int32_t *>(ws + p.o_split) + p.max_long};
-    a.curs = reinterpret_cast<int2 *>(ws + p.o_curs);
-    a.cand_score = reinterpret_cast<double *>(ws + p.o_score);
-    a.cand_fb = reinterpret_cast<int2 *>(ws + p.o_fb);
-    a.cand_nl = reinterpret_cast<int32_t *>(ws + p.o_nl);
-    a.cand_sl = reinterpret_cast<i64 *>(ws + p.o_sl);
-    a.gcnt = reinterpret_cast<unsigned *>(ws + p.o_gcnt);
-    a.gsum = reinterpret_cast<i64 *>(ws + p.o_gsum);
-    a.info = reinterpret_cast<TreeInfo *>(ws + p.o_info);
-    a.lvl = reinterpret_cast<Level *>(ws + p.o_lvl);
     auto side = [&](int cur) {
-        a.pos_in = pos[cur]; a.pos_out = pos[cur ^ 1];
-        a.items_cur = items[cur]; a.items_next = items[cur ^ 1];
-        a.chunks_cur = chunks[cur]; a.chunks_next = chunks[cur ^ 1];
-        a.split_cur = split[cur]; a.split_next = split[cur ^ 1];
+        a.pos_in = p.pos[cur]; a.pos_out = p.pos[cur ^ 1];
+        a.items_cur = p.items[cur]; a.items_next = p.items[cur ^ 1];
+        a.chunks_cur = p.chunks[cur]; a.chunks_next = p.chunks[cur ^ 1];
+        a.split_cur = p.split[cur]; a.split_next = p.split[cur ^ 1];
     };
     side(0);
     hipStream_t st = gae::as_stream(stream);

@@ -60,14 +60,20 @@ struct Plan {
     size_t assign_lds, sums_lds;
     int64_t R, P;                      // sums: rows per block, blocks
     int64_t seed_rows, seed_blocks;
-    int64_t dist2_at, changed_at, psum_at, pcount_at, pinertia_at, shift_at, empty_at, cand_at, need;
+    // the workspace regions (NULL when the plan was made for the size query) and their total
+    float *dist2, *psum;               // dist2 of a step; mind2 of the seeding
+    int32_t *changed_part, *pcount, *empty_c;
+    double *pinertia, *shift_c;
+    Cand *cand;                        // the seeding's two candidate lists
+    int64_t need;
 };
 
 using gae::cdiv;
 using gae::launch_lds;
 using gae::up256;
 
-int plan(const char *fn, int64_t n, int64_t d, int64_t k, Plan &p)
+// the checks, the launch shapes and THE workspace layout, carved from `ws` (NULL: counted only)
+int plan(const char *fn, int64_t n, int64_t d, int64_t k, void *ws, Plan &p)
 {
     GAE_REQUIRE(d >= 1 && d <= kMaxD, GAE_E_RANGE, "%s: d = %lld outside 1..64", fn, (long long)d);
     GAE_REQUIRE(k >= 1 && k <= kMaxK, GAE_E_RANGE, "%s: k = %lld outside 1..256", fn, (long long)k);
@@ -91,15 +97,16 @@ int plan(const char *fn, int64_t n, int64_t d, int64_t k, Plan &p)
     // sized by bounds of P and the seeding grid that never shrink as n grows: the query is monotone in n
     const int64_t pmax = cdiv(n, kSumRows) < kSumBlocks ? cdiv(n, kSumRows) : kSumBlocks;
     const int64_t smax = sb < kSeedBlocks ? sb : kSeedBlocks;
-    p.dist2_at = 0;                                        // dist2 of a step; mind2 of the seeding
-    p.changed_at = up256(p.dist2_at + 4 * n);
-    p.psum_at = up256(p.changed_at + 4 * int64_t(2 * kNumCu));
-    p.pcount_at = up256(p.psum_at + 4 * pmax * k * d);
-    p.pinertia_at = up256(p.pcount_at + 4 * pmax * k);
-    p.shift_at = up256(p.pinertia_at + 8 * pmax);
-    p.empty_at = up256(p.shift_at + 8 * k);
-    p.cand_at = up256(p.empty_at + 4 * k);
-    p.need = up256(p.cand_at + 2 * int64_t(sizeof(Cand)) * smax);
+    gae::Carver c(ws);
+    p.dist2 = c.take<float>(n);
+    p.changed_part = c.take<int32_t>(2 * kNumCu);
+    p.psum = c.take<float>(pmax * k * d);
+    p.pcount = c.take<int32_t>(pmax * k);
+    p.pinertia = c.take<double>(pmax);
+    p.shift_c = c.take<double>(k);
+    p.empty_c = c.take<int32_t>(k);
+    p.cand = c.take<Cand>(2 * smax);
+    p.need = c.bytes();
     return GAE_OK;
 }
 
@@ -461,7 +468,7 @@ int check_x(const char *fn, const float *X, int64_t ldx, int64_t d, const void *
 extern "C" int64_t gae_kmeans_workspace_bytes(int64_t n, int64_t d, int64_t k)
 {
     Plan p;
-    if (const int rc = plan("gae_kmeans_workspace_bytes", n, d, k, p)) return rc;
+    if (const int rc = plan("gae_kmeans_workspace_bytes", n, d, k, nullptr, p)) return rc;
     return p.need;
 }
 
@@ -471,7 +478,7 @@ extern "C" int gae_kmeans_assign(const float *X, int64_t ldx, int64_t n, int64_t
 {
     const char *fn = "gae_kmeans_assign";
     Plan p;
-    if (const int rc = plan(fn, n, d, k, p)) return rc;
+    if (const int rc = plan(fn, n, d, k, workspace, p)) return rc;
     if (const int rc = check_x(fn, X, ldx, d, workspace, workspace_bytes, p)) return rc;
     GAE_REQUIRE(C && labels_out, GAE_E_NULL, "%s: C / labels_out is NULL", fn);
     const AssignArgs a{X, ldx, int(n), int(d), int(k), p.ktiles, p.panels, C, labels_out, dist2_out, nullptr, nullptr};
@@ -484,31 +491,23 @@ extern "C" int gae_kmeans_step(const float *X, int64_t ldx, int64_t n, int64_t d
 {
     const char *fn = "gae_kmeans_step";
     Plan p;
-    if (const int rc = plan(fn, n, d, k, p)) return rc;
+    if (const int rc = plan(fn, n, d, k, workspace, p)) return rc;
     GAE_REQUIRE(flags == 0, GAE_E_RANGE, "%s: unknown flags 0x%x", fn, flags);
     GAE_REQUIRE(tol_abs == tol_abs, GAE_E_RANGE, "%s: tol_abs is NaN", fn);
     if (const int rc = check_x(fn, X, ldx, d, workspace, workspace_bytes, p)) return rc;
     GAE_REQUIRE(C && labels && status, GAE_E_NULL, "%s: C / labels / status is NULL", fn);
-    char *ws = static_cast<char *>(workspace);
-    float *dist2 = reinterpret_cast<float *>(ws + p.dist2_at);
-    int32_t *changed_part = reinterpret_cast<int32_t *>(ws + p.changed_at);
-    float *psum = reinterpret_cast<float *>(ws + p.psum_at);
-    int32_t *pcount = reinterpret_cast<int32_t *>(ws + p.pcount_at);
-    double *pinertia = reinterpret_cast<double *>(ws + p.pinertia_at);
-    double *shift_c = reinterpret_cast<double *>(ws + p.shift_at);
-    int32_t *empty_c = reinterpret_cast<int32_t *>(ws + p.empty_at);
     hipStream_t st = gae::as_stream(stream);
 
-    const AssignArgs aa{X, ldx, int(n), int(d), int(k), p.ktiles, p.panels, C, labels, dist2, changed_part, status};
+    const AssignArgs aa{X, ldx, int(n), int(d), int(k), p.ktiles, p.panels, C, labels, p.dist2, p.changed_part, status};
     if (const int rc = launch_assign(p, aa, st)) return rc;
     int dp = 1;
     while (dp < d) dp *= 2;
-    const SumsArgs sa{X, ldx, int(n), int(d), int(k), dp, p.R, labels, dist2, psum, pcount, pinertia, status};
+    const SumsArgs sa{X, ldx, int(n), int(d), int(k), dp, p.R, labels, p.dist2, p.psum, p.pcount, p.pinertia, status};
     if (const int rc = launch_lds<&kmeans_sums_kernel>("kmeans_sums_kernel", p.P, kThreads, p.sums_lds, st, sa)) return rc;
-    const FoldArgs fa{C, int(d), int(k), p.P, psum, pcount, shift_c, empty_c, status};
+    const FoldArgs fa{C, int(d), int(k), p.P, p.psum, p.pcount, p.shift_c, p.empty_c, status};
     hipLaunchKernelGGL(kmeans_fold_kernel, dim3(unsigned(k)), dim3(kThreads), 0, st, fa);
     GAE_CHECK_LAUNCH("kmeans_fold_kernel");
-    const FinishArgs na{status, int(k), p.assign_blocks, p.P, pinertia, shift_c, empty_c, changed_part, tol_abs};
+    const FinishArgs na{status, int(k), p.assign_blocks, p.P, p.pinertia, p.shift_c, p.empty_c, p.changed_part, tol_abs};
     hipLaunchKernelGGL(kmeans_finish_kernel, dim3(1), dim3(64), 0, st, na);
     GAE_CHECK_LAUNCH("kmeans_finish_kernel");
     return GAE_OK;
@@ -520,18 +519,16 @@ extern "C" int gae_kmeans_init_pp(const float *X, int64_t ldx, int64_t n, int64_
 {
     const char *fn = "gae_kmeans_init_pp";
     Plan p;
-    if (const int rc = plan(fn, n, d, k, p)) return rc;
+    if (const int rc = plan(fn, n, d, k, workspace, p)) return rc;
     if (const int rc = check_x(fn, X, ldx, d, workspace, workspace_bytes, p)) return rc;
     GAE_REQUIRE(C_out && chosen_out, GAE_E_NULL, "%s: C_out / chosen_out is NULL", fn);
-    char *ws = static_cast<char *>(workspace);
-    Cand *cand = reinterpret_cast<Cand *>(ws + p.cand_at);
     SeedArgs a{X, ldx, int(n), int(d), int(k), 0, seed ^ 0x9E3779B97F4A7C15ull, p.seed_rows, p.seed_blocks,
-               reinterpret_cast<float *>(ws + p.dist2_at), nullptr, nullptr, C_out, chosen_out};
+               p.dist2, nullptr, nullptr, C_out, chosen_out};
     hipStream_t st = gae::as_stream(stream);
     for (int r = 1; r <= int(k); ++r) {
         a.round = r;
-        a.prev = cand + ((r - 1) & 1) * p.seed_blocks;         // two lists: a round reads one while it writes the other
-        a.out = cand + (r & 1) * p.seed_blocks;
+        a.prev = p.cand + ((r - 1) & 1) * p.seed_blocks;       // two lists: a round reads one while it writes the other
+        a.out = p.cand + (r & 1) * p.seed_blocks;
         hipLaunchKernelGGL(kmeans_seed_kernel, dim3(unsigned(r == int(k) ? 1 : p.seed_blocks)), dim3(kThreads), 0, st, a);
         GAE_CHECK_LAUNCH("kmeans_seed_kernel");
     }

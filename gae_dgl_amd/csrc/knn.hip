@@ -51,7 +51,6 @@ struct KnnArgs {
 };
 
 using gae::cdiv;
-using gae::up256;
 
 inline int64_t sweep_lds(int nw, int64_t d, int64_t k)
 {
@@ -82,9 +81,10 @@ inline int64_t part_rows(int64_t m, int64_t n, int splits)
     return b < by_span ? b : by_span;
 }
 
-struct Plan { int64_t half_at, part_at, need; };
+// the workspace regions (NULL for the size query): |x|^2 / 2 of the corpus, the partial lists (scores, then indices)
+struct Plan { float *half, *part; int64_t need; };
 
-int plan(const char *fn, int64_t m, int64_t n, int64_t d, int64_t k, int splits, Plan &p)
+int plan(const char *fn, int64_t m, int64_t n, int64_t d, int64_t k, int splits, void *ws, Plan &p)
 {
     GAE_REQUIRE(d >= 1 && d <= kMaxD, GAE_E_RANGE, "%s: d = %lld outside 1..256", fn, (long long)d);
     GAE_REQUIRE(k >= 1 && k <= kMaxK, GAE_E_RANGE, "%s: k = %lld outside 1..64", fn, (long long)k);
@@ -92,9 +92,10 @@ int plan(const char *fn, int64_t m, int64_t n, int64_t d, int64_t k, int splits,
     GAE_REQUIRE(m < (int64_t(1) << 31) && n < (int64_t(1) << 31), GAE_E_SIZE, "%s: m = %lld or n = %lld beyond int32 indices",
                 fn, (long long)m, (long long)n);
     GAE_REQUIRE(splits >= 0 && splits <= kMaxSplits, GAE_E_RANGE, "%s: splits = %d outside 0..16", fn, splits);
-    p.half_at = 0;
-    p.part_at = up256(4 * n);
-    p.need = up256(p.part_at + part_rows(m, n, splits) * k * 8) + 256;
+    gae::Carver c(ws);
+    p.half = c.take<float>(n);
+    p.part = c.take<float>(2 * part_rows(m, n, splits) * k);
+    p.need = c.bytes() + 256;
     return GAE_OK;
 }
 
@@ -266,7 +267,7 @@ int launch_sweep(int64_t blocks, size_t lds, hipStream_t st, const KnnArgs &a)
 extern "C" int64_t gae_knn_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int splits)
 {
     Plan p;
-    if (const int rc = plan("gae_knn_workspace_bytes", m, n, d, k, splits, p)) return rc;
+    if (const int rc = plan("gae_knn_workspace_bytes", m, n, d, k, splits, nullptr, p)) return rc;
     return p.need;
 }
 
@@ -276,7 +277,7 @@ extern "C" int gae_knn(const float *Q, int64_t ldq, int64_t m, const float *X, i
 {
     const char *fn = "gae_knn";
     Plan p;
-    if (const int rc = plan(fn, m, n, d, k, splits, p)) return rc;
+    if (const int rc = plan(fn, m, n, d, k, splits, workspace, p)) return rc;
     GAE_REQUIRE(metric == GAE_KNN_L2 || metric == GAE_KNN_DOT, GAE_E_RANGE, "%s: unknown metric %d", fn, metric);
     GAE_REQUIRE((flags & ~GAE_KNN_EXCLUDE_SAME_INDEX) == 0, GAE_E_RANGE, "%s: unknown flags 0x%x", fn, flags);
     GAE_REQUIRE(ldq >= d && ldx >= d && ldo >= k, GAE_E_SIZE,
@@ -292,16 +293,15 @@ extern "C" int gae_knn(const float *Q, int64_t ldq, int64_t m, const float *X, i
 
     const int S = splits_of(m, n, d, k, splits);
     const int nw = waves_of(d, k);
-    char *ws = static_cast<char *>(workspace);
     KnnArgs a;
     a.Q = Q; a.X = X; a.ldq = ldq; a.ldx = ldx; a.ldo = ldo;
     a.m = int(m); a.n = int(n); a.d = int(d); a.k = int(k); a.S = S;
     a.nch = chunks_of(d);
     a.l2 = metric == GAE_KNN_L2 ? 1 : 0;
     a.excl_same = (flags & GAE_KNN_EXCLUDE_SAME_INDEX) ? 1 : 0;
-    a.half = reinterpret_cast<const float *>(ws + p.half_at);
+    a.half = p.half;
     a.value_out = value_out; a.index_out = index_out;
-    a.part_s = reinterpret_cast<float *>(ws + p.part_at);
+    a.part_s = p.part;
     a.part_j = reinterpret_cast<int32_t *>(a.part_s + (S > 1 ? int64_t(S) * m * k : 0));
     hipStream_t st = gae::as_stream(stream);
 
@@ -315,7 +315,7 @@ extern "C" int gae_knn(const float *Q, int64_t ldq, int64_t m, const float *X, i
                 (long long)finish_blocks);
     if (a.l2 && n > 0) {
         hipLaunchKernelGGL(knn_half_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, st, X, ldx, int(n), int(d),
-                           reinterpret_cast<float *>(ws + p.half_at));
+                           p.half);
         GAE_CHECK_LAUNCH("knn_half_kernel");
     }
     const size_t lds = size_t(sweep_lds(nw, d, k));

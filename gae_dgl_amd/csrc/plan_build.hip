@@ -366,8 +366,39 @@ __global__ __launch_bounds__(256) void part_ptr_kernel(const int32_t *__restrict
     if (p <= np) part_ptr[p] = vfirst[p * 8];
 }
 
-inline int64_t al(int64_t x) { return (x + 255) / 256 * 256; }
-
+struct Scratch {
+    u64 *blk; int32_t *mid_base, *freq; unsigned *hist; int32_t *pin_edge_base, *cnt, *vfirst; u64 *keys_a, *keys_b;
+    int32_t *vals_a, *vals_b, *v_e0, *v_len; void *sort_tmp; size_t sort_bytes; int64_t *hstart; int64_t nv_bound, bytes;
+};
+// THE scratch layout (NULL: the regions are only counted, `bytes` is what the size query reports)
+Scratch carve(void *scratch, int64_t n_rows, int64_t n_cols, int64_t n_pinned, int64_t pinned_edges, int seg)
+{
+    Scratch c{};
+    gae::Carver w(scratch);
+    const int64_t nb = (n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
+    c.nv_bound = pinned_edges / seg + 8 * n_pinned + 8;                           // bound on the virtual rows
+    w.raw<char>(256);                                                            // the totals of gae_spmm_plan_sizes
+    c.blk = w.take<u64>(6 * nb);
+    c.mid_base = w.take<int32_t>(n_rows + 1);
+    c.freq = w.take<int32_t>(n_cols);
+    c.hist = w.take<unsigned>(kFreqBins);
+    c.pin_edge_base = w.take<int32_t>(n_pinned + 1);
+    c.cnt = w.take<int32_t>(n_pinned * 8);
+    c.vfirst = w.take<int32_t>(n_pinned * 8 + 1);
+    c.keys_a = w.take<u64>(c.nv_bound);
+    c.keys_b = w.take<u64>(c.nv_bound);
+    c.vals_a = w.take<int32_t>(c.nv_bound);
+    c.vals_b = w.take<int32_t>(c.nv_bound);
+    c.v_e0 = w.take<int32_t>(c.nv_bound);
+    c.v_len = w.take<int32_t>(c.nv_bound);
+    (void)rocprim::radix_sort_pairs(nullptr, c.sort_bytes, static_cast<u64 *>(nullptr), static_cast<u64 *>(nullptr),
+                                    static_cast<int32_t *>(nullptr), static_cast<int32_t *>(nullptr), size_t(c.nv_bound), 0u,
+                                    36u, hipStream_t(nullptr));
+    c.sort_tmp = w.take<char>(int64_t(c.sort_bytes));
+    c.hstart = w.take<int64_t>(16);
+    c.bytes = w.bytes() + 4096;
+    return c;
+}
 } // namespace
 
 extern "C" int gae_spmm_plan_sizes(const int32_t *indptr, int64_t n_rows, int32_t threshold, int32_t pin_degree,
@@ -400,50 +431,8 @@ extern "C" int64_t gae_spmm_plan_scratch_bytes(int64_t n_rows, int64_t n_cols, i
                                                int32_t segment_edges)
 {
     if (n_rows < 0 || n_cols < 0 || n_pinned < 0 || pinned_edges < 0 || segment_edges < 64) return GAE_E_SIZE;
-    const int64_t nb = (n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
-    const int64_t nv = pinned_edges / segment_edges + 8 * n_pinned + 8;          // bound on the virtual rows
-    size_t sort_bytes = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, static_cast<u64 *>(nullptr), static_cast<u64 *>(nullptr),
-                                    static_cast<int32_t *>(nullptr), static_cast<int32_t *>(nullptr), size_t(nv), 0u, 36u,
-                                    hipStream_t(nullptr));
-    return 256 + al(6 * nb * 8) + al((n_rows + 1) * 4) + al(n_cols * 4) + al(kFreqBins * 4) + al((n_pinned + 1) * 4) + al(n_pinned * 8 * 4) +
-           al((n_pinned * 8 + 1) * 4) + 2 * al(nv * 8) + 4 * al(nv * 4) + al(int64_t(sort_bytes)) + al(16 * 8) + 4096;
+    return carve(nullptr, n_rows, n_cols, n_pinned, pinned_edges, segment_edges).bytes;
 }
-
-namespace {
-struct Scratch {
-    u64 *blk; int32_t *mid_base, *freq; unsigned *hist; int32_t *pin_edge_base, *cnt, *vfirst; u64 *keys_a, *keys_b;
-    int32_t *vals_a, *vals_b, *v_e0, *v_len; void *sort_tmp; size_t sort_bytes; int64_t *hstart; int64_t nv_bound;
-};
-Scratch carve(void *scratch, int64_t n_rows, int64_t n_cols, int64_t n_pinned, int64_t pinned_edges, int seg)
-{
-    Scratch c{};
-    char *p = static_cast<char *>(scratch) + 256;
-    const int64_t nb = (n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
-    c.nv_bound = pinned_edges / seg + 8 * n_pinned + 8;
-    auto take = [&](int64_t bytes) { char *q = p; p += al(bytes); return q; };
-    c.blk = reinterpret_cast<u64 *>(take(6 * nb * 8));
-    c.mid_base = reinterpret_cast<int32_t *>(take((n_rows + 1) * 4));
-    c.freq = reinterpret_cast<int32_t *>(take(n_cols * 4));
-    c.hist = reinterpret_cast<unsigned *>(take(kFreqBins * 4));
-    c.pin_edge_base = reinterpret_cast<int32_t *>(take((n_pinned + 1) * 4));
-    c.cnt = reinterpret_cast<int32_t *>(take(n_pinned * 8 * 4));
-    c.vfirst = reinterpret_cast<int32_t *>(take((n_pinned * 8 + 1) * 4));
-    c.keys_a = reinterpret_cast<u64 *>(take(c.nv_bound * 8));
-    c.keys_b = reinterpret_cast<u64 *>(take(c.nv_bound * 8));
-    c.vals_a = reinterpret_cast<int32_t *>(take(c.nv_bound * 4));
-    c.vals_b = reinterpret_cast<int32_t *>(take(c.nv_bound * 4));
-    c.v_e0 = reinterpret_cast<int32_t *>(take(c.nv_bound * 4));
-    c.v_len = reinterpret_cast<int32_t *>(take(c.nv_bound * 4));
-    c.sort_bytes = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, c.sort_bytes, static_cast<u64 *>(nullptr), static_cast<u64 *>(nullptr),
-                                    static_cast<int32_t *>(nullptr), static_cast<int32_t *>(nullptr), size_t(c.nv_bound), 0u,
-                                    36u, hipStream_t(nullptr));
-    c.sort_tmp = take(int64_t(c.sort_bytes));
-    c.hstart = reinterpret_cast<int64_t *>(take(16 * 8));
-    return c;
-}
-} // namespace
 
 // Outputs (device arrays sized from gae_spmm_plan_sizes: sizes = {n_light, n_mid, mid_segments, mid_edges, n_pinned,
 // pinned_edges, max_degree}): light_desc [n_light][4]; heavy_rows, heavy_seg_base [n_mid]; seg_heavy [mid_segments];

@@ -1103,8 +1103,14 @@ int dispatch_segments(const int32_t *indptr, const int32_t *indices, const T *H,
 #undef GAE_SEG
 }
 
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 inline int plan_ldp(int64_t F) { return int((F + 3) / 4 * 4); }
+// THE workspace layout: the float partials of the heavy rows' segments, then those of the pinned rows' virtual rows
+inline int64_t spmm_carve(const gae_spmm_plan *plan, int64_t F, gae::Carver c, float *&heavy, float *&virt)
+{
+    heavy = c.take<float>(plan->n_heavy > 0 ? plan->n_segments * plan_ldp(F) : 0);
+    virt = c.take<float>(plan->vh_n_virtual > 0 ? plan->vh_n_virtual * plan_ldp(F) : 0);
+    return c.bytes();
+}
 
 template <typename T, int VEC>
 int run_spmm(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int64_t n_cols, const T *h, int64_t ldh,
@@ -1148,7 +1154,8 @@ int run_spmm(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int6
                                        (flags & GAE_SPMM_ACCUMULATE) ? 1 : 0, s);
     }
     if (rc || (!heavy && !homed)) return rc;
-    float *partial = static_cast<float *>(workspace);
+    float *partial, *pv;
+    spmm_carve(plan, f, gae::Carver(workspace), partial, pv);
     const int ldp = plan_ldp(f);
     const int acc_flag = (flags & GAE_SPMM_ACCUMULATE) ? 1 : 0;
     if (heavy) {
@@ -1166,7 +1173,6 @@ int run_spmm(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int6
         // XCD-pinned rows: the plan's virtual CSR (one virtual row = one segment = one (row, home, chunk) group of
         // column ids; position p is gathered by block p / 4, i.e. on XCD (p / 4) % 8 = the home of its columns) goes
         // through the same segment kernel into float partials, which are then added per real row in plan order
-        float *pv = partial + (heavy ? align256(plan->n_segments * ldp * 4) / 4 : 0);
         gae_spmm_plan v = *plan;
         v.n_heavy = v.n_segments = plan->vh_n_virtual;
         v.heavy_rows = v.heavy_seg_base = v.seg_heavy = g_spmm_desc ? nullptr : plan->vh_identity;   // NULL: segment s = row s
@@ -1219,10 +1225,8 @@ extern "C" int64_t gae_spmm_workspace_bytes(const gae_spmm_plan *plan, int64_t F
 {
     if (F < 0) return GAE_E_SIZE;
     if (!plan) return 0;
-    int64_t b = 0;
-    if (plan->n_heavy > 0) b += align256(plan->n_segments * plan_ldp(F) * 4);
-    if (plan->vh_n_virtual > 0) b += align256(plan->vh_n_virtual * plan_ldp(F) * 4);
-    return b;
+    float *heavy, *virt;
+    return spmm_carve(plan, F, gae::Carver(nullptr), heavy, virt);
 }
 
 static int spmm_csr_impl(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int64_t n_cols,
@@ -1375,8 +1379,4 @@ extern "C" int gae_spmm_csr_blockdiag(const int32_t *indptr, const int32_t *indi
     GAE_CHECK_LAUNCH("spmm_blockdiag_kernel");
     return GAE_OK;
 }
-
-// ---- hot-column tags of a plan: how often every column is gathered, and the ids with the sign bit on the hot ones
-namespace {
-} // namespace
 

@@ -685,7 +685,7 @@ bool xw_usable(const void *X, int64_t ldx, int64_t n, int64_t K, int64_t J, int 
 int64_t xw_fwd_workspace_bytes(int64_t n, int64_t K, int64_t J, int elem)
 {
     const FwdPlan p = fwd_plan(n, int(K), elem);
-    return p.splits > 1 ? (int64_t(p.splits) * n * J * 4 + 255) / 256 * 256 : 0;
+    return p.splits > 1 ? up256(int64_t(p.splits) * n * J * 4) : 0;
 }
 
 int xw_fwd_splits(int64_t n, int64_t K, int elem) { return fwd_plan(n, int(K), elem).splits; }

@@ -1,5 +1,6 @@
 """Shared plumbing of the operator wrappers: device pointers and streams, row layout helpers, the step context
-(what one training step defers to its optimiser launch), the workspace cache and the launch profiler.
+(what one training step defers to its optimiser launch), the checked workspace size query, the workspace cache and the
+launch profiler.
 
 Part of the package gae_dgl_amd.ops (one module until round 6).  Functions look each other up in the PACKAGE
 namespace (`_ops.<name>`) when they run: setting a flag or replacing a function on `gae_dgl_amd.ops` reaches every caller."""
@@ -16,7 +17,8 @@ __all__ = [
     '_vp', '_raw_stream', '_stream_handle', '_stream', '_ptr', '_gpu', 'row_quantum', 'padded_ld', 'pad_rows',
     'float_rows', '_rowmajor', '_f32', '_dtype_code', '_WS_CACHE', 'StepContext', '_STEP_STACK', '_STEP_LOCK',
     '_NO_STEP', '_StackView', '_step_stack', 'current_step', 'deferred_grad_reductions', 'deferred_loss_finalize',
-    'pending_loss_tail', 'pending_partials', '_workspace', '_on_device', 'device_info', 'EventProfiler', 'profiler',
+    'pending_loss_tail', 'pending_partials', '_ws_bytes', '_workspace', '_on_device', 'device_info', 'EventProfiler',
+    'profiler',
 ]
 
 
@@ -282,6 +284,15 @@ def pending_partials(grad):
     """(keep-alive, ptr, n_partials, partial_stride, row_len, row_pitch) of a gradient of the current step whose
     reduction was deferred (removed from the context), or None"""
     return _ops.current_step().take_partials(grad)
+
+
+def _ws_bytes(name, *args):
+    """bytes the size query ``name(*args)`` of the library reports; its negative answers are argument error codes and
+    raise through _lib.check"""
+    nbytes = int(getattr(_lib.load(), name)(*args))
+    if nbytes < 0:
+        _lib.check(nbytes, name)
+    return nbytes
 
 
 def _workspace(nbytes, device):

@@ -11,7 +11,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _f32, _gpu, _on_device, _ptr, _stream
+from ._base import _f32, _gpu, _on_device, _ptr, _stream, _ws_bytes
 
 __all__ = ['KMeansResult', 'kmeans_assign', 'kmeans', 'kmeans_init_pp']
 
@@ -45,8 +45,7 @@ def _centres(C, d, dev, who):
 
 def _ws(n, d, k, dev):
     """a workspace of this call's own (the seeding and the steps of one run share it)"""
-    nbytes = _lib.load().gae_kmeans_workspace_bytes(n, d, k)
-    _lib.check(min(int(nbytes), 0), "gae_kmeans_workspace_bytes")
+    nbytes = _ws_bytes("gae_kmeans_workspace_bytes", n, d, k)
     return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
 
 

@@ -10,7 +10,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import ACT_IDENTITY, ACT_RELU, GaeHipError
-from ._base import _f32, _gpu, _on_device, _ptr, _rowmajor, _stream, _workspace
+from ._base import _f32, _gpu, _on_device, _ptr, _rowmajor, _stream, _workspace, _ws_bytes
 
 __all__ = [
     'linear2_usable', '_dead_mask', 'linear2_fwd_raw', 'gcn2_bwd_dense_raw', 'linear_fwd_raw', 'linear_bwd_raw',
@@ -130,9 +130,7 @@ def gcn2_bwd_dense_raw(G, dZ, Y1, act1, M1, W2, W1=None, b1=None, m1_dead=None, 
     dW2 = torch.empty(f_out, f_mid, dtype=torch.float32, device=dev)
     db2 = torch.empty(f_out, dtype=torch.float32, device=dev)
     with _on_device(dev):
-        nbytes = _lib.load().gae_gcn2_bwd_dense_workspace_bytes(n, f_in, f_mid, f_out)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "gae_gcn2_bwd_dense_workspace_bytes")
+        nbytes = _ws_bytes("gae_gcn2_bwd_dense_workspace_bytes", n, f_in, f_mid, f_out)
         defer = _ops.current_step().defer_grads
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev) if defer else _workspace(nbytes, dev)
         lay = (ctypes.c_int64 * 5)()

@@ -10,7 +10,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _gpu, _on_device, _ptr, _stream
+from ._base import _gpu, _on_device, _ptr, _stream, _ws_bytes
 
 __all__ = ['EMBED_MAX_LAYERS', 'EMBED_MAX_WIDTH', 'EMBED_MAX_NODES', 'embed_graphs_usable', 'embed_graphs',
            'embed_graphs_bwd_usable', 'embed_graphs_bwd']
@@ -166,9 +166,7 @@ def embed_graphs_bwd(graph_ptr, indptr, indices, feat, weights, biases, acts, d_
     dbs = [torch.empty(widths[l], dtype=torch.float32, device=dev) if want_biases[l] and biases[l] is not None else None
            for l in range(L)]
     c_widths = (ctypes.c_int64 * L)(*widths)
-    nbytes = int(_lib.load().gae_embed_graphs_bwd_workspace_bytes(int(f_in), L, c_widths, B))
-    if nbytes < 0:
-        _lib.check(nbytes, "gae_embed_graphs_bwd_workspace_bytes")
+    nbytes = _ws_bytes("gae_embed_graphs_bwd_workspace_bytes", int(f_in), L, c_widths, B)
     ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
     p_dw, p_db, lddw = (ctypes.c_void_p * L)(), (ctypes.c_void_p * L)(), (ctypes.c_int64 * L)()
     for l in range(L):

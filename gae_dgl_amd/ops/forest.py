@@ -15,7 +15,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _gpu, _on_device, _ptr, _stream
+from ._base import _gpu, _on_device, _ptr, _stream, _ws_bytes
 from .cluster import _rows
 
 __all__ = ['ForestResult', 'forest', 'forest_predict', 'FOREST_MAX_D', 'FOREST_MAX_T', 'FOREST_MAX_TREES',
@@ -190,8 +190,8 @@ def forest(X, y, n_trees=100, *, max_depth=12, max_features=1.0, min_samples_lea
                 n_boot = n_used
             else:
                 n_boot = max_samples if isinstance(max_samples, int) else max(1, int(max_samples * n_used))
-            nbytes = lib.gae_forest_workspace_bytes(n_used, d, t, n_trees, n_boot, max_depth, max_bins)
-            _lib.check(min(int(nbytes), 0), "gae_forest_workspace_bytes")      # shape errors before any other work
+            # shape errors before any other work
+            nbytes = _ws_bytes("gae_forest_workspace_bytes", n_used, d, t, n_trees, n_boot, max_depth, max_bins)
             Xs = X if listed is None else X.index_select(0, listed.long())
             Ys = Y if listed is None else Y.index_select(0, listed.long())
             edges, n_edges = _edges(Xs, max_bins)

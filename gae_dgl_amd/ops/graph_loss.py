@@ -8,7 +8,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _f32, _gpu, _on_device, _ptr, _stream, _workspace
+from ._base import _f32, _gpu, _on_device, _ptr, _stream, _workspace, _ws_bytes
 
 __all__ = ['decoder_bce_graphs_raw', 'DecoderBCEGraphsFunction', 'decoder_bce_graphs']
 
@@ -55,9 +55,7 @@ def decoder_bce_graphs_raw(Z, mask, node_ptr, max_graph_nodes, csr, csc, want_gr
     indptr, indices = csr
     t_indptr, t_indices = csc
     with _on_device(dev):
-        nbytes = _lib.load().gae_decoder_bce_graphs_workspace_bytes(n, G, int(max_graph_nodes), d)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "gae_decoder_bce_graphs_workspace_bytes")
+        nbytes = _ws_bytes("gae_decoder_bce_graphs_workspace_bytes", n, G, int(max_graph_nodes), d)
         ws = _workspace(nbytes, dev)
         sync = _sync(dev)
 

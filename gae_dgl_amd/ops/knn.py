@@ -11,7 +11,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _on_device, _ptr, _stream
+from ._base import _on_device, _ptr, _stream, _ws_bytes
 from .cluster import _rows
 
 __all__ = ['KNNResult', 'knn', 'KNN_MAX_K', 'KNN_MAX_D', 'KNN_MAX_SPLITS']
@@ -70,8 +70,7 @@ def knn(Q, X=None, k=None, *, metric="l2", exclude_self=None, splits=0):
         value = torch.empty(m, kk, dtype=torch.float32, device=dev)
         flags = _lib.KNN_EXCLUDE_SAME_INDEX if exclude_self else 0
         with _on_device(dev):
-            nbytes = _lib.load().gae_knn_workspace_bytes(m, n, d, k, int(splits))
-            _lib.check(min(int(nbytes), 0), "gae_knn_workspace_bytes")
+            nbytes = _ws_bytes("gae_knn_workspace_bytes", m, n, d, k, int(splits))
             ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
 
             def launch():

@@ -11,7 +11,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import ACT_IDENTITY, ACT_RELU, GaeHipError
-from ._base import _f32, _gpu, _on_device, _ptr, _rowmajor, _stream, _workspace
+from ._base import _f32, _gpu, _on_device, _ptr, _rowmajor, _stream, _workspace, _ws_bytes
 from .aggregate import _scattered
 
 __all__ = [
@@ -112,9 +112,7 @@ def gcn_layer_fused_prep_raw(indptr, indices, H, n, plan, W, bias, row_scale, re
         mask = _f32(_gpu(mask, "mask"), "gcn_layer_fused_prep: mask").contiguous()
     counts = getattr(req.graph, "batch_counts", None)
     with _on_device(dev):
-        nbytes = _lib.load().gae_decoder_bce_workspace_bytes(n, n, J)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "gae_decoder_bce_workspace_bytes")
+        nbytes = _ws_bytes("gae_decoder_bce_workspace_bytes", n, n, J)
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)       # lives until the loss has run: not the scratch cache
         lay = _lib.BcePrep()
         _lib.call("gae_x_decoder_bce_prep_layout", n, J, _ptr(ws), ws.numel(), ctypes.byref(lay))
@@ -148,9 +146,7 @@ def gcn_layer_fused_wgrad_raw(t_indptr, t_indices, dY, n, plan_t, W, M, norm, wa
     db = torch.empty(f_out, dtype=torch.float32, device=dev) if want_db else None
     defer = _ops.current_step().defer_grads and (want_dW or want_db)
     with _on_device(dev):
-        nbytes = _lib.load().gae_x_gcn_layer_fused_wgrad_workspace_bytes(n, f_out, f_in)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "gae_x_gcn_layer_fused_wgrad_workspace_bytes")
+        nbytes = _ws_bytes("gae_x_gcn_layer_fused_wgrad_workspace_bytes", n, f_out, f_in)
         # deferred partials outlive the call: they must not sit in the per-stream scratch cache
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev) if defer else _workspace(nbytes, dev)
         lay = (ctypes.c_int64 * 3)()
@@ -288,9 +284,7 @@ class GCNTwoHeadFunction(torch.autograd.Function):
             db = torch.empty(f_out, dtype=torch.float32, device=dev) if need_db else None
             defer = _ops.current_step().defer_grads
             with _on_device(dev):
-                nbytes = _lib.load().gae_x_gcn_layer_fused_wgrad_workspace_bytes(n, f_out, f_in)
-                if nbytes < 0:
-                    _lib.check(int(nbytes), "gae_x_gcn_layer_fused_wgrad_workspace_bytes")
+                nbytes = _ws_bytes("gae_x_gcn_layer_fused_wgrad_workspace_bytes", n, f_out, f_in)
                 ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev) if defer else _workspace(nbytes, dev)
                 lay = (ctypes.c_int64 * 3)()
                 _lib.call("gae_x_gcn_layer_fused2_wgrad", _ptr(t_indptr), _ptr(t_indices), n, _ptr(dYc), f_out, f_out,

@@ -10,7 +10,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import ACT_IDENTITY, GaeHipError
-from ._base import _f32, _gpu, _on_device, _ptr, _rowmajor, _stream, _workspace
+from ._base import _f32, _gpu, _on_device, _ptr, _rowmajor, _stream, _workspace, _ws_bytes
 
 __all__ = [
     'dropout_mask', 'normal_noise', 'decoder_dense_raw', 'decoder_dense_bwd_raw', 'decoder_bce_raw',
@@ -103,9 +103,7 @@ def decoder_bce_raw(Z, mask, csr, csc, pos_weight, want_grad=True, row_begin=0, 
         if prepared is not None:
             ws = prepared["ws"]
         else:
-            nbytes = _lib.load().gae_decoder_bce_workspace_bytes(n, n_local, d)
-            if nbytes < 0:
-                _lib.check(int(nbytes), "gae_decoder_bce_workspace_bytes")
+            nbytes = _ws_bytes("gae_decoder_bce_workspace_bytes", n, n_local, d)
             # a deferred final reduction reads the partial sums in the optimiser launch: they must not sit in the
             # per-stream scratch cache, which any launch in between (dM of gae_linear_bwd, a weight-gradient
             # reduction) may hand out again

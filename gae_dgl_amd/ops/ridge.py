@@ -12,7 +12,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _gpu, _on_device, _ptr, _stream
+from ._base import _gpu, _on_device, _ptr, _stream, _ws_bytes
 from .cluster import _rows
 
 __all__ = ['RidgeResult', 'ridge', 'RIDGE_MAX_D', 'RIDGE_MAX_T', 'RIDGE_MAX_FOLDS', 'RIDGE_MAX_LAMBDAS', 'RIDGE_CHUNK_ROWS']
@@ -121,8 +121,7 @@ def ridge(X, y, lambdas=None, *, folds=5, fold=None, seed=0, fit_intercept=True,
         Y, ldy, _, t = _rows(y.reshape(n, 1).float() if y.dim() == 1 else y.float(), "ridge")
         L, W = len(lambdas), 1 + d + t
         with _on_device(dev):
-            nbytes = _lib.load().gae_ridge_workspace_bytes(n, d, t, F)     # shape errors before any other work
-            _lib.check(min(int(nbytes), 0), "gae_ridge_workspace_bytes")
+            nbytes = _ws_bytes("gae_ridge_workspace_bytes", n, d, t, F)     # shape errors before any other work
             rows, fold_ptr, counts = _fold_lists(fold, n, F, seed, dev)
             n_used = rows.shape[0]
             everything = n_used == n

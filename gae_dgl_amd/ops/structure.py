@@ -8,7 +8,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import F32, GaeHipError
-from ._base import _dtype_code, _f32, _gpu, _on_device, _ptr, _rowmajor, _stream, _workspace
+from ._base import _dtype_code, _f32, _gpu, _on_device, _ptr, _rowmajor, _stream, _workspace, _ws_bytes
 
 __all__ = [
     'csr_from_coo', 'degree_norm', 'rows_pack', 'csr_to_dense', 'batch_plan', 'batch_select', 'batch_plan_next',
@@ -29,9 +29,7 @@ def csr_from_coo(row, col, n_rows, n_cols, validate=True):
     with _on_device(dev):
         indptr = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
         indices = torch.empty(E, dtype=torch.int32, device=dev)
-        nbytes = _lib.load().gae_csr_from_coo_workspace_bytes(E, n_rows)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "gae_csr_from_coo_workspace_bytes")
+        nbytes = _ws_bytes("gae_csr_from_coo_workspace_bytes", E, n_rows)
         ws = _workspace(nbytes, dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         _lib.call("gae_csr_from_coo", _ptr(row), _ptr(col), E, n_rows, n_cols, _ptr(indptr), _ptr(indices),

@@ -9,7 +9,7 @@ import torch
 
 import gae_dgl_amd.ops as _ops
 from .. import _lib
-from ._base import _f32, _gpu, _on_device, _ptr, _stream, _vp, _workspace
+from ._base import _f32, _gpu, _on_device, _ptr, _stream, _vp, _workspace, _ws_bytes
 
 __all__ = [
     'VGAEHeadFunction', 'VGAEPackedHeadFunction', 'vgae_head_packed', 'VGAE_FUSED_LOSS', 'VGAEHeadLossFunction',
@@ -114,9 +114,7 @@ class VGAEHeadLossFunction(torch.autograd.Function):
         rec = torch.empty(1, dtype=torch.float32, device=dev)
         dZ = torch.empty(n, d, dtype=torch.float32, device=dev) if need else None
         with _on_device(dev):
-            nbytes = _lib.load().gae_decoder_bce_workspace_bytes(n, n, d)
-            if nbytes < 0:
-                _lib.check(int(nbytes), "gae_decoder_bce_workspace_bytes")
+            nbytes = _ws_bytes("gae_decoder_bce_workspace_bytes", n, n, d)
             ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
             klp = torch.empty((n + 63) // 64, dtype=torch.float64, device=dev)
             lay = _lib.BcePrep()

@@ -10,7 +10,7 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import ACT_IDENTITY, ACT_RELU, GaeHipError
-from ._base import _dtype_code, _f32, _gpu, _on_device, _ptr, _rowmajor, _stream, _workspace
+from ._base import _dtype_code, _f32, _gpu, _on_device, _ptr, _rowmajor, _stream, _workspace, _ws_bytes
 
 __all__ = [
     'xw_usable', 'xw_fwd_raw', 'xw_wgrad_raw', 'spmm_epilogue_raw', '_table_only', 'gcn_transform_first_usable',
@@ -47,9 +47,7 @@ def xw_fwd_raw(X, W, b, act, keep_splits=False):
     splits = int(lib.gae_xw_fwd_splits(n, f_in, f_out, code)) if keep_splits else 1
     keep = keep_splits and splits > 1
     with _on_device(X.device):
-        nbytes = lib.gae_xw_fwd_workspace_bytes(n, f_in, f_out, code)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "gae_xw_fwd_workspace_bytes")
+        nbytes = _ws_bytes("gae_xw_fwd_workspace_bytes", n, f_in, f_out, code)
         if keep:       # the partials ARE the result: a buffer of their own, not the shared scratch
             parts = torch.empty(splits, n, f_out, dtype=torch.float32, device=X.device)
             ws, ws_n, P = parts, parts.numel() * 4, None
