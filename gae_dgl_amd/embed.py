@@ -26,7 +26,14 @@ RMSE | R2 at the chosen lambda, one pair per target; ``--ridge_out PATH`` writes
 trees on the device, default 100 trees; ``--forest_depth D`` (default 12), ``--forest_features M`` features per split
 (default all)); needs ``--targets`` ([G] or [G, t]); prints the time of the call and the out-of-bag RMSE | R2, one pair
 per target; ``--forest_out PATH`` writes the node tables, 'edges', 'n_edges', 'oob_prediction', 'oob_rmse', 'oob_r2' and
-'importances' as .npz.  Combines with ``--ridge`` and ``--neighbours``."""
+'importances' as .npz.  Combines with ``--ridge`` and ``--neighbours``.
+``--mlp [H ...]`` trains the table's "GAE + MLP" head on the features just computed (``ops.mlp``: one block per model, every
+fold model of every (lr, alpha) pair side by side; hidden widths ``H`` (one or two, default 100); ``--mlp_epochs E`` (200),
+``--mlp_batch B`` (200), ``--mlp_lr LR ...`` (1e-3), ``--mlp_alpha A ...`` (1e-4), ``--mlp_folds F`` (5), ``--mlp_ensemble S``
+(1)); needs ``--targets`` ([G] or [G, t]); prints the time of the call and the cross-validated RMSE | R2 at the chosen
+pair, one pair per target; ``--mlp_out PATH`` writes 'hidden', 'lr', 'alpha', 'shift', 'scale', 'cv_rmse', 'cv_r2' and per
+layer 'weight{l}' [S, out, in], 'bias{l}' [S, out] as .npz (``finetune --head_init`` reads it).  Combines with ``--ridge``,
+``--forest`` and ``--neighbours``."""
 import argparse
 import os
 import time
@@ -86,6 +93,19 @@ def build_parser():
                     help="with --forest: write the model (.npz: the node tables 'feature', 'threshold_bin', 'threshold', "
                          "'left', 'count', 'value', 'gain', 'n_nodes', and 'edges', 'n_edges', 'oob_prediction', "
                          "'oob_rmse', 'oob_r2', 'importances')")
+    ap.add_argument("--mlp", type=int, nargs="*", default=None, metavar="H",
+                    help="also train an MLP regression head on the features (needs --targets; 3 d <= 128): one or two "
+                         "hidden widths in 1..128 (none given: 100); the (lr, alpha) pair is chosen by k-fold CV on the "
+                         "device; prints the cross-validated RMSE | R2")
+    ap.add_argument("--mlp_epochs", type=int, default=None, metavar="E", help="with --mlp: epochs (default 200)")
+    ap.add_argument("--mlp_batch", type=int, default=None, metavar="B", help="with --mlp: mini-batch size (default 200)")
+    ap.add_argument("--mlp_lr", type=float, nargs="+", default=None, metavar="LR", help="with --mlp: learning rates (default 1e-3)")
+    ap.add_argument("--mlp_alpha", type=float, nargs="+", default=None, metavar="A", help="with --mlp: L2 penalties (default 1e-4)")
+    ap.add_argument("--mlp_folds", type=int, default=None, metavar="F", help="with --mlp: CV folds, 2..32 (default 5)")
+    ap.add_argument("--mlp_ensemble", type=int, default=None, metavar="S", help="with --mlp: members per model (default 1)")
+    ap.add_argument("--mlp_out", type=str, default=None, metavar="PATH",
+                    help="with --mlp: write the chosen model (.npz: 'hidden', 'lr', 'alpha', 'shift', 'scale', 'cv_rmse', "
+                         "'cv_r2', 'weight{l}', 'bias{l}')")
     ap.add_argument("--norm", choices=["none", "both"], default="none",
                     help="none = the reference's plain in-edge sums; both = D^-1/2 A D^-1/2")
     ap.add_argument("--fused", choices=["auto", "on", "off"], default="auto",
@@ -149,8 +169,36 @@ def parse_args(argv=None):
             parser.error(f"--forest_features {args.forest_features}: M must lie in 1..{3 * args.hidden_dims[-1]}")
         if not os.path.exists(args.targets):
             parser.error(f"--targets {args.targets}: no such file")
+    if args.mlp is None:
+        if args.mlp_out or any(v is not None for v in (args.mlp_epochs, args.mlp_batch, args.mlp_lr, args.mlp_alpha,
+                                                        args.mlp_folds, args.mlp_ensemble)):
+            parser.error("--mlp_out / --mlp_epochs / --mlp_batch / --mlp_lr / --mlp_alpha / --mlp_folds / --mlp_ensemble "
+                         "need --mlp")
+    else:
+        if not args.targets:
+            parser.error("--mlp needs --targets PATH: the property (or properties) to regress on")
+        hidden = args.mlp or [100]
+        if not 1 <= len(hidden) <= 2 or not all(1 <= h <= ops.MLP_MAX_WIDTH for h in hidden):
+            parser.error(f"--mlp {' '.join(map(str, hidden))}: one or two hidden widths in 1..{ops.MLP_MAX_WIDTH}")
+        if 3 * args.hidden_dims[-1] > ops.MLP_MAX_WIDTH:
+            parser.error(f"--mlp: the feature width 3 d = {3 * args.hidden_dims[-1]} must not exceed {ops.MLP_MAX_WIDTH}")
+        if (args.mlp_epochs is not None and args.mlp_epochs < 1) or (args.mlp_batch is not None and args.mlp_batch < 1) \
+                or (args.mlp_ensemble is not None and args.mlp_ensemble < 1):
+            parser.error("--mlp_epochs, --mlp_batch and --mlp_ensemble take positive numbers")
+        if args.mlp_folds is not None and not 2 <= args.mlp_folds <= ops.MLP_MAX_FOLDS:
+            parser.error(f"--mlp_folds {args.mlp_folds}: F must lie in 2..{ops.MLP_MAX_FOLDS}")
+        if not all(0.0 < v < float("inf") for v in args.mlp_lr or []) \
+                or not all(0.0 <= v < float("inf") for v in args.mlp_alpha or []):
+            parser.error("--mlp_lr takes finite values > 0, --mlp_alpha finite values >= 0")
+        models = ((args.mlp_folds or 5) + 1) * len(args.mlp_lr or [0]) * len(args.mlp_alpha or [0]) * (args.mlp_ensemble or 1)
+        if models > ops.MLP_MAX_MODELS:
+            parser.error(f"--mlp: (folds + 1) x learning rates x penalties x members = {models} models, at most "
+                         f"{ops.MLP_MAX_MODELS} per call")
+        if not os.path.exists(args.targets):
+            parser.error(f"--targets {args.targets}: no such file")
     if args.neighbours is None:
-        if args.metric is not None or args.neighbours_out or (args.targets and args.ridge is None and args.forest is None):
+        if args.metric is not None or args.neighbours_out or (args.targets and args.ridge is None and args.forest is None
+                                                              and args.mlp is None):
             parser.error("--metric / --neighbours_out / --targets need --neighbours K (--targets: or --ridge / --forest)")
     else:
         if not 1 <= args.neighbours <= ops.KNN_MAX_K or 3 * args.hidden_dims[-1] > ops.KNN_MAX_D:
@@ -279,6 +327,35 @@ def main(argv=None):
                 "feature", "threshold_bin", "threshold", "left", "count", "value", "gain", "n_nodes", "edges", "n_edges",
                 "oob_prediction", "oob_rmse", "oob_r2", "importances")})
         main.forest = res
+    main.mlp = None
+    if args.mlp is not None:
+        y = np.load(args.targets)
+        if y.ndim not in (1, 2) or y.shape[0] != out.shape[0]:
+            raise ValueError(f"--targets of shape {y.shape} for {out.shape[0]} molecules: [G] or [G, t]")
+        y = torch.from_numpy(y.astype(np.float32)).to(device)
+        hidden = tuple(args.mlp or [100])
+        n_folds = args.mlp_folds or 5
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        res = ops.mlp(feats, y, hidden, lrs=args.mlp_lr or (1e-3,), alphas=args.mlp_alpha or (1e-4,),
+                      epochs=args.mlp_epochs or 200, batch_size=args.mlp_batch or 200, folds=n_folds,
+                      ensemble=args.mlp_ensemble or 1, seed=args.seed or 0)
+        torch.cuda.synchronize(device)
+        print(f"Trained an MLP head on {res.n_used} molecules, {res.info.numel()} models side by side | "
+              f"{(time.perf_counter() - t0) * 1e3:.3f} ms (one call, set-up included)")
+        chosen = res.lrs.index(res.lr) * len(res.alphas) + res.alphas.index(res.alpha)
+        pairs = " | ".join(f"RMSE: {r:.6f} | R2: {q:.6f}"
+                           for r, q in zip(res.cv_rmse[chosen].tolist(), res.cv_r2[chosen].tolist()))
+        print(f"MLP ({' x '.join(map(str, hidden))}, {n_folds}-fold CV, lr = {res.lr:g}, alpha = {res.alpha:g}) {pairs}")
+        if args.mlp_out:
+            arrays = {"hidden": np.asarray(hidden, np.int64), "lr": np.float64(res.lr), "alpha": np.float64(res.alpha),
+                      "shift": res.shift.cpu().numpy(), "scale": res.scale.cpu().numpy(),
+                      "cv_rmse": res.cv_rmse.cpu().numpy(), "cv_r2": res.cv_r2.cpu().numpy()}
+            for l, (W, b) in enumerate(zip(res.weights, res.biases)):
+                arrays[f"weight{l}"] = W.cpu().numpy()
+                arrays[f"bias{l}"] = b.cpu().numpy()
+            np.savez(args.mlp_out, **arrays)
+        main.mlp = res
     return out
 
 

@@ -12,7 +12,9 @@ Linear(64, 1)) sits on the 3 d-wide feature; head and encoder are trained with M
 fused launch each (K19 / K21) wherever both kernels take the molecules, the chunked differentiable route elsewhere.
 ``--freeze_encoder`` trains the head alone (the reference's frozen-feature setting).  Prints the train loss per epoch;
 writes ``encoder.pkl`` (the reference's state-dict keys, loadable by train_inductive / embed) and ``head.pkl`` to
-``--out``.  Plain host code: the head's GEMMs are torch's."""
+``--out``.  ``--head_init model.npz`` (with ``--head mlp``) starts the head from the model ``embed --mlp_out`` saved (``ops.mlp``
+trained it on the frozen features; its scaling is folded into the first and last layer) instead of a random
+Linear(3 d, 64), ReLU, Linear(64, 1).  Plain host code: the head's GEMMs are torch's."""
 import argparse
 import os
 
@@ -34,6 +36,8 @@ def build_parser():
                     help="generate G ZINC-shaped molecules instead of reading --data_file")
     ap.add_argument("--targets", "-t", type=str, default=None, help=".npy with one target per molecule")
     ap.add_argument("--head", choices=["linear", "mlp"], default="linear")
+    ap.add_argument("--head_init", type=str, default=None, metavar="PATH",
+                    help="with --head mlp: start the head from the .npz that `embed --mlp_out` wrote")
     ap.add_argument("--freeze_encoder", action="store_true", help="train the head alone on frozen features")
     ap.add_argument("--epochs", "-e", type=int, default=10)
     ap.add_argument("--batch_size", "-b", type=int, default=4096, help="molecules per step")
@@ -66,6 +70,11 @@ def parse_args(argv=None):
         parser.error("--synthetic, --batch_size, --in_dim, --epochs and --hidden_dims take positive numbers")
     if not args.lr > 0:
         parser.error("--lr takes a positive number")
+    if args.head_init:
+        if args.head != "mlp":
+            parser.error("--head_init needs --head mlp: it holds an MLP head")
+        if not os.path.exists(args.head_init):
+            parser.error(f"--head_init {args.head_init}: no such file")
     if args.fused == "on" and not args.freeze_encoder:
         from gae_dgl_amd import ops
         if not ops.embed_graphs_bwd_usable(args.in_dim, args.hidden_dims, 0):
@@ -102,7 +111,15 @@ def main(argv=None):
         raise ValueError(f"{args.targets} holds {len(y)} targets, the dataset {len(graphs)} molecules")
     y = torch.from_numpy(y).to(device)
     print(f"Loaded {len(graphs)} molecules")
-    head = make_head(args.head, 3 * args.hidden_dims[-1]).to(device)
+    if args.head_init:
+        from gae_dgl_amd import ops
+        head = ops.mlp_load_head(args.head_init)
+        if head[0].in_features != 3 * args.hidden_dims[-1] or head[-1].out_features != 1:
+            raise ValueError(f"{args.head_init} holds a head {head[0].in_features} -> ... -> {head[-1].out_features}, the "
+                             f"feature is {3 * args.hidden_dims[-1]} wide and there is one target")
+        head = head.to(device)
+    else:
+        head = make_head(args.head, 3 * args.hidden_dims[-1]).to(device)
     for p in model.parameters():
         p.requires_grad_(not args.freeze_encoder)
     params = list(head.parameters()) + ([] if args.freeze_encoder else list(model.parameters()))

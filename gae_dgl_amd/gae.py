@@ -372,6 +372,23 @@ class GAE(nn.Module):
         with torch.no_grad():
             return ops.forest(self.embed_graphs(data, **embed_kw), y, **kw)
 
+    def mlp_graphs(self, data, y, **kw):
+        """``ops.MLPResult``: an MLP regression of the per-molecule targets ``y`` ([G] or [G, t]) on the molecule features
+        of ``embed_graphs`` -- the reference's "GAE + MLP" head, every fold model of every (lr, alpha) pair trained side
+        by side on the device (``ops.mlp``; its arguments pass through: hidden, lrs, alphas, epochs, batch_size, folds,
+        fold, ensemble, seed, solver, momentum, shuffle, standardize).  ``fused`` and ``embed_batch_size`` go to the
+        embedding (``batch_size`` is the head's mini-batch).  Rows are in the order ``embed_graphs(data)`` returns them.
+        Runs under no_grad."""
+        if "grad" in kw:
+            raise ValueError("mlp_graphs runs under no_grad: the trained head carries no gradient into the encoder")
+        embed_kw = {}
+        if "fused" in kw:
+            embed_kw["fused"] = kw.pop("fused")
+        if "embed_batch_size" in kw:
+            embed_kw["batch_size"] = kw.pop("embed_batch_size")
+        with torch.no_grad():
+            return ops.mlp(self.embed_graphs(data, **embed_kw), y, **kw)
+
     def embed_graphs(self, data, *, fused="auto", batch_size=4096, grad=False):
         """fp32 [n_graphs, 3 d]: the molecule feature of the reference's chemistry table (README.md:54: mean | sum |
         max of the hidden vectors, 48 numbers for ``--hidden_dims 32 16``) of every graph of ``data`` -- a

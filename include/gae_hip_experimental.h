@@ -813,6 +813,102 @@ int gae_forest_predict(const float *X, int64_t ldx, int64_t m, int64_t d, int64_
                        const int32_t *feature, const float *threshold, const int32_t *left, const double *value,
                        const uint8_t *skip, double *out, gae_forest_status *status, void *stream);
 
+/* ---- K27: a small MLP regression head trained on a frozen feature (ops.mlp, GAE.mlp_graphs, embed --mlp)
+ * The best row of the reference's chemistry table ("GAE + MLP").  d -> h1 [-> h2] -> t (h2 = 0: one hidden layer), ReLU
+ * on the hidden layers, identity on the output, squared error; regression only.  ONE block of 256 threads per model, all
+ * models of a call in one grid; no grid-wide synchronisation and no atomics on floats; csrc/mlp.hip is built with
+ * -ffp-contract=off.  The result is a function of the listed values and the arguments alone: the same bits run to run,
+ * for any ldx / ldy, any number of models in the call and any cut into launches; tests/mlp_ref.py restates it in numpy.
+ *   1 <= d, h1 <= 128, 0 <= h2 <= 128, 1 <= t <= 8, 1 <= n_models <= 4096, 1 <= n_lists <= 1024, batch_size >= 1 (else
+ *   GAE_E_RANGE).  A shape inside these limits whose on-chip state passes a block's 160 KB of LDS (128 -> 128 -> 128 -> t)
+ *   is GAE_E_RANGE from every entry point, gae_mlp_workspace_bytes included.  There is no fallback.
+ * DATA: X fp32 [n, d] (ldx), Y fp32 [n, t] (ldy).  shift / scale: fp32 [d + t] each (features, then targets) or NULL (0 and
+ *   1).  The model sees v' = (v - shift) * scale: a subtraction, then a multiplication, in fp32.
+ *   rows int32 [n_rows]: lists of row ids, one after another; list k is rows[list_ptr[k] .. list_ptr[k + 1]) (list_ptr:
+ *   DEVICE int32 [n_lists + 1], each pair 0 <= lo <= hi <= n_rows; lists may overlap).  Model m trains on list train_list[m]
+ *   and is scored on list eval_list[m] (-1: none); lr, alpha fp32 [n_models], seed uint64 [n_models]: all DEVICE arrays.
+ *   Rows in no list that a model of the call uses are never read.
+ * LAYERS l = 0 .. L - 1 (L = 2 or 3) with W_l fp32 [out_l][in_l] (torch.nn.Linear layout) and b_l [out_l]:
+ *   z_l = chain_k(a_l[k], W_l[j][k]) + b_l[j];  a_{l+1} = relu(z_l) = (z_l > 0 ? z_l : +0) for l < L - 1;  yhat = z_{L-1}.
+ * ARITHMETIC.  chain_k(p_k, q_k) is ONE fp32 fma chain from +0 over the summed index in ascending order,
+ *   c <- fma(p_k, q_k, c): the fp32-input matrix instruction (v_mfma_f32_16x16x4_f32) computes exactly that.  One chain
+ *   per output element; waves split output tiles, never the summed index.  Operands past a matrix's edge are zeros.
+ *     forward      summed over the in_l features / hidden units;
+ *     output error delta_{L-1}[r][j] = yhat[r][j] - y'[r][j];
+ *     dW_l[j][k]   = chain over the batch's rows r in batch order of (delta_l[r][j], a_l[r][k]): the batch is walked in
+ *                  panels of 32 rows, the accumulators stay in registers across panels, so the chain continues;
+ *     db_l[j]      = chain over the same rows of (delta_l[r][j], 1), that is c <- c + delta_l[r][j];
+ *     delta_{l-1}[r][k] = (a_l[r][k] > 0) ? chain over j ascending of (delta_l[r][j], W_l[j][k]) : +0.
+ *   Everything else is a single correctly rounded fp32 operation, in this order (B = the batch's own size as fp32):
+ *     g = ((chain + alpha * w) / B) for a weight, g = chain / B for a bias (alpha * w = +0 there);
+ *     GAE_MLP_ADAM: m = beta1 * m + (1 - beta1) * g;  v = beta2 * v + ((1 - beta2) * (g * g));
+ *                  w = w - step * (m / (sqrtf(v) / c2 + eps)), with step = fp32(double(lr) / (1 - beta1^s)) and c2 =
+ *                  fp32(sqrt(1 - beta2^s)) taken in fp64 and rounded once; s counts the model's batches from 1; beta^s is a
+ *                  double in the state block, advanced by one multiplication per batch (as K12 does); (1 - beta) is fp32.
+ *     GAE_MLP_SGD:  vel = momentum * vel - lr * g;  w = w + vel (vel lives in the first moment's place).
+ *   fp32 division and sqrtf are the correctly rounded forms.
+ * INITIALISATION (a launch with e0 == 0): Glorot uniform as sklearn's MLPRegressor draws it for ReLU: bound_l =
+ *   fp32(sqrt(6.0 / (in_l + out_l))) (fp64, rounded once); element e (row-major) of W_l takes word e & 3 of
+ *   philox4x32_10(ctr = e >> 2, draw = 2 l, key = seed) (csrc/common.h), element e of b_l the same with draw = 2 l + 1;
+ *   u = (word >> 8) * 2^-24;  value = ((2 * u) - 1) * bound_l.  The moments start at 0, s at 0, the beta powers at 1.
+ * MINI-BATCH ORDER: epoch e visits list positions perm_e(0), perm_e(1), ...; batch b is positions [b B, min((b + 1) B,
+ *   n_train)): the last batch is short, B > n_train is one batch.  Without GAE_MLP_SHUFFLE perm_e(p) = p.  With it perm_e
+ *   is a keyed bijection computed per position: let hb >= 1 be the smallest integer with 4^hb >= n_train, mask = 2^hb - 1;
+ *   v = p; repeat { (hi, lo) = (v >> hb, v & mask); four rounds r = 0 .. 3: (hi, lo) <- (lo, hi ^ (F & mask)) with F = word
+ *   0 of philox4x32_10(ctr = (r << 32) | lo, draw = 2^32 + e, key = seed); v = (hi << hb) | lo } until v < n_train.
+ *   (draw >= 2^32: disjoint from the initialisation's streams.)
+ * LOSS: loss_curve[m][e] (fp64 [n_models][epochs]) = (sum of double(delta)^2 on the scaled targets, added in fp64 in
+ *   batch, row, target order) / (2 n_train).  After each epoch: if that value or any updated weight or bias of the epoch
+ *   is not finite, info[m] = 1 + e, the model stops updating and the later entries of loss_curve are NaN.
+ * EVALUATION (GAE_MLP_FINAL, after epoch e1 - 1): the rows of list eval_list[m] in list order, the same forward;
+ *   err = ((yhat / scale_y) + shift_y) - y in fp32 (the targets' own units); eval_sse[m][j] (fp64 [n_models][t]) = the sum
+ *   of double(err)^2 over the rows in that order.  NaN without an evaluation list or where info[m] != 0.
+ * STATE: the workspace is n_models state blocks of S = gae_mlp_workspace_bytes(d, h1, h2, t, 1) bytes each (so the
+ *   query is linear in n_models).  A block: int64 s; double beta1^s, beta2^s; int32 info, epochs done; 8 reserved floats
+ *   (GAE_MLP_STATE_HEADER = 16 floats in all); then W_0, b_0, W_1, b_1 [, W_2, b_2] as fp32, P values; then the first
+ *   moments in the same layout; then the second moments; zeros up to S (e0 == 0 writes the whole block).
+ *   gae_mlp_fit runs epochs [e0, e1) of `epochs` from the block;
+ *   e0 == 0 initialises it; e0 must equal the block's epochs done (else GAE_MLP_ERR_RESUME and info = -2).  ops.mlp cuts
+ *   a fit into launches of at most GAE_MLP_LAUNCH_ROW_VISITS row visits per model (whole epochs, one at least), so a long
+ *   fit is never one long-running kernel.  AN ESTIMATE until it is measured: about 1 us per row visit at the widest
+ *   shape, a quarter of a second per launch.
+ * info int32 [n_models]: 0; 1 + e as above; -1: the training list is empty or not a list; -2: a resume mismatch.
+ * STATUS: a 32-byte device block the caller zeroes; launches only add to it (integer atomics).  nonfinite_rows: entries
+ *   of the used lists whose row holds a NaN or an infinity in X or Y (counted by the e0 == 0 launch; a row in two lists
+ *   counts twice), rows of gae_mlp_predict with a non-finite feature.  errors: GAE_MLP_ERR_LIST_PTR (a list_ptr pair outside
+ *   0 <= lo <= hi <= n_rows: such a list is not read), GAE_MLP_ERR_ROW_ID (a row id outside [0, n): the row is taken as
+ *   zeros), GAE_MLP_ERR_LIST_ID, GAE_MLP_ERR_RESUME.
+ * PREDICTION (gae_mlp_predict): out fp32 [n_models][n][t] = (yhat / scale_y) + shift_y for every row of X and every state
+ *   block of `state` (blocks S bytes apart, as the workspace holds them), with the forward chains of training.  A row
+ *   holding a non-finite feature gives NaN and is counted (status may be NULL).
+ * Argument errors are returned before anything is dereferenced or launched (no GPU is needed to see them): the limits
+ *   above, an unknown solver or flag, betas or momentum outside [0, 1), eps <= 0, an epoch interval outside 0 <= e0 < e1 <=
+ *   epochs (GAE_E_RANGE), n, n_rows outside int32, ldx < d, ldy < t (GAE_E_SIZE), a NULL array (GAE_E_NULL), a short
+ *   workspace (GAE_E_WORKSPACE). */
+enum { GAE_MLP_LAUNCH_ROW_VISITS = 262144 };
+enum { GAE_MLP_STATE_HEADER = 16 };
+enum { GAE_MLP_ADAM = 0, GAE_MLP_SGD = 1 };
+enum { GAE_MLP_SHUFFLE = 1, GAE_MLP_FINAL = 2 };
+enum { GAE_MLP_ERR_LIST_PTR = 1, GAE_MLP_ERR_ROW_ID = 2, GAE_MLP_ERR_LIST_ID = 4, GAE_MLP_ERR_RESUME = 8 };
+
+typedef struct gae_mlp_status {
+    int64_t nonfinite_rows, errors, reserved[2];
+} gae_mlp_status;
+
+int64_t gae_mlp_workspace_bytes(int64_t d, int64_t h1, int64_t h2, int64_t t, int64_t n_models);
+
+int gae_mlp_fit(const float *X, int64_t ldx, const float *Y, int64_t ldy, int64_t n, int64_t d, int64_t h1, int64_t h2,
+                int64_t t, const float *shift, const float *scale, const int32_t *rows, int64_t n_rows,
+                const int32_t *list_ptr, int64_t n_lists, const int32_t *train_list, const int32_t *eval_list,
+                const float *lr, const float *alpha, const uint64_t *seed, int64_t n_models, int64_t batch_size,
+                float beta1, float beta2, float eps, int solver, float momentum, int flags, int64_t e0, int64_t e1,
+                int64_t epochs, double *loss_curve, double *eval_sse, int32_t *info, gae_mlp_status *status,
+                void *workspace, int64_t workspace_bytes, void *stream);
+
+int gae_mlp_predict(const float *X, int64_t ldx, int64_t n, int64_t d, int64_t h1, int64_t h2, int64_t t,
+                    const float *shift, const float *scale, const void *state, int64_t n_models, float *out,
+                    gae_mlp_status *status, void *stream);
+
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
 int gae_x_decoder_bce_finalize(const gae_bce_tail *tail, void *stream);
