@@ -1396,7 +1396,7 @@ __global__ __launch_bounds__(256) void normal_noise_kernel(float *__restrict__ o
         float z[4];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const float u1 = (float(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);     // (0, 1)
+            const float u1 = (float(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);     // (0, 1]: the sum rounds to even from 2^23 on
             const float u2 = float(c[2 * h + 1] >> 8) * (1.0f / 16777216.0f);          // [0, 1)
             const float rad = sqrtf(-2.0f * __logf(u1));
             float sn, cs;
@@ -1448,7 +1448,7 @@ __device__ __forceinline__ void normal_quad(int64_t q, uint64_t seed, uint64_t o
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const float u1 = (float(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);     // (0, 1)
+        const float u1 = (float(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);     // (0, 1]: the sum rounds to even from 2^23 on
         const float u2 = float(c[2 * h + 1] >> 8) * (1.0f / 16777216.0f);          // [0, 1)
         const float rad = sqrtf(-2.0f * __logf(u1));
         float sn, cs;
@@ -1805,9 +1805,13 @@ extern "C" int64_t gae_vgae_head_workspace_bytes(int64_t n_elems) { return n_ele
 extern "C" int gae_vgae_head_fwd(const float *mu, const float *logstd, int64_t ldm, const float *eps, int64_t n, int64_t d,
                                  float *z, float *kl_out, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    GAE_REQUIRE(n > 0 && d > 0 && ldm >= d && d < (1 << 24), GAE_E_SIZE, "gae_vgae_head_fwd: needs n, d > 0 and ldm >= d");
-    GAE_REQUIRE(mu && logstd && eps && z && kl_out && workspace, GAE_E_NULL, "gae_vgae_head_fwd: NULL pointer");
-    GAE_REQUIRE(workspace_bytes >= 1024 * 8, GAE_E_WORKSPACE, "gae_vgae_head_fwd: workspace too small");
+    GAE_REQUIRE(n > 0 && d > 0 && d < (1 << 24), GAE_E_SIZE, "gae_vgae_head_fwd: n = %lld, d = %lld: needs n > 0 and 0 < d < 2^24",
+                (long long)n, (long long)d);
+    GAE_REQUIRE(ldm >= d, GAE_E_SIZE, "gae_vgae_head_fwd: ldm = %lld < d = %lld", (long long)ldm, (long long)d);
+    const char *missing = !mu ? "mu" : !logstd ? "logstd" : !eps ? "eps" : !z ? "z" : !kl_out ? "kl_out" : !workspace ? "workspace" : nullptr;
+    GAE_REQUIRE(!missing, GAE_E_NULL, "gae_vgae_head_fwd: %s is NULL", missing);
+    GAE_REQUIRE(workspace_bytes >= 1024 * 8, GAE_E_WORKSPACE, "gae_vgae_head_fwd: workspace of %lld bytes, %d needed",
+                (long long)workspace_bytes, 1024 * 8);
     hipStream_t s = gae::as_stream(stream);
     const int g = vgae_blocks(n * d);
     double *partial = static_cast<double *>(workspace);
@@ -1827,14 +1831,22 @@ extern "C" int gae_x_vgae_head_prep(const float *mu, const float *logstd, int64_
                                   int64_t *n_blocks_out, void *stream)
 {
     GAE_REQUIRE(d == 16, GAE_E_RANGE, "gae_x_vgae_head_prep: the fused form takes d = 16 (got %lld): use gae_vgae_head_fwd", (long long)d);
-    GAE_REQUIRE(n > 0 && ldm >= d && ldm % 4 == 0, GAE_E_SIZE, "gae_x_vgae_head_prep: needs n > 0 and rows of whole 16-byte vectors");
-    GAE_REQUIRE(mu && logstd && eps && z && prep && kl_partial && n_blocks_out, GAE_E_NULL, "gae_x_vgae_head_prep: NULL pointer");
-    GAE_REQUIRE(gae::aligned16(mu) && gae::aligned16(logstd) && gae::aligned16(eps) && gae::aligned16(z), GAE_E_ALIGN,
-                "gae_x_vgae_head_prep: operands must be 16-byte aligned");
+    GAE_REQUIRE(n > 0, GAE_E_SIZE, "gae_x_vgae_head_prep: n = %lld: needs n > 0", (long long)n);
+    GAE_REQUIRE(ldm >= d && ldm % 4 == 0, GAE_E_SIZE, "gae_x_vgae_head_prep: ldm = %lld: needs rows of whole 16-byte vectors, ldm >= d",
+                (long long)ldm);
+    const char *missing = !mu ? "mu" : !logstd ? "logstd" : !eps ? "eps" : !z ? "z" : !prep ? "prep" : !kl_partial ? "kl_partial"
+                          : !n_blocks_out ? "n_blocks_out" : nullptr;
+    GAE_REQUIRE(!missing, GAE_E_NULL, "gae_x_vgae_head_prep: %s is NULL", missing);
+    const char *odd = !gae::aligned16(mu) ? "mu" : !gae::aligned16(logstd) ? "logstd" : !gae::aligned16(eps) ? "eps"
+                      : !gae::aligned16(z) ? "z" : nullptr;
+    GAE_REQUIRE(!odd, GAE_E_ALIGN, "gae_x_vgae_head_prep: %s is not 16-byte aligned", odd);
     const int64_t blocks = (n + 63) / 64;
-    GAE_REQUIRE(prep->DP == 16 && blocks <= prep->max_blocks && blocks <= kl_capacity && prep->Zt && prep->Zhi &&
-                    prep->Zlo && prep->colsum_partial,
-                GAE_E_WORKSPACE, "gae_x_vgae_head_prep: layout / KL buffer too small for %lld blocks", (long long)blocks);
+    GAE_REQUIRE(prep->DP == 16 && prep->Zt && prep->Zhi && prep->Zlo && prep->colsum_partial, GAE_E_WORKSPACE,
+                "gae_x_vgae_head_prep: prep is not a layout of gae_x_decoder_bce_prep_layout for d = 16");
+    GAE_REQUIRE(blocks <= prep->max_blocks, GAE_E_WORKSPACE, "gae_x_vgae_head_prep: prep->max_blocks = %lld < %lld blocks",
+                (long long)prep->max_blocks, (long long)blocks);
+    GAE_REQUIRE(blocks <= kl_capacity, GAE_E_WORKSPACE, "gae_x_vgae_head_prep: kl_capacity = %lld < %lld blocks",
+                (long long)kl_capacity, (long long)blocks);
     *n_blocks_out = blocks;
     hipLaunchKernelGGL(vgae_head_prep_kernel, dim3(unsigned(blocks)), dim3(256), 0, gae::as_stream(stream), mu, logstd, ldm,
                        eps, draw_eps, seed, offset, draw_dev, n, z, prep->Zt, prep->Zhi, prep->Zlo, prep->colsum_partial,
@@ -1846,8 +1858,11 @@ extern "C" int gae_x_vgae_head_prep(const float *mu, const float *logstd, int64_
 extern "C" int gae_vgae_head_bwd(const float *dz, const float *mu, const float *logstd, int64_t ldm, const float *eps,
                                  const float *gkl_dev, int64_t n, int64_t d, float *dmu, float *dlogstd, void *stream)
 {
-    GAE_REQUIRE(n > 0 && d > 0 && ldm >= d && d < (1 << 24), GAE_E_SIZE, "gae_vgae_head_bwd: needs n, d > 0 and ldm >= d");
-    GAE_REQUIRE(mu && logstd && eps && dmu && dlogstd, GAE_E_NULL, "gae_vgae_head_bwd: NULL pointer");
+    GAE_REQUIRE(n > 0 && d > 0 && d < (1 << 24), GAE_E_SIZE, "gae_vgae_head_bwd: n = %lld, d = %lld: needs n > 0 and 0 < d < 2^24",
+                (long long)n, (long long)d);
+    GAE_REQUIRE(ldm >= d, GAE_E_SIZE, "gae_vgae_head_bwd: ldm = %lld < d = %lld", (long long)ldm, (long long)d);
+    const char *missing = !mu ? "mu" : !logstd ? "logstd" : !eps ? "eps" : !dmu ? "dmu" : !dlogstd ? "dlogstd" : nullptr;
+    GAE_REQUIRE(!missing, GAE_E_NULL, "gae_vgae_head_bwd: %s is NULL", missing);
     hipLaunchKernelGGL(vgae_head_bwd_kernel, dim3(vgae_blocks(n * d)), dim3(256), 0, gae::as_stream(stream), dz, mu,
                        logstd, eps, gkl_dev, float(1.0 / (double(n) * double(n))), n * d, dmu, dlogstd, ldm, int(d));
     GAE_CHECK_LAUNCH("vgae_head_bwd_kernel");

@@ -398,11 +398,16 @@ int gae_linear_bwd(const float *dY, int64_t lddy, const float *Y, int64_t ldy, i
  * activation GAE passes (gae_dgl/gae.py:47).
  * gae_dropout_mask: inverted-dropout multiplier (0 or 1/(1-p)), Philox4x32-10
  * counter RNG keyed by (seed, offset + element index): reproducible for bwd.
- * draw_dev (device uint64, may be NULL): number of masks drawn so far.  The
+ * draw_dev (device uint64, may be NULL = 0): number of masks drawn so far.  The
  * Philox counter of element block q is (offset + q) in its low 64 bits and
  * *draw_dev in its high 64 bits: every draw is a stream of its own, whatever the
  * sizes of earlier draws, and a captured HIP graph draws a fresh mask on every
  * replay once the caller bumps the counter.
+ * `offset` counts BLOCKS OF FOUR ELEMENTS, not elements: block q = elements
+ * 4 q .. 4 q + 3 takes the four output words of the counter
+ * {lo32(offset + q), hi32(offset + q), lo32(draw), hi32(draw)} under the key
+ * {lo32(seed), hi32(seed)}; element 4 q + i has u = float(word_i >> 8) * 2^-24
+ * and is kept (value 1.0f / (1.0f - p), an fp32 quotient) iff u >= p.
  * gae_decoder_dense: out = Zt Zt^T with Zt = Z (.) mask (mask may be NULL). */
 int gae_dropout_mask(float *mask, int64_t n_elems, float p, uint64_t seed, uint64_t offset,
                      const uint64_t *draw_dev, void *stream);
@@ -415,8 +420,23 @@ int gae_decoder_dense_bwd(const float *G, int64_t ldg, const float *Z, const flo
                           void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- VGAE head (BASELINE config 5; not in the reference: README.md:58 only cites Kipf & Welling 2016) ----
- * gae_normal_noise : eps ~ N(0,1), Philox4x32-10 + Box-Muller, same (seed, offset, draw_dev) contract as
- *                    gae_dropout_mask.
+ * gae_normal_noise : eps ~ N(0,1), Philox4x32-10 + Box-Muller, four values per counter.  seed, offset and draw_dev
+ *                    mean what they mean for gae_dropout_mask (offset counts blocks of four elements; draw_dev NULL =
+ *                    draw 0), but the counter layout is its own, so that noise draw j and dropout draw j of one seed
+ *                    are different streams: block q = elements 4 q .. 4 q + 3 takes the output words w0 .. w3 of
+ *                      {lo32(offset + q), hi32(offset + q), 0x6e6f726d ^ hi32(draw), lo32(draw)}
+ *                    (a tag word, then the draw index with its HIGH half folded into the tag) under the key
+ *                    {lo32(seed), hi32(seed)}.  Pair h = 0, 1 of the block uses
+ *                      u1 = (float(w[2h] >> 8) + 0.5f) * 2^-24   in fp32: the sum rounds to even from 2^23 on, so
+ *                           u1 lies in (0, 1] -- smallest value 2^-25, a grid of 2^-23 above 0.5, and the top word
+ *                           gives exactly 1 (an exact zero for both values of the pair);
+ *                      u2 = float(w[2h + 1] >> 8) * 2^-24        in [0, 1), exact;
+ *                      rad = sqrtf(-2 log(u1)),  angle = 6.28318530717958648f * u2 (one fp32 product);
+ *                      element 4 q + 2 h = rad * cos(angle),  element 4 q + 2 h + 1 = rad * sin(angle).
+ *                    log, sin and cos are the fast device intrinsics (__logf, __sincosf): the values are reproducible
+ *                    on the device, run to run and between this entry point and gae_x_vgae_head_prep, but agree with a
+ *                    host restatement only inside a measured bound (MEASUREMENTS.md, "VGAE head and random draws";
+ *                    tests/noise_ref.py).  |value| < 5.9.
  * gae_vgae_head_fwd: z = mu + eps * exp(logstd);  kl_out = -(0.5/N) * mean_i sum_j (1 + 2 logstd - mu^2 -
  *                    exp(2 logstd))   (one fp32 on the device); eps / z contiguous [n, d]; the rows of mu and of
  *                    logstd (and of their gradients in gae_vgae_head_bwd) are ldm floats apart -- ldm = d for
