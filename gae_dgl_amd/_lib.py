@@ -33,6 +33,9 @@ MLP_STATE_HEADER = 16             # GAE_MLP_STATE_HEADER (floats)
 MLP_ADAM, MLP_SGD = 0, 1
 MLP_SHUFFLE, MLP_FINAL = 1, 2
 MLP_ERR_LIST_PTR, MLP_ERR_ROW_ID, MLP_ERR_LIST_ID, MLP_ERR_RESUME = 1, 2, 4, 8
+LOGREG_CHUNK_ROWS, LOGREG_SLAB_CHUNKS = 64, 8     # GAE_LOGREG_CHUNK_ROWS, GAE_LOGREG_SLAB_CHUNKS
+LOGREG_EVAL = 1
+LOGREG_ERR_FOLD_PTR, LOGREG_ERR_ROW_ID, LOGREG_ERR_LAMBDA, LOGREG_ERR_LABEL, LOGREG_ERR_NONFINITE = 1, 2, 4, 8, 16
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _p, _f, _int = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
@@ -205,6 +208,13 @@ SIGNATURES = {
     "gae_mlp_fit": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p,
                            _i64, _i64, _f, _f, _f, _int, _f, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p]),
     "gae_mlp_predict": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p, _p]),
+    "gae_logreg_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "gae_logreg_factor": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "gae_logreg_pass": (_int, [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _int, _p, _p,
+                               _p, _p, _i64, _p]),
+    "gae_logreg_update": (_int, [_i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_double, _p, _p, _p,
+                                 _p, _p, _p, _p, _p, _i64, _p]),
+    "gae_logreg_predict": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

@@ -26,6 +26,7 @@
 #include <float.h>
 
 #include "common.h"
+#include "cholesky.h"
 
 namespace {
 
@@ -40,35 +41,19 @@ static_assert(kChunk % kStage == 0, "a chunk is a whole number of stages");
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 
-__host__ __device__ inline int64_t tri(int64_t w) { return w * (w + 1) / 2; }
-// entry (i, j), i <= j, of a packed upper triangle of order W (rows one after another)
-__device__ __forceinline__ int64_t upper_at(int i, int j, int W) { return int64_t(i) * W - int64_t(i) * (i - 1) / 2 + (j - i); }
+using gae::tri;
+using gae::upper_at;
 
 __device__ __forceinline__ void flag(gae_ridge_status *st, int64_t bits)
 {
     atomicOr(reinterpret_cast<unsigned long long *>(&st->errors), static_cast<unsigned long long>(bits));
 }
 
-// the fp64 form of common.h's sum_partials: the same lists, the same order
+// the fp64 form of common.h's sum_partials (cholesky.h): the same lists, the same order
 __device__ __forceinline__ double sum_partials(const double *__restrict__ p0, int64_t n_partials, int64_t stride, int lane,
                                                int L)
 {
-    double g = 0.0;
-    for (int64_t q0 = lane; q0 < n_partials; q0 += int64_t(16) * L) {
-        double v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int64_t q = q0 + int64_t(u) * L;
-            v[u] = p0[(q < n_partials ? q : n_partials - 1) * stride];
-        }
-#pragma unroll
-        for (int u = 0; u < 16; ++u) g += q0 + int64_t(u) * L < n_partials ? v[u] : 0.0;
-    }
-    if (L == 64) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) g += __shfl_down(g, off, 64);
-    }
-    return g;
+    return gae::sum_partials_f64(p0, n_partials, stride, lane, L);
 }
 
 // ------------------------------------------------------------------------------------------------------ stats
@@ -379,23 +364,7 @@ __global__ __launch_bounds__(kThreads) void ridge_solve_kernel(const SolveArgs a
         }
         __syncthreads();
         // ---- Cholesky-Crout, column by column; thread r owns row j + r, the rows d .. D - 1 are the right-hand sides
-        for (int j = 0; j < d; ++j) {
-            const int i = j + tid;
-            const bool on = i < D;
-            const double *rj = Lm + row_at(j);
-            double *ri = Lm + row_at(on ? i : j);
-            double piv = rj[j], s = ri[j];
-            for (int k = 0; k < j; ++k) {
-                const double ljk = rj[k];
-                piv -= ljk * ljk;
-                s -= ri[k] * ljk;
-            }
-            if (!(piv > 0.0 && piv <= DBL_MAX)) { info = j + 1; break; }       // the same value in every thread
-            const double ljj = sqrt(piv);
-            if (i == j) dg[j] = ljj;                                   // rj[j] keeps its value: others may still read it
-            else if (on) ri[j] = s / ljj;
-            __syncthreads();
-        }
+        info = gae::cholesky_crout(Lm, dg, d, D, tid, row_at);
     }
     if (info == 0) {
         // ---- back substitution L^T w = z, row d - 1 first

@@ -33,7 +33,12 @@ fold model of every (lr, alpha) pair side by side; hidden widths ``H`` (one or t
 (1)); needs ``--targets`` ([G] or [G, t]); prints the time of the call and the cross-validated RMSE | R2 at the chosen
 pair, one pair per target; ``--mlp_out PATH`` writes 'hidden', 'lr', 'alpha', 'shift', 'scale', 'cv_rmse', 'cv_r2' and per
 layer 'weight{l}' [S, out, in], 'bias{l}' [S, out] as .npz (``finetune --head_init`` reads it).  Combines with ``--ridge``,
-``--forest`` and ``--neighbours``."""
+``--forest`` and ``--neighbours``.
+``--labels y.npy --logreg [LAMBDA ...]`` fits the head of a classification property on the features just computed
+(``ops.logreg``: multinomial logistic regression, every fold x lambda model in the same launches, lambda chosen by
+``--logreg_folds F``-fold CV on the device; classes are integers, -1 = unlabelled) and prints accuracy | macro-F1 | log-loss
+of the pooled held-out predictions at the chosen lambda; ``--logreg_out PATH`` writes 'coef', 'intercept', 'pivot', 'lam',
+'lambdas', 'cv_logloss' and 'cv_accuracy' as .npz.  Combines with ``--ridge``, ``--forest``, ``--mlp`` and ``--neighbours``."""
 import argparse
 import os
 import time
@@ -106,6 +111,16 @@ def build_parser():
     ap.add_argument("--mlp_out", type=str, default=None, metavar="PATH",
                     help="with --mlp: write the chosen model (.npz: 'hidden', 'lr', 'alpha', 'shift', 'scale', 'cv_rmse', "
                          "'cv_r2', 'weight{l}', 'bias{l}')")
+    ap.add_argument("--labels", type=str, default=None, metavar="PATH",
+                    help="with --logreg: .npy file [G] of integer classes in the order of --out (-1 = unlabelled)")
+    ap.add_argument("--logreg", type=float, nargs="*", default=None, metavar="LAMBDA",
+                    help="also fit a multinomial logistic regression head on the features (needs --labels; 3 d <= 128, at "
+                         "most 32 classes): the penalty is chosen by k-fold CV among the LAMBDAs (default 10^-3 .. 10^3, "
+                         "13 values), all on the device; prints accuracy | macro-F1 | log-loss of the held-out predictions")
+    ap.add_argument("--logreg_folds", type=int, default=None, metavar="F", help="with --logreg: CV folds, 2..32 (default 5)")
+    ap.add_argument("--logreg_out", type=str, default=None, metavar="PATH",
+                    help="with --logreg: write the model (.npz: 'coef' [c, 3 d], 'intercept' [c], 'pivot', 'lam', 'lambdas', "
+                         "'cv_logloss', 'cv_accuracy')")
     ap.add_argument("--norm", choices=["none", "both"], default="none",
                     help="none = the reference's plain in-edge sums; both = D^-1/2 A D^-1/2")
     ap.add_argument("--fused", choices=["auto", "on", "off"], default="auto",
@@ -196,6 +211,20 @@ def parse_args(argv=None):
                          f"{ops.MLP_MAX_MODELS} per call")
         if not os.path.exists(args.targets):
             parser.error(f"--targets {args.targets}: no such file")
+    if args.logreg is None:
+        if args.logreg_out or args.logreg_folds is not None or args.labels:
+            parser.error("--logreg_out / --logreg_folds / --labels need --logreg")
+    else:
+        if not args.labels:
+            parser.error("--logreg needs --labels PATH: the class of every molecule")
+        if 3 * args.hidden_dims[-1] > ops.LOGREG_MAX_D:
+            parser.error(f"--logreg: the feature width 3 d = {3 * args.hidden_dims[-1]} must not exceed {ops.LOGREG_MAX_D}")
+        if args.logreg_folds is not None and not 2 <= args.logreg_folds <= ops.LOGREG_MAX_FOLDS:
+            parser.error(f"--logreg_folds {args.logreg_folds}: F must lie in 2..{ops.LOGREG_MAX_FOLDS}")
+        if len(args.logreg) > ops.LOGREG_MAX_LAMBDAS or not all(v >= 0.0 and v < float("inf") for v in args.logreg):
+            parser.error(f"--logreg: at most {ops.LOGREG_MAX_LAMBDAS} finite values >= 0")
+        if not os.path.exists(args.labels):
+            parser.error(f"--labels {args.labels}: no such file")
     if args.neighbours is None:
         if args.metric is not None or args.neighbours_out or (args.targets and args.ridge is None and args.forest is None
                                                               and args.mlp is None):
@@ -356,6 +385,42 @@ def main(argv=None):
                 arrays[f"bias{l}"] = b.cpu().numpy()
             np.savez(args.mlp_out, **arrays)
         main.mlp = res
+    main.logreg = None
+    if args.logreg is not None:
+        from gae_dgl_amd import metrics
+        from gae_dgl_amd.ops.logreg import _default_fold
+        y = np.load(args.labels)
+        if y.ndim != 1 or y.shape[0] != out.shape[0] or not np.issubdtype(y.dtype, np.integer):
+            raise ValueError(f"--labels of shape {y.shape}, {y.dtype} for {out.shape[0]} molecules: integer classes [G]")
+        y = torch.from_numpy(y.astype(np.int64)).to(device)
+        n_folds = args.logreg_folds or 5
+        fold = _default_fold(out.shape[0], n_folds, args.seed or 0).to(device)
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        res = ops.logreg(feats, y, args.logreg or None, folds=n_folds, fold=fold)
+        torch.cuda.synchronize(device)
+        print(f"Fitted logistic regression on {res.n_used} molecules, {res.coef.shape[0]} classes, {len(res.lambdas)} lambdas x "
+              f"{n_folds} folds | passes: {int(res.n_iter.max())} at most"
+              f"{'' if bool(res.converged.all()) else ' (not all converged)'} | "
+              f"{(time.perf_counter() - t0) * 1e3:.3f} ms (one call, set-up included)")
+        chosen = res.lambdas.tolist().index(res.lam)
+        c = res.coef.shape[0]
+        pred = torch.full((out.shape[0],), -1, dtype=torch.int32, device=device)
+        proba = torch.full((out.shape[0], c), float("nan"), dtype=torch.float32, device=device)
+        for f in range(n_folds):                                       # every labelled molecule by the model that did not see it
+            idx = ((fold == f) & (y >= 0)).nonzero().reshape(-1)
+            pf, qf = ops.logreg_predict(feats.index_select(0, idx).contiguous(), res.fold_coef[f, chosen],
+                                        res.fold_intercept[f, chosen], res.pivot, proba=True)
+            pred[idx], proba[idx] = pf, qf
+        cm = metrics.classification_metrics(pred, y, proba, n_classes=c)
+        print(f"LogReg ({n_folds}-fold CV, lambda = {res.lam:g}) accuracy: {cm['accuracy']:.4f} | "
+              f"macro-F1: {cm['macro_f1']:.4f} | log-loss: {cm['log_loss']:.4f}")
+        if args.logreg_out:
+            np.savez(args.logreg_out, coef=res.coef.cpu().numpy(), intercept=res.intercept.cpu().numpy(),
+                     pivot=res.pivot.cpu().numpy(), lam=np.float64(res.lam), lambdas=res.lambdas.cpu().numpy(),
+                     cv_logloss=res.cv_logloss.cpu().numpy(), cv_accuracy=res.cv_accuracy.cpu().numpy())
+        main.logreg = res
+        main.logreg_scores = cm
     return out
 
 

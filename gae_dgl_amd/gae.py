@@ -334,6 +334,21 @@ class GAE(nn.Module):
                 g.ndata['h'] = feat
         return ops.knn(z, k=k, metric=metric)
 
+    def classify_nodes(self, g, labels, **kw):
+        """``ops.LogRegResult``: the standard protocol for an unsupervised node embedding -- freeze encode(g), fit a
+        multinomial logistic regression on the labelled nodes (``labels``: an int tensor [n], -1 = unlabelled), choose
+        the penalty by k-fold CV, on the device (ops.logreg; its keyword arguments pass through: lambdas, folds, fold,
+        seed, n_classes, max_iter, tol, check_every, model_batch; ``fold = -1`` keeps a test set out).
+        ``metrics.classification_metrics`` scores ``result.predict(z)`` on the nodes kept out.  Runs encode(g) under
+        no_grad; ``g.ndata['h']`` is restored on exit."""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                z = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return ops.logreg(z, labels, **kw)
+
     def nearest_graphs(self, data, k, *, queries=None, metric="l2", **embed_kw):
         """``ops.KNNResult(index, value)``: similarity search over the molecule features of ``embed_graphs`` (its
         keyword arguments pass through: fused, batch_size).  ``queries=None``: the kNN graph of ``data`` -- for every
@@ -359,6 +374,18 @@ class GAE(nn.Module):
         embed_kw = {k: kw.pop(k) for k in ("fused", "batch_size") if k in kw}
         with torch.no_grad():
             return ops.ridge(self.embed_graphs(data, **embed_kw), y, **kw)
+
+    def logreg_graphs(self, data, y, **kw):
+        """``ops.LogRegResult``: multinomial logistic regression of the per-molecule classes ``y`` (an int tensor [G], -1 =
+        unlabelled) on the molecule features of ``embed_graphs`` -- the head of a classification property, lambda chosen
+        by k-fold CV on the device (``ops.logreg``; its keyword arguments pass through: lambdas, folds, fold, seed,
+        n_classes, max_iter, tol, check_every, model_batch).  ``fused`` and ``batch_size`` go to the embedding.  Rows are
+        in the order ``embed_graphs(data)`` returns them.  Runs under no_grad."""
+        if "grad" in kw:
+            raise ValueError("logreg_graphs runs under no_grad: the fitted head carries no gradient into the encoder")
+        embed_kw = {k: kw.pop(k) for k in ("fused", "batch_size") if k in kw}
+        with torch.no_grad():
+            return ops.logreg(self.embed_graphs(data, **embed_kw), y, **kw)
 
     def forest_graphs(self, data, y, **kw):
         """``ops.ForestResult``: a random forest regression of the per-molecule targets ``y`` ([G] or [G, t]) on the

@@ -387,3 +387,54 @@ def regression_metrics(pred, y):
     sst = float(((t - t.mean()) ** 2).sum())
     return {"rmse": (sse / n) ** 0.5, "mae": float(err.abs().mean()), "r2": 1.0 - sse / sst if sst > 0 else nan, "n": n,
             "left_out": int(pred.numel()) - n}
+
+
+def classification_metrics(pred, true, proba=None, n_classes=None):
+    """``accuracy``, ``macro_f1``, per-class ``precision`` / ``recall`` / ``f1`` (lists, 0 where the denominator is 0), the
+    ``confusion`` matrix (int64 [c, c] as nested lists: row = true class, column = predicted class) and ``n`` of class
+    predictions ``pred`` [m] against classes ``true`` [m]; with ``proba`` [m, c] also ``log_loss`` (the mean of -log of
+    the true class's probability, clipped at 1e-15) and, for two classes, ``roc_auc`` of column 1.  Rows whose true label
+    is -1 are not scored; a scored row whose prediction is -1 (``LogRegResult.predict``: a non-finite row) counts as an
+    error in ``accuracy`` and the recalls, is in no column of the matrix, is left out of the probability scores and is
+    counted in ``unpredicted``.  Torch on the device of ``pred``, fp64; Python numbers out."""
+    pred = torch.as_tensor(pred).long().reshape(-1)
+    true = torch.as_tensor(true).to(pred.device).long().reshape(-1)
+    if pred.shape != true.shape:
+        raise ValueError(f"classification_metrics: {pred.numel()} predictions for {true.numel()} labels")
+    hi = int(max(pred.max(), true.max())) if pred.numel() else -1
+    c = hi + 1 if n_classes is None else int(n_classes)
+    if proba is not None:
+        proba = torch.as_tensor(proba).to(pred.device).double()
+        if proba.dim() != 2 or proba.shape[0] != pred.numel():
+            raise ValueError(f"classification_metrics: proba must be [{pred.numel()}, c], got {tuple(proba.shape)}")
+        c = max(c, proba.shape[1]) if n_classes is None else c
+        if proba.shape[1] != c:
+            raise ValueError(f"classification_metrics: proba has {proba.shape[1]} columns for {c} classes")
+    if c < 1 or hi >= c or (pred.numel() and int(min(pred.min(), true.min())) < -1):
+        raise ValueError(f"classification_metrics: labels must lie in -1..{c - 1}")
+    scored = true >= 0
+    n = int(scored.sum())
+    nan = float("nan")
+    t, p = true[scored], pred[scored]
+    seen = p >= 0
+    conf = torch.bincount(t[seen] * c + p[seen], minlength=c * c).reshape(c, c)
+    tp = conf.diagonal().double()
+    support, called = torch.bincount(t, minlength=c).double(), conf.sum(0).double()
+    zero = torch.zeros_like(tp)
+    precision = torch.where(called > 0, tp / called.clamp_min(1), zero)
+    recall = torch.where(support > 0, tp / support.clamp_min(1), zero)
+    f1 = torch.where(precision + recall > 0, 2 * precision * recall / (precision + recall).clamp_min(1e-300), zero)
+    present = support > 0                                               # macro-F1 over the classes that occur
+    out = {"accuracy": float(tp.sum()) / n if n else nan, "macro_f1": float(f1[present].mean()) if n else nan,
+           "precision": precision.tolist(), "recall": recall.tolist(), "f1": f1.tolist(), "confusion": conf.tolist(),
+           "n": n, "unpredicted": int((~seen).sum())}
+    if proba is not None:
+        P = proba[scored][seen]
+        ts = t[seen]
+        ok = ~torch.isnan(P).any(1)
+        P, ts = P[ok], ts[ok]
+        out["log_loss"] = float(-torch.log(P.gather(1, ts[:, None]).clamp_min(1e-15)).mean()) if P.shape[0] else nan
+        if c == 2:
+            pos, neg = P[ts == 1, 1], P[ts == 0, 1]
+            out["roc_auc"] = roc_auc(pos, neg) if pos.numel() and neg.numel() else nan
+    return out

@@ -7,6 +7,7 @@ epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
   python -m gae_dgl_amd.train_transductive --dataset cora [--norm both] [--eval [--rank]] [--topk 10 [--topk_out top.npz]]
       [--loss_samples M] [--decode_out graph.npz [--decode_prob P] [--decode_max_pairs M]]
       [--cluster K [--cluster_seed S] [--cluster_out clusters.npz]] [--knn K [--knn_metric l2|dot|cosine]]
+      [--classify [LAMBDA ...] [--classify_folds F] [--classify_test_frac Q] [--classify_seed S] [--classify_out model.npz]]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -82,6 +83,20 @@ def build_parser():
                          "neighbours (GAE.nearest_nodes, on the device); unlabelled nodes neither vote nor are scored")
     ap.add_argument("--knn_metric", choices=["l2", "dot", "cosine"], default=None,
                     help="with --knn: squared Euclidean distance (default), inner product or cosine similarity")
+    ap.add_argument("--classify", type=float, nargs="*", default=None, metavar="LAMBDA",
+                    help="after training, the standard protocol for the frozen node embedding: a seeded split of the "
+                         "labelled nodes, multinomial logistic regression on the training part with the penalty chosen "
+                         "by F-fold CV among the LAMBDAs (default 10^-3 .. 10^3, 13 values) on the device "
+                         "(GAE.classify_nodes), then accuracy | macro-F1 | log-loss on the test part")
+    ap.add_argument("--classify_folds", type=int, default=None, metavar="F", help="with --classify: CV folds, 2..32 (default 5)")
+    ap.add_argument("--classify_test_frac", type=float, default=None, metavar="Q",
+                    help="with --classify: the share of the labelled nodes kept out as the test part, inside (0, 1) "
+                         "(default 0.2)")
+    ap.add_argument("--classify_seed", type=int, default=None, metavar="S",
+                    help="with --classify: the seed of the split and of the folds (default 0)")
+    ap.add_argument("--classify_out", default=None, metavar="PATH",
+                    help="with --classify: write PATH (.npz with 'coef' fp64 [c, d], 'intercept' [c], 'lam', 'lambdas', "
+                         "'cv_logloss', 'cv_accuracy', 'test_index' int64 and 'test_pred' int32)")
     return ap
 
 
@@ -118,6 +133,18 @@ def parse_args(argv=None):
             ap.error("--knn_metric needs --knn K")
     elif not 1 <= args.knn <= 64:
         ap.error(f"--knn {args.knn}: K must lie in 1..64")
+    if args.classify is None:
+        if any(v is not None for v in (args.classify_folds, args.classify_test_frac, args.classify_seed, args.classify_out)):
+            ap.error("--classify_folds / --classify_test_frac / --classify_seed / --classify_out need --classify")
+    else:
+        if len(args.classify) > 64:
+            ap.error(f"--classify: at most 64 LAMBDAs, not {len(args.classify)}")
+        if not all(v >= 0.0 and v < float("inf") for v in args.classify):
+            ap.error(f"--classify {args.classify}: finite values >= 0")
+        if args.classify_folds is not None and not 2 <= args.classify_folds <= 32:
+            ap.error(f"--classify_folds {args.classify_folds}: F must lie in 2..32")
+        if args.classify_test_frac is not None and not 0.0 < args.classify_test_frac < 1.0:
+            ap.error(f"--classify_test_frac {args.classify_test_frac}: Q must lie inside (0, 1)")
     return args
 
 
@@ -251,6 +278,38 @@ def main(argv=None):
                   f"nodes scored: {int(scored.sum())} of {n_nodes}")
             main.last_knn = {"acc": acc, "n": int(scored.sum()), "result": nn, "pred": pred, "model": model, "graph": g,
                              "features": features}
+    if args.classify is not None:
+        import numpy as np
+        main.last_classify = None
+        if data.labels is None:
+            print("LogReg: the dataset carries no class labels, nothing to fit")
+        else:
+            F = args.classify_folds or 5
+            labels = torch.as_tensor(data.labels, dtype=torch.int64, device=device)
+            known = (labels >= 0).nonzero().reshape(-1).cpu()
+            gen = torch.Generator(device="cpu").manual_seed(args.classify_seed or 0)
+            perm = known[torch.randperm(known.numel(), generator=gen)]
+            n_test = max(1, int(round((0.2 if args.classify_test_frac is None else args.classify_test_frac) * perm.numel())))
+            test, train = perm[:n_test], perm[n_test:]
+            fold = torch.full((n_nodes,), -1, dtype=torch.int64)
+            fold[train] = torch.arange(train.numel()) % F               # the test part enters as fold = -1: never read
+            g.ndata['h'] = features
+            res = model.classify_nodes(g, labels, lambdas=args.classify or None, folds=F, fold=fold.to(device))
+            g.ndata['h'] = features
+            with torch.no_grad():
+                z = model.encode(g)
+            g.ndata['h'] = features
+            z = z[0] if isinstance(z, tuple) else z
+            zt = z.index_select(0, test.to(device)).contiguous()
+            pred, proba = ops.logreg_predict(zt, res.coef, res.intercept, res.pivot, proba=True)
+            cm = metrics.classification_metrics(pred, labels[test.to(device)], proba, n_classes=res.coef.shape[0])
+            print(f"LogReg ({F}-fold CV, lambda = {res.lam:g}) test accuracy: {cm['accuracy']:.4f} | "
+                  f"macro-F1: {cm['macro_f1']:.4f} | log-loss: {cm['log_loss']:.4f}")
+            main.last_classify = {"result": res, "metrics": cm, "test": test, "pred": pred}
+            if args.classify_out is not None:
+                np.savez(args.classify_out, coef=res.coef.cpu().numpy(), intercept=res.intercept.cpu().numpy(), lam=res.lam,
+                         lambdas=res.lambdas.cpu().numpy(), cv_logloss=res.cv_logloss.cpu().numpy(),
+                         cv_accuracy=res.cv_accuracy.cpu().numpy(), test_index=test.numpy(), test_pred=pred.cpu().numpy())
     return [float(l) for l in losses]
 
 

@@ -146,6 +146,17 @@ class VGAE(nn.Module):
                 g.ndata['h'] = feat
         return ops.kmeans(mu, k, **kw)
 
+    def classify_nodes(self, g, labels, **kw):
+        """GAE.classify_nodes on the mean embedding mu (no noise): ``ops.LogRegResult`` of ops.logreg; mu is read in
+        place where the two heads are packed in one buffer; ``g.ndata['h']`` is restored on exit"""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                mu, _ = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return ops.logreg(mu, labels, **kw)
+
     def nearest_nodes(self, g, k, *, metric="l2"):
         """GAE.nearest_nodes on the mean embedding mu (no noise): ``ops.KNNResult`` of ops.knn, the node itself left
         out; mu is read in place where the two heads are packed in one buffer; ``g.ndata['h']`` is restored on exit"""

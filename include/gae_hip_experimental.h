@@ -13,7 +13,8 @@
  * and gae_score_graphs, the per-molecule reconstruction scores (AUC counts, average precision, loss) of a resident set,
  * and gae_kmeans_*, node clustering on the device: k-means++ seeding, Lloyd iterations and assignment over an embedding,
  * and gae_knn, the exact k nearest rows of one embedding for every row of another,
- * and gae_ridge_*, ridge regression on a frozen feature: per-fold fp64 moments in one pass, the k-fold CV lambda path.
+ * and gae_ridge_*, ridge regression on a frozen feature: per-fold fp64 moments in one pass, the k-fold CV lambda path,
+ * and gae_logreg_*, softmax regression on a frozen feature: every fold x lambda model of a CV call in the same launches.
  * Same conventions as gae_hip.h: caller-owned buffers, 0 / negative / hipError_t return codes, asynchronous launches on
  * the stream passed last.  These signatures may change between versions without a GAE_VERSION major bump. */
 #ifndef GAE_HIP_EXPERIMENTAL_H
@@ -908,6 +909,103 @@ int gae_mlp_fit(const float *X, int64_t ldx, const float *Y, int64_t ldy, int64_
 int gae_mlp_predict(const float *X, int64_t ldx, int64_t n, int64_t d, int64_t h1, int64_t h2, int64_t t,
                     const float *shift, const float *scale, const void *state, int64_t n_models, float *out,
                     gae_mlp_status *status, void *stream);
+
+/* ---- K28: multinomial logistic regression on a frozen feature with a k-fold CV lambda path (ops.logreg,
+ * GAE.classify_nodes, GAE.logreg_graphs, embed --logreg, train_transductive --classify)
+ * The standard protocol for an unsupervised embedding: freeze it, fit a softmax classifier on the labelled rows, report
+ * held-out accuracy.  Per model
+ *   J(b, W) = sum_{i in training rows} -log softmax(b + W x~_i)[y_i] + (lambda / 2) sum_k |w_k|^2,   x~ = x - p
+ * (sklearn's C = 1 / lambda; the intercepts are not penalised; p, the pivot, is fp32 [d] or NULL = zeros).
+ *   X fp32 [n, d], rows ldx >= d floats apart;  y int32 [n] with the class of every LISTED row in 0 .. c - 1 (another value
+ *   sets GAE_LOGREG_ERR_LABEL and the row enters without a label);  rows / fold_ptr: gae_ridge_stats' lists (rows int32
+ *   [n_rows] ascending inside each fold, fold_ptr DEVICE int32 [folds + 1]).  Rows that are not listed are never read.
+ *   1 <= d <= 128, 2 <= c <= 32, 1 <= folds <= 32, 1 <= n_lambdas <= 64, 1 <= model_batch <= models (else GAE_E_RANGE);
+ *   0 <= n, n_rows < 2^31 (else GAE_E_SIZE).  There is no fallback for other shapes.
+ * MODELS: models = (folds + 1) n_lambdas; model g = m n_lambdas + l trains at lambdas[l] on every fold but m (m < folds)
+ * or on all listed rows (m = folds).  With D1 = d + 1 its parameters are [c][D1], column 0 the intercept about the pivot.
+ * A caller may cut the models into launches [model_lo, model_lo + model_count), model_count <= model_batch; no model's
+ * numbers depend on the cut or on the other models.
+ * SOLVER: first order in the metric of a fixed majoriser, accelerated, with gradient restart.
+ *   majoriser  S = sum [1, x~][1, x~]^T over the training rows; the Hessian is below S / 2 (x) I_c (Boehning), so
+ *              A = S / 2 + lambda diag(0, 1 .. 1) is factorised ONCE per model and shared by the classes.  The step is
+ *              invariant to an affine rescaling of the features.
+ *   gae_logreg_factor: one block per model.  stats: gae_ridge_stats' output for t = 1 (width d + 2; the target's
+ *              entries are ignored), taken with pivot [p, anything].  The training folds are added in ascending order, A
+ *              is factorised by K25's fp64 Cholesky-Crout in LDS, the factor goes to the workspace.  The call also resets
+ *              the state (W = W_prev = V = 0, t = 1) and the tables: info (LAPACK style as gae_ridge_solve: 0; j: pivot j
+ *              <= 0 or not finite; -1: no training row; -2: lambda negative or not finite; later -3: the iteration left
+ *              the finite numbers), n_iter = 0, converged = 0, coef / intercept 0 (NaN where info != 0);
+ *              status.active_models += the models with info == 0.
+ *   iteration  pass k = 1, 2, ...:  t' = (1 + sqrt(1 + 4 t^2)) / 2;  V = W + ((t - 1) / t') (W - W_prev), rounded to fp32;
+ *              G = X~^T (softmax(X~ V) - Y) + lambda D V;  dV = -A^-1 G;  W_new = V + dV;  if <G, W_new - W> > 0 then
+ *              t = 1 (gradient restart) else t = t'.  A model is done when max|dV| <= tol max(1, max|W_new|); a done
+ *              model is frozen -- its blocks exit at once in later launches -- so its result depends neither on the
+ *              other models nor on how often the caller looks at the status.  Reaching max_iter is not an error:
+ *              converged stays 0.
+ *   gae_logreg_pass: grid (slabs, tiles of 4 models).  Each fold's list is cut into chunks of GAE_LOGREG_CHUNK_ROWS rows
+ *              (a chunk never straddles folds); a slab is GAE_LOGREG_SLAB_CHUNKS consecutive chunks of the list, so the
+ *              number of slabs, ceil((ceil(n_rows / chunk) + folds) / slab), is a function of the list sizes alone.  A
+ *              block stages a chunk once in LDS, x~ formed in fp32 by one rounded subtraction, and uses it for every
+ *              model of its tile.  Logits on v_mfma_f32_16x16x4_f32 (d + 1 and c padded with zeros to the tile; a wave
+ *              owns whole output tiles, the summed index is never split); the row softmax in fp32: max, subtract, exp,
+ *              ascending sum, one reciprocal, each probability the product with it; the residual subtracts the one-hot
+ *              label; the chunk's gradient R^T X~ on the same instruction, accumulated in fp32 over the slab's chunks in
+ *              ascending order.  A chunk of fold f is skipped, not masked, for model f.  One partial per (slab, model).
+ *              GAE_LOGREG_EVAL: the same staging and product at V (after a fit: fp32 of the final W), then per row in fp64
+ *              the negative log-likelihood log sum exp(z - max) - (z_y - max) and the test arg max == y (ties to the
+ *              lower class), for fold model m over its OWN fold and for the all-rows model over every row: nll fp64
+ *              [models] and correct int64 [models] (NaN / 0 where the model failed), rows added in ascending order, slabs
+ *              in THE order of partial lists.
+ *   gae_logreg_update: one block per model, after the pass of the same models.  The slab partials are added in fp64 in
+ *              THE order of partial lists (csrc/common.h sum_partials: <= 32 one lane in order; more: 64 lanes, lane l
+ *              adds l, l + 64 ..., then the shuffle-down tree); + lambda D V; the c systems are solved with the stored
+ *              factor; the restart test and the stopping rule run in fp64 in a fixed order (per thread ascending, then a
+ *              fixed tree).  At a stop (done, or iteration == max_iter) V = fp32(W), coef fp64 [models][c][d] and
+ *              intercept fp64 [models][c] are written, the intercept mapped back through the pivot in fp64
+ *              (b = W[k][0] - sum_j p_j W[k][1 + j]), n_iter = iteration, converged = done, status.active_models -= 1.
+ *              Because W starts at 0 and every update sums to zero over the classes, the parameters sum to (about) zero
+ *              over the classes: the minimum-norm representative of the shift-invariant intercepts.
+ *   status     a 32-byte device block the caller zeroes: active_models (see above), nonfinite_rows (gae_logreg_predict),
+ *              errors: GAE_LOGREG_ERR_FOLD_PTR (fold_ptr not monotone from >= 0 to n_rows: nothing is read through it),
+ *              _ROW_ID (a row id outside [0, n): skipped), _LAMBDA, _LABEL, _NONFINITE (a model's gradient or iterate
+ *              left the finite numbers -- a non-finite feature in a listed row does that; info = -3).
+ *   workspace  gae_logreg_workspace_bytes(n_rows, d, c, folds, n_lambdas, model_batch): a pure host function, positive,
+ *              non-decreasing in n_rows, in the model count and in model_batch.  The same block, with the same arguments,
+ *              is passed to every call of a fit: it holds the factors and the iteration state, then one launch's partials.
+ *   No float atomics: the result has the same bits run to run, for any ldx, any stream and any cut of the models.
+ * gae_logreg_predict: labels int32 [n] (arg max, ties to the lower class) and, when proba is not NULL, fp32 [n, c] rows
+ * ldp apart, of the model (coef fp64 [c][d], intercept fp64 [c]) through the pass kernel's staging, product and softmax
+ * code about `pivot`.  A row that holds a non-finite feature gives -1 / NaN and adds to status.nonfinite_rows.
+ * Argument errors are returned before anything is dereferenced or launched (no GPU is needed to see them). */
+enum { GAE_LOGREG_CHUNK_ROWS = 64, GAE_LOGREG_SLAB_CHUNKS = 8 };
+enum { GAE_LOGREG_EVAL = 1 };
+enum { GAE_LOGREG_ERR_FOLD_PTR = 1, GAE_LOGREG_ERR_ROW_ID = 2, GAE_LOGREG_ERR_LAMBDA = 4, GAE_LOGREG_ERR_LABEL = 8,
+       GAE_LOGREG_ERR_NONFINITE = 16 };
+
+typedef struct gae_logreg_status {
+    int64_t active_models, nonfinite_rows, errors, reserved;
+} gae_logreg_status;
+
+int64_t gae_logreg_workspace_bytes(int64_t n_rows, int64_t d, int64_t c, int64_t folds, int64_t n_lambdas,
+                                   int64_t model_batch);
+
+int gae_logreg_factor(const double *stats, int64_t d, int64_t c, int64_t folds, const double *lambdas, int64_t n_lambdas,
+                      int64_t n_rows, int64_t model_batch, double *coef, double *intercept, int32_t *info, int32_t *n_iter,
+                      int32_t *converged, gae_logreg_status *status, void *workspace, int64_t workspace_bytes, void *stream);
+
+int gae_logreg_pass(const float *X, int64_t ldx, const int32_t *y, int64_t n, int64_t d, int64_t c, const float *pivot,
+                    const int32_t *rows, int64_t n_rows, const int32_t *fold_ptr, int64_t folds, int64_t n_lambdas,
+                    int64_t model_batch, int64_t model_lo, int64_t model_count, int flags, double *nll, int64_t *correct,
+                    gae_logreg_status *status, void *workspace, int64_t workspace_bytes, void *stream);
+
+int gae_logreg_update(int64_t d, int64_t c, int64_t folds, const double *lambdas, int64_t n_lambdas, int64_t n_rows,
+                      int64_t model_batch, int64_t model_lo, int64_t model_count, int64_t iteration, int64_t max_iter,
+                      double tol, const float *pivot, double *coef, double *intercept, int32_t *info, int32_t *n_iter,
+                      int32_t *converged, gae_logreg_status *status, void *workspace, int64_t workspace_bytes, void *stream);
+
+int gae_logreg_predict(const float *X, int64_t ldx, int64_t n, int64_t d, int64_t c, const double *coef,
+                       const double *intercept, const float *pivot, int32_t *labels, float *proba, int64_t ldp,
+                       gae_logreg_status *status, void *stream);
 
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
