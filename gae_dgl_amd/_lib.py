@@ -36,6 +36,9 @@ MLP_ERR_LIST_PTR, MLP_ERR_ROW_ID, MLP_ERR_LIST_ID, MLP_ERR_RESUME = 1, 2, 4, 8
 LOGREG_CHUNK_ROWS, LOGREG_SLAB_CHUNKS = 64, 8     # GAE_LOGREG_CHUNK_ROWS, GAE_LOGREG_SLAB_CHUNKS
 LOGREG_EVAL = 1
 LOGREG_ERR_FOLD_PTR, LOGREG_ERR_ROW_ID, LOGREG_ERR_LAMBDA, LOGREG_ERR_LABEL, LOGREG_ERR_NONFINITE = 1, 2, 4, 8, 16
+TSNE_MAX_K, TSNE_BISECT_ITERS = 64, 100            # GAE_TSNE_MAX_K, GAE_TSNE_BISECT_ITERS
+TSNE_KEY_XOR = 0x2545F4914F6CDD1D
+TSNE_STATUS_WORDS = 8             # gae_tsne_status: int64 done, iteration, nonfinite, ticket; double p_log_d, log_z, grad2, z
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _p, _f, _int = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
@@ -215,6 +218,13 @@ SIGNATURES = {
     "gae_logreg_update": (_int, [_i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_double, _p, _p, _p,
                                  _p, _p, _p, _p, _p, _i64, _p]),
     "gae_logreg_predict": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "gae_tsne_chunk": (_i64, [_i64]),
+    "gae_tsne_workspace_bytes": (_i64, [_i64, _i64]),
+    "gae_tsne_init": (_int, [_p, _i64, _i64, _u64, _p]),
+    "gae_tsne_affinities": (_int, [_p, _p, _i64, _i64, _i64, ctypes.c_double, _p, _i64, _p, _p]),
+    "gae_tsne_repulsion": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p]),
+    "gae_tsne_update": (_int, [_p, _i64, _i64, _p, _p, _p, _i64, _p, _p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                               ctypes.c_double, _p, _p, _i64, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

@@ -38,7 +38,11 @@ layer 'weight{l}' [S, out, in], 'bias{l}' [S, out] as .npz (``finetune --head_in
 (``ops.logreg``: multinomial logistic regression, every fold x lambda model in the same launches, lambda chosen by
 ``--logreg_folds F``-fold CV on the device; classes are integers, -1 = unlabelled) and prints accuracy | macro-F1 | log-loss
 of the pooled held-out predictions at the chosen lambda; ``--logreg_out PATH`` writes 'coef', 'intercept', 'pivot', 'lam',
-'lambdas', 'cv_logloss' and 'cv_accuracy' as .npz.  Combines with ``--ridge``, ``--forest``, ``--mlp`` and ``--neighbours``."""
+'lambdas', 'cv_logloss' and 'cv_accuracy' as .npz.  Combines with ``--ridge``, ``--forest``, ``--mlp`` and ``--neighbours``.
+``--map_out map.npz`` maps the features just computed into the plane (``ops.tsne``: exact t-SNE on the device,
+``--map_perplexity P`` (20), ``--map_iters T`` (1000), ``--map_seed S`` (0)), prints the KL divergence and the 10-NN
+preservation of the map and writes 'embedding' [G, 2], 'labels' (those of ``--labels``, else -1), 'kl_divergence' and
+'kl_curve'.  Combines with every flag above."""
 import argparse
 import os
 import time
@@ -121,6 +125,14 @@ def build_parser():
     ap.add_argument("--logreg_out", type=str, default=None, metavar="PATH",
                     help="with --logreg: write the model (.npz: 'coef' [c, 3 d], 'intercept' [c], 'pivot', 'lam', 'lambdas', "
                          "'cv_logloss', 'cv_accuracy')")
+    ap.add_argument("--map_out", type=str, default=None, metavar="PATH",
+                    help="the 2-D map of the features by exact t-SNE on the device (ops.tsne) and its 10-NN preservation; "
+                         "writes PATH (.npz: 'embedding' fp32 [G, 2], 'labels' int64 [G] (--labels, else -1), "
+                         "'kl_divergence', 'kl_curve')")
+    ap.add_argument("--map_perplexity", type=float, default=None, metavar="P",
+                    help="with --map_out: the perplexity, at least 1 and below min(G - 1, 64) (default 20)")
+    ap.add_argument("--map_iters", type=int, default=None, metavar="T", help="with --map_out: iterations (default 1000)")
+    ap.add_argument("--map_seed", type=int, default=None, metavar="S", help="with --map_out: the seed of the start (default 0)")
     ap.add_argument("--norm", choices=["none", "both"], default="none",
                     help="none = the reference's plain in-edge sums; both = D^-1/2 A D^-1/2")
     ap.add_argument("--fused", choices=["auto", "on", "off"], default="auto",
@@ -225,6 +237,16 @@ def parse_args(argv=None):
             parser.error(f"--logreg: at most {ops.LOGREG_MAX_LAMBDAS} finite values >= 0")
         if not os.path.exists(args.labels):
             parser.error(f"--labels {args.labels}: no such file")
+    if not args.map_out:
+        if any(v is not None for v in (args.map_perplexity, args.map_iters, args.map_seed)):
+            parser.error("--map_perplexity / --map_iters / --map_seed need --map_out PATH")
+    else:
+        if 3 * args.hidden_dims[-1] > ops.KNN_MAX_D:
+            parser.error(f"--map_out: the feature width 3 d = {3 * args.hidden_dims[-1]} must not exceed {ops.KNN_MAX_D}")
+        if args.map_perplexity is not None and not 1.0 <= args.map_perplexity < 64.0:
+            parser.error(f"--map_perplexity {args.map_perplexity}: P must lie in [1, 64)")
+        if args.map_iters is not None and args.map_iters < 1:
+            parser.error(f"--map_iters {args.map_iters}: T must be at least 1")
     if args.neighbours is None:
         if args.metric is not None or args.neighbours_out or (args.targets and args.ridge is None and args.forest is None
                                                               and args.mlp is None):
@@ -421,6 +443,21 @@ def main(argv=None):
                      cv_logloss=res.cv_logloss.cpu().numpy(), cv_accuracy=res.cv_accuracy.cpu().numpy())
         main.logreg = res
         main.logreg_scores = cm
+    main.map = None
+    if args.map_out:
+        from gae_dgl_amd import metrics
+        P = 20.0 if args.map_perplexity is None else args.map_perplexity
+        res = ops.tsne(feats, perplexity=P, n_iter=1000 if args.map_iters is None else args.map_iters,
+                       seed=args.map_seed or 0)
+        k10 = min(10, out.shape[0] - 1)
+        keep = metrics.neighbourhood_preservation(ops.knn(feats, k=k10).index, ops.knn(res.embedding, k=k10).index)
+        print(f"t-SNE (perplexity {P:g}, {res.n_iter} iterations) KL: {res.kl_divergence:.4f} | "
+              f"10-NN preservation: {keep:.4f}")
+        labels = np.load(args.labels).astype(np.int64).reshape(-1) if args.labels else np.full(out.shape[0], -1, np.int64)
+        np.savez(args.map_out, embedding=res.embedding.cpu().numpy(), labels=labels, kl_divergence=res.kl_divergence,
+                 kl_curve=np.asarray(res.kl_curve, np.float64).reshape(-1, 2))
+        main.map = res
+        main.map_preservation = keep
     return out
 
 

@@ -334,6 +334,30 @@ class GAE(nn.Module):
                 g.ndata['h'] = feat
         return ops.knn(z, k=k, metric=metric)
 
+    def map_nodes(self, g, **kw):
+        """``ops.TSNEResult``: the 2-D map of the embedding encode(g) -- the Cora figure of the GAE / VGAE papers -- by
+        exact t-SNE on the device (ops.tsne; its keyword arguments pass through: perplexity, n_iter, learning_rate,
+        early_exaggeration, exaggeration_iters, seed, init, neighbours, min_grad_norm, check_every).
+        ``metrics.neighbourhood_preservation`` scores the map against the embedding.  Runs encode(g) under no_grad;
+        ``g.ndata['h']`` is restored on exit."""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                z = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return ops.tsne(z, **kw)
+
+    def map_graphs(self, data, **kw):
+        """``ops.TSNEResult``: the 2-D map of the molecule features of ``embed_graphs`` by exact t-SNE on the device
+        (``ops.tsne``; its keyword arguments pass through).  ``fused`` and ``batch_size`` go to the embedding.  Rows are
+        in the order ``embed_graphs(data)`` returns them.  Runs under no_grad."""
+        if "grad" in kw:
+            raise ValueError("map_graphs runs under no_grad: the map carries no gradient into the encoder")
+        embed_kw = {k: kw.pop(k) for k in ("fused", "batch_size") if k in kw}
+        with torch.no_grad():
+            return ops.tsne(self.embed_graphs(data, **embed_kw), **kw)
+
     def classify_nodes(self, g, labels, **kw):
         """``ops.LogRegResult``: the standard protocol for an unsupervised node embedding -- freeze encode(g), fit a
         multinomial logistic regression on the labelled nodes (``labels``: an int tensor [n], -1 = unlabelled), choose

@@ -367,6 +367,30 @@ def knn_predict(index, value, y, *, task="regression", weights="uniform", n_clas
     return torch.where(votes.any(1), pred, torch.full_like(pred, -1))
 
 
+def neighbourhood_preservation(index_a, index_b, chunk_rows=65536):
+    """mean, over the rows, of the fraction of a row's neighbours in ``index_a`` [n, k] that are also among its
+    neighbours in ``index_b`` [n, k'] -- two ``ops.knn`` index tables of the same rows in two spaces (an embedding and
+    its 2-D map): 1.0 when every neighbourhood survives, about k' / n for unrelated spaces.  Entries of -1 are padding;
+    a row without neighbours in ``index_a`` is left out (NaN when every row is).  No n x n matrix and no ranks: the
+    tables are compared k x k' per row, in chunks of ``chunk_rows`` rows.  Torch on the device of ``index_a``; a Python
+    number out."""
+    a = torch.as_tensor(index_a)
+    b = torch.as_tensor(index_b).to(a.device)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"neighbourhood_preservation: two [n, k] index tables of the same rows, got {tuple(a.shape)} and "
+                         f"{tuple(b.shape)}")
+    total, rows = 0.0, 0
+    for r0 in range(0, a.shape[0], int(chunk_rows)):
+        x, y = a[r0:r0 + chunk_rows].long(), b[r0:r0 + chunk_rows].long()
+        valid = x >= 0
+        hit = ((x.unsqueeze(2) == y.unsqueeze(1)).any(2) & valid).sum(1).double()
+        cnt = valid.sum(1)
+        keep = cnt > 0
+        total += float((hit[keep] / cnt[keep].double()).sum())
+        rows += int(keep.sum())
+    return total / rows if rows else float("nan")
+
+
 def regression_metrics(pred, y):
     """``rmse``, ``mae``, ``r2`` (1 - SSE / SST about the mean of the scored targets; NaN when they are constant) and ``n``
     of predictions ``pred`` [m] against targets ``y`` [m], as the reference's chemistry table reports them (README.md:

@@ -8,6 +8,7 @@ epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
       [--loss_samples M] [--decode_out graph.npz [--decode_prob P] [--decode_max_pairs M]]
       [--cluster K [--cluster_seed S] [--cluster_out clusters.npz]] [--knn K [--knn_metric l2|dot|cosine]]
       [--classify [LAMBDA ...] [--classify_folds F] [--classify_test_frac Q] [--classify_seed S] [--classify_out model.npz]]
+      [--map_out map.npz [--map_perplexity P] [--map_iters T] [--map_seed S]]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -97,6 +98,14 @@ def build_parser():
     ap.add_argument("--classify_out", default=None, metavar="PATH",
                     help="with --classify: write PATH (.npz with 'coef' fp64 [c, d], 'intercept' [c], 'lam', 'lambdas', "
                          "'cv_logloss', 'cv_accuracy', 'test_index' int64 and 'test_pred' int32)")
+    ap.add_argument("--map_out", default=None, metavar="PATH",
+                    help="after training: the 2-D map of the embedding by exact t-SNE on the device (GAE.map_nodes) and its "
+                         "10-NN preservation; writes PATH (.npz with 'embedding' fp32 [N, 2], 'labels' int64 [N] (-1 where "
+                         "the dataset has none), 'kl_divergence' and 'kl_curve')")
+    ap.add_argument("--map_perplexity", type=float, default=None, metavar="P",
+                    help="with --map_out: the perplexity, at least 1 and below min(N - 1, 64) (default 20)")
+    ap.add_argument("--map_iters", type=int, default=None, metavar="T", help="with --map_out: iterations (default 1000)")
+    ap.add_argument("--map_seed", type=int, default=None, metavar="S", help="with --map_out: the seed of the start (default 0)")
     return ap
 
 
@@ -145,6 +154,14 @@ def parse_args(argv=None):
             ap.error(f"--classify_folds {args.classify_folds}: F must lie in 2..32")
         if args.classify_test_frac is not None and not 0.0 < args.classify_test_frac < 1.0:
             ap.error(f"--classify_test_frac {args.classify_test_frac}: Q must lie inside (0, 1)")
+    if args.map_out is None:
+        if any(v is not None for v in (args.map_perplexity, args.map_iters, args.map_seed)):
+            ap.error("--map_perplexity / --map_iters / --map_seed need --map_out PATH")
+    else:
+        if args.map_perplexity is not None and not 1.0 <= args.map_perplexity < 64.0:
+            ap.error(f"--map_perplexity {args.map_perplexity}: P must lie in [1, 64)")
+        if args.map_iters is not None and args.map_iters < 1:
+            ap.error(f"--map_iters {args.map_iters}: T must be at least 1")
     return args
 
 
@@ -310,6 +327,22 @@ def main(argv=None):
                 np.savez(args.classify_out, coef=res.coef.cpu().numpy(), intercept=res.intercept.cpu().numpy(), lam=res.lam,
                          lambdas=res.lambdas.cpu().numpy(), cv_logloss=res.cv_logloss.cpu().numpy(),
                          cv_accuracy=res.cv_accuracy.cpu().numpy(), test_index=test.numpy(), test_pred=pred.cpu().numpy())
+    if args.map_out is not None:
+        import numpy as np
+        P = 20.0 if args.map_perplexity is None else args.map_perplexity
+        T = 1000 if args.map_iters is None else args.map_iters
+        g.ndata['h'] = features
+        res = model.map_nodes(g, perplexity=P, n_iter=T, seed=args.map_seed or 0)
+        g.ndata['h'] = features
+        k10 = min(10, n_nodes - 1)
+        keep = metrics.neighbourhood_preservation(model.nearest_nodes(g, k10).index, ops.knn(res.embedding, k=k10).index)
+        g.ndata['h'] = features
+        print(f"t-SNE (perplexity {P:g}, {res.n_iter} iterations) KL: {res.kl_divergence:.4f} | "
+              f"10-NN preservation: {keep:.4f}")
+        labels = np.full(n_nodes, -1, np.int64) if data.labels is None else np.asarray(data.labels, np.int64)
+        np.savez(args.map_out, embedding=res.embedding.cpu().numpy(), labels=labels, kl_divergence=res.kl_divergence,
+                 kl_curve=np.asarray(res.kl_curve, np.float64).reshape(-1, 2))
+        main.last_map = {"result": res, "preservation": keep}
     return [float(l) for l in losses]
 
 

@@ -146,6 +146,17 @@ class VGAE(nn.Module):
                 g.ndata['h'] = feat
         return ops.kmeans(mu, k, **kw)
 
+    def map_nodes(self, g, **kw):
+        """GAE.map_nodes on the mean embedding mu (no noise): ``ops.TSNEResult`` of ops.tsne; mu is read in place where
+        the two heads are packed in one buffer; ``g.ndata['h']`` is restored on exit"""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                mu, _ = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return ops.tsne(mu, **kw)
+
     def classify_nodes(self, g, labels, **kw):
         """GAE.classify_nodes on the mean embedding mu (no noise): ``ops.LogRegResult`` of ops.logreg; mu is read in
         place where the two heads are packed in one buffer; ``g.ndata['h']`` is restored on exit"""

@@ -1007,6 +1007,91 @@ int gae_logreg_predict(const float *X, int64_t ldx, int64_t n, int64_t d, int64_
                        const double *intercept, const float *pivot, int32_t *labels, float *proba, int64_t ldp,
                        gae_logreg_status *status, void *stream);
 
+/* ---- K29: exact t-SNE of an embedding into the plane (ops.tsne, ops.tsne_affinities, GAE.map_nodes, GAE.map_graphs)
+ * The 2-D map of a latent space -- the Cora figure of the GAE / VGAE papers -- without an n x n matrix and without
+ * float atomics.  Definitions are sklearn's:
+ *   Y fp32 [n, 2], rows ldy >= 2 floats apart (any ldy; what lies between the rows is never read)
+ *   q_ij = 1 / (1 + |y_i - y_j|^2),  Z = sum_{i != j} q_ij,  P sparse, symmetric, sum P = 1 (a CSR with int32 indptr)
+ *   g_i = 4 (alpha sum_j P_ij q_ij (y_i - y_j) - (1 / Z) sum_{j != i} q_ij^2 (y_i - y_j)),  alpha the exaggeration
+ *   gain_c += 0.2 where sign(g_c) != sign(v_c) (sign in {-1, 0, 1}), else gain_c *= 0.8; then gain_c = max(gain_c, 0.01)
+ *   v = mu v - eta gain g;  y += v.  No recentring.
+ *   KL = sum_{P_ij > 0} P_ij log(P_ij Z / q_ij) = sum P log P + log Z sum P + sum P log(1 + d^2): the status block
+ *   carries the last two pieces, the caller owns the first.
+ * INIT (gae_tsne_init): y[i][c] = (2 u - 1) 1e-4f in fp32, u = (w >> 8) 2^-24, w = word 0 of philox4x32_10(ctr = 2 i + c,
+ *   draw = 0, key = seed ^ GAE_TSNE_KEY_XOR): 2 u - 1 is exact, the product rounds once.
+ * AFFINITIES (gae_tsne_affinities): neighbour lists index int32 [n, k] / dist2 fp32 [n, k] (rows ld apart; gae_knn's
+ *   output) -> p_out fp32 [n, k] (ldp), p_{j|i} = exp(-beta_i (D_ij - D_i,min)) / sum, and perplexity_out fp64 [n], the
+ *   perplexity each row reached, exp(H_i) with H_i = log S + beta T / S, S = sum e, T = sum (D - D_min) e.  An entry is
+ *   a neighbour when index >= 0 and dist2 is finite; other entries get p = 0.  All arithmetic is fp64, one wave per
+ *   row, lane l holds entry l, wave sums by the xor butterfly 32, 16, ..., 1.  beta is found by
+ *   GAE_TSNE_BISECT_ITERS = 100 steps from beta = 1 on the bracket [0, open): H > log(perplexity) -> lo = beta, beta =
+ *   2 beta while the bracket is open, else (beta + hi) / 2; otherwise hi = beta, beta = (lo + beta) / 2; p is evaluated
+ *   at the beta the last step leaves.  A row whose entropy cannot reach the target (ties at the minimum, all-equal
+ *   distances) ends at the limit distribution: uniform over the tied minima / over the row.  A row with fewer than
+ *   2 neighbours gets p = 1 on its neighbour (perplexity_out = the neighbour count).
+ * CHUNKS  gae_tsne_chunk(n) = 256 for n <= 8192, 1024 for n <= 32768, 8192 beyond: a pure host function of n, never of the
+ *   device, the grid or a knob.  Chunk c owns the columns [c chunk, min((c + 1) chunk, n)).
+ * REPULSION (gae_tsne_repulsion; the hot path): for every row i and every chunk c in [chunk_lo, chunk_hi) one partial
+ *   (fx, fy, z) at workspace floats [(3 c + {0, 1, 2}) n + i] -- the partials are the FIRST region of the workspace --,
+ *   each an fp32 chain from 0.f over the chunk's j ascending, j = i left out by predicate:
+ *     dx = y_ix - y_jx; dy = y_iy - y_jy; d2 = fmaf(dy, dy, dx * dx); q = rcp(1.0f + d2);
+ *     z += q; fx = fmaf(q * q, dx, fx); fy = fmaf(q * q, dy, fy)
+ *   rcp is v_rcp_f32 (1 ulp; exact at 1.0f, so a duplicated row adds exactly 1 to z and 0 to the force), not an IEEE
+ *   division.  Columns and rows past n are clamped for loads and never added or stored.  Nothing is written per pair.
+ *   Any cut of [0, chunks) into calls gives the same bits.
+ * UPDATE (gae_tsne_update): two launches.  reduce: a row's chunk partials in the library's one order for partial
+ *   lists (common.h sum_partials: one lane for <= 32 chunks, 64 lanes beyond); the attraction over the row's CSR entries
+ *   e ascending, fp32 chains from 0.f: w = P_e / (1.0f + d2) (IEEE division), ax = fmaf(w, dx, ax), ay likewise (dx, dy, d2
+ *   as above); the row's KL term sum_e P_e log1p(d2) in fp64; the rows' z of a block of 256 rows (4 rows beyond 32
+ *   chunks) in sum_partials' order, one Z partial per block.  update: Z = the block partials in sum_partials' order;
+ *   g_c = 4.0f * fmaf(alpha, a_c, -(r_c * (1.0f / Z))); the gain rule; v = fmaf(mu, v, -((eta * gain) * g)); y += v.
+ *   velocity and gains are dense fp32 [n, 2], the caller's state (zeros and ones before the first iteration).
+ *   alpha, mu, eta are rounded to fp32 once.  tsne.hip is compiled without contraction: the products above are fused
+ *   exactly where fmaf is written.
+ *   status       a 64-byte device block, zeroed by the caller before the first iteration:
+ *                  done        set when sqrt(grad2) <= min_grad_norm; every kernel of a later iteration then returns at
+ *                              once: iterations may be enqueued in groups and the block read once per group
+ *                  iteration   += 1 per update that ran
+ *                  nonfinite   += the rows whose new y is not finite
+ *                  ticket      the library's (an integer ticket; 0 between calls)
+ *                  p_log_d     sum P log(1 + d^2) of the Y on entry: fp64, per block of 256 rows a halving tree, the
+ *                              blocks by thread t adding blocks t, t + 256, ... and the same tree
+ *                  log_z, z    log Z (fp64 log of the fp32 Z) and Z
+ *                  grad2       sum |g|^2, fp64, in the order of p_log_d
+ * DETERMINISM  No float atomics.  The grids are functions of n alone: the same bits run to run, for any ldy, any
+ *   stream, any grouping of the iterations and any cut of the chunks into calls.
+ * WORKSPACE  gae_tsne_workspace_bytes(n, nnz): a pure host function; 12 n ceil(n / chunk) bytes of partials plus O(n).
+ *   A call whose partials would exceed GAE_TSNE_MAX_WORKSPACE = 2^33 bytes is GAE_E_SIZE, not a fallback.
+ * Argument errors are returned before any launch and need no GPU: negative sizes, n or nnz >= 2^31, update with n < 2
+ *   (GAE_E_SIZE); k outside 1..64, perplexity < 1 or >= k, a chunk range outside [0, chunks], exaggeration <= 0, momentum
+ *   outside [0, 1), learning_rate <= 0, NaN min_grad_norm (GAE_E_RANGE); ld / ldp < k, ldy < 2 (GAE_E_SIZE); NULL
+ *   pointers (GAE_E_NULL); a short workspace (GAE_E_WORKSPACE). */
+enum { GAE_TSNE_MAX_K = 64, GAE_TSNE_BISECT_ITERS = 100 };
+#define GAE_TSNE_KEY_XOR 0x2545F4914F6CDD1DULL
+#define GAE_TSNE_MAX_WORKSPACE (1LL << 33)
+
+typedef struct gae_tsne_status {
+    int64_t done, iteration, nonfinite, ticket;
+    double p_log_d, log_z, grad2, z;
+} gae_tsne_status;
+
+int64_t gae_tsne_chunk(int64_t n);
+
+int64_t gae_tsne_workspace_bytes(int64_t n, int64_t nnz);
+
+int gae_tsne_init(float *Y, int64_t ldy, int64_t n, uint64_t seed, void *stream);
+
+int gae_tsne_affinities(const int32_t *index, const float *dist2, int64_t ld, int64_t n, int64_t k, double perplexity,
+                        float *p_out, int64_t ldp, double *perplexity_out, void *stream);
+
+int gae_tsne_repulsion(const float *Y, int64_t ldy, int64_t n, int64_t chunk_lo, int64_t chunk_hi,
+                       const gae_tsne_status *status, void *workspace, int64_t workspace_bytes, void *stream);
+
+int gae_tsne_update(float *Y, int64_t ldy, int64_t n, const int32_t *indptr, const int32_t *indices, const float *P,
+                    int64_t nnz, float *velocity, float *gains, double exaggeration, double momentum,
+                    double learning_rate, double min_grad_norm, gae_tsne_status *status, void *workspace,
+                    int64_t workspace_bytes, void *stream);
+
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
 int gae_x_decoder_bce_finalize(const gae_bce_tail *tail, void *stream);
