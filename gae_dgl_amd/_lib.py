@@ -28,6 +28,8 @@ FOREST_SPLIT_ROWS = 8192          # GAE_FOREST_SPLIT_ROWS
 FOREST_BOOTSTRAP = 1
 FOREST_ERR_ROW_ID, FOREST_ERR_NODE, FOREST_ERR_CODE = 1, 2, 4
 FOREST_KEY_XOR = 0xA0761D6478BD642F
+BOOST_SQUARED, BOOST_LOGISTIC = 0, 1
+BOOST_ERR_TARGET, BOOST_ERR_FOLD = 8, 16
 MLP_LAUNCH_ROW_VISITS = 262144    # GAE_MLP_LAUNCH_ROW_VISITS
 MLP_STATE_HEADER = 16             # GAE_MLP_STATE_HEADER (floats)
 MLP_ADAM, MLP_SGD = 0, 1
@@ -42,6 +44,7 @@ TSNE_STATUS_WORDS = 8             # gae_tsne_status: int64 done, iteration, nonf
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _p, _f, _int = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
+_d = ctypes.c_double
 
 
 class DeviceInfo(ctypes.Structure):
@@ -207,6 +210,10 @@ SIGNATURES = {
     "gae_forest_fit": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64,
                               _int, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _p]),
     "gae_forest_predict": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gae_boost_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "gae_boost_fit": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _int, _d, _i32, _p, _p, _i64, _i64, _i64, _i64, _i64,
+                             _d, _d, _u64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "gae_boost_predict": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _d, _p, _p, _p]),
     "gae_mlp_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64]),
     "gae_mlp_fit": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p,
                            _i64, _i64, _f, _f, _f, _int, _f, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p]),

@@ -31,6 +31,7 @@
 #include <float.h>
 
 #include "common.h"
+#include "forest_cells.h"
 
 namespace {
 
@@ -39,8 +40,7 @@ using gae::up256;
 
 constexpr int kMaxD = 256, kMaxT = 8, kMaxTrees = 1024, kMaxDepth = 16, kMaxBins = 256;
 constexpr int kSplitRows = GAE_FOREST_SPLIT_ROWS;
-constexpr int kThreads = 256, kWaves = kThreads / gae::kWave;
-constexpr int kHistBytes = 64 * 1024;      // LDS cells of one feature tile
+constexpr int kThreads = gae::cells::kThreads, kWaves = gae::cells::kWaves;
 constexpr int kWalkSteps = 64;             // a walk longer than this is a broken node table, not a tree
 
 __host__ __device__ inline int chunks_of(int rows) { return (rows + kSplitRows - 1) / kSplitRows; }
@@ -55,30 +55,6 @@ __device__ __forceinline__ void flag(gae_forest_status *st, int64_t bits)
 __device__ __forceinline__ void count_nonfinite(gae_forest_status *st, int64_t v)
 {
     atomicAdd(reinterpret_cast<u64 *>(&st->nonfinite), static_cast<u64>(v));
-}
-
-// exclusive scan of v over the block's 256 threads (all must call); total = the block's sum.  w: 4 ints of LDS
-__device__ __forceinline__ int block_scan(int v, int *w, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) w[wave] = x;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int q = 0; q < kWaves; ++q) {
-        const int s = w[q];
-        if (q < wave) base += s;
-        total += s;
-    }
-    __syncthreads();
-    return base + x - v;
 }
 
 struct Item { int tree, node, slot, pad; };                // slot >= 0: a node longer than one chunk, its global cells
@@ -204,67 +180,18 @@ __global__ __launch_bounds__(kThreads) void forest_root_kernel(const FitArgs a, 
 }
 
 // ------------------------------------------------------------------------------------------------------ a level
-struct HistLds {
-    unsigned *cnt;                         // [ft][bins]
-    i64 *sum;                              // [ft][bins][t]
-    double *rs;                            // [256] reduction: score, feature, bin
-    int *rf, *rb;
-    unsigned *rkey;                        // [256] Philox words of the feature subset
-    unsigned char *sel;                    // [256]
-};
+using HistLds = gae::cells::Lds;
+using gae::cells::better;
+using gae::cells::block_scan;
 
-__host__ __device__ inline size_t hist_lds_bytes(int ft, int bins, int t)
-{
-    const size_t cells = size_t(ft) * bins;
-    return (cells * 4 + 7) / 8 * 8 + cells * t * 8 + kThreads * (8 + 4 + 4 + 4 + 1);
-}
+inline size_t hist_lds_bytes(int ft, int bins, int t) { return gae::cells::lds_bytes(ft, bins, t); }
 
-__device__ __forceinline__ HistLds carve(unsigned char *lds, const FitArgs &a)
-{
-    HistLds h;
-    const size_t cells = size_t(a.ft) * a.bins;
-    h.cnt = reinterpret_cast<unsigned *>(lds);
-    h.sum = reinterpret_cast<i64 *>(lds + (cells * 4 + 7) / 8 * 8);
-    h.rs = reinterpret_cast<double *>(h.sum + cells * a.t);
-    h.rf = reinterpret_cast<int *>(h.rs + kThreads);
-    h.rb = h.rf + kThreads;
-    h.rkey = reinterpret_cast<unsigned *>(h.rb + kThreads);
-    h.sel = reinterpret_cast<unsigned char *>(h.rkey + kThreads);
-    return h;
-}
+__device__ __forceinline__ HistLds carve(unsigned char *lds, const FitArgs &a) { return gae::cells::carve(lds, a.ft, a.bins, a.t); }
 
 // the candidate features of node `node` of tree `tree`: all of them, or the m with the smallest (r_f, f).  Ends in a barrier
 __device__ __forceinline__ void select_features(const FitArgs &a, const HistLds &h, int tree, int node)
 {
-    const int f = threadIdx.x;             // d <= 256 = the block
-    if (a.m_feat >= a.d) {
-        h.sel[f] = 1;
-        __syncthreads();
-        return;
-    }
-    if (f < a.d) {
-        uint32_t c[4];
-        gae::philox4x32_10((uint64_t(node) << 8) | uint64_t(f), (uint64_t(1) << 32) + uint64_t(tree), a.key, c);
-        h.rkey[f] = c[0];
-    }
-    __syncthreads();
-    if (f < a.d) {
-        const unsigned mine = h.rkey[f];
-        int rank = 0;
-        for (int g = 0; g < a.d; ++g) {
-            const unsigned other = h.rkey[g];
-            rank += (other < mine || (other == mine && g < f)) ? 1 : 0;
-        }
-        h.sel[f] = rank < a.m_feat ? 1 : 0;
-    } else {
-        h.sel[f] = 0;
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ bool better(double s, int f, int b, double s2, int f2, int b2)
-{
-    return s > s2 || (s == s2 && (f < f2 || (f == f2 && b < b2)));
+    gae::cells::select_subset(h.sel, h.rkey, a.d, a.m_feat, node, (uint64_t(1) << 32) + uint64_t(tree), a.key);
 }
 
 // the cells of features [f0, f0 + ftw) are in LDS: prefix sums over the bins, every candidate's score, the tile's best
@@ -687,9 +614,7 @@ int plan(const char *fn, int64_t n_used, int64_t d, int64_t t, int64_t T, int64_
     p.max_items = T * ((p.M + 1) / 2);                     // a level of a binary tree of M nodes holds (M + 1) / 2 at most
     p.max_chunks = p.max_items + T * cdiv(n_boot, kSplitRows);
     p.max_long = T * (n_boot / kSplitRows + 1);
-    const int64_t per_feature = bins * (4 + 8 * t);
-    p.ft = kHistBytes / per_feature;
-    p.ft = p.ft < 1 ? 1 : (p.ft > d ? d : p.ft);
+    p.ft = gae::cells::tile_features(d, bins, t);
     p.nft = cdiv(d, p.ft);
     GAE_REQUIRE(p.max_chunks * p.nft < (int64_t(1) << 31), GAE_E_SIZE,
                 "%s: %lld trees of %lld samples in %lld feature tiles are beyond a grid of 2^31 blocks", fn, (long long)T,

@@ -125,6 +125,22 @@ def build_parser():
     ap.add_argument("--logreg_out", type=str, default=None, metavar="PATH",
                     help="with --logreg: write the model (.npz: 'coef' [c, 3 d], 'intercept' [c], 'pivot', 'lam', 'lambdas', "
                          "'cv_logloss', 'cv_accuracy')")
+    ap.add_argument("--boost", type=int, nargs="?", const=100, default=None, metavar="N_ROUNDS",
+                    help="also fit gradient-boosted histogram trees on the features (3 d <= 256), N_ROUNDS rounds at most "
+                         "(default 100), on the device: with --targets PATH ([G], one property) the squared objective, "
+                         "prints the RMSE | R2 of the held-out predictions; with --labels PATH (classes 0 / 1, -1 = "
+                         "unlabelled) the logistic objective, prints accuracy | ROC-AUC | log-loss; the learning rate, "
+                         "lambda and the number of rounds are chosen by k-fold CV")
+    ap.add_argument("--boost_depth", type=int, default=None, metavar="D", help="with --boost: depth limit, 1..8 (default 4)")
+    ap.add_argument("--boost_lr", type=float, nargs="+", default=None, metavar="LR",
+                    help="with --boost: learning rates in (0, 1] (default 0.1)")
+    ap.add_argument("--boost_lambda", type=float, nargs="+", default=None, metavar="L",
+                    help="with --boost: L2 penalties of the leaf weights (default 1)")
+    ap.add_argument("--boost_folds", type=int, default=None, metavar="F", help="with --boost: CV folds, 2..32 (default 5)")
+    ap.add_argument("--boost_out", type=str, default=None, metavar="PATH",
+                    help="with --boost: write the model (.npz: the node tables 'feature', 'threshold_bin', 'threshold', "
+                         "'left', 'count', 'value', 'gain', 'n_nodes', and 'edges', 'n_edges', 'base_score', 'lr', 'lam', "
+                         "'best_round', 'cv_curve', 'importances'; with both --targets and --labels the logistic model)")
     ap.add_argument("--map_out", type=str, default=None, metavar="PATH",
                     help="the 2-D map of the features by exact t-SNE on the device (ops.tsne) and its 10-NN preservation; "
                          "writes PATH (.npz: 'embedding' fp32 [G, 2], 'labels' int64 [G] (--labels, else -1), "
@@ -224,8 +240,8 @@ def parse_args(argv=None):
         if not os.path.exists(args.targets):
             parser.error(f"--targets {args.targets}: no such file")
     if args.logreg is None:
-        if args.logreg_out or args.logreg_folds is not None or args.labels:
-            parser.error("--logreg_out / --logreg_folds / --labels need --logreg")
+        if args.logreg_out or args.logreg_folds is not None or (args.labels and args.boost is None):
+            parser.error("--logreg_out / --logreg_folds / --labels need --logreg (--labels: or --boost)")
     else:
         if not args.labels:
             parser.error("--logreg needs --labels PATH: the class of every molecule")
@@ -237,6 +253,30 @@ def parse_args(argv=None):
             parser.error(f"--logreg: at most {ops.LOGREG_MAX_LAMBDAS} finite values >= 0")
         if not os.path.exists(args.labels):
             parser.error(f"--labels {args.labels}: no such file")
+    if args.boost is None:
+        if args.boost_out or any(v is not None for v in (args.boost_depth, args.boost_lr, args.boost_lambda, args.boost_folds)):
+            parser.error("--boost_out / --boost_depth / --boost_lr / --boost_lambda / --boost_folds need --boost")
+    else:
+        if not args.targets and not args.labels:
+            parser.error("--boost needs --targets PATH (a property: the squared objective) or --labels PATH (classes 0 / 1: "
+                         "the logistic objective)")
+        if not 1 <= args.boost <= ops.BOOST_MAX_ROUNDS or 3 * args.hidden_dims[-1] > ops.BOOST_MAX_D:
+            parser.error(f"--boost {args.boost}: N_ROUNDS must lie in 1..{ops.BOOST_MAX_ROUNDS} and the feature width 3 d = "
+                         f"{3 * args.hidden_dims[-1]} must not exceed {ops.BOOST_MAX_D}")
+        if args.boost_depth is not None and not 1 <= args.boost_depth <= ops.BOOST_MAX_DEPTH:
+            parser.error(f"--boost_depth {args.boost_depth}: D must lie in 1..{ops.BOOST_MAX_DEPTH}")
+        if args.boost_folds is not None and not 2 <= args.boost_folds <= 32:
+            parser.error(f"--boost_folds {args.boost_folds}: F must lie in 2..32")
+        if not all(0.0 < v <= 1.0 for v in args.boost_lr or []) \
+                or not all(0.0 <= v < float("inf") for v in args.boost_lambda or []):
+            parser.error("--boost_lr takes values in (0, 1], --boost_lambda finite values >= 0")
+        models = ((args.boost_folds or 5) + 1) * len(args.boost_lr or [0]) * len(args.boost_lambda or [0])
+        if models > ops.BOOST_MAX_MODELS:
+            parser.error(f"--boost: (folds + 1) x learning rates x lambdas = {models} models, at most "
+                         f"{ops.BOOST_MAX_MODELS} per call")
+        for path in (args.targets, args.labels):
+            if path and not os.path.exists(path):
+                parser.error(f"{path}: no such file")
     if not args.map_out:
         if any(v is not None for v in (args.map_perplexity, args.map_iters, args.map_seed)):
             parser.error("--map_perplexity / --map_iters / --map_seed need --map_out PATH")
@@ -249,8 +289,9 @@ def parse_args(argv=None):
             parser.error(f"--map_iters {args.map_iters}: T must be at least 1")
     if args.neighbours is None:
         if args.metric is not None or args.neighbours_out or (args.targets and args.ridge is None and args.forest is None
-                                                              and args.mlp is None):
-            parser.error("--metric / --neighbours_out / --targets need --neighbours K (--targets: or --ridge / --forest)")
+                                                              and args.mlp is None and args.boost is None):
+            parser.error("--metric / --neighbours_out / --targets need --neighbours K (--targets: or --ridge / --forest / "
+                         "--boost)")
     else:
         if not 1 <= args.neighbours <= ops.KNN_MAX_K or 3 * args.hidden_dims[-1] > ops.KNN_MAX_D:
             parser.error(f"--neighbours {args.neighbours}: K must lie in 1..{ops.KNN_MAX_K} and the feature width 3 d = "
@@ -443,6 +484,50 @@ def main(argv=None):
                      cv_logloss=res.cv_logloss.cpu().numpy(), cv_accuracy=res.cv_accuracy.cpu().numpy())
         main.logreg = res
         main.logreg_scores = cm
+    main.boost = None
+    if args.boost is not None:
+        from gae_dgl_amd import metrics
+        depth, n_folds = args.boost_depth or 4, args.boost_folds or 5
+        lrs, lams = tuple(args.boost_lr or (0.1,)), tuple(args.boost_lambda or (1.0,))
+        runs = []
+        if args.targets:
+            y = np.load(args.targets)
+            if y.shape[0] != out.shape[0] or (y.ndim > 1 and int(np.prod(y.shape[1:])) != 1):
+                raise ValueError(f"--targets of shape {y.shape} for --boost on {out.shape[0]} molecules: one property per "
+                                 f"molecule")
+            runs.append(("squared", torch.from_numpy(y.reshape(-1).astype(np.float32)).to(device)))
+        if args.labels:
+            y = np.load(args.labels)
+            if y.ndim != 1 or y.shape[0] != out.shape[0] or not np.issubdtype(y.dtype, np.integer):
+                raise ValueError(f"--labels of shape {y.shape}, {y.dtype} for {out.shape[0]} molecules: integer classes [G]")
+            runs.append(("logistic", torch.from_numpy(y.astype(np.int64)).to(device)))
+        main.boost_scores = {}
+        for objective, y in runs:
+            torch.cuda.synchronize(device)
+            t0 = time.perf_counter()
+            res = ops.boost(feats, y, objective, args.boost, max_depth=depth, learning_rates=lrs, lambdas=lams, folds=n_folds,
+                            seed=args.seed or 0, oof=True)
+            torch.cuda.synchronize(device)
+            print(f"Boosted {objective} trees on {res.n_used} molecules, {(n_folds + 1) * len(lrs) * len(lams)} models side by "
+                  f"side | {(time.perf_counter() - t0) * 1e3:.3f} ms (two calls, set-up included)")
+            head = f"Boosting ({res.best_round} of {args.boost} rounds, depth {depth}, {n_folds}-fold CV, lr = {res.lr:g}, " \
+                   f"lambda = {res.lam:g})"
+            if objective == "squared":
+                sc = metrics.regression_metrics(res.oof_score, y.double())
+                print(f"{head} RMSE: {sc['rmse']:.6f} | R2: {sc['r2']:.6f}")
+            else:
+                keep = y >= 0
+                p1 = torch.sigmoid(res.oof_score)
+                proba = torch.stack([1.0 - p1, p1], 1)
+                sc = metrics.classification_metrics((res.oof_score >= 0).to(torch.int32), y[keep], proba, n_classes=2)
+                print(f"{head} accuracy: {sc['accuracy']:.4f} | ROC-AUC: {sc['roc_auc']:.4f} | log-loss: {sc['log_loss']:.4f}")
+            main.boost_scores[objective] = sc
+            main.boost = res
+        if args.boost_out:
+            np.savez(args.boost_out, base_score=np.float64(res.base_score), lr=np.float64(res.lr), lam=np.float64(res.lam),
+                     best_round=np.int64(res.best_round), **{k: getattr(res, k).cpu().numpy() for k in (
+                         "feature", "threshold_bin", "threshold", "left", "count", "value", "gain", "n_nodes", "edges",
+                         "n_edges", "cv_curve", "importances")})
     main.map = None
     if args.map_out:
         from gae_dgl_amd import metrics

@@ -423,6 +423,19 @@ class GAE(nn.Module):
         with torch.no_grad():
             return ops.forest(self.embed_graphs(data, **embed_kw), y, **kw)
 
+    def boost_graphs(self, data, y, objective="squared", n_rounds=100, **kw):
+        """``ops.BoostResult``: gradient-boosted histogram trees on the molecule features of ``embed_graphs`` for the
+        per-molecule targets ``y`` (fp32 [G] with ``objective="squared"``; an int tensor [G] in {0, 1}, -1 = unlabelled,
+        with ``"logistic"``), the learning rate, lambda and the number of rounds chosen by k-fold CV on the device
+        (``ops.boost``; its keyword arguments pass through: max_depth, learning_rates, lambdas, min_child_weight,
+        min_samples_leaf, min_gain, max_features, max_bins, folds, fold, rows, seed, check_every, oof).  ``fused`` and
+        ``batch_size`` go to the embedding.  Rows are in the order ``embed_graphs(data)`` returns them.  Runs under no_grad."""
+        if "grad" in kw:
+            raise ValueError("boost_graphs runs under no_grad: boosted trees carry no gradient")
+        embed_kw = {k: kw.pop(k) for k in ("fused", "batch_size") if k in kw}
+        with torch.no_grad():
+            return ops.boost(self.embed_graphs(data, **embed_kw), y, objective, n_rounds, **kw)
+
     def mlp_graphs(self, data, y, **kw):
         """``ops.MLPResult``: an MLP regression of the per-molecule targets ``y`` ([G] or [G, t]) on the molecule features
         of ``embed_graphs`` -- the reference's "GAE + MLP" head, every fold model of every (lr, alpha) pair trained side

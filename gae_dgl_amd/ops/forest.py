@@ -2,8 +2,8 @@
 Random Forest" row of the reference's chemistry table on the device.  Histogram trees grown level by level, all trees of
 a call at once; every accumulated quantity is an integer (bin codes, fixed-point int64 targets, integer histogram cells),
 so the integer atomics the kernels use are exact: no float atomics, the same bits run to run, for any row stride and
-stream.  ``GAE.forest_graphs``; ``python -m gae_dgl_amd.embed --forest``.  Regression only: classification and gradient
-boosting are out of scope.
+stream.  ``GAE.forest_graphs``; ``python -m gae_dgl_amd.embed --forest``.  Regression only; gradient boosting on the same
+cells, with binary classification, is ``ops.boost`` (K30).
 
 Part of the package gae_dgl_amd.ops; names are resolved through the package namespace (`_ops.<name>`) at call time."""
 import collections
@@ -165,7 +165,7 @@ def forest(X, y, n_trees=100, *, max_depth=12, max_features=1.0, min_samples_lea
     histogram cell is an integer and every tree is reproduced node for node by tests/forest_ref.py.  Each tree trains on a
     Philox bootstrap of ``max_samples`` rows (None: as many as listed; an int, or a float share of the listed rows) or,
     with ``bootstrap=False``, on every listed row; a split looks at ``max_features`` features (an int in 1..d or a float
-    share, at least one) drawn per node.  Regression only -- no classification, no gradient boosting.  1 <= d <= 256,
+    share, at least one) drawn per node.  Regression only (boosting and binary classification: ``ops.boost``).  1 <= d <= 256,
     n_trees <= 1024, max_depth <= 16, max_bins <= 256; a non-finite value in a listed row raises GaeHipError; there is no
     CPU fallback."""
     _options(n_trees, max_depth, max_features, min_samples_leaf, max_bins, bootstrap, max_samples, seed)

@@ -728,7 +728,7 @@ int gae_ridge_solve(const double *stats, int64_t d, int64_t t, int64_t folds, co
  * features become bin codes, targets fixed-point int64, histogram cells integer counts and integer sums.  Integer atomics
  * in LDS and in global memory are exact and free of order: no float atomics, the same bits run to run, for any row
  * stride, stream or launch split, and a numpy restatement (tests/forest_ref.py) reproduces every tree node for node.
- * Regression only; classification and gradient boosting are not built.
+ * Regression only; gradient boosting (with binary classification) is K30.
  *   1 <= d <= 256, 1 <= t <= 8, 1 <= n_trees <= 1024, 1 <= max_depth <= 16, 2 <= max_bins <= 256 (else GAE_E_RANGE);
  *   1 <= n_used, n_boot < 2^31, 0 <= n, m < 2^31 (else GAE_E_SIZE).  There is no fallback for other shapes.
  * BINNING (gae_forest_bin): per feature f an ascending fp32 edge list edges[f][0 .. n_edges[f]), n_edges[f] <= max_bins - 1
@@ -813,6 +813,76 @@ int gae_forest_fit(const uint8_t *codes, const int32_t *n_edges, const float *ed
 int gae_forest_predict(const float *X, int64_t ldx, int64_t m, int64_t d, int64_t t, int64_t n_trees, int64_t node_capacity,
                        const int32_t *feature, const float *threshold, const int32_t *left, const double *value,
                        const uint8_t *skip, double *out, gae_forest_status *status, void *stream);
+
+/* ---- K30: second-order histogram gradient boosting on a frozen feature (ops.boost, GAE.boost_graphs, embed --boost)
+ * XGBoost's objective on integer histograms, for regression ("squared") and binary classification ("logistic").  EVERY
+ * ACCUMULATED QUANTITY IS AN INTEGER and every floating-point step is a stated fp64 operation without contraction
+ * (csrc/boost.hip is built with -ffp-contract=off), so tests/boost_ref.py restates a whole fit bit for bit, and the
+ * results do not depend on the run, the stream, check_every or on which other configurations share the call.
+ *   1 <= d <= 256, 2 <= max_bins <= 256, 1 <= max_depth <= 8, 1 <= n_rounds <= 4096, folds = 0 or 2..255,
+ *   (folds + 1) n_cfg <= 256 models, 0 < learning_rates[c] <= 1, lambdas[c] >= 0, min_child_weight > 0 or every lambda > 0
+ *   (else GAE_E_RANGE); 1 <= n_used < 2^31 (else GAE_E_SIZE).  One target, binary labels.  There is no fallback.
+ * INPUTS, all by LISTED row: codes uint8 [n_used][d] with edges / n_edges as gae_forest_bin made them (K26 BINNING); y fp32
+ *   [n_used] (logistic: exactly 0 or 1, else GAE_BOOST_ERR_TARGET; squared: finite, else the same flag); fold int32 [n_used]
+ *   in 0 .. folds - 1 (else GAE_BOOST_ERR_FOLD; NULL with folds = 0).  learning_rates, lambdas: HOST fp64 [n_cfg], one pair
+ *   per configuration.
+ * MODELS: m = cfg (folds + 1) + k; k < folds trains on the rows with fold != k and is scored on the rows with fold == k,
+ *   k == folds trains on every row.  All models start from F = base_score and run side by side in the same launches.
+ * FRAME: g and h become int64 fixed point, q = llrint(v 2^e) (ties to even).  logistic: e = 30 for both.  squared: h is the
+ *   integer 1 and g uses the caller's exponent; ops.boost takes base_score = the fp32-rounded fp64 mean of y and e = 29 - E
+ *   with frexp(max |y - base_score|) = (m, E) (e = 0 when that max is 0), so |g 2^e| stays below 2^31 while |F - y| is at
+ *   most twice that max, and a sum over 2^31 rows fits an int64.  A value with |v 2^e| > 2^31 (or a non-finite F) sets
+ *   bad[m] = 1 and contributes 0: nothing wraps.  G = double(sum q_g) 2^-e and H = double(sum q_h) 2^-e_h below.
+ * SIGMA, no libm: a = min(|F|, 40) (a NaN takes 40); k = rint(-a 1.44269504088896338700e+00); r = (-a - k
+ *   6.93147180369123816490e-01) - k 1.90821492927058770002e-10; P = the Horner form p = 1/13!, p = p r + 1/j! for j = 12 .. 0
+ *   (coefficients the correctly rounded quotients); e = P 2^k (exact scaling); q = e / (1 + e); sigma = F >= 0 ? 1 - q : q.
+ *   p = sigma(F), g = p - y, h = p (1 - p).  squared: g = F - double(y).
+ * ROUND r = 0 .. n_rounds - 1.  Prologue, per (model, listed row): F += value[leaf of the model's tree of round r - 1 on
+ *   the row's codes] (r > 0; code_f <= threshold_bin goes left), then g, h, q as above; the model's training rows and their
+ *   integer sums make the root.  Held-out rows add their loss -- squared (F - y)^2; logistic log1p(e) + (|F| when the sign of
+ *   F disagrees with y), e as in SIGMA (libm's log1p: it feeds the selection, never a tree) -- per chunk of 256 listed rows:
+ *   within a wave the shuffle-down tree 32, 16, .., 1, then ((w0 + w1) + w2) + w3; the chunks are folded in the order of
+ *   csrc/common.h's sum_partials (<= 32 chunks: ascending; more: 64 strided lanes ascending, then the same tree) into
+ *   loss[m][r].  correct[m][r] counts held-out rows with (F >= 0) == (y == 1) (logistic; 0 for squared).  So loss[m][r] is the
+ *   model's held-out loss SUM with r trees; a last prologue after the last round fills index n_rounds and leaves the final F
+ *   in score.  There are no float atomics.
+ * GROWTH as K26's, level by level: the root is node 0; a node at depth < max_depth with count >= 2 min_samples_leaf is
+ *   offered a split.  Candidate (f, b), 0 <= b < n_edges[f], needs n_L, n_R >= min_samples_leaf, H_L, H_R >= min_child_weight
+ *   and H_L + lambda, H_R + lambda > 0; score = (G_L G_L) / (H_L + lambda) + (G_R G_R) / (H_R + lambda), the right side from
+ *   the integer differences to the node's sums.  The largest score wins, ties to the lower f, then the lower b.  The node
+ *   splits iff best > parent + min_gain with parent = (G G) / (H + lambda) (0 when H + lambda is not > 0); gain = best -
+ *   parent.  value = -(lr (G / (H + lambda))) for EVERY node (0 when H + lambda is not > 0): the leaf weight with the
+ *   learning rate applied.  max_features = m < d: K26's subset rule with draw = 2^32 + ((r << 8) | k) -- the model's fold
+ *   slot k, not its configuration, so a configuration gives the same trees alone or inside a grid.  NODE NUMBERING as K26.
+ * OUTPUTS: the all-rows models' node tables [n_cfg][n_rounds][node_capacity], node_capacity = 2^(max_depth + 1) - 1, with
+ *   K26's fields and defaults (value fp64 [..] one per node); n_nodes int32 [n_cfg][n_rounds]; loss fp64 and correct int64
+ *   [models][n_rounds + 1]; score fp64 [models][n_used]; bad int32 [models].  The fold models' trees live in per-round scratch.
+ * HOT PATH: the level kernels of K26 with (count, G, H) cells; each model owns fixed regions of the work lists and a 16-byte
+ *   level record that stays on the device; every grid is sized by its bound -- level l has at most 2^l nodes and 2^l +
+ *   ceil(n_used / GAE_FOREST_SPLIT_ROWS) chunks per model -- and surplus blocks return at once.  3 + 4 max_depth launches per
+ *   round at most.  The host reads the status block once per check_every rounds (and stops early only when it already holds an
+ *   error or every model is bad) -- no result depends on check_every.
+ * PREDICTION (gae_boost_predict): tables of ONE configuration [n_rounds][node_capacity]; out fp64 [m] = base_score + the
+ *   reached leaves' values added in ascending round order; a row goes left iff x_f <= threshold.  A row holding a non-finite
+ *   feature is counted in status.nonfinite and gets NaN; a walk that leaves the table: GAE_FOREST_ERR_NODE, NaN.
+ * STATUS: gae_forest_status, zeroed by the caller; errors holds GAE_FOREST_ERR_* and GAE_BOOST_ERR_* bits, reserved[0] the
+ *   number of models marked bad.  Argument errors are returned before anything is dereferenced or launched. */
+enum { GAE_BOOST_SQUARED = 0, GAE_BOOST_LOGISTIC = 1 };
+enum { GAE_BOOST_ERR_TARGET = 8, GAE_BOOST_ERR_FOLD = 16 };
+
+int64_t gae_boost_workspace_bytes(int64_t n_used, int64_t d, int64_t max_bins, int64_t max_depth, int64_t folds, int64_t n_cfg);
+
+int gae_boost_fit(const uint8_t *codes, const int32_t *n_edges, const float *edges, int64_t n_used, int64_t d, int64_t max_bins,
+                  const float *y, const int32_t *fold, int64_t folds, int objective, double base_score, int32_t exponent,
+                  const double *learning_rates, const double *lambdas, int64_t n_cfg, int64_t n_rounds, int64_t max_depth,
+                  int64_t max_features, int64_t min_samples_leaf, double min_child_weight, double min_gain, uint64_t seed,
+                  int64_t check_every, int32_t *feature, int32_t *threshold_bin, float *threshold, int32_t *left, int32_t *count,
+                  double *value, double *gain, int32_t *n_nodes, double *loss, int64_t *correct, double *score, int32_t *bad,
+                  gae_forest_status *status, void *workspace, int64_t workspace_bytes, void *stream);
+
+int gae_boost_predict(const float *X, int64_t ldx, int64_t m, int64_t d, int64_t n_rounds, int64_t node_capacity,
+                      const int32_t *feature, const float *threshold, const int32_t *left, const double *value,
+                      double base_score, double *out, gae_forest_status *status, void *stream);
 
 /* ---- K27: a small MLP regression head trained on a frozen feature (ops.mlp, GAE.mlp_graphs, embed --mlp)
  * The best row of the reference's chemistry table ("GAE + MLP").  d -> h1 [-> h2] -> t (h2 = 0: one hidden layer), ReLU
