@@ -40,6 +40,11 @@ LOGREG_EVAL = 1
 LOGREG_ERR_FOLD_PTR, LOGREG_ERR_ROW_ID, LOGREG_ERR_LAMBDA, LOGREG_ERR_LABEL, LOGREG_ERR_NONFINITE = 1, 2, 4, 8, 16
 TSNE_MAX_K, TSNE_BISECT_ITERS = 64, 100            # GAE_TSNE_MAX_K, GAE_TSNE_BISECT_ITERS
 TSNE_KEY_XOR = 0x2545F4914F6CDD1D
+PCA_MAX_D, PCA_MAX_SWEEPS = 128, 30   # GAE_PCA_MAX_D, GAE_PCA_MAX_SWEEPS
+PCA_WHITEN = 1
+PCA_ERR_ROW_ID = 1
+PCA_STATUS_WORDS = 8              # gae_pca_status: int64 info, n_sweeps, n_rotations, nonfinite_rows, nonpositive_components,
+                                  # errors; double off_norm, total_variance
 TSNE_STATUS_WORDS = 8             # gae_tsne_status: int64 done, iteration, nonfinite, ticket; double p_log_d, log_z, grad2, z
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
@@ -232,6 +237,9 @@ SIGNATURES = {
     "gae_tsne_repulsion": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p]),
     "gae_tsne_update": (_int, [_p, _i64, _i64, _p, _p, _p, _i64, _p, _p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                ctypes.c_double, _p, _p, _i64, _p]),
+    "gae_pca_workspace_bytes": (_i64, [_i64]),
+    "gae_pca_solve": (_int, [_p, _i64, _i64, _p, _i64, _i64, _int, _p, _p, _p, _p, _p, _i64, _p]),
+    "gae_pca_transform": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _int, _p, _i64, _p, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

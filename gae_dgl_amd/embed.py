@@ -42,7 +42,12 @@ of the pooled held-out predictions at the chosen lambda; ``--logreg_out PATH`` w
 ``--map_out map.npz`` maps the features just computed into the plane (``ops.tsne``: exact t-SNE on the device,
 ``--map_perplexity P`` (20), ``--map_iters T`` (1000), ``--map_seed S`` (0)), prints the KL divergence and the 10-NN
 preservation of the map and writes 'embedding' [G, 2], 'labels' (those of ``--labels``, else -1), 'kl_divergence' and
-'kl_curve'.  Combines with every flag above."""
+'kl_curve'.  ``--map_init pca`` starts the map from the first two principal scores (sklearn's rule) instead of the Philox
+draw.  Combines with every flag above.
+``--pca K`` takes the K leading principal components of the features just computed (``ops.pca``: exact-order fp64 moments
+in one pass, an fp64 Jacobi eigensolver in one block, the same bits run to run; ``--pca_whiten`` scales every score to unit
+variance), prints the explained variance and, with ``--pca_out pca.npz``, writes 'components' [K, 3 d], 'mean', 'explained_variance',
+'explained_variance_ratio' and 'scores' [G, K].  Combines with every flag above."""
 import argparse
 import os
 import time
@@ -149,6 +154,14 @@ def build_parser():
                     help="with --map_out: the perplexity, at least 1 and below min(G - 1, 64) (default 20)")
     ap.add_argument("--map_iters", type=int, default=None, metavar="T", help="with --map_out: iterations (default 1000)")
     ap.add_argument("--map_seed", type=int, default=None, metavar="S", help="with --map_out: the seed of the start (default 0)")
+    ap.add_argument("--map_init", choices=["random", "pca"], default=None,
+                    help="with --map_out: the start of the map, the library's Philox draw (default) or the first two principal "
+                         "scores scaled to a standard deviation of 1e-4 (ops.pca)")
+    ap.add_argument("--pca", type=int, default=None, metavar="K",
+                    help="the K leading principal components of the features on the device (ops.pca) and their explained variance")
+    ap.add_argument("--pca_whiten", action="store_true", help="with --pca: scores of unit variance")
+    ap.add_argument("--pca_out", type=str, default=None, metavar="PATH",
+                    help="with --pca: write components, mean, explained_variance, explained_variance_ratio and scores as .npz")
     ap.add_argument("--norm", choices=["none", "both"], default="none",
                     help="none = the reference's plain in-edge sums; both = D^-1/2 A D^-1/2")
     ap.add_argument("--fused", choices=["auto", "on", "off"], default="auto",
@@ -278,15 +291,23 @@ def parse_args(argv=None):
             if path and not os.path.exists(path):
                 parser.error(f"{path}: no such file")
     if not args.map_out:
-        if any(v is not None for v in (args.map_perplexity, args.map_iters, args.map_seed)):
-            parser.error("--map_perplexity / --map_iters / --map_seed need --map_out PATH")
+        if any(v is not None for v in (args.map_perplexity, args.map_iters, args.map_seed, args.map_init)):
+            parser.error("--map_perplexity / --map_iters / --map_seed / --map_init need --map_out PATH")
     else:
+        if args.map_init == "pca" and 3 * args.hidden_dims[-1] > ops.PCA_MAX_D:
+            parser.error(f"--map_init pca: the feature width 3 d = {3 * args.hidden_dims[-1]} must not exceed {ops.PCA_MAX_D}")
         if 3 * args.hidden_dims[-1] > ops.KNN_MAX_D:
             parser.error(f"--map_out: the feature width 3 d = {3 * args.hidden_dims[-1]} must not exceed {ops.KNN_MAX_D}")
         if args.map_perplexity is not None and not 1.0 <= args.map_perplexity < 64.0:
             parser.error(f"--map_perplexity {args.map_perplexity}: P must lie in [1, 64)")
         if args.map_iters is not None and args.map_iters < 1:
             parser.error(f"--map_iters {args.map_iters}: T must be at least 1")
+    if args.pca is None:
+        if args.pca_whiten or args.pca_out:
+            parser.error("--pca_whiten / --pca_out need --pca K")
+    elif not 1 <= args.pca <= 3 * args.hidden_dims[-1] or 3 * args.hidden_dims[-1] > ops.PCA_MAX_D:
+        parser.error(f"--pca {args.pca}: K must lie in 1..3 d = {3 * args.hidden_dims[-1]}, and 3 d must not exceed "
+                     f"{ops.PCA_MAX_D}")
     if args.neighbours is None:
         if args.metric is not None or args.neighbours_out or (args.targets and args.ridge is None and args.forest is None
                                                               and args.mlp is None and args.boost is None):
@@ -528,12 +549,23 @@ def main(argv=None):
                      best_round=np.int64(res.best_round), **{k: getattr(res, k).cpu().numpy() for k in (
                          "feature", "threshold_bin", "threshold", "left", "count", "value", "gain", "n_nodes", "edges",
                          "n_edges", "cv_curve", "importances")})
+    main.pca = None
+    if args.pca is not None:
+        res = ops.pca(feats, args.pca, whiten=args.pca_whiten)
+        ratio = res.explained_variance_ratio.cpu().numpy()
+        print(f"PCA ({args.pca} of {out.shape[1]} components) explained variance: "
+              f"{' '.join(f'{v:.4f}' for v in ratio)} (cumulative {float(ratio.sum()):.4f})")
+        if args.pca_out:
+            np.savez(args.pca_out, components=res.components.cpu().numpy(), mean=res.mean.cpu().numpy(),
+                     explained_variance=res.explained_variance.cpu().numpy(), explained_variance_ratio=ratio,
+                     scores=res.transform(feats).cpu().numpy())
+        main.pca = res
     main.map = None
     if args.map_out:
         from gae_dgl_amd import metrics
         P = 20.0 if args.map_perplexity is None else args.map_perplexity
         res = ops.tsne(feats, perplexity=P, n_iter=1000 if args.map_iters is None else args.map_iters,
-                       seed=args.map_seed or 0)
+                       seed=args.map_seed or 0, init="pca" if args.map_init == "pca" else None)
         k10 = min(10, out.shape[0] - 1)
         keep = metrics.neighbourhood_preservation(ops.knn(feats, k=k10).index, ops.knn(res.embedding, k=k10).index)
         print(f"t-SNE (perplexity {P:g}, {res.n_iter} iterations) KL: {res.kl_divergence:.4f} | "

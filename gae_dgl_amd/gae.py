@@ -358,6 +358,29 @@ class GAE(nn.Module):
         with torch.no_grad():
             return ops.tsne(self.embed_graphs(data, **embed_kw), **kw)
 
+    def pca_nodes(self, g, k=None, **kw):
+        """``ops.PCAResult``: the ``k`` leading principal components of the embedding encode(g) (default: all) -- the
+        explained-variance spectrum, a linear projection (``result.transform(z)``), whitening -- on the device
+        (ops.pca; its keyword arguments pass through: rows, whiten, pivot).  Runs encode(g) under no_grad;
+        ``g.ndata['h']`` is restored on exit."""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                z = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return ops.pca(z, k, **kw)
+
+    def pca_graphs(self, data, k=None, **kw):
+        """``ops.PCAResult``: the ``k`` leading principal components of the molecule features of ``embed_graphs`` on the
+        device (``ops.pca``; its keyword arguments pass through).  ``fused`` and ``batch_size`` go to the embedding.  Rows
+        are in the order ``embed_graphs(data)`` returns them.  Runs under no_grad."""
+        if "grad" in kw:
+            raise ValueError("pca_graphs runs under no_grad: the decomposition carries no gradient into the encoder")
+        embed_kw = {key: kw.pop(key) for key in ("fused", "batch_size") if key in kw}
+        with torch.no_grad():
+            return ops.pca(self.embed_graphs(data, **embed_kw), k, **kw)
+
     def classify_nodes(self, g, labels, **kw):
         """``ops.LogRegResult``: the standard protocol for an unsupervised node embedding -- freeze encode(g), fit a
         multinomial logistic regression on the labelled nodes (``labels``: an int tensor [n], -1 = unlabelled), choose

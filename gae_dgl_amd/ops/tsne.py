@@ -143,6 +143,23 @@ def _check_y(Y, n, dev, who):
     return Y
 
 
+def _pca_start(X, n, d, dev):
+    """fp32 [n, 2]: sklearn's ``init="pca"`` -- the first two scores of ``ops.pca`` (K31) times the fp32 rounding of
+    1e-4 / sigma, sigma = sqrt(lambda_1 (n - 1) / n) the standard deviation of the first score (from its variance, in
+    fp64: no further pass); one fp32 product per entry.  d = 1: the second coordinate is zero.  n < 2: zeros"""
+    Y = torch.zeros(n, 2, dtype=torch.float32, device=dev)
+    if n < 2:
+        return Y
+    res = _ops.pca(X, min(2, d))
+    lam = float(res.explained_variance[0])
+    if not lam > 0.0:
+        raise GaeHipError(f"tsne: init='pca' on a feature without variance (lambda_1 = {lam})")
+    scale = torch.tensor(1e-4 / math.sqrt(lam * (n - 1) / n), dtype=torch.float64, device=dev).float()
+    Z = res.transform(X)
+    Y[:, :Z.shape[1]] = Z * scale
+    return Y
+
+
 def tsne(X, *, perplexity=20.0, n_iter=1000, learning_rate="auto", early_exaggeration=12.0, exaggeration_iters=250, seed=0,
          init=None, neighbours=None, metric="l2", min_grad_norm=1e-7, check_every=50):
     """``TSNEResult`` of exact t-SNE on the rows of ``X`` [n, d] (fp32, on the GPU; read in place when its inner stride is
@@ -157,7 +174,8 @@ def tsne(X, *, perplexity=20.0, n_iter=1000, learning_rate="auto", early_exagger
     64 nearest.  ``perplexity`` must be at least 1 and below k.
 
     ``init=None`` starts from (2 u - 1) 1e-4 with u from the library's Philox stream keyed by (``seed``, element);
-    ``init=`` takes a [n, 2] tensor (copied).  The iterations are enqueued in groups of ``check_every`` and the
+    ``init=`` takes a [n, 2] tensor (copied); ``init="pca"`` starts from the first two principal scores (``ops.pca``, d <=
+    128) divided by the standard deviation of the first and multiplied by 1e-4, sklearn's rule.  The iterations are enqueued in groups of ``check_every`` and the
     device's status block is read once per group (``kl_curve`` holds one point per read); the run stops early, on the
     device, once |g| <= ``min_grad_norm``.  The embedding has the same bits run to run, for any row stride of ``X``, any
     stream and any ``check_every``.  Two output dimensions only; 1 <= d <= 256.  ``n = 0`` gives an empty result,
@@ -187,6 +205,10 @@ def tsne(X, *, perplexity=20.0, n_iter=1000, learning_rate="auto", early_exagger
         with _on_device(dev):
             if init is None:
                 Y = tsne_init(n, seed, dev)
+            elif isinstance(init, str):
+                if init != "pca":
+                    raise ValueError(f"init: None, 'pca' or a [n, 2] tensor, not {init!r}")
+                Y = _pca_start(X, n, d, dev)
             else:
                 Y = _check_y(init, n, dev, "tsne").clone().contiguous()
             empty = torch.empty(0, dtype=torch.float64, device=dev)

@@ -8,7 +8,8 @@ epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
       [--loss_samples M] [--decode_out graph.npz [--decode_prob P] [--decode_max_pairs M]]
       [--cluster K [--cluster_seed S] [--cluster_out clusters.npz]] [--knn K [--knn_metric l2|dot|cosine]]
       [--classify [LAMBDA ...] [--classify_folds F] [--classify_test_frac Q] [--classify_seed S] [--classify_out model.npz]]
-      [--map_out map.npz [--map_perplexity P] [--map_iters T] [--map_seed S]]
+      [--map_out map.npz [--map_perplexity P] [--map_iters T] [--map_seed S] [--map_init random|pca]]
+      [--pca K [--pca_out pca.npz]]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -106,6 +107,15 @@ def build_parser():
                     help="with --map_out: the perplexity, at least 1 and below min(N - 1, 64) (default 20)")
     ap.add_argument("--map_iters", type=int, default=None, metavar="T", help="with --map_out: iterations (default 1000)")
     ap.add_argument("--map_seed", type=int, default=None, metavar="S", help="with --map_out: the seed of the start (default 0)")
+    ap.add_argument("--map_init", choices=["random", "pca"], default=None,
+                    help="with --map_out: the start of the map, the library's Philox draw (default) or the first two principal "
+                         "scores scaled to a standard deviation of 1e-4 (ops.pca)")
+    ap.add_argument("--pca", type=int, default=None, metavar="K",
+                    help="after training: the K leading principal components of the node embedding on the device "
+                         "(GAE.pca_nodes) and their explained variance")
+    ap.add_argument("--pca_out", default=None, metavar="PATH",
+                    help="with --pca: write PATH (.npz with 'components' fp64 [K, d], 'mean', 'explained_variance', "
+                         "'explained_variance_ratio' and 'scores' fp32 [N, K])")
     return ap
 
 
@@ -155,13 +165,18 @@ def parse_args(argv=None):
         if args.classify_test_frac is not None and not 0.0 < args.classify_test_frac < 1.0:
             ap.error(f"--classify_test_frac {args.classify_test_frac}: Q must lie inside (0, 1)")
     if args.map_out is None:
-        if any(v is not None for v in (args.map_perplexity, args.map_iters, args.map_seed)):
-            ap.error("--map_perplexity / --map_iters / --map_seed need --map_out PATH")
+        if any(v is not None for v in (args.map_perplexity, args.map_iters, args.map_seed, args.map_init)):
+            ap.error("--map_perplexity / --map_iters / --map_seed / --map_init need --map_out PATH")
     else:
         if args.map_perplexity is not None and not 1.0 <= args.map_perplexity < 64.0:
             ap.error(f"--map_perplexity {args.map_perplexity}: P must lie in [1, 64)")
         if args.map_iters is not None and args.map_iters < 1:
             ap.error(f"--map_iters {args.map_iters}: T must be at least 1")
+    if args.pca is None:
+        if args.pca_out is not None:
+            ap.error("--pca_out needs --pca K")
+    elif not 1 <= args.pca <= args.hidden_dims[-1] or args.hidden_dims[-1] > 128:
+        ap.error(f"--pca {args.pca}: K must lie in 1..{args.hidden_dims[-1]} (the embedding width, 128 at the most)")
     return args
 
 
@@ -332,7 +347,8 @@ def main(argv=None):
         P = 20.0 if args.map_perplexity is None else args.map_perplexity
         T = 1000 if args.map_iters is None else args.map_iters
         g.ndata['h'] = features
-        res = model.map_nodes(g, perplexity=P, n_iter=T, seed=args.map_seed or 0)
+        res = model.map_nodes(g, perplexity=P, n_iter=T, seed=args.map_seed or 0,
+                              init="pca" if args.map_init == "pca" else None)
         g.ndata['h'] = features
         k10 = min(10, n_nodes - 1)
         keep = metrics.neighbourhood_preservation(model.nearest_nodes(g, k10).index, ops.knn(res.embedding, k=k10).index)
@@ -343,6 +359,23 @@ def main(argv=None):
         np.savez(args.map_out, embedding=res.embedding.cpu().numpy(), labels=labels, kl_divergence=res.kl_divergence,
                  kl_curve=np.asarray(res.kl_curve, np.float64).reshape(-1, 2))
         main.last_map = {"result": res, "preservation": keep}
+    if args.pca is not None:
+        import numpy as np
+        g.ndata['h'] = features
+        res = model.pca_nodes(g, args.pca)
+        g.ndata['h'] = features
+        ratio = res.explained_variance_ratio.cpu().numpy()
+        print(f"PCA ({args.pca} of {res.components.shape[1]} components) explained variance: "
+              f"{' '.join(f'{v:.4f}' for v in ratio)} (cumulative {float(ratio.sum()):.4f})")
+        if args.pca_out is not None:
+            with torch.no_grad():
+                z = model.encode(g)
+            g.ndata['h'] = features
+            z = z[0] if isinstance(z, tuple) else z
+            np.savez(args.pca_out, components=res.components.cpu().numpy(), mean=res.mean.cpu().numpy(),
+                     explained_variance=res.explained_variance.cpu().numpy(), explained_variance_ratio=ratio,
+                     scores=res.transform(z).cpu().numpy())
+        main.last_pca = res
     return [float(l) for l in losses]
 
 

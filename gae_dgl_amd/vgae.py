@@ -157,6 +157,17 @@ class VGAE(nn.Module):
                 g.ndata['h'] = feat
         return ops.tsne(mu, **kw)
 
+    def pca_nodes(self, g, k=None, **kw):
+        """GAE.pca_nodes on the mean embedding mu (no noise): ``ops.PCAResult`` of ops.pca; mu is read in place where
+        the two heads are packed in one buffer; ``g.ndata['h']`` is restored on exit"""
+        feat = g.ndata['h']
+        with torch.no_grad():
+            try:
+                mu, _ = self.encode(g)
+            finally:
+                g.ndata['h'] = feat
+        return ops.pca(mu, k, **kw)
+
     def classify_nodes(self, g, labels, **kw):
         """GAE.classify_nodes on the mean embedding mu (no noise): ``ops.LogRegResult`` of ops.logreg; mu is read in
         place where the two heads are packed in one buffer; ``g.ndata['h']`` is restored on exit"""

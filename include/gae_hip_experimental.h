@@ -1162,6 +1162,75 @@ int gae_tsne_update(float *Y, int64_t ldy, int64_t n, const int32_t *indptr, con
                     double learning_rate, double min_grad_norm, gae_tsne_status *status, void *workspace,
                     int64_t workspace_bytes, void *stream);
 
+/* ---- K31: principal components of a frozen feature (ops.pca, ops.pca_transform, GAE.pca_nodes, GAE.pca_graphs)
+ * An fp64 symmetric eigensolver in one block plus one projection pass.  No float atomics, no libm: the same bits run to
+ * run, for any ldx and any stream.  pca.hip is compiled without contraction; nothing below is fused unless fma is written.
+ * SOLVE (gae_pca_solve): one launch of ONE block.
+ *   stats        ONE fold's packed upper triangle as gae_ridge_stats writes it, width W = 1 + d + t; the t trailing rows
+ *                and columns are ignored.  pivot: the fp32 [>= d] one the moments were taken with, or NULL = zeros.
+ *                n_rows_used: the length of the list the moments were taken over (checked on the host: 0 .. 2^31 - 1;
+ *                the device takes the count c from the moments themselves).
+ *   centring     c = S[0][0], s_j = S[0][1 + j], mu_j = s_j / c;  for i <= j: C_ij = C_ji = (S_xx[i][j] - s_j mu_i) / (c - 1)
+ *                (sklearn's n - 1 denominator);  mean[j] = (double)pivot[j] + mu_j.
+ *   Jacobi       cyclic, two-sided, on the full symmetric C in LDS; V (as V^T, starting from I) beside it for d <= 96,
+ *                else in the workspace: the bits do not depend on which.  dp = d rounded up to even, m = dp / 2.  A sweep
+ *                is the dp - 1 rounds r = 0 .. dp - 2 of the round-robin tournament: pair 0 = {r, dp - 1}, pair k =
+ *                {(r + k) mod (dp - 1), (r - k) mod (dp - 1)}, k = 1 .. m - 1; p = the smaller index, q = the larger.  For
+ *                odd d index dp - 1 does not exist: its partner r sits the round out (a pair that is not rotated).
+ *   rotation     of the pair (p, q), from the matrix at the start of the round: it is skipped when a_pq == 0 or
+ *                |a_pq| <= 2^-53 sqrt(|a_pp| |a_qq|).  Otherwise tau = (a_qq - a_pp) / (2 a_pq), t = sgn(tau) / (|tau| +
+ *                sqrt(1 + tau tau)) (sgn(0) = +1), c = 1 / sqrt(1 + t t), s = t c; every +, -, x, /, sqrt a single
+ *                correctly rounded fp64 operation in the order written.  A skipped pair has c = 1, s = 0.
+ *   a round      A <- J^T A J for J the product of the round's disjoint rotations, in 2 x 2 blocks: for pairs k < l
+ *                ((p, q) with c1, s1 and (r, u) with c2, s2) FIRST the column rotation x' = c2 x - s2 y, y' = s2 x + c2 y on
+ *                (x, y) = (a_pr, a_pu) and (a_qr, a_qu), THEN the row rotation x' = c1 x - s1 y, y' = s1 x + c1 y on the
+ *                results (a'_pr, a'_qr) and (a'_pu, a'_qu); each product rounded, then the sum.  The block's transpose is a
+ *                copy, so A stays symmetric bit for bit.  A pair's own block: a_pp -= t a_pq, a_qq += t a_pq, a_pq = a_qp
+ *                = 0 (untouched when skipped).  V^T rows p, q take the row rotation.  Threads split blocks and columns,
+ *                never a sum.
+ *   stopping     after the first sweep that rotates nothing (info 0), or after GAE_PCA_MAX_SWEEPS sweeps (info 1).
+ *   ordering     eigenvalues = the final diagonal, descending; equal values to the lower index of the diagonal (a NaN, which only
+ *                non-finite moments give, sorts last).  The first
+ *                n_components go out: values fp64 [k] as computed (a tiny negative value is reported, not clamped),
+ *                components fp64 [k][d] = the columns of V; the entry of largest magnitude of each is made positive (ties
+ *                to the lower index) by negating the row: sklearn's v-based svd_flip.
+ *   status       a 64-byte device block.  gae_pca_solve WRITES info, n_sweeps (sweeps run, the one that rotated nothing
+ *                included), n_rotations, off_norm = sqrt(sum_i (sum_{j != i} a_ij a_ij)) (j, then i ascending) and
+ *                total_variance = the sum of all d eigenvalues in their output order; gae_pca_transform ADDS to
+ *                nonfinite_rows, nonpositive_components and errors (integer atomics).
+ *   info         0 converged; 1 the sweep cap was reached; -1 c < 2 (fewer than two rows).  Where info != 0 mean, values,
+ *                components, off_norm and total_variance are NaN.
+ *   workspace    gae_pca_workspace_bytes(d) bytes: a pure host function of d, positive; GAE_E_RANGE for d outside 1..128.
+ * PROJECT (gae_pca_transform): Z[i][c] = sum_j (x_ij - m_j) v_cj, fp32 [n_rows, k], rows ldz >= k apart.  m and v are
+ *   rounded to fp32 once, the subtraction is one fp32 operation, the sum one fp32 fma chain from +0 over j ascending on
+ *   v_mfma_f32_16x16x4_f32 (K27's chains; the padding of j and c to tiles adds exact zeros).  GAE_PCA_WHITEN: then one fp32
+ *   product by (float)(1 / sqrt(values[c])), the fp64 quotient of the fp64 root; a component whose value is not > 0 gives
+ *   score 0 and is counted once in nonpositive_components.  rows: int32 [n_rows] ids or NULL = rows 0 .. n - 1 (then n_rows
+ *   == n); rows that are not listed are never read.  A listed row holding a non-finite value gives a NaN row and is
+ *   counted in nonfinite_rows; a row id outside [0, n) gives a NaN row and sets GAE_PCA_ERR_ROW_ID.  X is streamed once.
+ * Argument errors are returned before any launch and need no GPU: d outside 1..128, n_components outside 1..d, t outside
+ *   0..8, unknown flag bits (GAE_E_RANGE); negative sizes, n or n_rows >= 2^31, ldx < d, ldz < k, rows = NULL with n_rows
+ *   != n (GAE_E_SIZE); NULL pointers -- values only under GAE_PCA_WHITEN, X only with n_rows > 0 -- (GAE_E_NULL); a short
+ *   workspace (GAE_E_WORKSPACE). */
+enum { GAE_PCA_MAX_D = 128, GAE_PCA_MAX_SWEEPS = 30 };
+enum { GAE_PCA_WHITEN = 1 };
+enum { GAE_PCA_ERR_ROW_ID = 1 };
+
+typedef struct gae_pca_status {
+    int64_t info, n_sweeps, n_rotations, nonfinite_rows, nonpositive_components, errors;
+    double off_norm, total_variance;
+} gae_pca_status;
+
+int64_t gae_pca_workspace_bytes(int64_t d);
+
+int gae_pca_solve(const double *stats, int64_t d, int64_t t, const float *pivot, int64_t n_rows_used, int64_t n_components,
+                  int flags, double *mean, double *values, double *components, gae_pca_status *status, void *workspace,
+                  int64_t workspace_bytes, void *stream);
+
+int gae_pca_transform(const float *X, int64_t ldx, int64_t n, int64_t d, const int32_t *rows, int64_t n_rows,
+                      const double *mean, const double *components, const double *values, int64_t k, int flags, float *Z,
+                      int64_t ldz, gae_pca_status *status, void *stream);
+
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
 int gae_x_decoder_bce_finalize(const gae_bce_tail *tail, void *stream);
