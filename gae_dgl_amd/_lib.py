@@ -45,6 +45,12 @@ PCA_WHITEN = 1
 PCA_ERR_ROW_ID = 1
 PCA_STATUS_WORDS = 8              # gae_pca_status: int64 info, n_sweeps, n_rotations, nonfinite_rows, nonpositive_components,
                                   # errors; double off_norm, total_variance
+SPECTRAL_MAX_B, SPECTRAL_MAX_K, SPECTRAL_MAX_DEGREE, SPECTRAL_CHUNK_ROWS = 128, 64, 12, 256    # GAE_SPECTRAL_*
+SPECTRAL_SCALE_NONE, SPECTRAL_SCALE_DEGREE, SPECTRAL_SCALE_VALUE = 0, 1, 2
+SPECTRAL_ERR_INDEX = 1
+SPECTRAL_KEY_XOR = 0x5851F42D4C957F2D
+SPECTRAL_STATUS_WORDS = 8         # gae_spectral_status: int64 info, n_converged, n_spmm, nonfinite, errors; double theta_1,
+                                  # theta_k, res_max
 TSNE_STATUS_WORDS = 8             # gae_tsne_status: int64 done, iteration, nonfinite, ticket; double p_log_d, log_z, grad2, z
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
@@ -240,6 +246,14 @@ SIGNATURES = {
     "gae_pca_workspace_bytes": (_i64, [_i64]),
     "gae_pca_solve": (_int, [_p, _i64, _i64, _p, _i64, _i64, _int, _p, _p, _p, _p, _p, _i64, _p]),
     "gae_pca_transform": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _int, _p, _i64, _p, _p]),
+    "gae_spectral_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "gae_spectral_scale": (_int, [_p, _i64, _d, _p, _p]),
+    "gae_spectral_init": (_int, [_p, _i64, _i64, _u64, _p]),
+    "gae_spectral_spmm": (_int, [_p, _p, _i64, _i64, _p, _d, _p, _p, _p, _i64, _p, _p, _p]),
+    "gae_spectral_gram": (_int, [_p, _p, _i64, _i64, _p, _p, _i64, _p, _i64, _p]),
+    "gae_spectral_solve": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p]),
+    "gae_spectral_rotate": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _d, _p, _p, _p, _i64, _p]),
+    "gae_spectral_finish": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _int, _p, _p, _p, _i64, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

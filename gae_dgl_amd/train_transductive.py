@@ -10,6 +10,7 @@ epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
       [--classify [LAMBDA ...] [--classify_folds F] [--classify_test_frac Q] [--classify_seed S] [--classify_out model.npz]]
       [--map_out map.npz [--map_perplexity P] [--map_iters T] [--map_seed S] [--map_init random|pca]]
       [--pca K [--pca_out pca.npz]]
+      [--spectral K [--spectral_self_loops] [--spectral_scaling none|degree|value] [--spectral_seed N] [--spectral_out sc.npz]]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -116,6 +117,16 @@ def build_parser():
     ap.add_argument("--pca_out", default=None, metavar="PATH",
                     help="with --pca: write PATH (.npz with 'components' fp64 [K, d], 'mean', 'explained_variance', "
                          "'explained_variance_ratio' and 'scores' fp32 [N, K])")
+    ap.add_argument("--spectral", type=int, default=None, metavar="K",
+                    help="with --eval: the spectral-clustering baseline of the GAE tables -- the K leading eigenvectors of "
+                         "the normalised adjacency of the TRAINING graph (ops.spectral_embedding), scored like the "
+                         "model's embedding; with --cluster / --classify the same k-means and log-reg lines for it")
+    ap.add_argument("--spectral_self_loops", action="store_true", help="with --spectral: the GCN operator (A + I)")
+    ap.add_argument("--spectral_scaling", choices=["none", "degree", "value"], default=None,
+                    help="with --spectral: the scaling of the embedding (default none)")
+    ap.add_argument("--spectral_seed", type=int, default=None, metavar="N", help="with --spectral: the seed of the start block (default 0)")
+    ap.add_argument("--spectral_out", default=None, metavar="PATH",
+                    help="with --spectral: write PATH (.npz with 'embedding' fp32 [N, K], 'vectors' fp64, 'values', 'residuals')")
     return ap
 
 
@@ -177,6 +188,16 @@ def parse_args(argv=None):
             ap.error("--pca_out needs --pca K")
     elif not 1 <= args.pca <= args.hidden_dims[-1] or args.hidden_dims[-1] > 128:
         ap.error(f"--pca {args.pca}: K must lie in 1..{args.hidden_dims[-1]} (the embedding width, 128 at the most)")
+    if args.spectral is None:
+        if args.spectral_self_loops or any(v is not None for v in (args.spectral_scaling, args.spectral_seed, args.spectral_out)):
+            ap.error("--spectral_self_loops / --spectral_scaling / --spectral_seed / --spectral_out need --spectral K")
+    else:
+        if not 1 <= args.spectral <= 64:
+            ap.error(f"--spectral {args.spectral}: K must lie in 1..64")
+        if not args.eval:
+            ap.error("--spectral needs --eval (it scores the held-out edges)")
+        if args.spectral_seed is not None and args.spectral_seed < 0:
+            ap.error(f"--spectral_seed {args.spectral_seed}: N must be at least 0")
     return args
 
 
@@ -376,6 +397,40 @@ def main(argv=None):
                      explained_variance=res.explained_variance.cpu().numpy(), explained_variance_ratio=ratio,
                      scores=res.transform(z).cpu().numpy())
         main.last_pca = res
+    if args.spectral is not None:
+        import numpy as np
+        K = args.spectral
+        sc = ops.spectral_embedding(g, K, self_loops=args.spectral_self_loops, scaling=args.spectral_scaling or "none",
+                                    seed=args.spectral_seed or 0)
+        main.last_spectral = {"result": sc}
+        for name, pairs in held_out.items():
+            scores = metrics.evaluate(sc.embedding, pairs)
+            print(f"spectral ({K}) {name} ROC-AUC: {scores['auc']:.4f} | AP: {scores['ap']:.4f}")
+            main.last_spectral[name] = scores
+        if args.cluster is not None:
+            res = ops.kmeans(sc.embedding, args.cluster, seed=args.cluster_seed or 0)
+            print(f"spectral k-means K = {args.cluster}: inertia {res.inertia:.6g} | iterations: {res.n_iter}"
+                  f"{'' if res.converged else ' (not converged)'} | sizes: {res.counts.tolist()}")
+            main.last_spectral["cluster"] = {"result": res}
+            if data.labels is not None:
+                cm = metrics.clustering_metrics(res.labels.cpu().numpy(), data.labels)
+                print(f"spectral NMI: {cm['nmi']:.4f} | ARI: {cm['ari']:.4f} | ACC: {cm['acc']:.4f}")
+                main.last_spectral["cluster"].update(cm)
+        if args.classify is not None and main.last_classify is not None:
+            # the split and the folds of the model's own head, so the two lines compare like with like
+            test = main.last_classify["test"]
+            labels = torch.as_tensor(data.labels, dtype=torch.int64, device=device)
+            F = args.classify_folds or 5
+            res = ops.logreg(sc.embedding, labels, lambdas=args.classify or None, folds=F, fold=fold.to(device))
+            zt = sc.embedding.index_select(0, test.to(device)).contiguous()
+            pred, proba = ops.logreg_predict(zt, res.coef, res.intercept, res.pivot, proba=True)
+            cm = metrics.classification_metrics(pred, labels[test.to(device)], proba, n_classes=res.coef.shape[0])
+            print(f"spectral LogReg ({F}-fold CV, lambda = {res.lam:g}) test accuracy: {cm['accuracy']:.4f} | "
+                  f"macro-F1: {cm['macro_f1']:.4f} | log-loss: {cm['log_loss']:.4f}")
+            main.last_spectral["classify"] = {"result": res, "metrics": cm, "pred": pred}
+        if args.spectral_out is not None:
+            np.savez(args.spectral_out, embedding=sc.embedding.cpu().numpy(), vectors=sc.vectors.cpu().numpy(),
+                     values=sc.values.cpu().numpy(), residuals=sc.residuals.cpu().numpy())
     return [float(l) for l in losses]
 
 

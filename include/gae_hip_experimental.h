@@ -1231,6 +1231,98 @@ int gae_pca_transform(const float *X, int64_t ldx, int64_t n, int64_t d, const i
                       const double *mean, const double *components, const double *values, int64_t k, int flags, float *Z,
                       int64_t ldz, gae_pca_status *status, void *stream);
 
+/* ---- K32: spectral embedding of a graph (ops.spectral_embedding): the k algebraically largest eigenpairs of
+ * S = D^-1/2 (A + sigma I) D^-1/2 by Chebyshev-filtered block subspace iteration with a Rayleigh-Ritz step, in fp64.
+ * No float atomics, no rocSOLVER / rocSPARSE, no host linear algebra: the same bits run to run, for any stream and any
+ * grid.  spectral.hip is compiled without contraction; a product and a sum are fused exactly where fma is written.
+ * The host drives the launches (ops/spectral.py); everything it needs between them stays on the device.
+ * OPERANDS   tall blocks fp64 [n][b], row-major, rows b apart, 16-byte aligned; b even, 2 <= b <= 128; 1 <= k <= 64, k <= b;
+ *            n < 2^31.  CSR: int32 indptr [n + 1], int32 indices [nnz] (graph.csr()); a duplicate edge counts once per
+ *            copy; an index outside [0, n) is skipped and sets GAE_SPECTRAL_ERR_INDEX.
+ * SCALE      (gae_spectral_scale) deg_i = indptr[i + 1] - indptr[i]; t = (double)deg_i + sigma; s_i = t > 0 ? 1 / sqrt(t) : 0.
+ * INIT       (gae_spectral_init) element e = i b + c of V: block q = e >> 2 is philox4x32_10(ctr = q, draw = 0, key = seed ^
+ *            GAE_SPECTRAL_KEY_XOR) (csrc/common.h); the pair h = (e >> 1) & 1 of the block has u1 = ((w[2h] >> 8) + 0.5) 2^-24,
+ *            u2 = (w[2h + 1] >> 8) 2^-24 (exact in fp64), rad = sqrt(-2 log(u1)), ang = 6.283185307179586 u2; the even element is
+ *            rad cos(ang), the odd one rad sin(ang) (fp64 library functions: a few ulp, not restated bit for bit).
+ * PRODUCT    (gae_spectral_spmm) for every row i and column c, coef = {alpha, beta, gamma} read from the DEVICE:
+ *              acc = +0;  for e = indptr[i] .. indptr[i + 1] - 1 ascending, j = indices[e]: acc = fma(s_j, Yin[j][c], acc);
+ *              sigma != 0: acc = fma(sigma s_i, Yin[i][c], acc)   (sigma s_i one rounded product);
+ *              t = s_i acc;  o = alpha t;  o = fma(beta, Yin[i][c], o);  Yprev != NULL: o = fma(gamma, Yprev[i][c], o);
+ *              Yout[i][c] = o.
+ *            A row goes to a group of lanes that split the columns in 16-byte pairs, never the sum.  Yout must not
+ *            alias Yin; it may alias Yprev.
+ * GRAM       (gae_spectral_gram) G = V^T V and H = V^T AV, both written as full symmetric [b][b] matrices from their computed
+ *            upper triangles.  Rows go in chunks of GAE_SPECTRAL_CHUNK_ROWS = 256; a chunk's sums run on
+ *            v_mfma_f64_16x16x4_f64, four rows a step, rows ascending; the chunk partials are added in the library's one
+ *            order for partial sums (common.h: <= 32 partials one lane in order, more 64 lanes and the fixed tree).
+ *            max_blocks > 0 caps the grid (blocks then walk chunks b, b + grid, ...): the bits do not depend on it.
+ * SOLVE      (gae_spectral_solve) three launches of ONE block each; every -, x, / and sqrt one rounded operation:
+ *   factor     G = L L^T by cholesky.h's Cholesky-Crout (column j: piv = g_jj - sum_{k<j} l_jk l_jk, l_ij = (g_ij - sum_{k<j}
+ *              l_ik l_jk) / sqrt(piv), k ascending, each product subtracted as it is formed), from the lower triangle.
+ *   reduce     X = L^-1 H: column c, i ascending: x = h_ic; k < i ascending: x = x - l_ik x_kc; x_ic = x / l_ii.
+ *              H' = X L^-T: row r, j ascending: y = x_rj; k < j ascending: y = y - l_jk y_rk; y_rj = y / l_jj.  The upper
+ *              triangle (r <= j) is H'; the lower one is its copy.
+ *   Jacobi     gae_pca_solve (K31) as it stands, on a packed triangle of width 1 + b with S[0][0] = 2, S[0][1..] = 0, S_xx =
+ *              H', pivot = NULL, t = 0: its centring returns H' bit for bit ((S - 0 . 0) / 1).  theta [b] = its values
+ *              (descending), W = its components (row c = vector c, K31's sign rule).
+ *   back       T = L^-T W^T: column c, i descending: x = w_ci; k = i + 1 .. b - 1 ascending: x = x - l_ki t_kc; t_ic = x / l_ii.
+ *              T fp64 [b][b] row-major, theta and the filter's coefficients go to the workspace, theta also to values.
+ *   filter     a = max(min(theta_b, theta_k - 0.02), -0.5);  e = (a + 1) 0.5;  c = (a - 1) 0.5;  s1 = e / (theta_1 - c);
+ *              coef[0] = {1, 0, 0} (the plain product);  coef[1] = {s1 / e, -(c alpha), 0};  s = s1;  for d = 2 .. degree:
+ *              s2 = 1 / (2 / s1 - s);  alpha = (2 s2) / e;  coef[d] = {alpha, -(c alpha), -(s s2)};  s = s2.
+ *              Degree d of the filter is the PRODUCT with coef[d], Yprev = NULL at d = 1 (Zhou & Saad's scaled Chebyshev
+ *              recurrence on [-1, a], scaling point theta_1).
+ *   info       0; j >= 1: the Cholesky met pivot j <= 0 or not finite; -1: the Jacobi reached its sweep cap; -2: a Ritz
+ *              value is not finite.  Where info != 0, T and theta are NaN.
+ * ROTATE     (gae_spectral_rotate) V <- V T and AV <- AV T in place, row by row: out[i][c] = the fma chain from +0 over j
+ *            ascending of in[i][j] T[j][c].  Residual: d = AV'[i][c] - theta_c V'[i][c] (product rounded, then the difference),
+ *            chunk partial = the sum over the chunk's rows ascending of d d from +0; the partials of a column are added in
+ *            the library's one order; res_c = sqrt(sum).  n_converged = the longest prefix of the first k columns with res_c
+ *            <= tol.  A non-finite res_c among the first k sets nonfinite.
+ * FINISH     (gae_spectral_finish) column c of the output is column first + c of V.  The entry of largest magnitude of a
+ *            column (chunks of 256 rows ascending, rows ascending, a later entry wins only when strictly larger) is made
+ *            positive by negating the column.  vectors fp64 [n][k]; embedding fp32 [n][k] = (float) of the vector entry
+ *            times s_i (GAE_SPECTRAL_SCALE_DEGREE) or times sqrt(max(theta_c, 0)) (GAE_SPECTRAL_SCALE_VALUE), one fp64 product.
+ * STATUS     a 64-byte device block the host reads once per checked iteration; n_spmm counts PRODUCT launches.
+ * WORKSPACE  gae_spectral_workspace_bytes(n, nnz, b): a pure host function; one carve serves every entry point.
+ * Argument errors are returned before any launch and need no GPU: b odd or outside 2..128, k outside 1..min(b, 64), degree
+ *   outside 1..GAE_SPECTRAL_MAX_DEGREE, unknown scaling, sigma < 0 or tol < 0 or not finite (GAE_E_RANGE); n < 1 or n >= 2^31,
+ *   nnz < 0 or nnz >= 2^31, first + k > b, negative max_blocks, Yout aliasing Yin, AV aliasing V, a tall operand off a 16-byte
+ *   boundary (GAE_E_SIZE); NULL pointers (GAE_E_NULL); a short workspace (GAE_E_WORKSPACE). */
+enum { GAE_SPECTRAL_MAX_B = 128, GAE_SPECTRAL_MAX_K = 64, GAE_SPECTRAL_MAX_DEGREE = 12, GAE_SPECTRAL_CHUNK_ROWS = 256 };
+enum { GAE_SPECTRAL_SCALE_NONE = 0, GAE_SPECTRAL_SCALE_DEGREE = 1, GAE_SPECTRAL_SCALE_VALUE = 2 };
+enum { GAE_SPECTRAL_ERR_INDEX = 1 };
+#define GAE_SPECTRAL_KEY_XOR 0x5851F42D4C957F2Dull
+
+typedef struct gae_spectral_status {
+    int64_t info, n_converged, n_spmm, nonfinite, errors;
+    double theta_1, theta_k, res_max;      /* res_max: the largest residual of the first k columns */
+} gae_spectral_status;
+
+int64_t gae_spectral_workspace_bytes(int64_t n, int64_t nnz, int64_t b);
+
+int gae_spectral_scale(const int32_t *indptr, int64_t n, double sigma, double *s, void *stream);
+
+int gae_spectral_init(double *V, int64_t n, int64_t b, uint64_t seed, void *stream);
+
+int gae_spectral_spmm(const int32_t *indptr, const int32_t *indices, int64_t n, int64_t nnz, const double *s, double sigma,
+                      const double *Yin, const double *Yprev, double *Yout, int64_t b, const double *coef_dev,
+                      gae_spectral_status *status, void *stream);
+
+int gae_spectral_gram(const double *V, const double *AV, int64_t n, int64_t b, double *G, double *H, int64_t max_blocks,
+                      void *workspace, int64_t workspace_bytes, void *stream);
+
+int gae_spectral_solve(const double *G, const double *H, int64_t b, int64_t k, int64_t degree, double *T, double *values,
+                       double *coef, gae_spectral_status *status, void *workspace, int64_t workspace_bytes, void *stream);
+
+int gae_spectral_rotate(double *V, double *AV, int64_t n, int64_t b, int64_t k, const double *T, const double *values,
+                        double tol, double *residuals, gae_spectral_status *status, void *workspace,
+                        int64_t workspace_bytes, void *stream);
+
+int gae_spectral_finish(const double *V, int64_t n, int64_t b, int64_t first, int64_t k, const double *values, const double *s,
+                        int scaling, double *vectors, float *embedding, void *workspace, int64_t workspace_bytes,
+                        void *stream);
+
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
 int gae_x_decoder_bce_finalize(const gae_bce_tail *tail, void *stream);
