@@ -23,7 +23,9 @@
 //   root      one block per model: folds the loss chunks, resets the model's table, node 0, the level-0 lists
 //   then per level: hist (chunk, feature tile, model), scan (long node, feature tile, model; only when n_used exceeds a
 //   chunk), decide (model: the split test, the children, the next level's lists), partition (chunk, model; not after the
-//   last level); and keep (configuration): the all-rows model's table to the output.
+//   last level); and keep (configuration): the all-rows model's table to the output.  The bodies of hist, scan and
+//   partition and the tree walk of predict are the level pass of forest_cells.h, K26's too; what is boost's own there is
+//   its lists (node_of) and the GradHess and Gain policies.
 // After the last round one more prologue + root give the final score and the last point of the loss curve.  The host
 // reads the 32-byte status once per check_every rounds and once at the end; nothing else synchronises.
 #include <float.h>
@@ -37,33 +39,30 @@
 namespace {
 
 using gae::cdiv;
-using gae::cells::better;
+using gae::cells::add_i64;
 using gae::cells::block_scan;
+using gae::cells::Chunk;
+using gae::cells::chunks_of;
+using gae::cells::flag;
+using gae::cells::i64;
+using gae::cells::take_halves;
+using gae::cells::u64;
 
 constexpr int kMaxD = 256, kMaxBins = 256, kMaxDepth = 8, kMaxRounds = 4096, kMaxModels = 256;
-constexpr int kSplitRows = GAE_FOREST_SPLIT_ROWS;
+constexpr int kSplitRows = gae::cells::kSplitRows;
 constexpr int kThreads = gae::cells::kThreads, kWaves = gae::cells::kWaves;
 constexpr int kLossRows = 256;             // rows per held-out loss partial = the prologue's block
 
-typedef unsigned long long u64;
-typedef long long i64;
-
-__host__ __device__ inline int chunks_of(int rows) { return (rows + kSplitRows - 1) / kSplitRows; }
-
 struct Item { int node, slot; };           // slot >= 0: a node longer than one chunk, its global cells
-struct Chunk { int item, chunk; };
 struct Level { int n_items, n_chunks, n_long, pad; };
 
-struct Args {
-    const uint8_t *codes;
-    const int32_t *n_edges;
+struct Args : gae::cells::Frame {                          // (the level pass's own arrays are the Frame's)
     const float *edges;
     const float *y;
     const int32_t *fold;
-    int n_used, d, bins, folds, n_cfg, Mo, depth, M, m_feat, msl, objective, R, ft, nft, maxI, maxC, maxL, n_parts;
+    int folds, n_cfg, Mo, depth, M, objective, R, maxI, maxC, maxL, n_parts;
     int round, level, gx, gl;              // gx, gl: blocks per model of this level's hist and scan launches
     double mcw, min_gain, base, g_up, g_step, h_up, h_step;
-    uint64_t key;
     const double *lr, *lam;                // [n_cfg] (workspace)
     // outputs
     int32_t *o_feature, *o_bin, *o_left, *o_count, *o_n_nodes;
@@ -71,28 +70,18 @@ struct Args {
     double *o_value, *o_gain, *loss, *score;
     i64 *correct;
     int32_t *bad;
-    gae_forest_status *status;
     // workspace
-    int32_t *feature, *bin, *left, *count, *seg_start, *n_nodes;
+    int32_t *n_nodes;
     float *threshold;
     double *value, *gain;
     i64 *nG, *nH, *gq, *hq, *root;
-    int32_t *pos_in, *pos_out, *split_cur, *split_next, *cand_nl;
+    int32_t *split_cur, *split_next;
     Item *items_cur, *items_next;
     Chunk *chunks_cur, *chunks_next;
-    int2 *curs_cur, *curs_next, *cand_fb;
+    int2 *curs_next;
     Level *lvl_cur, *lvl_next;
-    double *cand_score, *part;
-    i64 *cand_gh;                          // [..][2]
-    unsigned *gcnt;
-    i64 *gsum;                             // [..][2]
+    double *part;
 };
-
-__device__ __forceinline__ void flag(gae_forest_status *st, int64_t bits)
-{
-    atomicOr(reinterpret_cast<u64 *>(&st->errors), static_cast<u64>(bits));
-}
-__device__ __forceinline__ void add_i64(i64 *p, i64 v) { atomicAdd(reinterpret_cast<u64 *>(p), static_cast<u64>(v)); }
 
 // a model left the fixed-point frame or went non-finite: marked once, counted once in status.reserved[0]
 __device__ __forceinline__ void mark_bad(const Args &a, int m)
@@ -277,7 +266,7 @@ __global__ __launch_bounds__(kThreads) void boost_root_kernel(const Args a)
         a.value[tb] = leaf_weight(a, G, H, a.lr[cfg], a.lam[cfg]);
         a.n_nodes[m] = 1;
         a.items_cur[int64_t(m) * a.maxI] = Item{0, is_long ? 0 : -1};
-        a.curs_cur[int64_t(m) * a.maxI] = make_int2(0, 0);
+        a.curs[int64_t(m) * a.maxI] = make_int2(0, 0);
         if (is_long) a.split_cur[int64_t(m) * a.maxL] = 0;
         a.lvl_cur[m] = offered ? Level{1, nch, is_long ? 1 : 0, 0} : Level{0, 0, 0, 0};
         a.root[m * 4] = 0; a.root[m * 4 + 1] = 0; a.root[m * 4 + 2] = 0;
@@ -285,67 +274,45 @@ __global__ __launch_bounds__(kThreads) void boost_root_kernel(const Args a)
 }
 
 // ------------------------------------------------------------------------------------------------------ a level
-using HistLds = gae::cells::Lds;
+using gae::cells::Lds;
+using gae::cells::Node;
 
-__device__ __forceinline__ void select_features(const Args &a, const HistLds &h, int m, int node)
+// work item `item` of model m's level: its node as the level pass sees it
+__device__ __forceinline__ Node node_of(const Args &a, int m, int item)
 {
-    const int k = m % (a.folds + 1);
-    gae::cells::select_subset(h.sel, h.rkey, a.d, a.m_feat, node, (uint64_t(1) << 32) + ((uint64_t(a.round) << 8) | uint64_t(k)),
-                              a.key);
+    const Item it = a.items_cur[int64_t(m) * a.maxI + item];
+    return Node{int64_t(m) * a.M + it.node, int64_t(m) * a.n_used, int64_t(m) * a.maxI + item,
+                it.slot >= 0 ? int64_t(m) * a.maxL + it.slot : -1, it.node,
+                (uint64_t(1) << 32) + ((uint64_t(a.round) << 8) | uint64_t(m % (a.folds + 1)))};
 }
 
-// the cells of features [f0, f0 + ftw) are in LDS: prefix sums over the bins, every candidate's score, the tile's best
-__device__ __forceinline__ void scan_best(const Args &a, const HistLds &h, int m, int node, int item, int tile, int f0, int ftw)
-{
-    const int tid = threadIdx.x, bins = a.bins;
-    for (int p = tid; p < ftw * 3; p += kThreads) {
-        const int fl = p / 3, w = p % 3;
-        if (w == 0) {
-            unsigned run = 0;
-            for (int b = 0; b < bins; ++b) { run += h.cnt[fl * bins + b]; h.cnt[fl * bins + b] = run; }
-        } else {
-            i64 run = 0;
-            for (int b = 0; b < bins; ++b) { run += h.sum[(fl * bins + b) * 2 + (w - 1)]; h.sum[(fl * bins + b) * 2 + (w - 1)] = run; }
-        }
-    }
-    __syncthreads();
-    const int64_t at = int64_t(m) * a.M + node;
-    const int n = a.count[at];
-    const i64 G = a.nG[at], H = a.nH[at];
-    const double lam = a.lam[m / (a.folds + 1)];
-    double bs = -1.0;                      // every score is >= 0
-    int bf = 0x7fffffff, bb = 0x7fffffff;
-    for (int idx = tid; idx < ftw * bins; idx += kThreads) {
-        const int fl = idx / bins, b = idx % bins, f = f0 + fl;
-        if (b >= min(a.n_edges[f], bins - 1) || !h.sel[f]) continue;
-        const int nl = int(h.cnt[idx]), nr = n - nl;
-        if (nl < a.msl || nr < a.msl) continue;
+// a cell holds two sums: the model's fixed-point g and h of the listed rows
+struct GradHess {
+    const i64 *gq, *hq;
+    __device__ GradHess(const Args &a, int m) : gq(a.gq + int64_t(m) * a.n_used), hq(a.hq + int64_t(m) * a.n_used) {}
+    __device__ constexpr int words() const { return 2; }
+    __device__ i64 word(int s, int j) const { return j == 0 ? gq[s] : hq[s]; }
+};
+
+// the score of a split of node `at` of model m: G_l^2 / (H_l + lambda) + G_r^2 / (H_r + lambda), under min_child_weight
+struct Gain {
+    const Args &a;
+    i64 G, H;
+    double lam;
+    __device__ Gain(const Args &a_, int m, int64_t at) : a(a_), G(a_.nG[at]), H(a_.nH[at]), lam(a_.lam[m / (a_.folds + 1)]) {}
+    __device__ constexpr int words() const { return 2; }
+    __device__ double score(const Lds &h, int idx, int, int) const
+    {
         const i64 glq = h.sum[idx * 2], hlq = h.sum[idx * 2 + 1];
         const double gl = double(glq) * a.g_step, gr = double(G - glq) * a.g_step;
         const double hl = double(hlq) * a.h_step, hr = double(H - hlq) * a.h_step;
-        if (!(hl >= a.mcw) || !(hr >= a.mcw)) continue;
+        if (!(hl >= a.mcw) || !(hr >= a.mcw)) return -1.0;
         const double dl = hl + lam, dr = hr + lam;
-        if (!(dl > 0.0) || !(dr > 0.0)) continue;
+        if (!(dl > 0.0) || !(dr > 0.0)) return -1.0;
         const double score = (gl * gl) / dl + (gr * gr) / dr;
-        if (better(score, f, b, bs, bf, bb)) { bs = score; bf = f; bb = b; }
+        return score;
     }
-    h.rs[tid] = bs; h.rf[tid] = bf; h.rb[tid] = bb;
-    __syncthreads();
-    for (int off = kThreads / 2; off > 0; off >>= 1) {
-        if (tid < off && better(h.rs[tid + off], h.rf[tid + off], h.rb[tid + off], h.rs[tid], h.rf[tid], h.rb[tid])) {
-            h.rs[tid] = h.rs[tid + off]; h.rf[tid] = h.rf[tid + off]; h.rb[tid] = h.rb[tid + off];
-        }
-        __syncthreads();
-    }
-    const int64_t c = (int64_t(m) * a.maxI + item) * a.nft + tile;
-    const bool found = h.rs[0] >= 0.0;
-    if (tid == 0) {
-        a.cand_score[c] = h.rs[0];
-        a.cand_fb[c] = found ? make_int2(h.rf[0], h.rb[0]) : make_int2(-1, -1);
-        a.cand_nl[c] = found ? int(h.cnt[(h.rf[0] - f0) * bins + h.rb[0]]) : 0;
-    }
-    if (tid < 2) a.cand_gh[c * 2 + tid] = found ? h.sum[((h.rf[0] - f0) * bins + h.rb[0]) * 2 + tid] : 0;
-}
+};
 
 // grid models . gx, gx = chunk bound . nft: block b of a model is tile b % nft of its chunk b / nft
 __global__ __launch_bounds__(kThreads) void boost_hist_kernel(const Args a)
@@ -353,47 +320,11 @@ __global__ __launch_bounds__(kThreads) void boost_hist_kernel(const Args a)
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int m = blockIdx.x / a.gx, bx = blockIdx.x % a.gx, c = bx / a.nft, tile = bx % a.nft;
     if (c >= a.lvl_cur[m].n_chunks) return;
-    const HistLds h = gae::cells::carve(lds, a.ft, a.bins, 2);
-    const int tid = threadIdx.x, bins = a.bins;
+    const Lds h = gae::cells::carve(lds, a.ft, a.bins, 2);
     const Chunk ch = a.chunks_cur[int64_t(m) * a.maxC + c];
-    const Item it = a.items_cur[int64_t(m) * a.maxI + ch.item];
-    const int64_t at = int64_t(m) * a.M + it.node;
-    const int f0 = tile * a.ft, ftw = min(a.ft, a.d - f0);
-    const int start = a.seg_start[at], n = a.count[at];
-    const int r0 = ch.chunk * kSplitRows, nr = min(n - r0, kSplitRows);
-    const int cells = ftw * bins;
-    for (int q = tid; q < cells; q += kThreads) h.cnt[q] = 0u;
-    for (int q = tid; q < cells * 2; q += kThreads) h.sum[q] = 0;
-    select_features(a, h, m, it.node);                     // (its barrier also covers the zeroing)
-    const int32_t *pos = a.pos_in + int64_t(m) * a.n_used + start + r0;
-    const i64 *gq = a.gq + int64_t(m) * a.n_used, *hq = a.hq + int64_t(m) * a.n_used;
-    bool bad = false;
-    for (int idx = tid; idx < nr * ftw; idx += kThreads) {
-        const int r = idx / ftw, fl = idx % ftw;
-        if (!h.sel[f0 + fl]) continue;
-        const int s = pos[r];
-        if (unsigned(s) >= unsigned(a.n_used)) { bad = true; continue; }       // (cannot happen: the lists hold listed rows)
-        const int code = a.codes[int64_t(s) * a.d + f0 + fl];
-        if (code >= bins) { bad = true; continue; }
-        const int cell = fl * bins + code;
-        atomicAdd(&h.cnt[cell], 1u);
-        atomicAdd(reinterpret_cast<u64 *>(&h.sum[cell * 2]), static_cast<u64>(gq[s]));
-        atomicAdd(reinterpret_cast<u64 *>(&h.sum[cell * 2 + 1]), static_cast<u64>(hq[s]));
-    }
-    if (bad) flag(a.status, GAE_FOREST_ERR_CODE);
-    __syncthreads();
-    if (it.slot >= 0) {                                    // a node of several chunks: merge the cells, scan later
-        const int64_t g0 = ((int64_t(m) * a.maxL + it.slot) * a.d + f0) * bins;
-        for (int q = tid; q < cells; q += kThreads) {
-            const unsigned v = h.cnt[q];
-            if (!v) continue;
-            atomicAdd(&a.gcnt[g0 + q], v);
-            add_i64(&a.gsum[(g0 + q) * 2], h.sum[q * 2]);
-            add_i64(&a.gsum[(g0 + q) * 2 + 1], h.sum[q * 2 + 1]);
-        }
-        return;
-    }
-    scan_best(a, h, m, it.node, ch.item, tile, f0, ftw);
+    const Node nd = node_of(a, m, ch.item);
+    if (gae::cells::fill_tile(a, h, GradHess(a, m), nd, ch, tile)) return;  // a node of several chunks: scanned later
+    gae::cells::scan_tile(a, h, Gain(a, m, nd.at), nd, tile);
 }
 
 // grid models . gl, gl = long-node bound . nft: the merged cells of a long node; the slot is left zeroed for the next level
@@ -402,17 +333,10 @@ __global__ __launch_bounds__(kThreads) void boost_scan_kernel(const Args a)
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int m = blockIdx.x / a.gl, bx = blockIdx.x % a.gl, slot = bx / a.nft, tile = bx % a.nft;
     if (slot >= a.lvl_cur[m].n_long) return;
-    const HistLds h = gae::cells::carve(lds, a.ft, a.bins, 2);
-    const int tid = threadIdx.x, bins = a.bins;
-    const int item = a.split_cur[int64_t(m) * a.maxL + slot];
-    const Item it = a.items_cur[int64_t(m) * a.maxI + item];
-    const int f0 = tile * a.ft, ftw = min(a.ft, a.d - f0);
-    const int cells = ftw * bins;
-    const int64_t g0 = ((int64_t(m) * a.maxL + slot) * a.d + f0) * bins;
-    for (int q = tid; q < cells; q += kThreads) { h.cnt[q] = a.gcnt[g0 + q]; a.gcnt[g0 + q] = 0u; }
-    for (int q = tid; q < cells * 2; q += kThreads) { h.sum[q] = a.gsum[g0 * 2 + q]; a.gsum[g0 * 2 + q] = 0; }
-    select_features(a, h, m, it.node);
-    scan_best(a, h, m, it.node, item, tile, f0, ftw);
+    const Lds h = gae::cells::carve(lds, a.ft, a.bins, 2);
+    const Node nd = node_of(a, m, a.split_cur[int64_t(m) * a.maxL + slot]);
+    gae::cells::load_slot<true>(a, h, 2, nd, int64_t(m) * a.maxL + slot, tile);
+    gae::cells::scan_tile(a, h, Gain(a, m, nd.at), nd, tile);
 }
 
 // one block per model; a level holds at most 2^(depth - 1) <= 128 items: one per thread
@@ -455,7 +379,7 @@ __global__ __launch_bounds__(kThreads) void boost_decide_kernel(const Args a)
             a.gain[at] = best - parent;
             const int64_t lt = int64_t(m) * a.M + L, rt = lt + 1;
             const int start = a.seg_start[at];
-            const i64 gl = a.cand_gh[cbest * 2], hl = a.cand_gh[cbest * 2 + 1];
+            const i64 gl = a.cand_sum[cbest * 2], hl = a.cand_sum[cbest * 2 + 1];
             const i64 gr = a.nG[at] - gl, hr = a.nH[at] - hl;
             a.count[lt] = nl; a.count[rt] = n - nl;
             a.seg_start[lt] = start; a.seg_start[rt] = start + nl;
@@ -497,43 +421,10 @@ __global__ __launch_bounds__(kThreads) void boost_decide_kernel(const Args a)
 // grid (chunk bound, models)
 __global__ __launch_bounds__(kThreads) void boost_partition_kernel(const Args a)
 {
-    __shared__ int w[kWaves];
-    __shared__ int bases[2];
-    const int m = blockIdx.y, tid = threadIdx.x;
+    const int m = blockIdx.y;
     if (int(blockIdx.x) >= a.lvl_cur[m].n_chunks) return;
     const Chunk ch = a.chunks_cur[int64_t(m) * a.maxC + blockIdx.x];
-    const int64_t item = int64_t(m) * a.maxI + ch.item;
-    const int64_t tb = int64_t(m) * a.M, at = tb + a.items_cur[item].node;
-    const int f = a.feature[at];
-    if (f < 0) return;                                     // a leaf: its segment is never read again
-    const int b = a.bin[at], n = a.count[at], start = a.seg_start[at];
-    const int nl = a.count[tb + a.left[at]], nrt = n - nl;
-    const int r0 = ch.chunk * kSplitRows, r1 = min(n, r0 + kSplitRows);
-    const int32_t *src = a.pos_in + int64_t(m) * a.n_used + start;
-    int32_t *dst = a.pos_out + int64_t(m) * a.n_used + start;
-    bool bad = false;
-    for (int i0 = r0; i0 < r1; i0 += kThreads) {
-        const int r = i0 + tid;
-        const bool on = r < r1;
-        int s = on ? src[r] : 0;
-        if (unsigned(s) >= unsigned(a.n_used)) { bad = true; s = 0; }
-        const int goes_left = (on && int(a.codes[int64_t(s) * a.d + f]) <= b) ? 1 : 0;
-        int totl;
-        const int kl = block_scan(goes_left, w, totl);
-        if (tid == 0) {
-            const int live = min(kThreads, r1 - i0);
-            bases[0] = atomicAdd(&a.curs_cur[item].x, totl);
-            bases[1] = atomicAdd(&a.curs_cur[item].y, live - totl);
-        }
-        __syncthreads();
-        if (on) {
-            const int o = goes_left ? bases[0] + kl : bases[1] + (tid - kl);
-            if (goes_left ? o < nl : o < nrt) dst[goes_left ? o : nl + o] = s;
-            else bad = true;
-        }
-        __syncthreads();
-    }
-    if (bad) flag(a.status, GAE_FOREST_ERR_NODE);
+    gae::cells::partition_chunk(a, node_of(a, m, ch.item), ch.chunk);
 }
 
 // one block per configuration: the all-rows model's table of this round to the output
@@ -574,15 +465,9 @@ __global__ __launch_bounds__(kThreads) void boost_predict_kernel(const PredictAr
     if (finite) {
         for (int r = 0; r < a.R && !broken; ++r) {
             const int64_t t0 = int64_t(r) * a.M;
-            int node = 0, steps = 0;
-            while (true) {
-                const int f = a.feature[t0 + node];
-                if (f < 0) break;
-                const int L = a.left[t0 + node];
-                if (f >= a.d || L < 1 || L + 1 >= a.M || ++steps > kMaxDepth) { broken = true; break; }
-                node = L + (x[f] <= a.threshold[t0 + node] ? 0 : 1);
-            }
-            if (!broken) acc = acc + a.value[t0 + node];
+            const int node = gae::cells::walk(a.feature + t0, a.left + t0, a.threshold + t0, x, a.d, a.M, kMaxDepth);
+            if (node < 0) broken = true;
+            else acc = acc + a.value[t0 + node];
         }
     } else {
         atomicAdd(reinterpret_cast<u64 *>(&a.status->nonfinite), u64(1));
@@ -601,13 +486,6 @@ struct Plan {
     Level *lvl[2];
     double *cfg;                                            // lr [n_cfg], lambda [n_cfg]
 };
-
-template <class T>
-void take_halves(gae::Carver &c, T *(&two)[2], int64_t half)
-{
-    two[0] = c.take<T>(2 * half);
-    two[1] = two[0] ? two[0] + half : nullptr;
-}
 
 // the checks, the sizes and THE workspace layout: on ws = NULL the regions are only counted (p.need), on the caller's buffer
 // they are bound into `a` and the halves of `p`
@@ -650,7 +528,7 @@ int plan(const char *fn, int64_t n_used, int64_t d, int64_t bins, int64_t depth,
     a.cand_score = c.take<double>(Mo * p.maxI * p.nft);
     a.cand_fb = c.take<int2>(Mo * p.maxI * p.nft);
     a.cand_nl = c.take<int32_t>(Mo * p.maxI * p.nft);
-    a.cand_gh = c.take<i64>(Mo * p.maxI * p.nft * 2);
+    a.cand_sum = c.take<i64>(Mo * p.maxI * p.nft * 2);
     a.gcnt = c.take<unsigned>(Mo * lmax * d * bins);
     a.gsum = c.take<i64>(Mo * lmax * d * bins * 2);
     a.part = c.take<double>(Mo * p.n_parts);
@@ -733,7 +611,7 @@ extern "C" int gae_boost_fit(const uint8_t *codes, const int32_t *n_edges, const
         a.items_cur = p.items[cur]; a.items_next = p.items[cur ^ 1];
         a.chunks_cur = p.chunks[cur]; a.chunks_next = p.chunks[cur ^ 1];
         a.split_cur = p.split[cur]; a.split_next = p.split[cur ^ 1];
-        a.curs_cur = p.curs[cur]; a.curs_next = p.curs[cur ^ 1];
+        a.curs = p.curs[cur]; a.curs_next = p.curs[cur ^ 1];
         a.lvl_cur = p.lvl[cur]; a.lvl_next = p.lvl[cur ^ 1];
     };
     hipStream_t st = gae::as_stream(stream);

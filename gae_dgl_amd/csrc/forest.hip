@@ -28,6 +28,8 @@
 //   emit      one block per tree: the next level's work items, chunk list and long-node slots, and the 32-byte level
 //             status the host reads once per level (it sizes the next grids and stops the loop early)
 // The node x feature x bin histogram never reaches HBM except the merged cells of nodes longer than one chunk.
+// The bodies of hist, scan and partition and the tree walk of predict are the level pass of forest_cells.h, which K30
+// (boost.hip) runs too; what is the forest's own there is its lists (node_of) and the Targets and Variance policies.
 #include <float.h>
 
 #include "common.h"
@@ -39,54 +41,45 @@ using gae::cdiv;
 using gae::up256;
 
 constexpr int kMaxD = 256, kMaxT = 8, kMaxTrees = 1024, kMaxDepth = 16, kMaxBins = 256;
-constexpr int kSplitRows = GAE_FOREST_SPLIT_ROWS;
+constexpr int kSplitRows = gae::cells::kSplitRows;
 constexpr int kThreads = gae::cells::kThreads, kWaves = gae::cells::kWaves;
 constexpr int kWalkSteps = 64;             // a walk longer than this is a broken node table, not a tree
 
-__host__ __device__ inline int chunks_of(int rows) { return (rows + kSplitRows - 1) / kSplitRows; }
+using gae::cells::block_scan;
+using gae::cells::Chunk;
+using gae::cells::chunks_of;
+using gae::cells::flag;
+using gae::cells::i64;
+using gae::cells::take_halves;
+using gae::cells::u64;
 
-typedef unsigned long long u64;
-typedef long long i64;
-
-__device__ __forceinline__ void flag(gae_forest_status *st, int64_t bits)
-{
-    atomicOr(reinterpret_cast<u64 *>(&st->errors), static_cast<u64>(bits));
-}
 __device__ __forceinline__ void count_nonfinite(gae_forest_status *st, int64_t v)
 {
     atomicAdd(reinterpret_cast<u64 *>(&st->nonfinite), static_cast<u64>(v));
 }
 
 struct Item { int tree, node, slot, pad; };                // slot >= 0: a node longer than one chunk, its global cells
-struct Chunk { int item, chunk; };
 struct TreeInfo { int item_lo, item_n, base, n_new, tot_work, tot_chunks, tot_long, pad; };
 struct Level { int64_t n_items, n_chunks, n_long, pad; };
 
-struct FitArgs {
-    const uint8_t *codes;
-    const int32_t *n_edges;
+struct FitArgs : gae::cells::Frame {                      // (the level pass's own arrays are the Frame's)
     const float *edges;
     const float *Y;
     const int32_t *rows;
     int64_t ldy;
-    int n, n_used, d, t, bins, T, n_boot, max_depth, m_feat, msl, bootstrap, M, ft, nft, level;
-    uint64_t key;
+    int n, t, T, n_boot, max_depth, bootstrap, M, level;
     float pivot[kMaxT];
     double up[kMaxT], inv[kMaxT], scale[kMaxT];            // 2^e, 2^-e, 4^-e
     // outputs
-    int32_t *feature, *bin, *left, *count, *n_nodes;
+    int32_t *n_nodes;
     float *threshold;
     double *value, *gain;
     uint8_t *inbag;
-    gae_forest_status *status;
     // workspace
-    i64 *yq, *node_sum, *cand_sl, *gsum;
-    int32_t *pos_in, *pos_out, *seg_start, *cand_nl, *split_cur, *split_next;
-    unsigned *gcnt;
+    i64 *yq, *node_sum;
+    int32_t *split_cur, *split_next;
     Item *items_cur, *items_next;
     Chunk *chunks_cur, *chunks_next;
-    int2 *curs, *cand_fb;
-    double *cand_score;
     TreeInfo *info;
     Level *lvl;
 };
@@ -180,45 +173,32 @@ __global__ __launch_bounds__(kThreads) void forest_root_kernel(const FitArgs a, 
 }
 
 // ------------------------------------------------------------------------------------------------------ a level
-using HistLds = gae::cells::Lds;
-using gae::cells::better;
-using gae::cells::block_scan;
+using gae::cells::Lds;
+using gae::cells::Node;
 
-inline size_t hist_lds_bytes(int ft, int bins, int t) { return gae::cells::lds_bytes(ft, bins, t); }
-
-__device__ __forceinline__ HistLds carve(unsigned char *lds, const FitArgs &a) { return gae::cells::carve(lds, a.ft, a.bins, a.t); }
-
-// the candidate features of node `node` of tree `tree`: all of them, or the m with the smallest (r_f, f).  Ends in a barrier
-__device__ __forceinline__ void select_features(const FitArgs &a, const HistLds &h, int tree, int node)
+// work item `item` of the level: its node as the level pass sees it
+__device__ __forceinline__ Node node_of(const FitArgs &a, int item)
 {
-    gae::cells::select_subset(h.sel, h.rkey, a.d, a.m_feat, node, (uint64_t(1) << 32) + uint64_t(tree), a.key);
+    const Item it = a.items_cur[item];
+    return Node{int64_t(it.tree) * a.M + it.node, int64_t(it.tree) * a.n_boot, item, it.slot, it.node,
+                (uint64_t(1) << 32) + uint64_t(it.tree)};
 }
 
-// the cells of features [f0, f0 + ftw) are in LDS: prefix sums over the bins, every candidate's score, the tile's best
-__device__ __forceinline__ void scan_best(const FitArgs &a, const HistLds &h, int tree, int node, int item, int tile, int f0,
-                                          int ftw)
-{
-    const int tid = threadIdx.x, bins = a.bins, t = a.t;
-    for (int p = tid; p < ftw * (t + 1); p += kThreads) {
-        const int fl = p / (t + 1), w = p % (t + 1);
-        if (w == 0) {
-            unsigned run = 0;
-            for (int b = 0; b < bins; ++b) { run += h.cnt[fl * bins + b]; h.cnt[fl * bins + b] = run; }
-        } else {
-            i64 run = 0;
-            for (int b = 0; b < bins; ++b) { run += h.sum[(fl * bins + b) * t + (w - 1)]; h.sum[(fl * bins + b) * t + (w - 1)] = run; }
-        }
-    }
-    __syncthreads();
-    const int64_t at = int64_t(tree) * a.M + node;
-    const int n = a.count[at];
-    double bs = -1.0;                      // every score is >= 0
-    int bf = 0x7fffffff, bb = 0x7fffffff;
-    for (int idx = tid; idx < ftw * bins; idx += kThreads) {
-        const int fl = idx / bins, b = idx % bins, f = f0 + fl;
-        if (b >= min(a.n_edges[f], bins - 1) || !h.sel[f]) continue;
-        const int nl = int(h.cnt[idx]), nr = n - nl;
-        if (nl < a.msl || nr < a.msl) continue;
+// a cell holds t sums: the fixed-point targets of the listed rows
+struct Targets {
+    const FitArgs &a;
+    __device__ int words() const { return a.t; }
+    __device__ i64 word(int s, int j) const { return a.yq[int64_t(s) * a.t + j]; }
+};
+
+// the score of a split of node `at`: the sum over the targets of S_l^2 / n_l + S_r^2 / n_r, each in its own scale
+struct Variance {
+    const FitArgs &a;
+    int64_t at;
+    __device__ int words() const { return a.t; }
+    __device__ double score(const Lds &h, int idx, int nl, int nr) const
+    {
+        const int t = a.t;
         double score = 0.0;
         for (int j = 0; j < t; ++j) {
             const i64 sl = h.sum[int64_t(idx) * t + j], sr = a.node_sum[at * t + j] - sl;
@@ -226,87 +206,31 @@ __device__ __forceinline__ void scan_best(const FitArgs &a, const HistLds &h, in
             const double term = (dl * dl / double(nl) + dr * dr / double(nr)) * a.scale[j];
             score = score + term;
         }
-        if (better(score, f, b, bs, bf, bb)) { bs = score; bf = f; bb = b; }
+        return score;
     }
-    h.rs[tid] = bs; h.rf[tid] = bf; h.rb[tid] = bb;
-    __syncthreads();
-    for (int off = kThreads / 2; off > 0; off >>= 1) {
-        if (tid < off && better(h.rs[tid + off], h.rf[tid + off], h.rb[tid + off], h.rs[tid], h.rf[tid], h.rb[tid])) {
-            h.rs[tid] = h.rs[tid + off]; h.rf[tid] = h.rf[tid + off]; h.rb[tid] = h.rb[tid + off];
-        }
-        __syncthreads();
-    }
-    const int64_t c = int64_t(item) * a.nft + tile;
-    const bool found = h.rs[0] >= 0.0;
-    if (tid == 0) {
-        a.cand_score[c] = h.rs[0];
-        a.cand_fb[c] = found ? make_int2(h.rf[0], h.rb[0]) : make_int2(-1, -1);
-        a.cand_nl[c] = found ? int(h.cnt[(h.rf[0] - f0) * bins + h.rb[0]]) : 0;
-    }
-    if (tid < t) a.cand_sl[c * t + tid] = found ? h.sum[int64_t((h.rf[0] - f0) * bins + h.rb[0]) * t + tid] : 0;
-}
+};
 
 // grid n_chunks . nft: block b is tile b % nft of chunk b / nft
 __global__ __launch_bounds__(kThreads) void forest_hist_kernel(const FitArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const HistLds h = carve(lds, a);
-    const int tid = threadIdx.x, tile = blockIdx.x % a.nft, bins = a.bins, t = a.t;
+    const Lds h = gae::cells::carve(lds, a.ft, a.bins, a.t);
+    const int tile = blockIdx.x % a.nft;
     const Chunk ch = a.chunks_cur[blockIdx.x / a.nft];
-    const Item it = a.items_cur[ch.item];
-    const int64_t at = int64_t(it.tree) * a.M + it.node;
-    const int f0 = tile * a.ft, ftw = min(a.ft, a.d - f0);
-    const int start = a.seg_start[at], n = a.count[at];
-    const int r0 = ch.chunk * kSplitRows, nr = min(n - r0, kSplitRows);
-    const int cells = ftw * bins;
-    for (int c = tid; c < cells; c += kThreads) h.cnt[c] = 0u;
-    for (int c = tid; c < cells * t; c += kThreads) h.sum[c] = 0;
-    select_features(a, h, it.tree, it.node);               // (its barrier also covers the zeroing)
-    const int32_t *pos = a.pos_in + int64_t(it.tree) * a.n_boot + start + r0;
-    bool bad = false;
-    for (int idx = tid; idx < nr * ftw; idx += kThreads) {      // <= 8192 . 256
-        const int r = idx / ftw, fl = idx % ftw;
-        if (!h.sel[f0 + fl]) continue;
-        const int s = pos[r];
-        if (unsigned(s) >= unsigned(a.n_used)) { bad = true; continue; }       // (cannot happen: the lists hold listed rows)
-        const int code = a.codes[int64_t(s) * a.d + f0 + fl];
-        if (code >= bins) { bad = true; continue; }
-        const int cell = fl * bins + code;
-        atomicAdd(&h.cnt[cell], 1u);
-        for (int j = 0; j < t; ++j)
-            atomicAdd(reinterpret_cast<u64 *>(&h.sum[cell * t + j]), static_cast<u64>(a.yq[int64_t(s) * t + j]));
-    }
-    if (bad) flag(a.status, GAE_FOREST_ERR_CODE);
-    __syncthreads();
-    if (it.slot >= 0) {                                    // a node of several chunks: merge the cells, scan later
-        const int64_t g0 = (int64_t(it.slot) * a.d + f0) * bins;
-        for (int c = tid; c < cells; c += kThreads) {
-            const unsigned v = h.cnt[c];
-            if (!v) continue;
-            atomicAdd(&a.gcnt[g0 + c], v);
-            for (int j = 0; j < t; ++j)
-                atomicAdd(reinterpret_cast<u64 *>(&a.gsum[(g0 + c) * t + j]), static_cast<u64>(h.sum[c * t + j]));
-        }
-        return;
-    }
-    scan_best(a, h, it.tree, it.node, ch.item, tile, f0, ftw);
+    const Node nd = node_of(a, ch.item);
+    if (gae::cells::fill_tile(a, h, Targets{a}, nd, ch, tile)) return;     // a node of several chunks: scanned later
+    gae::cells::scan_tile(a, h, Variance{a, nd.at}, nd, tile);
 }
 
-// grid n_long . nft
+// grid n_long . nft (the slots are cleared by the host before every level)
 __global__ __launch_bounds__(kThreads) void forest_scan_kernel(const FitArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const HistLds h = carve(lds, a);
-    const int tid = threadIdx.x, tile = blockIdx.x % a.nft, bins = a.bins, t = a.t;
-    const int slot = blockIdx.x / a.nft, item = a.split_cur[slot];
-    const Item it = a.items_cur[item];
-    const int f0 = tile * a.ft, ftw = min(a.ft, a.d - f0);
-    const int cells = ftw * bins;
-    const int64_t g0 = (int64_t(slot) * a.d + f0) * bins;
-    for (int c = tid; c < cells; c += kThreads) h.cnt[c] = a.gcnt[g0 + c];
-    for (int c = tid; c < cells * t; c += kThreads) h.sum[c] = a.gsum[g0 * t + c];
-    select_features(a, h, it.tree, it.node);
-    scan_best(a, h, it.tree, it.node, item, tile, f0, ftw);
+    const Lds h = gae::cells::carve(lds, a.ft, a.bins, a.t);
+    const int tile = blockIdx.x % a.nft, slot = blockIdx.x / a.nft;
+    const Node nd = node_of(a, a.split_cur[slot]);
+    gae::cells::load_slot<false>(a, h, a.t, nd, slot, tile);
+    gae::cells::scan_tile(a, h, Variance{a, nd.at}, nd, tile);
 }
 
 // one block per tree
@@ -355,7 +279,7 @@ __global__ __launch_bounds__(kThreads) void forest_decide_kernel(const FitArgs a
                 a.count[lt] = nl; a.count[rt] = n - nl;
                 a.seg_start[lt] = start; a.seg_start[rt] = start + nl;
                 for (int j = 0; j < t; ++j) {
-                    const i64 sl = a.cand_sl[cbest * t + j];
+                    const i64 sl = a.cand_sum[cbest * t + j];
                     a.node_sum[lt * t + j] = sl;
                     a.node_sum[rt * t + j] = a.node_sum[at * t + j] - sl;
                 }
@@ -387,42 +311,8 @@ __global__ __launch_bounds__(kThreads) void forest_decide_kernel(const FitArgs a
 // grid n_chunks
 __global__ __launch_bounds__(kThreads) void forest_partition_kernel(const FitArgs a)
 {
-    __shared__ int w[kWaves];
-    __shared__ int bases[2];
-    const int tid = threadIdx.x;
     const Chunk ch = a.chunks_cur[blockIdx.x];
-    const Item it = a.items_cur[ch.item];
-    const int64_t at = int64_t(it.tree) * a.M + it.node;
-    const int f = a.feature[at];
-    if (f < 0) return;                                     // a leaf: its segment is never read again
-    const int b = a.bin[at], n = a.count[at], start = a.seg_start[at];
-    const int nl = a.count[int64_t(it.tree) * a.M + a.left[at]], nrt = n - nl;
-    const int r0 = ch.chunk * kSplitRows, r1 = min(n, r0 + kSplitRows);
-    const int32_t *src = a.pos_in + int64_t(it.tree) * a.n_boot + start;
-    int32_t *dst = a.pos_out + int64_t(it.tree) * a.n_boot + start;
-    bool bad = false;
-    for (int i0 = r0; i0 < r1; i0 += kThreads) {
-        const int r = i0 + tid;
-        const bool on = r < r1;
-        int s = on ? src[r] : 0;
-        if (unsigned(s) >= unsigned(a.n_used)) { bad = true; s = 0; }
-        const int goes_left = (on && a.codes[int64_t(s) * a.d + f] <= b) ? 1 : 0;
-        int totl;
-        const int kl = block_scan(goes_left, w, totl);
-        if (tid == 0) {
-            const int live = min(kThreads, r1 - i0);
-            bases[0] = atomicAdd(&a.curs[ch.item].x, totl);
-            bases[1] = atomicAdd(&a.curs[ch.item].y, live - totl);
-        }
-        __syncthreads();
-        if (on) {
-            const int o = goes_left ? bases[0] + kl : bases[1] + (tid - kl);
-            if (goes_left ? o < nl : o < nrt) dst[goes_left ? o : nl + o] = s;
-            else bad = true;
-        }
-        __syncthreads();
-    }
-    if (bad) flag(a.status, GAE_FOREST_ERR_NODE);
+    gae::cells::partition_chunk(a, node_of(a, ch.item), ch.chunk);
 }
 
 // one block per tree
@@ -550,16 +440,8 @@ __global__ __launch_bounds__(kThreads) void forest_predict_kernel(const PredictA
         for (int tree = 0; tree < a.T; ++tree) {
             if (a.skip && a.skip[int64_t(tree) * a.m + row]) continue;
             const int64_t t0 = int64_t(tree) * a.M;
-            int node = 0, steps = 0;
-            bool ok = true;
-            while (true) {
-                const int f = a.feature[t0 + node];
-                if (f < 0) break;
-                const int L = a.left[t0 + node];
-                if (f >= a.d || L < 1 || L + 1 >= a.M || ++steps > kWalkSteps) { ok = false; break; }
-                node = L + (x[f] <= a.threshold[t0 + node] ? 0 : 1);
-            }
-            if (!ok) { broken = true; continue; }
+            const int node = gae::cells::walk(a.feature + t0, a.left + t0, a.threshold + t0, x, a.d, a.M, kWalkSteps);
+            if (node < 0) { broken = true; continue; }
 #pragma unroll
             for (int j = 0; j < kMaxT; ++j)
                 if (j < a.t) acc[j] += a.value[(t0 + node) * a.t + j];
@@ -581,13 +463,6 @@ struct Plan {
     Item *items[2];
     Chunk *chunks[2];
 };
-
-template <class T>
-void take_halves(gae::Carver &c, T *(&two)[2], int64_t half)
-{
-    two[0] = c.take<T>(2 * half);
-    two[1] = two[0] ? two[0] + half : nullptr;
-}
 
 int64_t node_capacity(int64_t n_boot, int64_t max_depth)
 {
@@ -631,7 +506,7 @@ int plan(const char *fn, int64_t n_used, int64_t d, int64_t t, int64_t T, int64_
     a.cand_score = c.take<double>(p.max_items * p.nft);
     a.cand_fb = c.take<int2>(p.max_items * p.nft);
     a.cand_nl = c.take<int32_t>(p.max_items * p.nft);
-    a.cand_sl = c.take<i64>(p.max_items * p.nft * t);
+    a.cand_sum = c.take<i64>(p.max_items * p.nft * t);
     a.gcnt = c.take<unsigned>(p.max_long * d * bins);
     a.gsum = c.take<i64>(p.max_long * d * bins * t);
     a.info = c.take<TreeInfo>(T);
@@ -757,7 +632,7 @@ extern "C" int gae_forest_fit(const uint8_t *codes, const int32_t *n_edges, cons
         lv.n_chunks = n_trees * cdiv(n_boot, kSplitRows);
         lv.n_long = n_boot > kSplitRows ? n_trees : 0;
     }
-    const size_t lds = hist_lds_bytes(int(p.ft), int(max_bins), int(t));
+    const size_t lds = gae::cells::lds_bytes(int(p.ft), int(max_bins), int(t));
     int cur = 0;
     for (int level = 0; level < max_depth && lv.n_items > 0; ++level) {
         GAE_REQUIRE(lv.n_items <= p.max_items && lv.n_chunks <= p.max_chunks && lv.n_long <= p.max_long && lv.n_chunks >= lv.n_items,

@@ -97,6 +97,9 @@ def _case(name):
     if name == "root_across_blocks":                                   # the all-rows model's root: two chunks
         X, y = _regression(B.SPLIT_ROWS + 5, 3, 2)
         return X, y, "squared", 3, dict(max_depth=2, folds=2, max_bins=16)
+    if name == "long_children_tiles":                                  # long nodes below the root, their slots in two tiles
+        X, y = _regression(3 * B.SPLIT_ROWS + 7, 13, 12)
+        return X, y, "squared", 2, dict(max_depth=3, folds=2, max_bins=256)
     if name == "depth8":
         X, y = _regression(200, 4, 3)
         return X, y, "squared", 3, dict(max_depth=8, folds=2, learning_rates=(0.5,), lambdas=(0.0,))
@@ -132,7 +135,7 @@ def _case(name):
     raise KeyError(name)
 
 
-CASES = ["small", "two_tiles", "root_across_blocks", "depth8", "min_samples_leaf", "max_features", "duplicated_rows", "two_bins",
+CASES = ["small", "two_tiles", "root_across_blocks", "long_children_tiles", "depth8", "min_samples_leaf", "max_features", "duplicated_rows", "two_bins",
          "grid", "fold_minus_one", "logistic_small", "logistic_separable"]
 
 
@@ -149,6 +152,8 @@ def test_bit_for_bit_against_the_reference(name):
         assert int(ref.count[0, :k][ref.feature[0, :k] < 0].min()) == 1 and k > 2 ** 5
     if name == "root_across_blocks":
         assert int(ref.count[0, 0]) == B.SPLIT_ROWS + 5
+    if name == "long_children_tiles":                                  # the all-rows model's first tree
+        assert int(ref.count[0, 1]) > B.SPLIT_ROWS and int(ref.count[0, 2]) > B.SPLIT_ROWS and X.shape[1] > 12
 
 
 @pytest.fixture(scope="module")

@@ -4,7 +4,9 @@ script) against the numpy restatement tests/forest_ref.py: every tree node for n
 Shapes are the smallest that reach each path: one feature tile and several (d = 37 with t = 3 is two tiles, bins = 256
 with t = 8 is three), feature subsets, min_samples_leaf, a bootstrap smaller than the set, no bootstrap, a root just
 longer than FOREST_SPLIT_ROWS (cut across blocks, its cells merged by integer atomics), depth 16 on 200 rows (segments
-of one sample, the 2 n_boot - 1 capacity), duplicate rows, lossless columns beside continuous ones.
+of one sample, the 2 n_boot - 1 capacity), duplicate rows, lossless columns beside continuous ones, a root of four chunks
+whose children are longer than a chunk too, over two feature tiles (slots handed out below the root, slot cells of a
+second tile).
 
 Targets are multiples of 2^-10 below 2^13, so their fp64 sum is exact in any order and the pivot (the fp64 mean rounded
 to fp32) is the same number on the device and in numpy."""
@@ -67,12 +69,18 @@ CASES = {
     "no_bootstrap": (dict(n=400, d=6, t=2, seed=6), dict(n_trees=2, max_depth=6, max_bins=32, bootstrap=False, seed=16)),
     "bins256":      (dict(n=700, d=7, t=8, seed=7), dict(n_trees=2, max_depth=5, max_bins=256, seed=17)),
     "long_root":    (dict(n=S + 5, d=3, t=1, seed=8), dict(n_trees=2, max_depth=3, max_bins=16, seed=18)),
+    "long_children_tiles": (dict(n=3 * S + 7, d=4, t=8, seed=12), dict(n_trees=2, max_depth=3, max_bins=256, seed=24)),
     "long_plain":   (dict(n=S + 1, d=3, t=2, seed=9), dict(n_trees=1, max_depth=2, max_bins=16, bootstrap=False, seed=19)),
     "depth16":      (dict(n=200, d=4, t=1, seed=10), dict(n_trees=2, max_depth=16, max_bins=64, seed=20)),
     "duplicates":   (dict(n=400, d=5, t=1, seed=11, kind="duplicates"), dict(n_trees=3, max_depth=10, max_bins=64, seed=21)),
     "one_tree":     (dict(n=300, d=5, t=1, seed=1), dict(n_trees=1, max_depth=5, max_bins=16, seed=22)),
     "bins2":        (dict(n=300, d=5, t=1, seed=1), dict(n_trees=2, max_depth=3, max_bins=2, seed=23)),
 }
+
+
+def tile_features(d, bins, words):
+    """features per LDS tile: 64 KiB of cells, a u32 count and `words` int64 sums each (csrc/forest_cells.h)"""
+    return max(1, min(d, 65536 // (bins * (4 + 8 * words))))
 
 
 def key_of(name):
@@ -139,6 +147,10 @@ def test_forest_equals_the_reference_node_for_node(dev, name):
         assert as_np(res.count)[leaves].min() == 1 and int(res.n_nodes.max()) > 150
     if name in ("long_root", "long_plain"):
         assert int(res.count[0, 0]) > S                                # the root was cut across blocks
+    if name == "long_children_tiles":                                  # long nodes at level 1, their slots in two tiles
+        count, kids = np.asarray(ref.count), np.asarray(ref.left)[:, 0]
+        assert (count[:, 0] > S).all() and (count[range(T), kids] > S).all() and (count[range(T), kids + 1] > S).all()
+        assert tile_features(4, 256, 8) < 4
     if name == "one_tree":                                             # T = 1: the rows the tree drew have no out-of-bag tree
         oob = as_np(res.oob_prediction)[:, 0]
         drawn = np.zeros(300, bool)
