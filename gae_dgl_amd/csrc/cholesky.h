@@ -1,8 +1,6 @@
-// fp64 pieces shared by the heads that solve small symmetric systems from fp64 moments (K25 ridge.hip, K28 logreg.hip):
-// the packed-triangle index maps, the fp64 form of common.h's sum_partials and the Cholesky-Crout factorisation in LDS.
+// fp64 pieces shared by the heads that solve small symmetric systems from fp64 moments (K25 ridge.hip, K28 logreg.hip,
+// K32 spectral.hip): the packed-triangle index maps and the Cholesky-Crout factorisation in LDS.
 #pragma once
-#include <float.h>
-
 #include "common.h"
 
 namespace gae {
@@ -10,28 +8,6 @@ namespace gae {
 __host__ __device__ inline int64_t tri(int64_t w) { return w * (w + 1) / 2; }
 // entry (i, j), i <= j, of a packed upper triangle of order W (rows one after another)
 __device__ __forceinline__ int64_t upper_at(int i, int j, int W) { return int64_t(i) * W - int64_t(i) * (i - 1) / 2 + (j - i); }
-
-// the fp64 form of common.h's sum_partials: the same lists, the same order; the partials are fp64 or fp32 (widened)
-template <class T>
-__device__ __forceinline__ double sum_partials_f64(const T *__restrict__ p0, int64_t n_partials, int64_t stride, int lane, int L)
-{
-    double g = 0.0;
-    for (int64_t q0 = lane; q0 < n_partials; q0 += int64_t(16) * L) {
-        double v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int64_t q = q0 + int64_t(u) * L;
-            v[u] = p0[(q < n_partials ? q : n_partials - 1) * stride];
-        }
-#pragma unroll
-        for (int u = 0; u < 16; ++u) g += q0 + int64_t(u) * L < n_partials ? v[u] : 0.0;
-    }
-    if (L == 64) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) g += __shfl_down(g, off, 64);
-    }
-    return g;
-}
 
 // Cholesky-Crout of rows 0 .. d - 1 of a matrix held row by row in LDS (row i at Lm + row_at(i), entries 0 .. min(i, d - 1)),
 // column by column; thread r of the block owns row j + r, so the block holds at least D threads.  Rows d .. D - 1 are

@@ -4,7 +4,10 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <float.h>
+
 #include <atomic>
+#include <type_traits>
 
 #include "gae_hip.h"
 #include "gae_hip_experimental.h"
@@ -139,6 +142,22 @@ typedef short v4s __attribute__((ext_vector_type(4)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
 
+// one v_mfma_f32_16x16x4_f32: lane l feeds A[l & 15][l >> 4] and B[l >> 4][l & 15]; D: column l & 15, rows 4 (l >> 4) + reg
+__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+__device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= FLT_MAX; }
+__device__ __forceinline__ bool finite64(double v) { return fabs(v) <= DBL_MAX; }
+
+// the int64 words of a status block: error flags are or-ed in, counts added (integer atomics, exact in any order)
+__device__ __forceinline__ void or_bits(int64_t *p, int64_t bits)
+{
+    atomicOr(reinterpret_cast<unsigned long long *>(p), static_cast<unsigned long long>(bits));
+}
+__device__ __forceinline__ void add_count(int64_t *p, int64_t n)
+{
+    atomicAdd(reinterpret_cast<unsigned long long *>(p), static_cast<unsigned long long>(n));
+}
+
 // split 4 fp32 values into bf16 hi and bf16 lo = bf16(v - hi): v_cvt_pk_bf16_f32 x 4, ~5 VALU ops per pair
 __device__ __forceinline__ void split_bf16x4(const v4f &v, v4s &hi, v4s &lo)
 {
@@ -194,19 +213,21 @@ __device__ __forceinline__ void split_bf16x4_3(const v4f &v, v4s &hi, v4s &mid, 
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ int partial_lanes(int64_t n_partials) { return n_partials > 32 ? 64 : 1; }
 
-__device__ __forceinline__ float sum_partials(const float *__restrict__ p0, int64_t n_partials, int64_t stride, int lane,
-                                              int L)
+// Acc: the type the partials are added in (default: their own); sum_partials<double>(const float *, ...) widens first
+template <class Acc = void, class T>
+__device__ __forceinline__ auto sum_partials(const T *__restrict__ p0, int64_t n_partials, int64_t stride, int lane, int L)
 {
-    float g = 0.f;
+    using A = std::conditional_t<std::is_void_v<Acc>, T, Acc>;
+    A g = A(0);
     for (int64_t q0 = lane; q0 < n_partials; q0 += int64_t(16) * L) {
-        float v[16];
+        A v[16];
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
             const int64_t q = q0 + int64_t(u) * L;
             v[u] = p0[(q < n_partials ? q : n_partials - 1) * stride];        // clamped: loads stay branch-free
         }
 #pragma unroll
-        for (int u = 0; u < 16; ++u) g += q0 + int64_t(u) * L < n_partials ? v[u] : 0.f;
+        for (int u = 0; u < 16; ++u) g += q0 + int64_t(u) * L < n_partials ? v[u] : A(0);
     }
     if (L == 64) {
 #pragma unroll

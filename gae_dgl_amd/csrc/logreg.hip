@@ -9,8 +9,8 @@
 // Launches (ordinary ones, no float atomics):
 //   factor  one block per model: A = S / 2 + lambda diag(0, 1 .. 1) from gae_ridge_stats' moments (the training folds,
 //           ascending), ridge's Cholesky-Crout in LDS (cholesky.h), the factor and the zeroed iteration state.
-//   pass    grid (slabs, model tiles): a slab is kSlabChunks consecutive chunks of kChunk listed rows (a chunk never
-//           straddles folds), a tile kTile consecutive models of the launch.  Per chunk the block stages x~ in LDS once;
+//   pass    grid (slabs, model tiles): a slab is kSlabChunks consecutive chunks of kChunk listed rows (fold_lists.h's chunk
+//           order: a chunk never straddles folds), a tile kTile consecutive models of the launch.  Per chunk the block stages x~ in LDS once;
 //           per model of the tile that uses the chunk: logits x~ V^T on v_mfma_f32_16x16x4_f32 (wave w owns row tile w,
 //           one k-ascending chain per element) -> LDS; one thread per row: max, subtract, exp, ascending sum, one
 //           reciprocal, minus the one-hot label -> LDS; gradient R^T x~ on the same instruction, its [CT][NT] output tiles
@@ -24,14 +24,16 @@
 // LDS (d = 128, c = 32: pitch 148, CP 32): pass 64 . 148 . 4 (x~) + 4 . 32 . 148 . 4 (V of the tile) + 64 . 33 . 4 (logits)
 // + pivot, row ids, labels, flags, 64 fp64 = 121 KB, one block per CU; d = 48, c = 2: 40 KB, three (registers).  factor
 // 67 KB, update 138 KB (the factor, two [c][D1] fp64 tables, the reduction scratch).
-#include <float.h>
-
 #include "common.h"
 #include "cholesky.h"
+#include "fold_lists.h"
 
 namespace {
 
+using gae::add_count;
 using gae::cdiv;
+using gae::mfma4;
+using gae::or_bits;
 using gae::tri;
 using gae::upper_at;
 using gae::v4f;
@@ -42,16 +44,6 @@ constexpr int kSlabChunks = GAE_LOGREG_SLAB_CHUNKS;
 constexpr int kTile = 4;                   // models per block of the pass
 constexpr int kThreads = 256, kWaves = kThreads / gae::kWave;
 static_assert(kChunk == 16 * kWaves, "the logits of a chunk: one row tile per wave");
-
-__device__ __forceinline__ void flag(gae_logreg_status *st, int64_t bits)
-{
-    atomicOr(reinterpret_cast<unsigned long long *>(&st->errors), static_cast<unsigned long long>(bits));
-}
-__device__ __forceinline__ void bump(int64_t *p, long long v)
-{
-    atomicAdd(reinterpret_cast<unsigned long long *>(p), static_cast<unsigned long long>(v));
-}
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // ------------------------------------------------------------------------------------------------------ shapes, state
 struct Shape {
@@ -160,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void logreg_factor_kernel(const FactorArg
     int info = 0;
     if (!(lam >= 0.0 && lam <= DBL_MAX)) {
         info = -2;
-        if (tid == 0 && m == 0) flag(a.status, GAE_LOGREG_ERR_LAMBDA);
+        if (tid == 0 && m == 0) or_bits(&a.status->errors, GAE_LOGREG_ERR_LAMBDA);
     } else if (!(S_at(0, 0) > 0.0)) {
         info = -1;
     }
@@ -198,7 +190,7 @@ __global__ __launch_bounds__(kThreads) void logreg_factor_kernel(const FactorArg
         a.info[g] = info;
         a.n_iter[g] = 0;
         a.converged[g] = 0;
-        if (info == 0) bump(&a.status->active_models, 1);
+        if (info == 0) add_count(&a.status->active_models, 1);
     }
 }
 
@@ -207,48 +199,31 @@ struct PassArgs {
     const float *X;
     int64_t ldx;
     const int32_t *y;
-    int n, d, c, F, L, n_rows;
+    int n, d, c, L;
     const float *pivot;                    // [d] or NULL
-    const int32_t *rows, *fold_ptr;
+    gae::FoldList list;                    // the listed rows (fold_lists.h)
     int model_lo, model_count, eval;
     Layout lay;
     gae_logreg_status *status;
 };
 
-// 0 <= fold_ptr[0] <= ... <= fold_ptr[F] == n_rows
-__device__ __forceinline__ bool folds_valid(const int32_t *fold_ptr, int F, int n_rows)
-{
-    int prev = fold_ptr[0];
-    bool ok = prev >= 0;
-    for (int f = 1; f <= F; ++f) {
-        const int v = fold_ptr[f];
-        ok = ok && v >= prev;
-        prev = v;
-    }
-    return ok && prev == n_rows;
-}
-
 // rows lo .. lo + nrows - 1 of a list (rows == NULL: the ids themselves) as x~ = [1, x - p, 0 ...] in Xa[kChunk][pitch], zero
 // rows past nrows and for ids outside [0, n); rid[] the ids (-1: no row); bad[] != 0: the row holds a non-finite value.
 // rid and bad are in place after the caller's next barrier; bad[] is zeroed before the previous one.
 __device__ __forceinline__ bool stage_rows(const Shape &s, const float *__restrict__ X, int64_t ldx, int n,
-                                           const int32_t *__restrict__ rows, int64_t lo, int nrows, const float *pv, float *Xa,
+                                           const gae::FoldList &list, int64_t lo, int nrows, const float *pv, float *Xa,
                                            int *rid, int *bad, int tid)
 {
     bool bad_id = false;
     for (int e = tid; e < kChunk * s.WP; e += kThreads) {
         const int r = e / s.WP, col = e - r * s.WP;
-        int id = -1;
-        if (r < nrows) {
-            id = rows ? rows[lo + r] : int(lo + r);
-            if (unsigned(id) >= unsigned(n)) { bad_id = true; id = -1; }
-        }
+        const int id = r < nrows ? gae::row_id(list, lo + r, n, bad_id) : -1;
         float v = 0.f;
         if (id >= 0) {
             if (col == 0) v = 1.f;
             else if (col <= s.d) {
                 const float x = X[int64_t(id) * ldx + (col - 1)];
-                if (!(fabsf(x) <= FLT_MAX)) atomicOr(&bad[r], 1);
+                if (!gae::finite32(x)) atomicOr(&bad[r], 1);
                 v = x - pv[col];                                       // one rounded subtraction
             }
         }
@@ -320,8 +295,8 @@ __global__ __launch_bounds__(kThreads) void logreg_pass_kernel(const PassArgs a)
         any = any || on[mi];
     }
     if (!any) return;                                                  // frozen models: the block exits at once
-    if (!folds_valid(a.fold_ptr, a.F, a.n_rows)) {
-        if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) flag(a.status, GAE_LOGREG_ERR_FOLD_PTR);
+    if (!gae::folds_valid(a.list)) {
+        if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) or_bits(&a.status->errors, GAE_LOGREG_ERR_FOLD_PTR);
         return;
     }
 #pragma unroll
@@ -347,34 +322,20 @@ __global__ __launch_bounds__(kThreads) void logreg_pass_kernel(const PassArgs a)
     bool bad_id = false, bad_label = false;
 
     for (int q = 0; q < kSlabChunks; ++q) {
-        // ---- chunk slab . kSlabChunks + q: folds in ascending order, chunks inside a fold in ascending order
-        int fold = -1, lo = 0, hi = 0;
-        {
-            int64_t b = int64_t(slab) * kSlabChunks + q;
-            for (int f = 0; f < a.F; ++f) {
-                const int flo = a.fold_ptr[f], fhi = a.fold_ptr[f + 1];
-                const int64_t nc = (int64_t(fhi) - flo + kChunk - 1) / kChunk;
-                if (b < nc) {
-                    fold = f;
-                    lo = int(flo + b * kChunk);
-                    hi = fhi - lo > kChunk ? lo + kChunk : fhi;
-                    break;
-                }
-                b -= nc;
-            }
-        }
-        if (fold < 0) break;                                           // past the last chunk
+        const gae::Chunk ch = gae::chunk_of(a.list, int64_t(slab) * kSlabChunks + q, kChunk);
+        if (ch.fold < 0) break;                                        // past the last chunk
+        const int fold = ch.fold, lo = ch.lo, hi = ch.hi;
         bool use[kTile];
         bool used = false;
 #pragma unroll
         for (int mi = 0; mi < kTile; ++mi) {                           // a chunk of fold f is not part of model f's training set:
-            use[mi] = on[mi] && (a.eval ? (mm[mi] == fold || mm[mi] == a.F) : mm[mi] != fold);     // skipped, not masked
+            use[mi] = on[mi] && (a.eval ? (mm[mi] == fold || mm[mi] == a.list.F) : mm[mi] != fold);     // skipped, not masked
             used = used || use[mi];
         }
         if (!used) continue;
         const int nrows = hi - lo;
         __syncthreads();                                               // the previous chunk is consumed; pv, Vs, bad are in place
-        bad_id = stage_rows(s, a.X, a.ldx, a.n, a.rows, lo, nrows, pv, Xa, rid, bad, tid) || bad_id;
+        bad_id = stage_rows(s, a.X, a.ldx, a.n, a.list, lo, nrows, pv, Xa, rid, bad, tid) || bad_id;
         __syncthreads();
         if (tid < kChunk) {
             int yy = -1;
@@ -432,8 +393,8 @@ __global__ __launch_bounds__(kThreads) void logreg_pass_kernel(const PassArgs a)
             __syncthreads();                                           // Zs is free for the next model
         }
     }
-    if (bad_id) flag(a.status, GAE_LOGREG_ERR_ROW_ID);
-    if (bad_label) flag(a.status, GAE_LOGREG_ERR_LABEL);
+    if (bad_id) or_bits(&a.status->errors, GAE_LOGREG_ERR_ROW_ID);
+    if (bad_label) or_bits(&a.status->errors, GAE_LOGREG_ERR_LABEL);
 
 #pragma unroll
     for (int mi = 0; mi < kTile; ++mi) {
@@ -476,7 +437,7 @@ __global__ __launch_bounds__(64) void logreg_eval_reduce_kernel(const EvalArgs a
     }
     const int L = gae::partial_lanes(a.slabs);
     if (L == 1 && lane > 0) return;
-    const double v = gae::sum_partials_f64(a.lay.enll + local, a.slabs, a.model_count, lane, L);
+    const double v = gae::sum_partials<double>(a.lay.enll + local, a.slabs, a.model_count, lane, L);
     long long h = 0;
     for (int64_t q = lane; q < a.slabs; q += L) h += a.lay.ecorrect[q * a.model_count + local];
     if (L == 64) {
@@ -540,10 +501,10 @@ __global__ __launch_bounds__(kThreads) void logreg_update_kernel(const UpdateArg
     const float *p0 = a.lay.part + int64_t(local) * cD;
     const int64_t stride = int64_t(a.model_count) * cD;
     if (gae::partial_lanes(a.slabs) == 1) {
-        for (int e = tid; e < cD; e += kThreads) G[e] = gae::sum_partials_f64(p0 + e, a.slabs, stride, 0, 1);
+        for (int e = tid; e < cD; e += kThreads) G[e] = gae::sum_partials<double>(p0 + e, a.slabs, stride, 0, 1);
     } else {
         for (int e = wave; e < cD; e += kWaves) {                      // all 64 lanes of the wave call
-            const double v = gae::sum_partials_f64(p0 + e, a.slabs, stride, lane, 64);
+            const double v = gae::sum_partials<double>(p0 + e, a.slabs, stride, lane, 64);
             if (lane == 0) G[e] = v;
         }
     }
@@ -605,8 +566,8 @@ __global__ __launch_bounds__(kThreads) void logreg_update_kernel(const UpdateArg
             a.n_iter[g] = a.iteration;
             a.lay.active[g] = 0;
             a.lay.ok[g] = 0;
-            flag(a.status, GAE_LOGREG_ERR_NONFINITE);
-            bump(&a.status->active_models, -1);
+            or_bits(&a.status->errors, GAE_LOGREG_ERR_NONFINITE);
+            add_count(&a.status->active_models, -1);
         }
         return;
     }
@@ -640,7 +601,7 @@ __global__ __launch_bounds__(kThreads) void logreg_update_kernel(const UpdateArg
         if (stop) {
             a.converged[g] = done;
             a.lay.active[g] = 0;
-            bump(&a.status->active_models, -1);
+            add_count(&a.status->active_models, -1);
         }
     }
 }
@@ -687,7 +648,7 @@ __global__ __launch_bounds__(kThreads) void logreg_predict_kernel(const PredictA
         Vs[e] = v;
     }
     __syncthreads();
-    stage_rows(s, a.X, a.ldx, a.n, nullptr, lo, nrows, pv, Xa, rid, bad, tid);
+    stage_rows(s, a.X, a.ldx, a.n, gae::FoldList{}, lo, nrows, pv, Xa, rid, bad, tid);
     __syncthreads();
     logits_to_lds(s, Xa, Vs, Zs, wave, lane);
     __syncthreads();
@@ -698,7 +659,7 @@ __global__ __launch_bounds__(kThreads) void logreg_predict_kernel(const PredictA
             a.labels[row] = -1;
             if (a.proba)
                 for (int k = 0; k < s.c; ++k) a.proba[row * a.ldp + k] = __builtin_nanf("");
-            bump(&a.status->nonfinite_rows, 1);
+            add_count(&a.status->nonfinite_rows, 1);
         } else {
             float mx = z[0];
             int arg = 0;
@@ -789,8 +750,9 @@ extern "C" int gae_logreg_pass(const float *X, int64_t ldx, const int32_t *y, in
     gae::Carver cv(workspace);
     PassArgs a;
     a.X = X; a.ldx = ldx; a.y = y;
-    a.n = int(n); a.d = int(d); a.c = int(c); a.F = int(folds); a.L = int(n_lambdas); a.n_rows = int(n_rows);
-    a.pivot = pivot; a.rows = rows; a.fold_ptr = fold_ptr;
+    a.n = int(n); a.d = int(d); a.c = int(c); a.L = int(n_lambdas);
+    a.pivot = pivot;
+    a.list = gae::FoldList{rows, fold_ptr, int(folds), int(n_rows)};
     a.model_lo = int(model_lo); a.model_count = int(model_count); a.eval = eval ? 1 : 0;
     a.lay = carve(cv, p, s);
     a.status = status;

@@ -25,13 +25,14 @@
 // LDS: sum over the layers of outP (inP + 4) + outP weights and biases, 32 (inP + 4) activations and 32 (outP + 4) errors,
 // plus 2 . 136 scaling values, 2 . 256 targets, 256 row ids and 16 words: 130 KB at 128 -> 128 -> 8, 38 KB at 48 -> 100 -> 1.
 // A shape whose sum passes 160 KB (two hidden layers of 128 behind 128 features) is refused by the workspace query.
-#include <float.h>
-
 #include "common.h"
 
 namespace {
 
 using gae::cdiv;
+using gae::finite32;
+using gae::mfma4;
+using gae::or_bits;
 using gae::v4f;
 
 constexpr int kThreads = 256, kWaves = kThreads / gae::kWave;
@@ -91,15 +92,6 @@ __host__ __device__ inline Shape make_shape(int d, int h1, int h2, int t)
     s.lds_floats = o;
     return s;
 }
-
-__device__ __forceinline__ void flag(gae_mlp_status *st, int64_t bits)
-{
-    atomicOr(reinterpret_cast<unsigned long long *>(&st->errors), static_cast<unsigned long long>(bits));
-}
-
-__device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= FLT_MAX; }
-
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // The wave's tiles of a 32-row product sum_k A(m, k) B(k, n): row tiles 0 and 1 of the column tiles `wave` and `wave + 4`
 // (those below ntn), continued from +0.  Element (m, k) of A at A[m am + k ak], element (k, n) of B at B[k bk + n bn], k =
@@ -249,14 +241,14 @@ __global__ __launch_bounds__(kThreads) void mlp_check_kernel(const FitArgs a)
     for (int i = tid; i < a.n_models; i += kThreads) {
         const int tl = a.train_list[i], el = a.eval_list[i];
         if (tl < 0 || tl >= a.n_lists || el < -1 || el >= a.n_lists) {
-            if (blockIdx.x == 0) flag(a.status, GAE_MLP_ERR_LIST_ID);
+            if (blockIdx.x == 0) or_bits(&a.status->errors, GAE_MLP_ERR_LIST_ID);
         }
         if (tl >= 0 && tl < a.n_lists) used[tl] = 1;
         if (el >= 0 && el < a.n_lists) used[el] = 1;
     }
     __syncthreads();
     if (bad) {
-        if (blockIdx.x == 0 && tid == 0) flag(a.status, GAE_MLP_ERR_LIST_PTR);
+        if (blockIdx.x == 0 && tid == 0) or_bits(&a.status->errors, GAE_MLP_ERR_LIST_PTR);
         return;
     }
     const int64_t i = int64_t(blockIdx.x) * kThreads + tid;
@@ -266,11 +258,11 @@ __global__ __launch_bounds__(kThreads) void mlp_check_kernel(const FitArgs a)
         mine = mine || (used[k] && i >= a.list_ptr[k] && i < a.list_ptr[k + 1]);
     if (!mine) return;
     const int id = a.rows[i];
-    if (unsigned(id) >= unsigned(a.n)) { flag(a.status, GAE_MLP_ERR_ROW_ID); return; }
+    if (unsigned(id) >= unsigned(a.n)) { or_bits(&a.status->errors, GAE_MLP_ERR_ROW_ID); return; }
     bool ok = true;
     for (int c = 0; c < a.s.d; ++c) ok = ok && finite32(a.X[int64_t(id) * a.ldx + c]);
     for (int c = 0; c < a.s.t; ++c) ok = ok && finite32(a.Y[int64_t(id) * a.ldy + c]);
-    if (!ok) atomicAdd(reinterpret_cast<unsigned long long *>(&a.status->nonfinite_rows), 1ull);
+    if (!ok) gae::add_count(&a.status->nonfinite_rows, 1);
 }
 
 // position p of epoch `epoch` -> an index of [0, ntr): four Feistel rounds on 2 `half` bits, cycle-walked
@@ -406,7 +398,7 @@ __global__ __launch_bounds__(kThreads) void mlp_fit_kernel(const FitArgs a)
         info = reinterpret_cast<const int *>(st)[6];
         if (info == 0 && reinterpret_cast<const int *>(st)[7] != a.e0) {
             info = -2;
-            if (tid == 0) flag(a.status, GAE_MLP_ERR_RESUME);
+            if (tid == 0) or_bits(&a.status->errors, GAE_MLP_ERR_RESUME);
         }
     }
     if (info != 0) {                                                   // nothing to train: the model stays as it is
@@ -585,7 +577,7 @@ __global__ __launch_bounds__(kThreads) void mlp_fit_kernel(const FitArgs a)
             const double twice = 2.0 * double(ntr);
             const double value = sse / twice;
             loss[ep] = value;
-            const bool fin = fabs(value) <= DBL_MAX;
+            const bool fin = gae::finite64(value);
             misc[1] = (misc[0] || !fin) ? 1 : 0;
         }
         __syncthreads();
@@ -709,7 +701,7 @@ __global__ __launch_bounds__(kThreads) void mlp_predict_kernel(const PredictArgs
         counted += __popc(nanrows);
     }
     if (m == 0 && tid == 0 && counted && a.status)
-        atomicAdd(reinterpret_cast<unsigned long long *>(&a.status->nonfinite_rows), static_cast<unsigned long long>(counted));
+        gae::add_count(&a.status->nonfinite_rows, counted);
 }
 
 // the workspace: n_models state blocks, one after another

@@ -18,16 +18,17 @@
 //              B[l >> 4][l & 15]; the result has column l & 15 and rows 4 (l >> 4) + reg.  Waves split rows, never j.
 //
 // LDS: solve 8 d (d | 1) (twice for d <= 96; the odd pitch keeps a column walk off a single bank) + 56 m + 32 d + 64 bytes; transform 4 (dP kP + 64 (dP + 4) + dP + 2 kP + 64).
-#include <float.h>
-
 #include "common.h"
 #include "cholesky.h"
+#include "fold_lists.h"
 
 namespace {
 
 using gae::cdiv;
+using gae::finite32;
 using gae::up256;
 using gae::upper_at;
+using gae::v4f;
 
 constexpr int kMaxD = GAE_PCA_MAX_D, kMaxT = 8;
 constexpr int kSolveThreads = 512;
@@ -36,8 +37,6 @@ constexpr int kMaxBlocks = (kMaxM * (kMaxM + 1) / 2 + kSolveThreads - 1) / kSolv
 constexpr int kVInLds = 96;                // V^T shares LDS with the matrix up to this d (2 . 96 . 97 . 8 = 146 KB)
 constexpr int kVBatch = 4;                 // V^T items a thread loads before it stores
 constexpr double kTol = 0x1p-53;
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------------ solve
 struct SolveArgs {
@@ -298,8 +297,6 @@ inline size_t proj_lds(int64_t d, int64_t k)
     return size_t(dP * kP + kTileRows * (dP + 4) + dP + 2 * kP + kTileRows) * 4;
 }
 
-__device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= FLT_MAX; }
-
 __global__ __launch_bounds__(kThreads) void pca_transform_kernel(const ProjArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float ldsf[];
@@ -327,7 +324,7 @@ __global__ __launch_bounds__(kThreads) void pca_transform_kernel(const ProjArgs 
                 const double root = sqrt(v);
                 sc = float(1.0 / root);
             } else if (blockIdx.x == 0) {
-                atomicAdd(reinterpret_cast<unsigned long long *>(&a.st->nonpositive_components), 1ull);
+                gae::add_count(&a.st->nonpositive_components, 1);
             }
         }
         scale[cidx] = sc;
@@ -337,6 +334,7 @@ __global__ __launch_bounds__(kThreads) void pca_transform_kernel(const ProjArgs 
     __syncthreads();
 
     const int64_t tiles = (int64_t(a.n_rows) + kTileRows - 1) / kTileRows;
+    const gae::FoldList list{a.rows, nullptr, 1, a.n_rows};
     const int lr = lane & 15, lq = lane >> 4;
     const int Q = dP / 4, r0 = tid / Q, jq0 = tid % Q, dr = kThreads / Q, djq = kThreads % Q;
     const bool vec = (a.ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15u) == 0;
@@ -350,8 +348,9 @@ __global__ __launch_bounds__(kThreads) void pca_transform_kernel(const ProjArgs 
             float x[4] = {0.f, 0.f, 0.f, 0.f};
             int live = 0;
             if (base + r < a.n_rows) {
-                const int id = a.rows ? a.rows[base + r] : int(base + r);
-                if (unsigned(id) < unsigned(a.n)) {
+                bool bad_id = false;
+                const int id = gae::row_id(list, base + r, a.n, bad_id);
+                if (!bad_id) {
                     const float *src = a.X + int64_t(id) * a.ldx + j;
                     live = d - j < 4 ? d - j : 4;
                     if (vec && live == 4) {
@@ -379,10 +378,8 @@ __global__ __launch_bounds__(kThreads) void pca_transform_kernel(const ProjArgs 
         }
         __syncthreads();
         if (tid < kTileRows && rowbad[tid]) {
-            if (rowbad[tid] & 1)
-                atomicAdd(reinterpret_cast<unsigned long long *>(&a.st->nonfinite_rows), 1ull);
-            if (rowbad[tid] & 2)
-                atomicOr(reinterpret_cast<unsigned long long *>(&a.st->errors), static_cast<unsigned long long>(GAE_PCA_ERR_ROW_ID));
+            if (rowbad[tid] & 1) gae::add_count(&a.st->nonfinite_rows, 1);
+            if (rowbad[tid] & 2) gae::or_bits(&a.st->errors, GAE_PCA_ERR_ROW_ID);
         }
         v4f acc[kMaxKT];
 #pragma unroll
@@ -393,7 +390,7 @@ __global__ __launch_bounds__(kThreads) void pca_transform_kernel(const ProjArgs 
             const float av = pa[4 * s];
 #pragma unroll
             for (int tt = 0; tt < kMaxKT; ++tt)
-                if (tt < KT) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, pb[4 * s * kP + 16 * tt], acc[tt], 0, 0, 0);
+                if (tt < KT) acc[tt] = gae::mfma4(av, pb[4 * s * kP + 16 * tt], acc[tt]);
         }
 #pragma unroll
         for (int tt = 0; tt < kMaxKT; ++tt) {

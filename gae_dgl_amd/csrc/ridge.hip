@@ -5,7 +5,8 @@
 // gae_ridge_stats / gae_ridge_solve in include/gae_hip_experimental.h.
 //
 // Launches (ordinary ones, no float atomics):
-//   stats   one block of four waves per chunk of GAE_RIDGE_CHUNK_ROWS listed rows of ONE fold.  The block stages 32 rows
+//   stats   one block of four waves per chunk of GAE_RIDGE_CHUNK_ROWS listed rows of ONE fold (fold_lists.h: the fold list,
+//           the chunk order, the row-id fetch, the tile deal and the pitch).  The block stages 32 rows
 //           at a time in LDS as v = [1, x - p_x, y - p_y] in fp64 (widened first, then subtracted), zero past W and past
 //           the chunk: two LDS buffers and two register sets, the global loads of stage s + 2 issued before the products
 //           of stage s, one barrier per stage.  M = sum_i v_i v_i^T runs on v_mfma_f64_16x16x4_f64: W is padded to NT tiles of 16, the
@@ -14,8 +15,8 @@
 //           holds v[row 4 s + (l >> 4)][16 ti + (l & 15)], B the same with tj; D: col = l & 15, row = (l >> 4) + 4 reg.
 //           The packed upper triangle of the chunk goes to the workspace.  Rows that hold a non-finite value are counted
 //           through a bit mask per stage in LDS (integer atomics), row ids outside [0, n) are flagged and skipped.
-//   reduce  one thread (<= 32 chunks) or one wave (more) per (fold, entry): the fold's chunk partials in the order of
-//           common.h's sum_partials, in fp64.
+//   reduce  fold_lists.h's reduce_entries per fold: the fold's chunk partials in the order of common.h's sum_partials, in
+//           fp64.
 //   solve   one block per (model, lambda): the training moments (folds other than the model's, ascending), centring,
 //           + lambda I, a Cholesky-Crout factorisation of the packed lower triangle in LDS whose row loop also carries
 //           the t right-hand sides (forward substitution), back substitution, the map back through the pivot, and the
@@ -23,10 +24,9 @@
 //
 // LDS: stats 2 . 32 . pitch . 8 + 1 KB of row ids + the pivot (76 KB at W = 137); solve (d (d + 1) / 2 + 2 t d + d +
 // 4 (d + t) + t + 8) . 8 bytes (87 KB at d = 128, t = 8).
-#include <float.h>
-
 #include "common.h"
 #include "cholesky.h"
+#include "fold_lists.h"
 
 namespace {
 
@@ -39,62 +39,28 @@ constexpr int kStage = 32;                 // rows per LDS stage: eight products
 constexpr int kThreads = 256, kWaves = kThreads / gae::kWave;
 static_assert(kChunk % kStage == 0, "a chunk is a whole number of stages");
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 using gae::tri;
 using gae::upper_at;
-
-__device__ __forceinline__ void flag(gae_ridge_status *st, int64_t bits)
-{
-    atomicOr(reinterpret_cast<unsigned long long *>(&st->errors), static_cast<unsigned long long>(bits));
-}
-
-// the fp64 form of common.h's sum_partials (cholesky.h): the same lists, the same order
-__device__ __forceinline__ double sum_partials(const double *__restrict__ p0, int64_t n_partials, int64_t stride, int lane,
-                                               int L)
-{
-    return gae::sum_partials_f64(p0, n_partials, stride, lane, L);
-}
+using gae::v4d;
 
 // ------------------------------------------------------------------------------------------------------ stats
 struct StatsArgs {
     const float *X, *Y;
     int64_t ldx, ldy;
-    int n, d, t, W, F, n_rows;
+    int n, d, t, W;
     const float *pivot;                    // [d + t] or NULL
-    const int32_t *rows;                   // [n_rows] or NULL: rows 0 .. n - 1, one fold
-    const int32_t *fold_ptr;               // [F + 1] (rows != NULL)
+    gae::FoldList list;                    // the listed rows (fold_lists.h)
     double *part;                          // [chunks][tri(W)]
     double *stats;                         // [F][tri(W)]
     gae_ridge_status *status;
 };
 
-__device__ __forceinline__ void fold_bounds(const StatsArgs &a, int f, int &lo, int &hi)
-{
-    if (a.rows) { lo = a.fold_ptr[f]; hi = a.fold_ptr[f + 1]; }
-    else { lo = 0; hi = a.n_rows; }
-}
-
-// 0 <= fold_ptr[0] <= ... <= fold_ptr[F] == n_rows
-__device__ __forceinline__ bool folds_valid(const StatsArgs &a)
-{
-    if (!a.rows) return true;
-    int prev = a.fold_ptr[0];
-    bool ok = prev >= 0;
-    for (int f = 1; f <= a.F; ++f) {
-        const int v = a.fold_ptr[f];
-        ok = ok && v >= prev;
-        prev = v;
-    }
-    return ok && prev == a.n_rows;
-}
-
 template <int NT>
 __global__ __launch_bounds__(kThreads) void ridge_stats_kernel(const StatsArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    constexpr int WP = 16 * NT, pitch = (NT & 1) ? WP : WP + 16;       // pitch / 16 odd: the four rows of a product
-    constexpr int T = NT * (NT + 1) / 2, TPW = (T + kWaves - 1) / kWaves;      // ... start 32 banks apart
+    constexpr int WP = 16 * NT, pitch = gae::tile_pitch(NT);
+    constexpr int T = NT * (NT + 1) / 2, TPW = (T + kWaves - 1) / kWaves;
     constexpr int PF = kStage * WP / kThreads;                         // staged values per thread and stage
     constexpr int kGroup = NT >= 9 ? 1 : 8;                            // ... whose LDS reads are issued together (NT = 9: registers)
     static_assert(PF * kThreads == kStage * WP, "a stage is a whole number of block passes");
@@ -104,40 +70,18 @@ __global__ __launch_bounds__(kThreads) void ridge_stats_kernel(const StatsArgs a
     unsigned *mask = reinterpret_cast<unsigned *>(rid + kChunk);       // [2]: rows of a stage that hold a non-finite value
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    if (!folds_valid(a)) {
-        if (blockIdx.x == 0 && tid == 0) flag(a.status, GAE_RIDGE_ERR_FOLD_PTR);
+    if (!gae::folds_valid(a.list)) {
+        if (blockIdx.x == 0 && tid == 0) gae::or_bits(&a.status->errors, GAE_RIDGE_ERR_FOLD_PTR);
         return;
     }
-    // ---- the block's chunk: folds in ascending order, chunks inside a fold in ascending order
-    int fold = -1, lo = 0, hi = 0;
-    {
-        int64_t b = blockIdx.x;
-        for (int f = 0; f < a.F; ++f) {
-            int flo, fhi;
-            fold_bounds(a, f, flo, fhi);
-            const int64_t nc = (int64_t(fhi) - flo + kChunk - 1) / kChunk;
-            if (b < nc) {
-                fold = f;
-                lo = int(flo + b * kChunk);
-                hi = fhi - lo > kChunk ? lo + kChunk : fhi;
-                break;
-            }
-            b -= nc;
-        }
-    }
-    if (fold < 0) return;                                              // a spare block of the grid's upper bound
-    const int nrows = hi - lo, nst = (nrows + kStage - 1) / kStage;
+    const gae::Chunk ch = gae::chunk_of(a.list, blockIdx.x, kChunk);   // the block's chunk
+    if (ch.fold < 0) return;                                           // a spare block of the grid's upper bound
+    const int lo = ch.lo, nrows = ch.hi - ch.lo, nst = (nrows + kStage - 1) / kStage;
 
     bool bad_id = false;
-    for (int i = tid; i < kChunk; i += kThreads) {
-        int id = -1;
-        if (i < nrows) {
-            id = a.rows ? a.rows[lo + i] : lo + i;
-            if (unsigned(id) >= unsigned(a.n)) { bad_id = true; id = -1; }
-        }
-        rid[i] = id;
-    }
-    if (bad_id) flag(a.status, GAE_RIDGE_ERR_ROW_ID);
+    for (int i = tid; i < kChunk; i += kThreads)
+        rid[i] = i < nrows ? gae::row_id(a.list, lo + i, a.n, bad_id) : -1;
+    if (bad_id) gae::or_bits(&a.status->errors, GAE_RIDGE_ERR_ROW_ID);
     for (int c = tid; c < WP; c += kThreads)
         pv[c] = (a.pivot && c >= 1 && c <= a.d + a.t) ? double(a.pivot[c - 1]) : 0.0;
     if (tid < 2) mask[tid] = 0u;
@@ -150,13 +94,10 @@ __global__ __launch_bounds__(kThreads) void ridge_stats_kernel(const StatsArgs a
     bool mine[TPW];
 #pragma unroll
     for (int u = 0; u < TPW; ++u) {
-        int e = wave + kWaves * u, r = 0;
+        const int e = wave + kWaves * u;
         ti[u] = 0; tj[u] = 0;
         mine[u] = e < T;
-        if (e < T) {
-            while (e >= NT - r) { e -= NT - r; ++r; }
-            ti[u] = r; tj[u] = r + e;
-        }
+        if (e < T) gae::upper_tile(e, NT, ti[u], tj[u]);
     }
     v4d acc[TPW];
 #pragma unroll
@@ -203,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void ridge_stats_kernel(const StatsArgs a
             for (int u = u0; u < u0 + kGroup && u < PF; ++u) {
                 const int e = tid + u * kThreads, r = e / WP, c = e % WP;
                 const bool on = (live >> u) & 1u;
-                if (on && !(fabsf(pf[u]) <= FLT_MAX)) atomicOr(&mask[it & 1], 1u << r);
+                if (on && !gae::finite32(pf[u])) atomicOr(&mask[it & 1], 1u << r);
                 dst[r * pitch + c] = on ? double(pf[u]) - p[u - u0] : 0.0;
             }
         }
@@ -249,44 +190,26 @@ __global__ __launch_bounds__(kThreads) void ridge_stats_kernel(const StatsArgs a
             if (row <= col && col < a.W) out[upper_at(row, col, a.W)] = acc[u][q];
         }
     }
-    if (tid == 0 && bad_rows)
-        atomicAdd(reinterpret_cast<unsigned long long *>(&a.status->nonfinite_rows), static_cast<unsigned long long>(bad_rows));
+    if (tid == 0 && bad_rows) gae::add_count(&a.status->nonfinite_rows, bad_rows);
 }
 
-// grid (ceil(tri(W) / 16), F).  A fold of <= 32 chunks: one thread per entry, in the first ceil(tri(W) / 256) blocks.  More
-// chunks: one wave per kWaveEntries entries (the mode is the fold's, known on the device only: the grid covers both)
-constexpr int kWaveEntries = 4;
-constexpr int kReduceEntries = kWaves * kWaveEntries;
+// grid (ceil(tri(W) / 16), F): fold_lists.h's reduce_entries over the chunks of fold blockIdx.y (their number is known on
+// the device only)
+constexpr int kReduceEntries = kWaves * gae::kWaveEntries;
 
 __global__ __launch_bounds__(kThreads) void ridge_reduce_kernel(const StatsArgs a)
 {
-    const int f = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t tw = tri(a.W), e1 = int64_t(blockIdx.x) * kThreads + tid;
+    const int f = blockIdx.y;
+    const int64_t tw = tri(a.W), e1 = int64_t(blockIdx.x) * kThreads + threadIdx.x;
     double *out = a.stats + int64_t(f) * tw;
-    if (!folds_valid(a)) {                                             // flagged by the stats launch
+    if (!gae::folds_valid(a.list)) {                                   // flagged by the stats launch
         if (e1 < tw) out[e1] = __builtin_nan("");
         return;
     }
-    int64_t base = 0;
     int lo, hi;
-    for (int g = 0; g < f; ++g) {
-        fold_bounds(a, g, lo, hi);
-        base += (int64_t(hi) - lo + kChunk - 1) / kChunk;
-    }
-    fold_bounds(a, f, lo, hi);
-    const int64_t P = (int64_t(hi) - lo + kChunk - 1) / kChunk;
-    const double *p0 = a.part + base * tw;
-    if (gae::partial_lanes(P) == 1) {
-        if (e1 < tw) out[e1] = sum_partials(p0 + e1, P, tw, 0, 1);
-    } else {
-#pragma unroll
-        for (int i = 0; i < kWaveEntries; ++i) {                       // all 64 lanes of the wave call
-            const int64_t e = (int64_t(blockIdx.x) * kWaves + wave) * kWaveEntries + i;
-            if (e >= tw) break;
-            const double s = sum_partials(p0 + e, P, tw, lane, 64);
-            if (lane == 0) out[e] = s;
-        }
-    }
+    const int64_t P = gae::fold_chunks(a.list, f, kChunk, lo, hi);
+    gae::reduce_entries<kThreads>(a.part + gae::chunks_before(a.list, f, kChunk) * tw, P, tw,
+                                  [](int64_t) { return true; }, [&](int64_t e, double s) { out[e] = s; });
 }
 
 // ------------------------------------------------------------------------------------------------------ solve
@@ -333,7 +256,7 @@ __global__ __launch_bounds__(kThreads) void ridge_solve_kernel(const SolveArgs a
     int info = 0;
     if (!(lam >= 0.0 && lam <= DBL_MAX)) {
         info = -2;
-        if (tid == 0 && m == 0) flag(a.status, GAE_RIDGE_ERR_LAMBDA);
+        if (tid == 0 && m == 0) gae::or_bits(&a.status->errors, GAE_RIDGE_ERR_LAMBDA);
     } else if (!(c > 0.0)) {
         info = -1;
     }
@@ -445,7 +368,7 @@ int plan(const char *fn, int64_t n_rows, int64_t d, int64_t t, int64_t folds, Pl
 template <int NT>
 int launch_stats(int64_t blocks, hipStream_t st, const StatsArgs &a)
 {
-    constexpr int WP = 16 * NT, pitch = (NT & 1) ? WP : WP + 16;
+    constexpr int WP = 16 * NT, pitch = gae::tile_pitch(NT);
     const size_t lds = size_t(2 * kStage * pitch + WP) * 8 + kChunk * 4 + 16;
     return gae::launch_lds<&ridge_stats_kernel<NT>>("ridge_stats_kernel", blocks, kThreads, lds, st, a);
 }
@@ -483,8 +406,9 @@ extern "C" int gae_ridge_stats(const float *X, int64_t ldx, const float *Y, int6
 
     StatsArgs a;
     a.X = X; a.Y = Y; a.ldx = ldx; a.ldy = ldy;
-    a.n = int(n); a.d = int(d); a.t = int(t); a.W = int(p.W); a.F = int(folds); a.n_rows = int(n_rows);
-    a.pivot = pivot; a.rows = rows; a.fold_ptr = fold_ptr;
+    a.n = int(n); a.d = int(d); a.t = int(t); a.W = int(p.W);
+    a.pivot = pivot;
+    a.list = gae::FoldList{rows, fold_ptr, int(folds), int(n_rows)};
     a.part = static_cast<double *>(workspace);
     a.stats = stats; a.status = status;
     hipStream_t st = gae::as_stream(stream);

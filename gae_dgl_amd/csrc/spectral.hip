@@ -11,9 +11,10 @@
 //            their ids, scales and operand pairs are loaded before the first fma, the fmas run in CSR order.  A hub row
 //            is one group's serial chain (the sum is never split).
 //   gram     one block of four waves per chunk of 256 rows; 16 rows at a time are staged in LDS (zero past b and n), the
-//            2 . NT (NT + 1) / 2 upper-triangle tiles of V^T V and V^T AV are dealt round-robin to the waves (ridge.hip's
-//            operand layout: A lane l = v[4 s + (l >> 4)][16 ti + (l & 15)], D col = l & 15, row = (l >> 4) + 4 reg).
-//   reduce   the chunk partials of an entry in the order of common.h's sum_partials (cholesky.h's fp64 form).
+//            2 . NT (NT + 1) / 2 upper-triangle tiles of V^T V and V^T AV are dealt round-robin to the waves (fold_lists.h's
+//            tile deal and pitch; ridge.hip's operand layout: A lane l = v[4 s + (l >> 4)][16 ti + (l & 15)], D col = l & 15,
+//            row = (l >> 4) + 4 reg).
+//   reduce   fold_lists.h's reduce_entries: the chunk partials of an entry in the order of common.h's sum_partials.
 //   solve    pre (Cholesky, the two triangular reductions, the packing) -- gae_pca_solve -- post (back substitution,
 //            coefficients, status): one block each.  The b x b matrix sits in LDS (pitch b | 1), L in the workspace.
 //   rotate   a block per chunk of 256 rows, 8 rows at a time: T (b x b) and the rows in LDS, one thread per (row, column)
@@ -22,17 +23,18 @@
 //   finish   chunk winners per column, one block folds them in chunk order, one elementwise pass writes.
 //
 // LDS: gram 2 . 16 . pitch . 8 (36 KB at b = 128); solve b (b | 1) 8 + 8 b (130 KB); rotate (b b + 2 . 8 b + b) 8 (145 KB).
-#include <float.h>
-
 #include "common.h"
 #include "cholesky.h"
+#include "fold_lists.h"
 
 namespace {
 
 using gae::cdiv;
+using gae::finite64;
 using gae::up256;
 using gae::upper_at;
 using gae::tri;
+using gae::v4d;
 
 constexpr int kMaxB = GAE_SPECTRAL_MAX_B, kMaxK = GAE_SPECTRAL_MAX_K, kMaxDegree = GAE_SPECTRAL_MAX_DEGREE;
 constexpr int kChunk = GAE_SPECTRAL_CHUNK_ROWS;
@@ -44,10 +46,7 @@ constexpr int kRotItems = kRotRows * kMaxB / kThreads;
 constexpr int kMaxGrid = 8192;
 static_assert(kChunk % kStage == 0 && kChunk % kRotRows == 0, "a chunk is a whole number of passes");
 
-typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool finite64(double v) { return fabs(v) <= DBL_MAX; }
 
 // ------------------------------------------------------------------------------------------------------ the carve
 // the regions the solve needs do not depend on n and come first
@@ -154,8 +153,7 @@ __global__ __launch_bounds__(kThreads) void spectral_spmm_kernel(const SpmmArgs 
     const int g = a.g, lg = threadIdx.x & (g - 1), rl = threadIdx.x / g, R = kThreads / g;
     const int nv = a.b >> 1, n = a.n;
     const double alpha = a.coef[0], beta = a.coef[1], gamma = a.coef[2];
-    if (blockIdx.x == 0 && threadIdx.x == 0 && a.st)
-        atomicAdd(reinterpret_cast<unsigned long long *>(&a.st->n_spmm), 1ull);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && a.st) gae::add_count(&a.st->n_spmm, 1);
     if (lg >= nv) return;
     bool bad = false;
     for (int64_t row = int64_t(blockIdx.x) * R + rl; row < n; row += int64_t(gridDim.x) * R) {
@@ -208,8 +206,7 @@ __global__ __launch_bounds__(kThreads) void spectral_spmm_kernel(const SpmmArgs 
         }
         reinterpret_cast<v2d *>(a.Yout)[row * nv + lg] = o;
     }
-    if (bad && a.st)
-        atomicOr(reinterpret_cast<unsigned long long *>(&a.st->errors), static_cast<unsigned long long>(GAE_SPECTRAL_ERR_INDEX));
+    if (bad && a.st) gae::or_bits(&a.st->errors, GAE_SPECTRAL_ERR_INDEX);
 }
 
 // ------------------------------------------------------------------------------------------------------ gram
@@ -224,7 +221,7 @@ struct GramArgs {
 template <int NT>
 __global__ __launch_bounds__(kThreads) void spectral_gram_kernel(const GramArgs a)
 {
-    constexpr int WP = 16 * NT, pitch = (NT & 1) ? WP : WP + 16;       // pitch / 16 odd (ridge.hip)
+    constexpr int WP = 16 * NT, pitch = gae::tile_pitch(NT);
     constexpr int T = NT * (NT + 1) / 2, TPW = (2 * T + kWaves - 1) / kWaves;
     constexpr int PF = kStage * WP / kThreads;
     static_assert(PF * kThreads == kStage * WP, "a stage is a whole number of block passes");
@@ -237,15 +234,11 @@ __global__ __launch_bounds__(kThreads) void spectral_gram_kernel(const GramArgs 
     bool mine[TPW], second[TPW];
 #pragma unroll
     for (int u = 0; u < TPW; ++u) {
-        int e = wave + kWaves * u, r = 0;
+        const int e = wave + kWaves * u;
         mine[u] = e < 2 * T;
         second[u] = e >= T;
-        if (e >= T) e -= T;
         ti[u] = 0; tj[u] = 0;
-        if (mine[u]) {
-            while (e >= NT - r) { e -= NT - r; ++r; }
-            ti[u] = r; tj[u] = r + e;
-        }
+        if (mine[u]) gae::upper_tile(second[u] ? e - T : e, NT, ti[u], tj[u]);
         boff[u] = (mine[u] && second[u]) ? kStage * pitch : 0;
     }
 
@@ -289,33 +282,19 @@ __global__ __launch_bounds__(kThreads) void spectral_gram_kernel(const GramArgs 
     }
 }
 
-constexpr int kWaveEntries = 4;
-
-// entries e of [2][b][b] with i <= j: the chunk partials in the library's order; the mirror is a copy
+// entries e of [2][b][b] with i <= j: the chunk partials in the library's order (fold_lists.h's reduce_entries); the mirror
+// is a copy
 __global__ __launch_bounds__(kThreads) void spectral_gram_reduce_kernel(const GramArgs a)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = a.b;
-    const int64_t E = int64_t(2) * b * b, P = a.chunks;
-    auto put = [&](int64_t e, double v) {
-        const int which = int(e / (b * b)), ij = int(e % (b * b)), i = ij / b, j = ij % b;
-        double *out = which ? a.H : a.G;
-        out[i * b + j] = v;
-        out[j * b + i] = v;
-    };
-    auto upper = [&](int64_t e) { const int ij = int(e % (b * b)); return ij / b <= ij % b; };
-    if (gae::partial_lanes(P) == 1) {
-        const int64_t e = int64_t(blockIdx.x) * kThreads + tid;
-        if (e < E && upper(e)) put(e, gae::sum_partials_f64(a.part + e, P, E, 0, 1));
-    } else {
-#pragma unroll
-        for (int i = 0; i < kWaveEntries; ++i) {                       // all 64 lanes of the wave call
-            const int64_t e = (int64_t(blockIdx.x) * kWaves + wave) * kWaveEntries + i;
-            if (e >= E) break;
-            if (!upper(e)) continue;
-            const double s = gae::sum_partials_f64(a.part + e, P, E, lane, 64);
-            if (lane == 0) put(e, s);
-        }
-    }
+    const int b = a.b;
+    gae::reduce_entries<kThreads>(
+        a.part, a.chunks, int64_t(2) * b * b, [&](int64_t e) { const int ij = int(e % (b * b)); return ij / b <= ij % b; },
+        [&](int64_t e, double v) {
+            const int which = int(e / (b * b)), ij = int(e % (b * b)), i = ij / b, j = ij % b;
+            double *out = which ? a.H : a.G;
+            out[i * b + j] = v;
+            out[j * b + i] = v;
+        });
 }
 
 // ------------------------------------------------------------------------------------------------------ solve
@@ -529,8 +508,8 @@ __global__ __launch_bounds__(kThreads) void spectral_residual_kernel(const RotAr
     const int L = gae::partial_lanes(P);
     for (int c = wave; c < b; c += kWaves) {                           // all 64 lanes of the wave call
         double s = 0.0;
-        if (L == 64) s = gae::sum_partials_f64(a.part + c, P, b, lane, 64);
-        else if (lane == 0) s = gae::sum_partials_f64(a.part + c, P, b, 0, 1);
+        if (L == 64) s = gae::sum_partials(a.part + c, P, b, lane, 64);
+        else if (lane == 0) s = gae::sum_partials(a.part + c, P, b, 0, 1);
         if (lane == 0) {
             const double r = sqrt(s);
             res[c] = r;
@@ -713,7 +692,7 @@ extern "C" int gae_spectral_gram(const double *V, const double *AV, int64_t n, i
     }
     if (rc) return rc;
     const int64_t E = 2 * b * b;
-    const int64_t rblocks = chunks <= 32 ? cdiv(E, kThreads) : cdiv(E, kWaves * kWaveEntries);
+    const int64_t rblocks = chunks <= 32 ? cdiv(E, kThreads) : cdiv(E, kWaves * gae::kWaveEntries);
     hipLaunchKernelGGL(spectral_gram_reduce_kernel, dim3(unsigned(rblocks)), dim3(kThreads), 0, st, a);
     GAE_CHECK_LAUNCH("spectral_gram_reduce_kernel");
     return GAE_OK;

@@ -472,7 +472,7 @@ def main(argv=None):
     main.logreg = None
     if args.logreg is not None:
         from gae_dgl_amd import metrics
-        from gae_dgl_amd.ops.logreg import _default_fold
+        from gae_dgl_amd.ops._heads import _default_fold
         y = np.load(args.labels)
         if y.ndim != 1 or y.shape[0] != out.shape[0] or not np.issubdtype(y.dtype, np.integer):
             raise ValueError(f"--labels of shape {y.shape}, {y.dtype} for {out.shape[0]} molecules: integer classes [G]")

@@ -18,7 +18,7 @@ __all__ = [
     'float_rows', '_rowmajor', '_f32', '_dtype_code', '_WS_CACHE', 'StepContext', '_STEP_STACK', '_STEP_LOCK',
     '_NO_STEP', '_StackView', '_step_stack', 'current_step', 'deferred_grad_reductions', 'deferred_loss_finalize',
     'pending_loss_tail', 'pending_partials', '_ws_bytes', '_workspace', '_on_device', 'device_info', 'EventProfiler',
-    'profiler',
+    'profiler', '_timed',
 ]
 
 
@@ -354,3 +354,10 @@ class EventProfiler:
 
 
 profiler = None  # set to an EventProfiler to time launches
+
+
+def _timed(key, launch):
+    """``launch()``, recorded under ``key`` when a profiler is set (``ops.profiler``)"""
+    if _ops.profiler is not None:
+        return _ops.profiler.wrap(key, launch)
+    return launch()

@@ -15,16 +15,16 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _gpu, _on_device, _ptr, _stream, _ws_bytes
-from .cluster import _rows
-from .forest import STATUS_WORDS, _edges
-from .logreg import _default_fold
+from ._base import _gpu, _on_device, _ptr, _stream, _timed, _ws_bytes
+from ._heads import (_check_max_bins, _check_max_features, _check_min_samples_leaf, _check_seed, _default_fold, _edges,
+                     _fold_arg, _rows, _status_arg, _whole)
 
 __all__ = ['BoostResult', 'boost', 'boost_predict', 'BOOST_MAX_D', 'BOOST_MAX_BINS', 'BOOST_MAX_DEPTH', 'BOOST_MAX_ROUNDS',
            'BOOST_MAX_MODELS']
 
 BOOST_MAX_D, BOOST_MAX_BINS, BOOST_MAX_DEPTH, BOOST_MAX_ROUNDS, BOOST_MAX_MODELS = 256, 256, 8, 4096, 256
 OBJECTIVES = {"squared": _lib.BOOST_SQUARED, "logistic": _lib.BOOST_LOGISTIC}
+STATUS_WORDS = 4          # gae_forest_status: int64 nonfinite, errors, reserved[2]
 
 
 class BoostResult(collections.namedtuple("BoostResult", [
@@ -58,10 +58,6 @@ class BoostResult(collections.namedtuple("BoostResult", [
         return torch.sigmoid(_ops.boost_predict(self, X, n_rounds=n_rounds))
 
 
-def _whole(v):
-    return not isinstance(v, bool) and isinstance(v, int)
-
-
 def _values(v, name):
     if isinstance(v, torch.Tensor):
         v = v.detach().double().cpu().reshape(-1).tolist()
@@ -81,21 +77,14 @@ def _options(X, y, objective, n_rounds, max_depth, learning_rates, lambdas, min_
         raise ValueError(f"n_rounds: an integer in 1..{BOOST_MAX_ROUNDS}, not {n_rounds!r}")
     if not _whole(max_depth) or not 1 <= max_depth <= BOOST_MAX_DEPTH:
         raise ValueError(f"max_depth: an integer in 1..{BOOST_MAX_DEPTH}, not {max_depth!r}")
-    if not _whole(max_bins) or not 2 <= max_bins <= BOOST_MAX_BINS:
-        raise ValueError(f"max_bins: an integer in 2..{BOOST_MAX_BINS}, not {max_bins!r}")
-    if not _whole(min_samples_leaf) or not 1 <= min_samples_leaf < 2 ** 30:
-        raise ValueError(f"min_samples_leaf: an integer >= 1, not {min_samples_leaf!r}")
+    _check_max_bins(max_bins, BOOST_MAX_BINS)
+    _check_min_samples_leaf(min_samples_leaf)
     if not _whole(check_every) or check_every < 1:
         raise ValueError(f"check_every: a positive integer, not {check_every!r}")
-    if not _whole(seed) or not 0 <= seed < 2 ** 64:
-        raise ValueError(f"seed: an integer in 0..2^64 - 1, not {seed!r}")
+    _check_seed(seed)
     if not _whole(folds) or not 1 <= folds < BOOST_MAX_MODELS:
         raise ValueError(f"folds: an integer in 1..{BOOST_MAX_MODELS - 1}, not {folds!r}")
-    if _whole(max_features):
-        if max_features < 1:
-            raise ValueError(f"max_features: an integer in 1..d or a float in (0, 1], not {max_features!r}")
-    elif not (isinstance(max_features, float) and 0.0 < max_features <= 1.0):
-        raise ValueError(f"max_features: an integer in 1..d or a float in (0, 1], not {max_features!r}")
+    _check_max_features(max_features)
     for name, v in (("min_child_weight", min_child_weight), ("min_gain", min_gain)):
         if isinstance(v, bool) or not isinstance(v, (int, float)) or not (v >= 0.0 and math.isfinite(v)):
             raise ValueError(f"{name}: a finite number >= 0, not {v!r}")
@@ -197,11 +186,7 @@ def boost(X, y, objective="squared", n_rounds=100, *, max_depth=4, learning_rate
     lrs, lams, F = _options(X, y, objective, n_rounds, max_depth, learning_rates, lambdas, min_child_weight, min_samples_leaf,
                             min_gain, max_features, max_bins, folds, seed, check_every)
     if fold is not None:
-        if not isinstance(fold, torch.Tensor) or fold.dtype.is_floating_point or fold.dtype == torch.bool or fold.dim() != 1 \
-                or fold.shape[0] != X.shape[0]:
-            raise ValueError(f"fold: an int tensor [{X.shape[0]}] with values in -1..{folds - 1}")
-        if fold.numel() and (int(fold.min()) < -1 or int(fold.max()) >= folds):
-            raise ValueError(f"fold: values in -1..{folds - 1} (-1 = left out), got {int(fold.min())}..{int(fold.max())}")
+        _fold_arg(fold, X.shape[0], folds)
     cfgs = [(lr, lam) for lr in lrs for lam in lams]
     n_cfg, Mo, R = len(cfgs), (F + 1) * len(cfgs), n_rounds
     with torch.no_grad():
@@ -271,10 +256,7 @@ def boost(X, y, objective="squared", n_rounds=100, *, max_depth=4, learning_rate
                               _ptr(out["count"]), _ptr(out["value"]), _ptr(out["gain"]), _ptr(out["n_nodes"]),
                               _ptr(out["loss"]), _ptr(out["correct"]), _ptr(out["score"]), _ptr(out["bad"]), _ptr(status),
                               _ptr(ws), ws.numel(), _stream())
-                if _ops.profiler is not None:
-                    _ops.profiler.wrap(("boost", n_used, d, k * (F + 1), rounds, max_depth, max_bins), launch)
-                else:
-                    launch()
+                _timed(("boost", n_used, d, k * (F + 1), rounds, max_depth, max_bins), launch)
                 st = status.cpu()
                 if int(st[0]):
                     raise GaeHipError(f"boost: {int(st[0])} values of the {n_used} listed rows of X are not finite")
@@ -343,11 +325,7 @@ def boost_predict(result, X, n_rounds=None, status=None):
         if X.device != dev or d != result.edges.shape[0]:
             raise GaeHipError(f"boost_predict: X must be [m, {result.edges.shape[0]}] on {dev}, got {tuple(X.shape)} on "
                               f"{X.device}")
-        if status is None:
-            status = torch.zeros(STATUS_WORDS, dtype=torch.int64, device=dev)
-        elif not (isinstance(status, torch.Tensor) and status.dtype == torch.int64 and status.numel() == STATUS_WORDS
-                  and status.device == dev and status.is_contiguous()):
-            raise GaeHipError(f"boost_predict: status must be a contiguous int64 [{STATUS_WORDS}] tensor on {dev}")
+        status = _status_arg(status, STATUS_WORDS, dev, "boost_predict")
         out = torch.empty(m, dtype=torch.float64, device=dev)
         with _on_device(dev):
             _lib.call("gae_boost_predict", _ptr(X), ldx, m, d, r, M, _ptr(result.feature), _ptr(result.threshold),

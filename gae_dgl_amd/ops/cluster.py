@@ -8,10 +8,10 @@ import collections
 
 import torch
 
-import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _f32, _gpu, _on_device, _ptr, _stream, _ws_bytes
+from ._base import _f32, _gpu, _on_device, _ptr, _stream, _timed, _ws_bytes
+from ._heads import _rows
 
 __all__ = ['KMeansResult', 'kmeans_assign', 'kmeans', 'kmeans_init_pp']
 
@@ -22,18 +22,6 @@ labels against the centres they were chosen with), n_iter, converged, n_empty (c
 iteration; they kept their centre)"""
 
 STATUS_WORDS = 6          # gae_kmeans_status: int64 done, iterations, changed, empty; double inertia, shift2
-
-
-def _rows(X, who):
-    """(X, ldx, n, d): a 2-D fp32 device tensor as it is when its inner stride is 1 (a column slice of a wider
-    buffer is read in place), else a contiguous copy"""
-    X = _f32(_gpu(X, f"{who}: X"), f"{who}: X").detach()
-    if X.dim() != 2:
-        raise GaeHipError(f"{who}: X must be 2-D, got {tuple(X.shape)}")
-    n, d = X.shape
-    if d > 0 and (X.stride(1) != 1 or (n > 1 and X.stride(0) < d)):
-        X = X.contiguous()
-    return X, (X.stride(0) if n > 1 else max(d, 1)), n, d
 
 
 def _centres(C, d, dev, who):
@@ -66,10 +54,7 @@ def kmeans_assign(X, C):
             def launch():
                 _lib.call("gae_kmeans_assign", _ptr(X), ldx, n, d, _ptr(C), k, _ptr(labels), _ptr(dist2), _ptr(ws),
                           ws.numel(), _stream())
-            if _ops.profiler is not None:
-                _ops.profiler.wrap(("kmeans_assign", n, d, k), launch)
-            else:
-                launch()
+            _timed(("kmeans_assign", n, d, k), launch)
     return labels, dist2
 
 

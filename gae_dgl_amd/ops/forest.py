@@ -15,8 +15,9 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _gpu, _on_device, _ptr, _stream, _ws_bytes
-from .cluster import _rows
+from ._base import _on_device, _ptr, _stream, _timed, _ws_bytes
+from ._heads import (_check_max_bins, _check_max_features, _check_min_samples_leaf, _check_seed, _edges, _listed, _rows,
+                     _status_arg, _targets, _whole)
 
 __all__ = ['ForestResult', 'forest', 'forest_predict', 'FOREST_MAX_D', 'FOREST_MAX_T', 'FOREST_MAX_TREES',
            'FOREST_MAX_DEPTH', 'FOREST_MAX_BINS', 'FOREST_SPLIT_ROWS']
@@ -45,84 +46,24 @@ class ForestResult(collections.namedtuple("ForestResult", [
 
 
 def _options(n_trees, max_depth, max_features, min_samples_leaf, max_bins, bootstrap, max_samples, seed):
-    def whole(v):
-        return not isinstance(v, bool) and isinstance(v, int)
-    if not whole(n_trees) or not 1 <= n_trees <= FOREST_MAX_TREES:
+    if not _whole(n_trees) or not 1 <= n_trees <= FOREST_MAX_TREES:
         raise ValueError(f"n_trees: an integer in 1..{FOREST_MAX_TREES}, not {n_trees!r}")
-    if not whole(max_depth) or not 1 <= max_depth <= FOREST_MAX_DEPTH:
+    if not _whole(max_depth) or not 1 <= max_depth <= FOREST_MAX_DEPTH:
         raise ValueError(f"max_depth: an integer in 1..{FOREST_MAX_DEPTH}, not {max_depth!r}")
-    if not whole(max_bins) or not 2 <= max_bins <= FOREST_MAX_BINS:
-        raise ValueError(f"max_bins: an integer in 2..{FOREST_MAX_BINS}, not {max_bins!r}")
-    if not whole(min_samples_leaf) or not 1 <= min_samples_leaf < 2 ** 30:
-        raise ValueError(f"min_samples_leaf: an integer >= 1, not {min_samples_leaf!r}")
+    _check_max_bins(max_bins, FOREST_MAX_BINS)
+    _check_min_samples_leaf(min_samples_leaf)
     if not isinstance(bootstrap, bool):
         raise ValueError(f"bootstrap: True or False, not {bootstrap!r}")
-    if whole(max_features):
-        if max_features < 1:
-            raise ValueError(f"max_features: an integer in 1..d or a float in (0, 1], not {max_features!r}")
-    elif not (isinstance(max_features, float) and 0.0 < max_features <= 1.0):
-        raise ValueError(f"max_features: an integer in 1..d or a float in (0, 1], not {max_features!r}")
+    _check_max_features(max_features)
     if max_samples is not None:
         if not bootstrap:
             raise ValueError("max_samples needs bootstrap=True: without the bootstrap every tree trains on every listed row")
-        if whole(max_samples):
+        if _whole(max_samples):
             if max_samples < 1:
                 raise ValueError(f"max_samples: an integer >= 1 or a float in (0, 1], not {max_samples!r}")
         elif not (isinstance(max_samples, float) and 0.0 < max_samples <= 1.0):
             raise ValueError(f"max_samples: an integer >= 1 or a float in (0, 1], not {max_samples!r}")
-    if not whole(seed) or not 0 <= seed < 2 ** 64:
-        raise ValueError(f"seed: an integer in 0..2^64 - 1, not {seed!r}")
-
-
-def _listed(rows, n, dev):
-    """int32 [n_used] row ids on the device, or None for all rows in order"""
-    if rows is None:
-        return None
-    if not isinstance(rows, torch.Tensor) or rows.dim() != 1 or rows.dtype.is_floating_point or rows.dtype.is_complex:
-        raise GaeHipError(f"forest: rows must be a 1-D int tensor of row ids or a bool mask [{n}]")
-    rows = _gpu(rows, "forest: rows")
-    if rows.device != dev:
-        raise GaeHipError(f"forest: rows on {rows.device}, X on {dev}")
-    if rows.dtype == torch.bool:
-        if rows.shape[0] != n:
-            raise GaeHipError(f"forest: a bool mask of {rows.shape[0]} entries for {n} rows")
-        return rows.nonzero().reshape(-1).to(torch.int32)
-    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n):
-        raise GaeHipError(f"forest: row ids outside 0..{n - 1}")
-    return rows.to(torch.int32).contiguous()
-
-
-def _edges(Xs, max_bins):
-    """(edges fp32 [d, max_bins - 1] padded with +inf, n_edges int32 [d]) of the listed rows ``Xs``: the rule of the K26
-    header comment, from one column sort"""
-    n, d = Xs.shape
-    E = max_bins - 1
-    dev = Xs.device
-    S = Xs.sort(dim=0).values
-    new = torch.zeros(n, d, dtype=torch.bool, device=dev)
-    new[1:] = S[1:] != S[:-1]
-    lossless = (new.sum(0) + 1) <= max_bins
-    edges = torch.full((d, E), float("inf"), dtype=torch.float32, device=dev)
-
-    def place(marks, values_at):
-        at = marks.t().nonzero()                                       # (f, i) in ascending f, then i
-        f, i = at[:, 0], at[:, 1]
-        cnt = torch.bincount(f, minlength=d)
-        rank = torch.arange(f.shape[0], device=dev) - (cnt.cumsum(0) - cnt)[f]
-        edges[f, rank] = values_at(f, i)
-        return cnt
-
-    def midpoint(f, i):
-        a, b = S[i - 1, f], S[i, f]
-        mid = ((a.double() + b.double()) / 2).float()
-        return torch.where(mid >= b, a, mid)                           # a <= edge < b
-    cnt_a = place(new & lossless, midpoint)
-    idx = (torch.arange(1, max_bins, device=dev, dtype=torch.int64) * n) // max_bins
-    Q = S[idx]                                                         # [E, d]
-    keep = torch.ones(E, d, dtype=torch.bool, device=dev)
-    keep[1:] = Q[1:] != Q[:-1]
-    cnt_b = place(keep & ~lossless, lambda f, k: Q[k, f])
-    return edges + 0.0, torch.where(lossless, cnt_a, cnt_b).to(torch.int32)        # (an edge of -0 is stored as +0)
+    _check_seed(seed)
 
 
 def _fsum_scores(pred, y):
@@ -172,17 +113,13 @@ def forest(X, y, n_trees=100, *, max_depth=12, max_features=1.0, min_samples_lea
     with torch.no_grad():
         X, ldx, n, d = _rows(X, "forest")
         dev = X.device
-        y = _gpu(y, "forest: y").detach()
-        if y.device != dev or y.dim() not in (1, 2) or y.shape[0] != n or not y.dtype.is_floating_point:
-            raise GaeHipError(f"forest: y must be a float tensor [{n}] or [{n}, t] on {dev}, got {tuple(y.shape)} "
-                              f"{y.dtype} on {y.device}")
-        Y, ldy, _, t = _rows(y.reshape(n, 1).float() if y.dim() == 1 else y.float(), "forest")
+        Y, ldy, t = _targets(y, n, dev, "forest")
         m_feat = max_features if isinstance(max_features, int) else max(1, int(max_features * d))
         if not 1 <= m_feat <= max(d, 1):
             raise ValueError(f"max_features = {max_features!r}: 1..{d} features")
         with _on_device(dev):
             lib = _lib.load()
-            listed = _listed(rows, n, dev)
+            listed = _listed(rows, n, dev, "forest")
             n_used = n if listed is None else int(listed.shape[0])
             if n_used < 1:
                 raise GaeHipError("forest: no rows to train on")
@@ -233,10 +170,7 @@ def forest(X, y, n_trees=100, *, max_depth=12, max_features=1.0, min_samples_lea
                     _lib.call("gae_forest_predict", _ptr(Xs), Xs.stride(0) if n_used > 1 else d, n_used, d, t, n_trees, M,
                               _ptr(feature), _ptr(threshold), _ptr(left), _ptr(value), _ptr(inbag), _ptr(oob),
                               _ptr(status), _stream())
-            if _ops.profiler is not None:
-                _ops.profiler.wrap(("forest", n_used, d, t, n_trees, max_depth, max_bins), launch)
-            else:
-                launch()
+            _timed(("forest", n_used, d, t, n_trees, max_depth, max_bins), launch)
             st = status.cpu()
             if int(st[1]) or int(st[0]):
                 raise GaeHipError(f"forest: the device reported error flags 0x{int(st[1]):x} and {int(st[0])} non-finite "
@@ -265,11 +199,7 @@ def forest_predict(result, X, status=None):
         if X.device != dev or d != result.edges.shape[0]:
             raise GaeHipError(f"forest_predict: X must be [m, {result.edges.shape[0]}] on {dev}, got {tuple(X.shape)} on "
                               f"{X.device}")
-        if status is None:
-            status = torch.zeros(STATUS_WORDS, dtype=torch.int64, device=dev)
-        elif not (isinstance(status, torch.Tensor) and status.dtype == torch.int64 and status.numel() == STATUS_WORDS
-                  and status.device == dev and status.is_contiguous()):
-            raise GaeHipError(f"forest_predict: status must be a contiguous int64 [{STATUS_WORDS}] tensor on {dev}")
+        status = _status_arg(status, STATUS_WORDS, dev, "forest_predict")
         out = torch.empty(m, t, dtype=torch.float64, device=dev)
         with _on_device(dev):
             _lib.call("gae_forest_predict", _ptr(X), ldx, m, d, t, T, M, _ptr(result.feature), _ptr(result.threshold),

@@ -8,11 +8,10 @@ import collections
 
 import torch
 
-import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _on_device, _ptr, _stream, _ws_bytes
-from .cluster import _rows
+from ._base import _on_device, _ptr, _stream, _timed, _ws_bytes
+from ._heads import _rows
 
 __all__ = ['KNNResult', 'knn', 'KNN_MAX_K', 'KNN_MAX_D', 'KNN_MAX_SPLITS']
 
@@ -76,8 +75,5 @@ def knn(Q, X=None, k=None, *, metric="l2", exclude_self=None, splits=0):
             def launch():
                 _lib.call("gae_knn", _ptr(Q), ldq, m, _ptr(X), ldx, n, d, k, _METRICS[metric], flags, int(splits),
                           _ptr(index), _ptr(value), kk, _ptr(ws), ws.numel(), _stream())
-            if _ops.profiler is not None:
-                _ops.profiler.wrap(("knn", m, n, d, k), launch)
-            else:
-                launch()
+            _timed(("knn", m, n, d, k), launch)
     return KNNResult(index, value)

@@ -13,9 +13,8 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _gpu, _on_device, _ptr, _stream, _ws_bytes
-from .cluster import _rows
-from .ridge import _choose, _fold_lists
+from ._base import _gpu, _on_device, _ptr, _stream, _timed, _ws_bytes
+from ._heads import _CV_PATH, _choose, _default_fold, _fold_arg, _fold_lists, _lambda_path, _rows, _status_arg
 
 __all__ = ['LogRegResult', 'logreg', 'logreg_predict', 'LOGREG_MAX_D', 'LOGREG_MAX_CLASSES', 'LOGREG_MAX_FOLDS',
            'LOGREG_MAX_LAMBDAS', 'LOGREG_CHUNK_ROWS', 'LOGREG_SLAB_CHUNKS']
@@ -63,20 +62,7 @@ class LogRegResult(collections.namedtuple("LogRegResult", [
 
 def _options(X, y, lambdas, folds, n_classes, max_iter, tol, check_every, model_batch):
     """the checks that need no device: (lambdas, F, c)"""
-    if isinstance(folds, bool) or int(folds) != folds or not 1 <= folds <= LOGREG_MAX_FOLDS:
-        raise ValueError(f"folds: an integer in 1..{LOGREG_MAX_FOLDS}, not {folds!r}")
-    if lambdas is None:
-        lambdas = [10.0 ** (e / 2.0) for e in range(-6, 7)] if int(folds) > 1 else [1.0]       # 10^-3 .. 10^3, 13 values
-    elif isinstance(lambdas, torch.Tensor):
-        lambdas = lambdas.detach().double().cpu().reshape(-1).tolist()
-    else:
-        lambdas = [float(v) for v in (lambdas if hasattr(lambdas, "__iter__") else [lambdas])]
-    if not 1 <= len(lambdas) <= LOGREG_MAX_LAMBDAS:
-        raise ValueError(f"lambdas: 1..{LOGREG_MAX_LAMBDAS} values, not {len(lambdas)}")
-    if not all(v >= 0.0 and math.isfinite(v) for v in lambdas):
-        raise ValueError(f"lambdas: finite values >= 0, not {lambdas!r}")
-    if int(folds) == 1 and len(lambdas) != 1:
-        raise ValueError(f"folds=1 is a plain fit without CV: it takes exactly one lambda, not {len(lambdas)}")
+    lambdas, folds = _lambda_path(lambdas, folds, LOGREG_MAX_LAMBDAS, [1.0] if folds == 1 else _CV_PATH, LOGREG_MAX_FOLDS)
     for name, v in (("max_iter", max_iter), ("check_every", check_every)):
         if isinstance(v, bool) or int(v) != v or not 1 <= v < 2 ** 31:
             raise ValueError(f"{name}: a positive integer, not {v!r}")
@@ -103,17 +89,7 @@ def _options(X, y, lambdas, folds, n_classes, max_iter, tol, check_every, model_
         raise ValueError(f"the number of classes c = {c} lies outside 2..{LOGREG_MAX_CLASSES}")
     if lo < -1 or hi >= c:
         raise ValueError(f"y: values in -1..{c - 1} (-1 = unlabelled), got {lo}..{hi}")
-    return lambdas, int(folds), c
-
-
-def _default_fold(n, F, seed):
-    if F == 1:
-        return torch.zeros(n, dtype=torch.int64)
-    g = torch.Generator(device="cpu").manual_seed(int(seed))
-    perm = torch.randperm(n, generator=g)
-    fold = torch.empty(n, dtype=torch.int64)
-    fold[perm] = torch.arange(n) % F                                   # a seeded permutation dealt round-robin
-    return fold
+    return lambdas, folds, c
 
 
 def logreg(X, y, lambdas=None, *, folds=5, fold=None, seed=0, n_classes=None, max_iter=1000, tol=1e-4, check_every=8,
@@ -143,11 +119,8 @@ def logreg(X, y, lambdas=None, *, folds=5, fold=None, seed=0, n_classes=None, ma
     n, d = X.shape
     if fold is None:
         fold = _default_fold(n, F, seed).to(y.device)
-    elif not isinstance(fold, torch.Tensor) or fold.dtype.is_floating_point or fold.dtype == torch.bool \
-            or fold.dim() != 1 or fold.shape[0] != n:
-        raise ValueError(f"fold: an int tensor [{n}] with values in -1..{F - 1}")
-    elif n and (int(fold.min()) < -1 or int(fold.max()) >= F):
-        raise ValueError(f"fold: values in -1..{F - 1} (-1 = left out), got {int(fold.min())}..{int(fold.max())}")
+    else:
+        _fold_arg(fold, n, F)
     fold = fold.to(y.device).long()
     fold = torch.where(y < 0, torch.full_like(fold, -1), fold)          # an unlabelled row is not listed
     rows, fold_ptr, counts = _fold_lists(fold, n, F, seed, y.device)    # (an empty fold: ValueError)
@@ -205,10 +178,7 @@ def logreg(X, y, lambdas=None, *, folds=5, fold=None, seed=0, n_classes=None, ma
                         break
                 for lo, cnt in cuts:
                     run_pass(lo, cnt, _lib.LOGREG_EVAL)
-            if _ops.profiler is not None:
-                _ops.profiler.wrap(("logreg", n_used, d, c, F, L), launch)
-            else:
-                launch()
+            _timed(("logreg", n_used, d, c, F, L), launch)
             host = torch.cat([rstatus.double(), status.double(), info.double().reshape(-1), nll.reshape(-1),
                               correct.double().reshape(-1)]).cpu()      # the one read of the tables
         bad, rerr, errors = int(host[0]), int(host[1]), int(host[6])
@@ -263,11 +233,7 @@ def logreg_predict(X, coef, intercept, pivot=None, *, proba=False, status=None):
             pivot = _gpu(pivot, "logreg_predict: pivot").detach().float().reshape(-1).contiguous()
             if pivot.shape[0] != d or pivot.device != dev:
                 raise GaeHipError(f"logreg_predict: pivot must hold d = {d} values on {dev}")
-        if status is None:
-            status = torch.zeros(STATUS_WORDS, dtype=torch.int64, device=dev)
-        elif not (isinstance(status, torch.Tensor) and status.dtype == torch.int64 and status.numel() == STATUS_WORDS
-                  and status.device == dev and status.is_contiguous()):
-            raise GaeHipError(f"logreg_predict: status must be a contiguous int64 [{STATUS_WORDS}] tensor on {dev}")
+        status = _status_arg(status, STATUS_WORDS, dev, "logreg_predict")
         labels = torch.empty(n, dtype=torch.int32, device=dev)
         P = torch.empty(n, c, dtype=torch.float32, device=dev) if proba else None
         with _on_device(dev):

@@ -13,9 +13,8 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _gpu, _on_device, _ptr, _stream, _ws_bytes
-from .cluster import _rows
-from .ridge import _choose, _fold_lists
+from ._base import _on_device, _ptr, _stream, _timed, _ws_bytes
+from ._heads import _check_seed, _choose, _fold_lists, _rows, _status_arg, _targets, _whole
 
 __all__ = ['MLPResult', 'mlp', 'mlp_predict', 'mlp_usable', 'mlp_load_head', 'MLP_MAX_WIDTH', 'MLP_MAX_T', 'MLP_MAX_MODELS', 'MLP_MAX_FOLDS',
            'MLP_LAUNCH_ROW_VISITS']
@@ -105,9 +104,6 @@ def mlp_usable(d, hidden, t):
 
 
 def _options(hidden, lrs, alphas, epochs, batch_size, folds, ensemble, seed, solver, momentum, shuffle, standardize):
-    def whole(v):
-        return not isinstance(v, bool) and isinstance(v, int)
-
     def values(v, name, low_ok):
         if isinstance(v, torch.Tensor):
             v = v.detach().double().cpu().reshape(-1).tolist()
@@ -117,13 +113,13 @@ def _options(hidden, lrs, alphas, epochs, batch_size, folds, ensemble, seed, sol
         return v
     hidden = _hidden(hidden)
     lrs, alphas = values(lrs, "lrs", False), values(alphas, "alphas", True)
-    if not whole(epochs) or not 1 <= epochs < 2 ** 31:
+    if not _whole(epochs) or not 1 <= epochs < 2 ** 31:
         raise ValueError(f"epochs: an integer >= 1, not {epochs!r}")
-    if not whole(batch_size) or not 1 <= batch_size < 2 ** 31:
+    if not _whole(batch_size) or not 1 <= batch_size < 2 ** 31:
         raise ValueError(f"batch_size: an integer >= 1, not {batch_size!r}")
-    if not whole(folds) or not 1 <= folds <= MLP_MAX_FOLDS:
+    if not _whole(folds) or not 1 <= folds <= MLP_MAX_FOLDS:
         raise ValueError(f"folds: an integer in 1..{MLP_MAX_FOLDS}, not {folds!r}")
-    if not whole(ensemble) or ensemble < 1:
+    if not _whole(ensemble) or ensemble < 1:
         raise ValueError(f"ensemble: an integer >= 1, not {ensemble!r}")
     C = len(lrs) * len(alphas)
     if folds == 1 and C != 1:
@@ -131,8 +127,7 @@ def _options(hidden, lrs, alphas, epochs, batch_size, folds, ensemble, seed, sol
     M = (folds + 1 if folds > 1 else 1) * C * ensemble
     if M > MLP_MAX_MODELS:
         raise ValueError(f"(folds + 1) * configurations * ensemble = {M} models, at most {MLP_MAX_MODELS} per call")
-    if not whole(seed) or not 0 <= seed < 2 ** 64:
-        raise ValueError(f"seed: an integer in 0..2^64 - 1, not {seed!r}")
+    _check_seed(seed)
     if solver not in ("adam", "sgd"):
         raise ValueError(f"solver: 'adam' or 'sgd', not {solver!r}")
     if isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0.0 <= momentum < 1.0:
@@ -193,11 +188,7 @@ def mlp(X, y, hidden=(100,), *, lrs=(1e-3,), alphas=(1e-4,), epochs=200, batch_s
     with torch.no_grad():
         X, ldx, n, d = _rows(X, "mlp")
         dev = X.device
-        y = _gpu(y, "mlp: y").detach()
-        if y.device != dev or y.dim() not in (1, 2) or y.shape[0] != n or not y.dtype.is_floating_point:
-            raise GaeHipError(f"mlp: y must be a float tensor [{n}] or [{n}, t] on {dev}, got {tuple(y.shape)} {y.dtype} "
-                              f"on {y.device}")
-        Y, ldy, _, t = _rows(y.reshape(n, 1).float() if y.dim() == 1 else y.float(), "mlp")
+        Y, ldy, t = _targets(y, n, dev, "mlp")
         slots = F + 1 if F > 1 else 1                                  # models per (configuration, member)
         M = slots * C * E
         h1, h2 = hidden[0], hidden[1] if len(hidden) > 1 else 0
@@ -261,10 +252,7 @@ def mlp(X, y, hidden=(100,), *, lrs=(1e-3,), alphas=(1e-4,), epochs=200, batch_s
                           _stream())
             for e0 in range(0, epochs, per_launch):
                 e1 = min(epochs, e0 + per_launch)
-                if _ops.profiler is not None:
-                    _ops.profiler.wrap(("mlp", n_used, d, hidden, t, M, e1 - e0), lambda: launch(e0, e1))
-                else:
-                    launch(e0, e1)
+                _timed(("mlp", n_used, d, hidden, t, M, e1 - e0), lambda: launch(e0, e1))
                 st = status.cpu()                                      # the launch cut's one read
                 if int(st[1]):
                     raise GaeHipError(f"mlp: the device reported error flags 0x{int(st[1]):x} (row lists)")
@@ -319,9 +307,8 @@ def mlp_predict(result, X, status=None):
         d0, t = result.weights[0].shape[2], result.weights[-1].shape[1]
         if X.device != dev or d != d0:
             raise GaeHipError(f"mlp_predict: X must be [n, {d0}] on {dev}, got {tuple(X.shape)} on {X.device}")
-        if status is not None and not (isinstance(status, torch.Tensor) and status.dtype == torch.int64
-                                       and status.numel() == STATUS_WORDS and status.device == dev and status.is_contiguous()):
-            raise GaeHipError(f"mlp_predict: status must be a contiguous int64 [{STATUS_WORDS}] tensor on {dev}")
+        if status is not None:                                         # (None: the kernel does not report)
+            _status_arg(status, STATUS_WORDS, dev, "mlp_predict")
         hidden = result.hidden
         out = torch.empty(E, n, t, dtype=torch.float32, device=dev)
         with _on_device(dev):

@@ -12,8 +12,8 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _gpu, _on_device, _ptr, _stream, _ws_bytes
-from .cluster import _rows
+from ._base import _gpu, _on_device, _ptr, _stream, _timed, _ws_bytes
+from ._heads import _listed, _rows
 
 __all__ = ['PCAResult', 'pca', 'pca_transform', 'PCA_MAX_D', 'PCA_MAX_SWEEPS']
 
@@ -41,24 +41,6 @@ class PCAResult(collections.namedtuple("PCAResult", [
         if self.whiten:
             Z = Z * torch.sqrt(self.explained_variance.clamp_min(0.0))
         return Z @ self.components + self.mean
-
-
-def _listed(rows, n, dev, who):
-    """int32 [n_used] row ids on the device, or None for all rows in order (``ops.forest``'s rule)"""
-    if rows is None:
-        return None
-    if not isinstance(rows, torch.Tensor) or rows.dim() != 1 or rows.dtype.is_floating_point or rows.dtype.is_complex:
-        raise GaeHipError(f"{who}: rows must be a 1-D int tensor of row ids or a bool mask [{n}]")
-    rows = _gpu(rows, f"{who}: rows")
-    if rows.device != dev:
-        raise GaeHipError(f"{who}: rows on {rows.device}, X on {dev}")
-    if rows.dtype == torch.bool:
-        if rows.shape[0] != n:
-            raise GaeHipError(f"{who}: a bool mask of {rows.shape[0]} entries for {n} rows")
-        return rows.nonzero().reshape(-1).to(torch.int32)
-    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n):
-        raise GaeHipError(f"{who}: row ids outside 0..{n - 1}")
-    return rows.to(torch.int32).contiguous()
 
 
 def pca(X, n_components=None, *, rows=None, whiten=False, pivot="mean"):
@@ -113,10 +95,7 @@ def pca(X, n_components=None, *, rows=None, whiten=False, pivot="mean"):
                           _ptr(fold_ptr), 1, _ptr(stats), _ptr(rstatus), _ptr(ws), ws.numel(), _stream())
                 _lib.call("gae_pca_solve", _ptr(stats), d, 1, _ptr(piv), n_used, k, 0, _ptr(mean), _ptr(values), _ptr(comps),
                           _ptr(status), _ptr(ws), ws.numel(), _stream())
-            if _ops.profiler is not None:
-                _ops.profiler.wrap(("pca", n_used, d, k), launch)
-            else:
-                launch()
+            _timed(("pca", n_used, d, k), launch)
             host = torch.cat([rstatus, status]).cpu()                      # the one read
         bad, errors = int(host[0]), int(host[1])
         info, sweeps = int(host[RIDGE_STATUS_WORDS]), int(host[RIDGE_STATUS_WORDS + 1])
@@ -165,8 +144,5 @@ def pca_transform(X, mean, components, values=None, whiten=False, *, rows=None, 
             def launch():
                 _lib.call("gae_pca_transform", _ptr(X), ldx, n, d, _ptr(listed), n_rows, _ptr(mean), _ptr(comps), _ptr(values),
                           k, _lib.PCA_WHITEN if whiten else 0, _ptr(Z), max(k, 1), _ptr(status), _stream())
-            if _ops.profiler is not None:
-                _ops.profiler.wrap(("pca_transform", n_rows, d, k), launch)
-            else:
-                launch()
+            _timed(("pca_transform", n_rows, d, k), launch)
     return Z

@@ -5,15 +5,13 @@ the final model follow from them in one more launch.  ``GAE.ridge_graphs``; ``py
 
 Part of the package gae_dgl_amd.ops; names are resolved through the package namespace (`_ops.<name>`) at call time."""
 import collections
-import math
 
 import torch
 
-import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _gpu, _on_device, _ptr, _stream, _ws_bytes
-from .cluster import _rows
+from ._base import _gpu, _on_device, _ptr, _stream, _timed, _ws_bytes
+from ._heads import _CV_PATH, _choose, _fold_lists, _lambda_path, _rows, _targets
 
 __all__ = ['RidgeResult', 'ridge', 'RIDGE_MAX_D', 'RIDGE_MAX_T', 'RIDGE_MAX_FOLDS', 'RIDGE_MAX_LAMBDAS', 'RIDGE_CHUNK_ROWS']
 
@@ -38,64 +36,12 @@ class RidgeResult(collections.namedtuple("RidgeResult", [
 
 
 def _options(lambdas, folds, fit_intercept, pivot):
-    if isinstance(folds, bool) or int(folds) != folds or not 1 <= folds <= RIDGE_MAX_FOLDS:
-        raise ValueError(f"folds: an integer in 1..{RIDGE_MAX_FOLDS}, not {folds!r}")
-    if lambdas is None:
-        lambdas = [10.0 ** (e / 2.0) for e in range(-6, 7)]            # 10^-3 .. 10^3, 13 values
-    elif isinstance(lambdas, torch.Tensor):
-        lambdas = lambdas.detach().double().cpu().reshape(-1).tolist()
-    else:
-        lambdas = [float(v) for v in (lambdas if hasattr(lambdas, "__iter__") else [lambdas])]
-    if not 1 <= len(lambdas) <= RIDGE_MAX_LAMBDAS:
-        raise ValueError(f"lambdas: 1..{RIDGE_MAX_LAMBDAS} values, not {len(lambdas)}")
-    if not all(v >= 0.0 and math.isfinite(v) for v in lambdas):
-        raise ValueError(f"lambdas: finite values >= 0, not {lambdas!r}")
-    if int(folds) == 1 and len(lambdas) != 1:
-        raise ValueError(f"folds=1 is a plain fit without CV: it takes exactly one lambda, not {len(lambdas)}")
+    lambdas, folds = _lambda_path(lambdas, folds, RIDGE_MAX_LAMBDAS, _CV_PATH, RIDGE_MAX_FOLDS)
     if not isinstance(fit_intercept, bool):
         raise ValueError(f"fit_intercept: True or False, not {fit_intercept!r}")
     if not (pivot is None or isinstance(pivot, torch.Tensor) or pivot == "mean"):
         raise ValueError(f"pivot: 'mean', None or a [d + t] tensor, not {pivot!r}")
-    return lambdas, int(folds)
-
-
-def _fold_lists(fold, n, F, seed, dev):
-    """(rows int32 [n_used], fold_ptr int32 [F + 1], counts int64 [F] on the host): the rows stably sorted by fold, -1
-    (left out) dropped"""
-    if fold is None:
-        if F == 1:
-            fold = torch.zeros(n, dtype=torch.int64, device=dev)
-        else:
-            g = torch.Generator(device="cpu").manual_seed(int(seed))
-            perm = torch.randperm(n, generator=g)
-            fold = torch.empty(n, dtype=torch.int64)
-            fold[perm] = torch.arange(n) % F                           # a seeded permutation dealt round-robin
-            fold = fold.to(dev)
-    else:
-        if not isinstance(fold, torch.Tensor) or fold.dtype.is_floating_point or fold.dtype == torch.bool \
-                or fold.dim() != 1 or fold.shape[0] != n:
-            raise ValueError(f"fold: an int tensor [{n}] with values in -1..{F - 1}")
-        fold = fold.to(dev).long()
-        if n and (int(fold.min()) < -1 or int(fold.max()) >= F):
-            raise ValueError(f"fold: values in -1..{F - 1} (-1 = left out), got {int(fold.min())}..{int(fold.max())}")
-    counts = torch.bincount(fold + 1, minlength=F + 1)[1:].cpu()
-    if int(counts.min()) == 0:
-        raise ValueError(f"fold: fold {int(counts.argmin())} holds no rows (sizes {counts.tolist()})")
-    key = torch.where(fold < 0, torch.full_like(fold, F), fold)
-    order = torch.sort(key, stable=True).indices
-    n_used = int(counts.sum())
-    rows = order[:n_used].to(torch.int32).contiguous()
-    fold_ptr = torch.cat([torch.zeros(1, dtype=torch.int64), counts.cumsum(0)]).to(torch.int32).to(dev)
-    return rows, fold_ptr, counts
-
-
-def _choose(ok, score):
-    """index of the smallest score among the eligible lambdas, the LOWER index among equal scores; -1: none"""
-    best = -1
-    for l, (good, v) in enumerate(zip(ok, score)):
-        if good and not math.isnan(v) and (best < 0 or v < score[best]):
-            best = l                                                   # a strict <: ties go to the lower index
-    return best
+    return lambdas, folds
 
 
 def ridge(X, y, lambdas=None, *, folds=5, fold=None, seed=0, fit_intercept=True, pivot="mean"):
@@ -114,11 +60,7 @@ def ridge(X, y, lambdas=None, *, folds=5, fold=None, seed=0, fit_intercept=True,
     with torch.no_grad():
         X, ldx, n, d = _rows(X, "ridge")
         dev = X.device
-        y = _gpu(y, "ridge: y").detach()
-        if y.device != dev or y.dim() not in (1, 2) or y.shape[0] != n or not y.dtype.is_floating_point:
-            raise GaeHipError(f"ridge: y must be a float tensor [{n}] or [{n}, t] on {dev}, got {tuple(y.shape)} "
-                              f"{y.dtype} on {y.device}")
-        Y, ldy, _, t = _rows(y.reshape(n, 1).float() if y.dim() == 1 else y.float(), "ridge")
+        Y, ldy, t = _targets(y, n, dev, "ridge")
         L, W = len(lambdas), 1 + d + t
         with _on_device(dev):
             nbytes = _ws_bytes("gae_ridge_workspace_bytes", n, d, t, F)     # shape errors before any other work
@@ -150,10 +92,7 @@ def ridge(X, y, lambdas=None, *, folds=5, fold=None, seed=0, fit_intercept=True,
                           _ptr(fold_ptr), F, _ptr(stats), _ptr(status), _ptr(ws), ws.numel(), _stream())
                 _lib.call("gae_ridge_solve", _ptr(stats), d, t, F, _ptr(piv), _ptr(lam_dev), L, flags, _ptr(coef),
                           _ptr(icpt), _ptr(sse), _ptr(info), _ptr(status), _stream())
-            if _ops.profiler is not None:
-                _ops.profiler.wrap(("ridge", n_used, d, t, F, L), launch)
-            else:
-                launch()
+            _timed(("ridge", n_used, d, t, F, L), launch)
             # SST of the listed rows about their overall mean, from the moments: S_yy - S_y^2 / c per target
             total = stats.sum(0)
             iy = [(1 + d + j) * W - (1 + d + j) * (d + j) // 2 for j in range(t)]

@@ -10,10 +10,9 @@ import collections
 
 import torch
 
-import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _on_device, _ptr, _stream, _ws_bytes
+from ._base import _on_device, _ptr, _stream, _timed, _ws_bytes
 
 __all__ = ['SpectralResult', 'spectral_embedding', 'SPECTRAL_MAX_K', 'SPECTRAL_MAX_B', 'SPECTRAL_MAX_DEGREE']
 
@@ -137,10 +136,7 @@ def spectral_embedding(graph, k=16, *, self_loops=False, oversample=None, degree
                     rest = [t for t in blocks if t is not cur]
                     V, AV, P, Q = cur, rest[0], rest[1], rest[2]
 
-            if _ops.profiler is not None:
-                V, n_iter, n_spmm, converged = _ops.profiler.wrap(("spectral", n, nnz, b), run)
-            else:
-                V, n_iter, n_spmm, converged = run()
+            V, n_iter, n_spmm, converged = _timed(("spectral", n, nnz, b), run)
             first = 1 if drop_first else 0
             _lib.call("gae_spectral_finish", _ptr(V), n, b, first, k, _ptr(values), _ptr(s), _SCALINGS[scaling], _ptr(vectors),
                       _ptr(embedding), _ptr(ws), ws.numel(), _stream())

@@ -12,8 +12,8 @@ import torch
 import gae_dgl_amd.ops as _ops
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _f32, _gpu, _on_device, _ptr, _stream, _ws_bytes
-from .cluster import _rows
+from ._base import _f32, _gpu, _on_device, _ptr, _stream, _timed, _ws_bytes
+from ._heads import _rows
 from .knn import KNN_MAX_D, KNN_MAX_K
 
 __all__ = ['TSNEResult', 'tsne', 'tsne_affinities', 'tsne_symmetrise', 'tsne_init', 'tsne_chunk', 'TSNEState']
@@ -58,10 +58,7 @@ def tsne_affinities(index, dist2, perplexity):
         def launch():
             _lib.call("gae_tsne_affinities", _ptr(index), _ptr(dist2), max(k, 1), n, k, float(perplexity), _ptr(p),
                       max(k, 1), _ptr(perp), _stream())
-        if _ops.profiler is not None:
-            _ops.profiler.wrap(("tsne_affinities", n, k), launch)
-        else:
-            launch()
+        _timed(("tsne_affinities", n, k), launch)
     return p[:, :k], perp
 
 
@@ -237,10 +234,7 @@ def tsne(X, *, perplexity=20.0, n_iter=1000, learning_rate="auto", early_exagger
 
                     def launch():
                         state.step(float(early_exaggeration) if early else 1.0, 0.5 if early else 0.8, eta, min_grad_norm)
-                    if _ops.profiler is not None:
-                        _ops.profiler.wrap(("tsne_step", n, state.nnz), launch)
-                    else:
-                        launch()
+                    _timed(("tsne_step", n, state.nnz), launch)
                 enqueued += group
                 last = state.read()                                     # the one host read of the group
                 if last["nonfinite"]:

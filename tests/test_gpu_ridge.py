@@ -144,6 +144,33 @@ def test_a_fold_without_rows_and_rows_that_no_fold_owns(dev):
     assert np.array_equal(got, R.moments(X, Y, rows, fold_ptr)) and not got[2].any() and got[0].any()
 
 
+def test_a_fold_shorter_than_a_chunk_between_two_longer_ones_and_no_row_list(dev):
+    """folds of C + 1, 7 and C + 5 rows: chunks 0-1, 2 and 3-4 of a grid of cdiv(2 C + 13, C) + 3 = 6 blocks, the last one
+    spare; then the same rows without a list (rows == NULL: one fold; that grid is cdiv(n, C) blocks and has no spare
+    one).  Exact as the grid cases"""
+    rng = np.random.default_rng(11)
+    n, d, t, F = 2 * C + 13 + 9, 17, 3, 3
+    X, Y, pivot = grid(rng, n, d), grid(rng, n, t), grid(rng, 1, d + t)[0]
+    fold = np.full(n, -1)
+    listed = rng.permutation(n)[:2 * C + 13]                           # 9 rows are left out
+    fold[listed[:C + 1]], fold[listed[C + 1:C + 8]], fold[listed[C + 8:]] = 0, 1, 2
+    X[fold < 0] = NAN
+    Y[fold < 0] = NAN
+    rows, fold_ptr = R.fold_lists(fold, F)
+    assert np.diff(fold_ptr).tolist() == [C + 1, 7, C + 5]
+    got, status = raw_stats(strided(X, 3, dev), strided(Y, 2, dev), pivot, torch.from_numpy(rows).to(dev),
+                            torch.from_numpy(fold_ptr).to(dev), F)
+    assert status.tolist() == [0, 0, 0, 0]
+    want = R.moments(X, Y, rows, fold_ptr, pivot)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:4]
+    Xl, Yl = X[fold >= 0], Y[fold >= 0]
+    got, status = raw_stats(strided(Xl, 3, dev), strided(Yl, 2, dev), pivot, None, None, 1)
+    assert status.tolist() == [0, 0, 0, 0]
+    want = R.moments(Xl, Yl, None, None, pivot)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:4]
+    assert np.array_equal(got[0], R.moments(X, Y, rows, fold_ptr, pivot).sum(0))       # exact sums: the folds add up
+
+
 # ------------------------------------------------------------------ 2. the same bits
 @pytest.mark.parametrize("n, d, t", [(2 * C + 3, 48, 1), (33 * C + 5, 16, 2)])
 def test_same_bits_run_to_run_for_any_stride_and_through_the_row_list(dev, n, d, t):

@@ -181,6 +181,30 @@ def test_gram_bound_and_determinism(name):
     assert torch.equal(G, G3) and torch.equal(H, H3)
 
 
+@pytest.mark.parametrize("max_blocks", [0, 1])
+@pytest.mark.parametrize("n", [1, 256 + 7, 33 * 256 + 5])
+@pytest.mark.parametrize("b", [2, 18, 128])
+def test_gram_exact_on_integers(b, n, max_blocks):
+    """V and AV hold integers in -3..3, so every product and every sum is exact in any order: the upper triangles of G and
+    H ARE V^T V and V^T AV (int64), the lower triangles their mirrors -- the kernel's contract, V^T AV itself is not
+    symmetric here.  b: one tile, a ragged second tile, all 36 tile pairs; n: one short chunk, a ragged second chunk, 34
+    chunks (the 64-lane order of the partials); on the default grid and on one block"""
+    from gae_dgl_amd import _lib
+    assert _lib.SPECTRAL_CHUNK_ROWS == 256
+    rng = np.random.default_rng(1000 * b + n)
+    V, AV = rng.integers(-3, 4, (n, b)), rng.integers(-3, 4, (n, b))
+    nbytes = _lib.load().gae_spectral_workspace_bytes(n, 0, b)
+    assert nbytes > 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    G, H = (torch.full((b, b), float("nan"), dtype=torch.float64, device=DEV) for _ in range(2))
+    Vd, Ad = dev(V, torch.float64), dev(AV, torch.float64)
+    _lib.call("gae_spectral_gram", _ptr(Vd), _ptr(Ad), n, b, _ptr(G), _ptr(H), max_blocks, _ptr(ws), nbytes, _stream())
+    iu, il = np.triu_indices(b), np.tril_indices(b, -1)
+    for got, want in ((host(G), V.T @ V), (host(H), V.T @ AV)):
+        assert np.array_equal(got[iu], want[iu].astype(np.float64)), np.argwhere(np.triu(got != want))[:4]
+        assert np.array_equal(got[il], got.T[il])
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_solve_rotate_finish_bit_for_bit(name):
     """gae_spectral_solve from the device's own G and H gives the restatement's T, Ritz values, coefficients and info;

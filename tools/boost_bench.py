@@ -53,7 +53,7 @@ def main():
     a = ap.parse_args()
     from gae_dgl_amd import _lib, ops
     from gae_dgl_amd.ops import _ptr, _stream
-    from gae_dgl_amd.ops.logreg import _default_fold
+    from gae_dgl_amd.ops._heads import _default_fold
     try:
         if a.no_sklearn:
             raise ImportError("--no_sklearn")

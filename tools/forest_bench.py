@@ -51,7 +51,7 @@ def main():
     a = ap.parse_args()
     from gae_dgl_amd import _lib, ops
     from gae_dgl_amd.ops import _ptr, _stream
-    from gae_dgl_amd.ops.forest import _edges
+    from gae_dgl_amd.ops._heads import _edges
     try:
         if a.no_sklearn:
             raise ImportError("--no_sklearn")

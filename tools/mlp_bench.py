@@ -100,7 +100,7 @@ def main():
     import bench
     from gae_dgl_amd import _lib, ops
     from gae_dgl_amd.ops import _ptr, _stream
-    from gae_dgl_amd.ops.ridge import _fold_lists
+    from gae_dgl_amd.ops._heads import _fold_lists
     try:
         if a.no_sklearn:
             raise ImportError("--no_sklearn")
