@@ -13,7 +13,7 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(LIBDIR, "libgae_hip.so")
 SOURCES = ["api.hip", "csr_build.hip", "plan_build.hip", "spmm.hip", "spmm_ell.hip", "dense.hip", "xw.hip", "tall.hip", "spfeat.hip", "decoder_bce.hip", "optim.hip", "readout.hip", "bce_dense.hip", "decoder_graphs.hip", "decoder_topk.hip", "decoder_sampled.hip",
-           "decoder_rank.hip", "decoder_threshold.hip", "embed.hip", "embed_bwd.hip", "kmeans.hip", "knn.hip", "ridge.hip", "forest.hip", "mlp.hip", "logreg.hip", "tsne.hip", "boost.hip", "pca.hip", "spectral.hip"]
+           "decoder_rank.hip", "decoder_threshold.hip", "embed.hip", "embed_bwd.hip", "kmeans.hip", "knn.hip", "ridge.hip", "forest.hip", "mlp.hip", "logreg.hip", "tsne.hip", "boost.hip", "pca.hip", "spectral.hip", "fingerprint.hip", "tanimoto.hip"]
 ARCH = "gfx950"
 # per-file extra flags.  decoder_bce: let MFMA accumulators live in VGPRs (gfx950 has a unified file) so the
 # VALU epilogue of every tile does not pay one v_accvgpr_read per logit.

@@ -254,6 +254,11 @@ SIGNATURES = {
     "gae_spectral_solve": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p]),
     "gae_spectral_rotate": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _d, _p, _p, _p, _i64, _p]),
     "gae_spectral_finish": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _int, _p, _p, _p, _i64, _p]),
+    "gae_fingerprint_workspace_bytes": (_i64, [_i64]),
+    "gae_fingerprint_graphs": (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _p, _i64, _int, _i64, _int, _p, _i64,
+                                      _p, _i64, _p]),
+    "gae_tanimoto_knn_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _int]),
+    "gae_tanimoto_knn": (_int, [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _int, _int, _p, _p, _i64, _p, _i64, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

@@ -284,6 +284,22 @@ class DeviceGraphDataset(Dataset):
         replicas -- every replica draws the SAME epoch order (same seed) and keeps its share of it"""
         return DeviceLoader(self, batch_size, shuffle, seed, shard)
 
+    # -------------------------------------------------------------- circular fingerprints
+    def fingerprints(self, radius=2, n_bits=1024, counts=False):
+        """int32 [len(self), n_bits / 32] bit words (``counts=True``: int32 [len(self), n_bits] slot counts): the circular
+        fingerprint of every graph of this set or ``subset()`` view, rows in the order of ``self.ids``
+        (``ops.fingerprint_graphs``: one launch per radius over the atoms of the listed graphs).  Called on a batched
+        ``Graph`` -- ``DeviceGraphDataset.fingerprints(g)`` -- its member graphs are taken through ``g.graph_ptr()``,
+        ``g.csr()`` and ``g.ndata['h']``, rows in member order."""
+        if isinstance(self, DeviceGraphDataset):
+            whole = len(self.ids) == len(self.sizes_host) and np.array_equal(self.ids, np.arange(len(self.ids)))
+            gids = None if whole else torch.from_numpy(np.ascontiguousarray(self.ids)).to(self.device)
+            return ops.fingerprint_graphs(self.graph_ptr, self.indptr, self.indices, self.feat, radius=radius,
+                                          n_bits=n_bits, counts=counts, graph_ids=gids)
+        indptr, indices = self.csr()
+        return ops.fingerprint_graphs(self.graph_ptr(), indptr, indices, self.ndata['h'], radius=radius, n_bits=n_bits,
+                                      counts=counts)
+
     # -------------------------------------------------------------- flat on-disk format
     @staticmethod
     def save(path, graph_ptr, src, dst, feat):

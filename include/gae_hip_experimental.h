@@ -14,7 +14,8 @@
  * and gae_kmeans_*, node clustering on the device: k-means++ seeding, Lloyd iterations and assignment over an embedding,
  * and gae_knn, the exact k nearest rows of one embedding for every row of another,
  * and gae_ridge_*, ridge regression on a frozen feature: per-fold fp64 moments in one pass, the k-fold CV lambda path,
- * and gae_logreg_*, softmax regression on a frozen feature: every fold x lambda model of a CV call in the same launches.
+ * and gae_logreg_*, softmax regression on a frozen feature: every fold x lambda model of a CV call in the same launches,
+ * and gae_fingerprint_graphs / gae_tanimoto_knn, circular fingerprints of a resident molecule set and their exact search.
  * Same conventions as gae_hip.h: caller-owned buffers, 0 / negative / hipError_t return codes, asynchronous launches on
  * the stream passed last.  These signatures may change between versions without a GAE_VERSION major bump. */
 #ifndef GAE_HIP_EXPERIMENTAL_H
@@ -1322,6 +1323,64 @@ int gae_spectral_rotate(double *V, double *AV, int64_t n, int64_t b, int64_t k, 
 int gae_spectral_finish(const double *V, int64_t n, int64_t b, int64_t first, int64_t k, const double *values, const double *s,
                         int scaling, double *vectors, float *embedding, void *workspace, int64_t workspace_bytes,
                         void *stream);
+
+/* ---- K33: circular fingerprints of the member graphs of a resident molecule set (ops.fingerprint_graphs)
+ * A Morgan / Weisfeiler-Lehman fingerprint on what the set stores: the featuriser rows as atom invariants, the
+ * block-diagonal CSR as neighbourhoods.  The set holds no bond orders, so the bits are NOT RDKit's ECFP: the same family
+ * of descriptor, not the same numbers.  All arithmetic is uint64 and wrapping; no float is used anywhere.
+ *   mix(x)     the splitmix64 finaliser: x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb;
+ *              x ^= x >> 31.   GOLD = 0x9e3779b97f4a7c15.
+ *   RADIUS 0   h = GOLD; for f = 0 .. f_in - 1 ascending: h = mix(h ^ bits_f); id_0(v) = h.  bits_f is the fp32 bit pattern
+ *              of feature f of atom v, zero-extended, -0.0 taken as +0.0; a GAE_U8 feature contributes the pattern of its
+ *              value as fp32 (the same fingerprints in either storage); non-finite values hash by their bits.
+ *   RADIUS r   id_r(v) = mix(mix(id_{r-1}(v) + r GOLD) + sum_u mix(id_{r-1}(u))), u over the entries of v's CSR row (a
+ *              duplicate entry counts twice; a column outside the graph's own node range is skipped).  The sum commutes:
+ *              the result does not depend on the order of the row, the edge list or the atoms.
+ *   EMISSION   every (v, r), 0 <= r <= radius, contributes slot id_r(v) mod n_bits.  counts = 0: the bit is set; out is
+ *              int32 words [n_out, n_bits / 32], bit j of word w is slot 32 w + j.  counts = 1: the slot is incremented;
+ *              out is int32 [n_out, n_bits].  Structurally duplicate neighbourhoods are not removed.
+ * Row k of out belongs to graph graph_ids[k] (NULL: graph k; any order, repeats allowed); rows are ldo int32 apart and
+ * only their first n_bits / 32 (or n_bits) columns are written: they are zeroed here, on the caller's stream.
+ * One launch per radius; launch r reads id_{r-1} from, and writes id_r to, the workspace (two uint64 arrays indexed by
+ * global node id).  Integer atomicOr / atomicAdd only: the same bits run to run.  Work is proportional to the atoms of
+ * the listed graphs; a graph of any size is walked in strides (0 nodes: a zero row).
+ * SAFETY  a graph id outside [0, n_graphs) or a node range outside [0, n_nodes] gives a zero row; a row pointer outside
+ * [0, n_edges] reads as an empty row: nothing outside the arrays is read or written.
+ * feat: [n_nodes, f_in] of feat_dtype GAE_F32 or GAE_U8, rows ldf elements apart, no alignment asked.
+ * radius 0 .. 8, n_bits a power of two in 64 .. 2048 (else GAE_E_RANGE), f_in >= 1, n_nodes, n_edges < 2^31 (GAE_E_SIZE).
+ * Argument errors are returned before anything is dereferenced or launched: the above, an unknown feat_dtype
+ * (GAE_E_DTYPE), ldf < f_in or ldo below the row width (GAE_E_SIZE), NULL graph_ptr / indptr / feat (n_nodes > 0) /
+ * indices (n_edges > 0) / out (n_out > 0) / workspace (GAE_E_NULL), a short workspace (GAE_E_WORKSPACE). */
+int64_t gae_fingerprint_workspace_bytes(int64_t n_nodes);
+
+int gae_fingerprint_graphs(const int64_t *graph_ptr, int64_t n_graphs, int64_t n_nodes, int64_t n_edges,
+                           const int32_t *indptr, const int32_t *indices, const void *feat, int feat_dtype, int64_t ldf,
+                           int64_t f_in, const int64_t *graph_ids, int64_t n_out, int radius, int64_t n_bits, int counts,
+                           int32_t *out, int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- K34: exact Tanimoto k-nearest-neighbour search over bit fingerprints (ops.tanimoto_knn)
+ * For every query row of Q int32 [m, n_words] (rows ldq words apart) the k rows of the database X int32 [n, n_words]
+ * (ldx) of the largest Tanimoto similarity, without the m x n matrix.  Rows are read in place; no alignment is asked.
+ * VALUE  a = popcount(q), b = popcount(x), c = popcount(q & x), u = a + b - c: the correctly rounded fp32 quotient
+ *   float(c) / float(u), or 0.0f when u = 0.  For u <= 4096 (n_words <= 64) different fractions never share an fp32
+ *   quotient and the quotients keep the exact order, so the order by value is the order by the exact fraction.
+ * CANDIDATES of query i: every database row j in [0, n), minus j = i under GAE_KNN_EXCLUDE_SAME_INDEX (for Q = X).
+ * ORDER OF A ROW  (value descending, j ascending).  Fewer than k candidates pad the tail with index -1 and value -inf.
+ * DETERMINISM  No float atomics, ordinary launches only: the same bits run to run, for any ldq / ldx / ldo and `splits`.
+ *   index_out int32 [m, ldo >= k], value_out fp32 [m, ldo >= k]: nothing beyond column k is written
+ *   splits    column splits per group of 256 queries: 0 = auto, else 1 .. 16
+ *   workspace at least gae_tanimoto_knn_workspace_bytes(m, n, n_words, k, splits) bytes: a pure host function, positive,
+ *             non-decreasing in m, n, k and splits; a negative error code for a shape error.  O(n + m k splits) bytes
+ * 1 <= n_words <= 64, 1 <= k <= 64 (else GAE_E_RANGE); 0 <= m, n < 2^31 (else GAE_E_SIZE).  Argument errors are returned
+ * before anything is dereferenced or launched: the shape errors, splits outside 0..16, an unknown flag bit (GAE_E_RANGE),
+ * ldq < n_words, ldx < n_words, ldo < k (GAE_E_SIZE), NULL index_out / value_out / Q (m > 0), NULL X (m, n > 0), NULL
+ * workspace (GAE_E_NULL), a short workspace (GAE_E_WORKSPACE).
+ * Launches: the database rows' bit counts, the sweep (k-best tail of csrc/topk_heap.h), the merge of the splits' lists. */
+int64_t gae_tanimoto_knn_workspace_bytes(int64_t m, int64_t n, int64_t n_words, int64_t k, int splits);
+
+int gae_tanimoto_knn(const int32_t *Q, int64_t ldq, int64_t m, const int32_t *X, int64_t ldx, int64_t n, int64_t n_words,
+                     int64_t k, int flags, int splits, int32_t *index_out, float *value_out, int64_t ldo, void *workspace,
+                     int64_t workspace_bytes, void *stream);
 
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
