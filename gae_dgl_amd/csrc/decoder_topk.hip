@@ -8,13 +8,12 @@
 // every size measured), each feature behind its own bounds test.  Every lane's 16 scores belong to ONE row, so the
 // threshold test needs no cross-lane traffic.
 //
-// Selection (topk_heap.h, shared with K24: offer_tile, merge_halves, merge_kernel).  Each lane keeps a running top-k of
-// its (row, lane half) in LDS as a heap with the worst entry at the root.  Per tile the fast path is the max of the
-// lane's 16 scores against the lane's k-th score (about 0.5 VALU op per pair); only lanes
-// with a passing score store the tile to an LDS scratch row and walk the passing columns: window, self, a 64-bit hash
-// of the CSR row (the row's indices are scanned only on a hash hit; any order, repeats allowed) and the heap insert.
-// One heapsort at the end turns each heap into a list sorted best first.
-// NaN and -inf never pass (the threshold starts at -FLT_MAX).
+// Selection (topk_heap.h, shared with K24 and K34: offer_tile, merge_halves, merge_kernel).  Each lane keeps a running
+// top-k of its (row, lane half) in LDS as a heap with the worst entry at the root.  Per tile the fast path is the max
+// of the lane's 16 scores against the lane's k-th score (about 0.5 VALU op per pair); only lanes with a passing score
+// store the tile to an LDS scratch row and walk the passing columns: window, self, a 64-bit hash of the CSR row (the
+// row's indices are scanned only on a hash hit; any order, repeats allowed) and the heap insert. One heapsort at the
+// end turns each heap into a list sorted best first. NaN and -inf never pass (the threshold starts at -FLT_MAX).
 //
 // Output.  The two lane halves of a row merge their lists in the wave.  With one column split the merged list is the
 // row of the output; with S > 1 splits every (panel, split) wave writes a sorted partial list to the workspace and a
@@ -162,7 +161,7 @@ extern "C" int gae_decoder_topk(const float *Z, int64_t ldz, int64_t n, int64_t 
     a.k = int(k); a.score_out = score_out; a.index_out = index_out; a.ldo = ldo;
     a.part_s = reinterpret_cast<float *>(static_cast<char *>(workspace) + 256);
     a.part_j = reinterpret_cast<int32_t *>(a.part_s + (S > 1 ? int64_t(S) * n * k : 0));
-    const size_t lds = size_t(2 * k + 16) * 64 * 4;
+    const size_t lds = size_t(lists_bytes(int(k)));
     hipStream_t st = gae::as_stream(stream);
     dispatch(d, [&](auto dh, auto one) {
         hipLaunchKernelGGL((topk_kernel<dh, one>), dim3(unsigned(panels * S)), dim3(64), lds, st, a);

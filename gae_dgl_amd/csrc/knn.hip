@@ -27,76 +27,35 @@
 #include <float.h>
 
 #include "decoder_pairs.h"
+#include "row_search.h"
 #include "topk_heap.h"
 
 namespace {
 
 using namespace gae::pairs;
+using namespace gae::search;
 using namespace gae::topk;
-
-constexpr int kMaxK = 64, kMaxD = 256;
-constexpr int64_t kLdsLimit = 160 * 1024;
-constexpr int kTargetBlocks = 1024;        // auto split: about four blocks per CU
-
-struct KnnArgs {
-    const float *Q, *X;
-    int64_t ldq, ldx, ldo;
-    int m, n, d, k, nch, S;
-    int l2, excl_same;
-    const float *half;                     // [n] (L2)
-    float *value_out;
-    int32_t *index_out;
-    float *part_s;                         // [S][m][k] (S > 1)
-    int32_t *part_j;
-};
-
 using gae::cdiv;
+
+constexpr int kMaxD = 256;
+constexpr int64_t kLdsLimit = 160 * 1024;
+
+struct KnnArgs : SearchArgs {
+    const float *Q, *X;
+    int d, nch, l2;
+    const float *half;                     // [n] (L2)
+};
 
 inline int64_t sweep_lds(int nw, int64_t d, int64_t k)
 {
-    return int64_t(nw) * (2 * k + 16) * 256 + 2 * kTile * (2 * dh_of(d) + 4) * 4 + 2 * kTile * 4;
+    return int64_t(nw) * lists_bytes(int(k)) + 2 * kTile * (2 * dh_of(d) + 4) * 4 + 2 * kTile * 4;
 }
 inline int waves_of(int64_t d, int64_t k) { return sweep_lds(4, d, k) <= kLdsLimit ? 4 : 2; }
 
-// column splits per block: the caller's, or (0 = auto) enough for ~kTargetBlocks blocks with parts of >= 256 rows
-inline int splits_of(int64_t m, int64_t n, int64_t d, int64_t k, int splits)
+// the workspace: |x|^2 / 2 of the corpus in front of the partial lists, whose bound is for blocks of at most 4 panels
+int plan(const char *fn, int64_t m, int64_t n, int64_t d, int64_t k, int splits, void *ws, Plan<float> &p)
 {
-    if (splits > 0) return splits;
-    if (m <= 0 || n <= 0) return 1;
-    const int64_t blocks = cdiv(m, int64_t(kRows) * waves_of(d, k));
-    int64_t S = cdiv(kTargetBlocks, blocks);
-    const int64_t by_span = cdiv(n, 256);
-    S = S < by_span ? S : by_span;
-    return int(S < 1 ? 1 : (S > kMaxSplits ? kMaxSplits : S));
-}
-
-// entries of the partial lists the workspace holds: a bound of S m that never shrinks as m, n or splits grow
-// (auto: S <= kTargetBlocks / blocks + 1 and m <= 128 blocks, S <= 16, S <= ceil(n / 256))
-inline int64_t part_rows(int64_t m, int64_t n, int splits)
-{
-    if (splits > 0) return int64_t(splits) * m;
-    int64_t b = int64_t(kMaxSplits) * m;
-    const int64_t by_blocks = int64_t(kTargetBlocks) * kRows * 4 + m, by_span = cdiv(n, 256) * m;
-    b = b < by_blocks ? b : by_blocks;
-    return b < by_span ? b : by_span;
-}
-
-// the workspace regions (NULL for the size query): |x|^2 / 2 of the corpus, the partial lists (scores, then indices)
-struct Plan { float *half, *part; int64_t need; };
-
-int plan(const char *fn, int64_t m, int64_t n, int64_t d, int64_t k, int splits, void *ws, Plan &p)
-{
-    GAE_REQUIRE(d >= 1 && d <= kMaxD, GAE_E_RANGE, "%s: d = %lld outside 1..256", fn, (long long)d);
-    GAE_REQUIRE(k >= 1 && k <= kMaxK, GAE_E_RANGE, "%s: k = %lld outside 1..64", fn, (long long)k);
-    GAE_REQUIRE(m >= 0 && n >= 0, GAE_E_SIZE, "%s: negative m = %lld or n = %lld", fn, (long long)m, (long long)n);
-    GAE_REQUIRE(m < (int64_t(1) << 31) && n < (int64_t(1) << 31), GAE_E_SIZE, "%s: m = %lld or n = %lld beyond int32 indices",
-                fn, (long long)m, (long long)n);
-    GAE_REQUIRE(splits >= 0 && splits <= kMaxSplits, GAE_E_RANGE, "%s: splits = %d outside 0..16", fn, splits);
-    gae::Carver c(ws);
-    p.half = c.take<float>(n);
-    p.part = c.take<float>(2 * part_rows(m, n, splits) * k);
-    p.need = c.bytes() + 256;
-    return GAE_OK;
+    return carve(fn, "d", d, kMaxD, m, n, k, splits, kRows * 4, ws, p);
 }
 
 // ------------------------------------------------------------------------------------------------------ half
@@ -266,7 +225,7 @@ int launch_sweep(int64_t blocks, size_t lds, hipStream_t st, const KnnArgs &a)
 
 extern "C" int64_t gae_knn_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t k, int splits)
 {
-    Plan p;
+    Plan<float> p;
     if (const int rc = plan("gae_knn_workspace_bytes", m, n, d, k, splits, nullptr, p)) return rc;
     return p.need;
 }
@@ -276,33 +235,22 @@ extern "C" int gae_knn(const float *Q, int64_t ldq, int64_t m, const float *X, i
                        void *workspace, int64_t workspace_bytes, void *stream)
 {
     const char *fn = "gae_knn";
-    Plan p;
+    Plan<float> p;
     if (const int rc = plan(fn, m, n, d, k, splits, workspace, p)) return rc;
     GAE_REQUIRE(metric == GAE_KNN_L2 || metric == GAE_KNN_DOT, GAE_E_RANGE, "%s: unknown metric %d", fn, metric);
-    GAE_REQUIRE((flags & ~GAE_KNN_EXCLUDE_SAME_INDEX) == 0, GAE_E_RANGE, "%s: unknown flags 0x%x", fn, flags);
-    GAE_REQUIRE(ldq >= d && ldx >= d && ldo >= k, GAE_E_SIZE,
-                "%s: leading dimension too small (ldq %lld < d, ldx %lld < d or ldo %lld < k)", fn, (long long)ldq,
-                (long long)ldx, (long long)ldo);
-    GAE_REQUIRE(m == 0 || (index_out && value_out), GAE_E_NULL, "%s: index_out / value_out is NULL", fn);
-    GAE_REQUIRE(m == 0 || Q, GAE_E_NULL, "%s: Q is NULL", fn);
-    GAE_REQUIRE(m == 0 || n == 0 || X, GAE_E_NULL, "%s: X is NULL", fn);
-    GAE_REQUIRE(workspace, GAE_E_NULL, "%s: workspace is NULL", fn);
-    GAE_REQUIRE(workspace_bytes >= p.need, GAE_E_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn,
-                (long long)workspace_bytes, (long long)p.need);
+    if (const int rc = check_call(fn, "d", d, flags, ldq, ldx, ldo, m, n, k, Q, X, index_out, value_out, workspace,
+                                  workspace_bytes, p.need))
+        return rc;
     if (m == 0) return GAE_OK;
 
-    const int S = splits_of(m, n, d, k, splits);
     const int nw = waves_of(d, k);
+    const int S = splits_of(m, n, kRows * nw, splits);
     KnnArgs a;
-    a.Q = Q; a.X = X; a.ldq = ldq; a.ldx = ldx; a.ldo = ldo;
-    a.m = int(m); a.n = int(n); a.d = int(d); a.k = int(k); a.S = S;
+    fill(a, ldq, ldx, ldo, m, n, k, S, flags, value_out, index_out, p.part);
+    a.Q = Q; a.X = X; a.d = int(d);
     a.nch = chunks_of(d);
     a.l2 = metric == GAE_KNN_L2 ? 1 : 0;
-    a.excl_same = (flags & GAE_KNN_EXCLUDE_SAME_INDEX) ? 1 : 0;
-    a.half = p.half;
-    a.value_out = value_out; a.index_out = index_out;
-    a.part_s = p.part;
-    a.part_j = reinterpret_cast<int32_t *>(a.part_s + (S > 1 ? int64_t(S) * m * k : 0));
+    a.half = p.rows;
     hipStream_t st = gae::as_stream(stream);
 
     // every grid of the call, before the first launch
@@ -315,7 +263,7 @@ extern "C" int gae_knn(const float *Q, int64_t ldq, int64_t m, const float *X, i
                 (long long)finish_blocks);
     if (a.l2 && n > 0) {
         hipLaunchKernelGGL(knn_half_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, st, X, ldx, int(n), int(d),
-                           p.half);
+                           p.rows);
         GAE_CHECK_LAUNCH("knn_half_kernel");
     }
     const size_t lds = size_t(sweep_lds(nw, d, k));

@@ -22,30 +22,24 @@
 // 152 KB at k = 64, W = 64.
 #include <float.h>
 
-#include "common.h"
+#include "row_search.h"
 #include "topk_heap.h"
 
 namespace {
 
+using namespace gae::search;
 using namespace gae::topk;
 using gae::cdiv;
 
-constexpr int kMaxK = 64, kMaxW = 64, kMaxSplits = 16;
+constexpr int kMaxW = 64;
 constexpr int kTile = 16;                  // database rows per tile: the 16 keys of offer_tile
 constexpr int kNW = 4;                     // waves per block
 constexpr int kQueries = 64 * kNW;         // queries per block
-constexpr int kTargetBlocks = 1024;        // auto split: about four blocks per CU
 
-struct TaniArgs {
+struct TaniArgs : SearchArgs {
     const int32_t *Q, *X;
-    int64_t ldq, ldx, ldo;
-    int m, n, W, k, S;
-    int excl_same;
+    int W;
     const int32_t *bcount;                 // [n]
-    float *value_out;
-    int32_t *index_out;
-    float *part_s;                         // [S][m][k] (S > 1)
-    int32_t *part_j;
 };
 
 inline int wr_of(int64_t W)
@@ -57,45 +51,13 @@ inline int wr_of(int64_t W)
 
 inline int64_t sweep_lds(int64_t W, int64_t k)
 {
-    return int64_t(kNW) * (2 * k + 16) * 256 + 2 * kTile * wr_of(W) * 4 + 2 * kTile * 4;
+    return int64_t(kNW) * lists_bytes(int(k)) + 2 * kTile * wr_of(W) * 4 + 2 * kTile * 4;
 }
 
-// column splits per block: the caller's, or (0 = auto) enough for ~kTargetBlocks blocks with parts of >= 256 rows
-inline int splits_of(int64_t m, int64_t n, int splits)
+// the workspace: the bit counts of the database rows in front of the partial lists
+int plan(const char *fn, int64_t m, int64_t n, int64_t W, int64_t k, int splits, void *ws, Plan<int32_t> &p)
 {
-    if (splits > 0) return splits;
-    if (m <= 0 || n <= 0) return 1;
-    int64_t S = cdiv(kTargetBlocks, cdiv(m, kQueries));
-    const int64_t by_span = cdiv(n, 256);
-    S = S < by_span ? S : by_span;
-    return int(S < 1 ? 1 : (S > kMaxSplits ? kMaxSplits : S));
-}
-
-// entries of the partial lists the workspace holds: a bound of S m that never shrinks as m, n or splits grow
-inline int64_t part_rows(int64_t m, int64_t n, int splits)
-{
-    if (splits > 0) return int64_t(splits) * m;
-    int64_t b = int64_t(kMaxSplits) * m;
-    const int64_t by_blocks = int64_t(kTargetBlocks) * kQueries + m, by_span = cdiv(n, 256) * m;
-    b = b < by_blocks ? b : by_blocks;
-    return b < by_span ? b : by_span;
-}
-
-struct Plan { int32_t *bcount; float *part; int64_t need; };
-
-int plan(const char *fn, int64_t m, int64_t n, int64_t W, int64_t k, int splits, void *ws, Plan &p)
-{
-    GAE_REQUIRE(W >= 1 && W <= kMaxW, GAE_E_RANGE, "%s: n_words = %lld outside 1..64", fn, (long long)W);
-    GAE_REQUIRE(k >= 1 && k <= kMaxK, GAE_E_RANGE, "%s: k = %lld outside 1..64", fn, (long long)k);
-    GAE_REQUIRE(m >= 0 && n >= 0, GAE_E_SIZE, "%s: negative m = %lld or n = %lld", fn, (long long)m, (long long)n);
-    GAE_REQUIRE(m < (int64_t(1) << 31) && n < (int64_t(1) << 31), GAE_E_SIZE, "%s: m = %lld or n = %lld beyond int32 indices",
-                fn, (long long)m, (long long)n);
-    GAE_REQUIRE(splits >= 0 && splits <= kMaxSplits, GAE_E_RANGE, "%s: splits = %d outside 0..16", fn, splits);
-    gae::Carver c(ws);
-    p.bcount = c.take<int32_t>(n);
-    p.part = c.take<float>(2 * part_rows(m, n, splits) * k);
-    p.need = c.bytes() + 256;
-    return GAE_OK;
+    return carve(fn, "n_words", W, kMaxW, m, n, k, splits, kQueries, ws, p);
 }
 
 // ------------------------------------------------------------------------------------------------------ count
@@ -214,7 +176,7 @@ int launch_sweep(int64_t blocks, size_t lds, hipStream_t st, const TaniArgs &a)
 
 extern "C" int64_t gae_tanimoto_knn_workspace_bytes(int64_t m, int64_t n, int64_t n_words, int64_t k, int splits)
 {
-    Plan p;
+    Plan<int32_t> p;
     if (const int rc = plan("gae_tanimoto_knn_workspace_bytes", m, n, n_words, k, splits, nullptr, p)) return rc;
     return p.need;
 }
@@ -224,29 +186,18 @@ extern "C" int gae_tanimoto_knn(const int32_t *Q, int64_t ldq, int64_t m, const 
                                 int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream)
 {
     const char *fn = "gae_tanimoto_knn";
-    Plan p;
+    Plan<int32_t> p;
     if (const int rc = plan(fn, m, n, n_words, k, splits, workspace, p)) return rc;
-    GAE_REQUIRE((flags & ~GAE_KNN_EXCLUDE_SAME_INDEX) == 0, GAE_E_RANGE, "%s: unknown flags 0x%x", fn, flags);
-    GAE_REQUIRE(ldq >= n_words && ldx >= n_words && ldo >= k, GAE_E_SIZE,
-                "%s: leading dimension too small (ldq %lld < n_words, ldx %lld < n_words or ldo %lld < k)", fn,
-                (long long)ldq, (long long)ldx, (long long)ldo);
-    GAE_REQUIRE(m == 0 || (index_out && value_out), GAE_E_NULL, "%s: index_out / value_out is NULL", fn);
-    GAE_REQUIRE(m == 0 || Q, GAE_E_NULL, "%s: Q is NULL", fn);
-    GAE_REQUIRE(m == 0 || n == 0 || X, GAE_E_NULL, "%s: X is NULL", fn);
-    GAE_REQUIRE(workspace, GAE_E_NULL, "%s: workspace is NULL", fn);
-    GAE_REQUIRE(workspace_bytes >= p.need, GAE_E_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn,
-                (long long)workspace_bytes, (long long)p.need);
+    if (const int rc = check_call(fn, "n_words", n_words, flags, ldq, ldx, ldo, m, n, k, Q, X, index_out, value_out,
+                                  workspace, workspace_bytes, p.need))
+        return rc;
     if (m == 0) return GAE_OK;
 
-    const int S = splits_of(m, n, splits);
+    const int S = splits_of(m, n, kQueries, splits);
     TaniArgs a;
-    a.Q = Q; a.X = X; a.ldq = ldq; a.ldx = ldx; a.ldo = ldo;
-    a.m = int(m); a.n = int(n); a.W = int(n_words); a.k = int(k); a.S = S;
-    a.excl_same = (flags & GAE_KNN_EXCLUDE_SAME_INDEX) ? 1 : 0;
-    a.bcount = p.bcount;
-    a.value_out = value_out; a.index_out = index_out;
-    a.part_s = p.part;
-    a.part_j = reinterpret_cast<int32_t *>(a.part_s + (S > 1 ? int64_t(S) * m * k : 0));
+    fill(a, ldq, ldx, ldo, m, n, k, S, flags, value_out, index_out, p.part);
+    a.Q = Q; a.X = X; a.W = int(n_words);
+    a.bcount = p.rows;
     hipStream_t st = gae::as_stream(stream);
 
     // every grid of the call, before the first launch
@@ -255,7 +206,7 @@ extern "C" int gae_tanimoto_knn(const int32_t *Q, int64_t ldq, int64_t m, const 
                 "%s: a grid of %lld / %lld blocks", fn, (long long)blocks, (long long)merge_blocks);
     if (n > 0) {
         hipLaunchKernelGGL(tanimoto_count_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, st, X, ldx, int(n),
-                           int(n_words), p.bcount);
+                           int(n_words), p.rows);
         GAE_CHECK_LAUNCH("tanimoto_count_kernel");
     }
     const size_t lds = size_t(sweep_lds(n_words, k));

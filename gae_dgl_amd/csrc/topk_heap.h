@@ -1,8 +1,9 @@
-// The k-best tail of K16 gae_decoder_topk (decoder_topk.hip) and K24 gae_knn (knn.hip), from a lane's 16 keys of a
-// tile to the output row: one total order (larger value first, then the lower index); a per-lane heap in LDS with the
-// WORST entry at the root; offer_tile, the walk that feeds it the keys of a tile that pass the running threshold, with
-// the kernel's own candidate tests as hooks; merge_halves, the merge of the two lane halves of a row; and merge_kernel,
-// the second launch that merges the sorted partial lists of the column splits by rank.
+// The k-best tail of K16 gae_decoder_topk, K24 gae_knn and K34 gae_tanimoto_knn (decoder_topk.hip, knn.hip,
+// tanimoto.hip), from a lane's 16 keys of a tile to the output row: one total order (larger value first, then the lower
+// index); a per-lane heap in LDS with the WORST entry at the root; offer_tile, the walk that feeds it the keys of a
+// tile that pass the running threshold, with the kernel's own candidate tests as hooks; merge_halves, the merge of the
+// two lane halves of a row; and merge_kernel, the second launch that merges the sorted partial lists of the column
+// splits by rank.
 #pragma once
 #include <stdint.h>
 
@@ -13,6 +14,9 @@ namespace topk {
 
 // (s, j) is better than (t, q): the total order of the output (score descending, then j ascending)
 __device__ __forceinline__ bool better(float s, int j, float t, int q) { return s > t || (s == t && j < q); }
+
+// LDS of one wave: ls [k][64] and lj [k][64], the lists of its 64 lanes, and scr [16][64], the scratch rows of offer_tile
+constexpr int lists_bytes(int k) { return (2 * k + 16) * 256; }
 
 // Each lane's running top-k is a binary heap in LDS (entry p of lane l at [p * 64 + l]) with the WORST entry at the
 // root: the threshold is the root, and an insert costs log2 k dependent LDS round trips instead of the k / 2 of a

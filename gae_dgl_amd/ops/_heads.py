@@ -1,18 +1,25 @@
-"""Host-side checks the heads on a frozen feature share (ridge, logreg, mlp, forest, boost, pca, tsne, cluster, knn): the
-row layout of ``X`` and ``y``, the lambda path, the fold lists, listed rows, a caller's status tensor, the tree options
-and the bin edges.  Every head imports from here and from ``_base``; none imports from another head.  Each message names
-the caller through ``who``.
+"""Host-side checks the heads on a frozen feature share (ridge, logreg, mlp, forest, boost, pca, tsne, cluster, knn,
+tanimoto): the row layout of ``X`` and ``y``, the lambda path, the fold lists, listed rows, a caller's status tensor, the
+tree options, the bin edges, and the result type, limits, option checks and launch of the two row searches.  Every head
+imports from here and from ``_base``; none imports from another head.  Each message names the caller through ``who``.
 
 Part of the package gae_dgl_amd.ops."""
+import collections
 import math
 
 import torch
 
+from .. import _lib
 from .._lib import GaeHipError
-from ._base import _f32, _gpu
+from ._base import _f32, _gpu, _on_device, _ptr, _stream, _timed, _ws_bytes
 
 MAX_FOLDS = 32                                                     # ridge and logreg: gae_ridge_stats' limit
 _CV_PATH = [10.0 ** (e / 2.0) for e in range(-6, 7)]               # 10^-3 .. 10^3, 13 values
+
+KNNResult = collections.namedtuple("KNNResult", ["index", "value"])
+KNNResult.__doc__ = """index int32 [m, k] (rows of the database, -1 = padding), value fp32 [m, k]: the squared distance
+("l2", ascending), the inner product ("dot") or the cosine ("cosine"), both descending; padding holds +inf / -inf"""
+KNN_MAX_K, KNN_MAX_SPLITS = 64, 16                                 # the row searches: gae_knn and gae_tanimoto_knn
 
 
 def _rows(X, who):
@@ -45,6 +52,38 @@ def _status_arg(status, words, dev, who):
             and status.device == dev and status.is_contiguous()):
         raise GaeHipError(f"{who}: status must be a contiguous int64 [{words}] tensor on {dev}")
     return status
+
+
+# ------------------------------------------------------------------ the row searches (knn, tanimoto_knn)
+def _search_options(X, k, exclude_self, splits):
+    """(same, k as an int, flags): ``same`` is a search of Q against itself (``X is None``), which leaves every row out of
+    its own list unless ``exclude_self`` says otherwise"""
+    if k is None or isinstance(k, bool) or int(k) != k:
+        raise ValueError(f"k: an integer in 1..{KNN_MAX_K}, not {k!r}")
+    if isinstance(splits, bool) or int(splits) != splits or not 0 <= splits <= KNN_MAX_SPLITS:
+        raise ValueError(f"splits: 0 (auto) or 1..{KNN_MAX_SPLITS}, not {splits!r}")
+    same = X is None
+    if exclude_self is None:
+        exclude_self = same
+    if exclude_self and not same:
+        raise ValueError("exclude_self needs X=None: rows of a separate X share no index with the queries")
+    return same, int(k), (_lib.KNN_EXCLUDE_SAME_INDEX if exclude_self else 0)
+
+
+def _search(entry, label, dev, sizes, args):
+    """``KNNResult`` of the row search ``entry(*args, index, value, ldo, workspace, bytes, stream)`` on ``dev``, timed as
+    ``label``; ``sizes`` = (m, n, width, k, splits) is what its workspace query takes"""
+    m, kk = sizes[0], max(sizes[3], 1)
+    index = torch.empty(m, kk, dtype=torch.int32, device=dev)
+    value = torch.empty(m, kk, dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        nbytes = _ws_bytes(entry + "_workspace_bytes", *sizes)
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+
+        def launch():
+            _lib.call(entry, *args, _ptr(index), _ptr(value), kk, _ptr(ws), ws.numel(), _stream())
+        _timed(label, launch)
+    return KNNResult(index, value)
 
 
 # ------------------------------------------------------------------ the lambda path and the folds

@@ -4,22 +4,16 @@ squared Euclidean distance, inner product or cosine similarity, without the m x 
 classifier.
 
 Part of the package gae_dgl_amd.ops; names are resolved through the package namespace (`_ops.<name>`) at call time."""
-import collections
-
 import torch
 
 from .. import _lib
 from .._lib import GaeHipError
-from ._base import _on_device, _ptr, _stream, _timed, _ws_bytes
-from ._heads import _rows
+from ._base import _ptr
+from ._heads import KNN_MAX_K, KNN_MAX_SPLITS, KNNResult, _rows, _search, _search_options
 
 __all__ = ['KNNResult', 'knn', 'KNN_MAX_K', 'KNN_MAX_D', 'KNN_MAX_SPLITS']
 
-KNNResult = collections.namedtuple("KNNResult", ["index", "value"])
-KNNResult.__doc__ = """index int32 [m, k] (rows of the database, -1 = padding), value fp32 [m, k]: the squared distance
-("l2", ascending), the inner product ("dot") or the cosine ("cosine"), both descending; padding holds +inf / -inf"""
-
-KNN_MAX_K, KNN_MAX_D, KNN_MAX_SPLITS = 64, 256, 16
+KNN_MAX_D = 256
 _METRICS = {"l2": _lib.KNN_L2, "dot": _lib.KNN_DOT, "cosine": _lib.KNN_DOT}
 
 
@@ -41,16 +35,7 @@ def knn(Q, X=None, k=None, *, metric="l2", exclude_self=None, splits=0):
     the result has the same bits for every value.  1 <= d <= 256, 1 <= k <= 64; there is no CPU fallback."""
     if metric not in _METRICS:
         raise ValueError(f"metric: 'l2', 'dot' or 'cosine', not {metric!r}")
-    if k is None or isinstance(k, bool) or int(k) != k:
-        raise ValueError(f"k: an integer in 1..{KNN_MAX_K}, not {k!r}")
-    if isinstance(splits, bool) or int(splits) != splits or not 0 <= splits <= KNN_MAX_SPLITS:
-        raise ValueError(f"splits: 0 (auto) or 1..{KNN_MAX_SPLITS}, not {splits!r}")
-    same = X is None
-    if exclude_self is None:
-        exclude_self = same
-    if exclude_self and not same:
-        raise ValueError("exclude_self needs X=None: rows of a separate X share no index with the queries")
-    k = int(k)
+    same, k, flags = _search_options(X, k, exclude_self, splits)
     with torch.no_grad():
         Q, ldq, m, d = _rows(Q, "knn")
         if metric == "cosine":
@@ -63,17 +48,5 @@ def knn(Q, X=None, k=None, *, metric="l2", exclude_self=None, splits=0):
                 raise GaeHipError(f"knn: X must be [n, {d}] on {Q.device}, got {tuple(X.shape)} on {X.device}")
             if metric == "cosine":
                 X, ldx = _unit_rows(X, "knn"), max(d, 1)
-        dev = Q.device
-        kk = max(k, 1)
-        index = torch.empty(m, kk, dtype=torch.int32, device=dev)
-        value = torch.empty(m, kk, dtype=torch.float32, device=dev)
-        flags = _lib.KNN_EXCLUDE_SAME_INDEX if exclude_self else 0
-        with _on_device(dev):
-            nbytes = _ws_bytes("gae_knn_workspace_bytes", m, n, d, k, int(splits))
-            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-
-            def launch():
-                _lib.call("gae_knn", _ptr(Q), ldq, m, _ptr(X), ldx, n, d, k, _METRICS[metric], flags, int(splits),
-                          _ptr(index), _ptr(value), kk, _ptr(ws), ws.numel(), _stream())
-            _timed(("knn", m, n, d, k), launch)
-    return KNNResult(index, value)
+        return _search("gae_knn", ("knn", m, n, d, k), Q.device, (m, n, d, k, int(splits)),
+                       (_ptr(Q), ldq, m, _ptr(X), ldx, n, d, k, _METRICS[metric], flags, int(splits)))

@@ -6,10 +6,9 @@ classifier.
 Part of the package gae_dgl_amd.ops; names are resolved through the package namespace (`_ops.<name>`) at call time."""
 import torch
 
-from .. import _lib
 from .._lib import GaeHipError
-from ._base import _gpu, _on_device, _ptr, _stream, _timed, _ws_bytes
-from .knn import KNN_MAX_K, KNN_MAX_SPLITS, KNNResult
+from ._base import _gpu, _ptr
+from ._heads import _search, _search_options
 
 __all__ = ['tanimoto_knn', 'TANIMOTO_MAX_WORDS']
 
@@ -36,16 +35,7 @@ def tanimoto_knn(Q, X=None, k=None, *, exclude_self=None, splits=0):
     its own list (``exclude_self`` defaults to True then; with a separate ``X`` it must stay off).  ``splits``: column
     splits of the launch, 0 = auto; the result has the same bits for every value.  1 <= W <= 64, 1 <= k <= 64; there is
     no CPU fallback."""
-    if k is None or isinstance(k, bool) or int(k) != k:
-        raise ValueError(f"k: an integer in 1..{KNN_MAX_K}, not {k!r}")
-    if isinstance(splits, bool) or int(splits) != splits or not 0 <= splits <= KNN_MAX_SPLITS:
-        raise ValueError(f"splits: 0 (auto) or 1..{KNN_MAX_SPLITS}, not {splits!r}")
-    same = X is None
-    if exclude_self is None:
-        exclude_self = same
-    if exclude_self and not same:
-        raise ValueError("exclude_self needs X=None: rows of a separate X share no index with the queries")
-    k = int(k)
+    same, k, flags = _search_options(X, k, exclude_self, splits)
     Q, ldq, m, W = _word_rows(Q, "tanimoto_knn")
     if same:
         X, ldx, n = Q, ldq, m
@@ -53,17 +43,5 @@ def tanimoto_knn(Q, X=None, k=None, *, exclude_self=None, splits=0):
         X, ldx, n, wx = _word_rows(X, "tanimoto_knn")
         if wx != W or X.device != Q.device:
             raise GaeHipError(f"tanimoto_knn: X must be [n, {W}] on {Q.device}, got {tuple(X.shape)} on {X.device}")
-    dev = Q.device
-    kk = max(k, 1)
-    index = torch.empty(m, kk, dtype=torch.int32, device=dev)
-    value = torch.empty(m, kk, dtype=torch.float32, device=dev)
-    flags = _lib.KNN_EXCLUDE_SAME_INDEX if exclude_self else 0
-    with _on_device(dev):
-        nbytes = _ws_bytes("gae_tanimoto_knn_workspace_bytes", m, n, W, k, int(splits))
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-
-        def launch():
-            _lib.call("gae_tanimoto_knn", _ptr(Q), ldq, m, _ptr(X), ldx, n, W, k, flags, int(splits), _ptr(index),
-                      _ptr(value), kk, _ptr(ws), ws.numel(), _stream())
-        _timed(("tanimoto_knn", m, n, W, k), launch)
-    return KNNResult(index, value)
+    return _search("gae_tanimoto_knn", ("tanimoto_knn", m, n, W, k), Q.device, (m, n, W, k, int(splits)),
+                   (_ptr(Q), ldq, m, _ptr(X), ldx, n, W, k, flags, int(splits)))

@@ -9,6 +9,16 @@ import torch
 
 import fingerprint_ref as R
 
+E_NULL, E_SIZE, E_WORKSPACE, E_RANGE = -1, -2, -5, -6
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+    ge.build()
+    from gae_dgl_amd import _lib
+    return _lib.load()
+
 
 @pytest.fixture(scope="module")
 def mols():
@@ -176,6 +186,77 @@ def test_argument_errors_of_both_entry_points():
     wb = lib.gae_tanimoto_knn_workspace_bytes
     assert wb(5, 7, 65, 10, 0) == -6 and wb(5, 7, 32, 65, 0) == -6 and wb(5, 7, 32, 10, 17) == -6
     assert 0 < wb(100, 1000, 32, 10, 0) <= wb(200, 1000, 32, 10, 0) <= wb(200, 2000, 32, 64, 0) <= wb(200, 2000, 32, 64, 16)
+
+
+def call_tanimoto(lib, *, ldq=8, m=4, ldx=8, n=10, W=8, k=3, flags=0, splits=0, index=1 << 20, value=1 << 21, ldo=3,
+                  ws=1 << 22, ws_bytes=1 << 30, Q=1 << 23, X=1 << 24):
+    """gae_tanimoto_knn with made-up non-NULL addresses: an argument error must return before any of them is touched"""
+    rc = lib.gae_tanimoto_knn(Q, ldq, m, X, ldx, n, W, k, flags, splits, index, value, ldo, ws, ws_bytes, None)
+    return rc, lib.gae_last_error().decode()
+
+
+@pytest.mark.parametrize("kw, code, text", [
+    (dict(W=0), E_RANGE, "n_words = 0 outside 1..64"),
+    (dict(W=65, ldq=80, ldx=80), E_RANGE, "n_words = 65 outside 1..64"),
+    (dict(k=0), E_RANGE, "k = 0 outside 1..64"),
+    (dict(k=65, ldo=65), E_RANGE, "k = 65 outside 1..64"),
+    (dict(m=-1), E_SIZE, "negative m = -1"),
+    (dict(n=-1), E_SIZE, "negative m = 4 or n = -1"),
+    (dict(m=1 << 31), E_SIZE, "m = 2147483648 or n = 10 beyond int32 indices"),
+    (dict(n=1 << 31), E_SIZE, "beyond int32 indices"),
+    (dict(ldq=7), E_SIZE, "leading dimension too small (ldq 7 < n_words, ldx 8 < n_words or ldo 3 < k)"),
+    (dict(ldx=7), E_SIZE, "ldx 7 < n_words"),
+    (dict(ldo=2), E_SIZE, "ldo 2 < k"),
+    (dict(flags=2), E_RANGE, "unknown flags 0x2"),
+    (dict(splits=17), E_RANGE, "splits = 17 outside 0..16"),
+    (dict(splits=-1), E_RANGE, "splits = -1 outside 0..16"),
+    (dict(index=None), E_NULL, "index_out / value_out is NULL"),
+    (dict(value=None), E_NULL, "index_out / value_out is NULL"),
+    (dict(Q=None), E_NULL, "Q is NULL"),
+    (dict(X=None), E_NULL, "X is NULL"),
+    (dict(ws=None), E_NULL, "workspace is NULL"),
+    (dict(ws_bytes=16), E_WORKSPACE, "workspace of 16 bytes, "),
+    # two bad arguments: the one that is checked first is the one reported
+    (dict(W=65, ldq=80, ldx=80, k=65, ldo=65), E_RANGE, "n_words = 65 outside 1..64"),
+    (dict(splits=17, flags=2), E_RANGE, "splits = 17 outside 0..16"),
+])
+def test_tanimoto_argument_errors_come_before_any_access(lib, kw, code, text):
+    rc, msg = call_tanimoto(lib, **kw)
+    assert rc == code, (rc, msg)
+    assert msg.startswith("gae_tanimoto_knn: ") and text in msg, msg
+
+
+def test_tanimoto_workspace_query_is_a_monotone_host_function(lib):
+    """the sweep of test_knn_cpu.py for K34: its blocks hold 256 queries, so the bound of the partial lists passes from
+    16 m to 1024 . 256 + m between m = 17476 and 17477, and the auto split is 1 from m = 1023 . 256 + 1 on"""
+    q = lib.gae_tanimoto_knn_workspace_bytes
+    assert q(0, 0, 1, 1, 0) > 0 and q(100, 1000, 32, 10, 0) == q(100, 1000, 32, 10, 0)
+    for splits in (0, 1, 3, 16):
+        prev = 0
+        for m in (0, 1, 31, 32, 33, 127, 128, 129, 4096, 17476, 17477, 249455, 261888, 261889, 262144, 262145, 10 ** 6,
+                  2 ** 31 - 1):
+            cur = q(m, 249455, 32, 10, splits)
+            assert cur >= prev > -1, (m, splits)
+            prev = cur
+        prev = 0
+        for n in (0, 1, 255, 256, 257, 4096, 249455, 2 ** 31 - 1):
+            cur = q(4096, n, 32, 10, splits)
+            assert cur >= prev > -1, (n, splits)
+            prev = cur
+        prev = 0
+        for k in range(1, 65):
+            cur = q(4096, 249455, 32, k, splits)
+            assert cur >= prev > -1, (k, splits)
+            prev = cur
+    prev = 0
+    for splits in range(1, 17):
+        cur = q(4096, 249455, 32, 10, splits)
+        assert cur > prev
+        prev = cur
+    # never the m x n matrix: linear in n + m k splits
+    assert q(249455, 249455, 32, 10, 0) < 4 * 249455 + 8 * 10 * 16 * 249455 + 4096
+    assert q(10, 10, 0, 1, 0) == E_RANGE and q(10, 10, 8, 65, 0) == E_RANGE and q(-1, 10, 8, 1, 0) == E_SIZE
+    assert q(10, 10, 8, 1, 17) == E_RANGE and b"splits = 17" in lib.gae_last_error()
 
 
 def test_ops_refuse_host_tensors_and_bad_options():

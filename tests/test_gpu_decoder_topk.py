@@ -298,6 +298,16 @@ def test_short_lists_merge_the_same_for_any_split(dev, tuning):
         assert np.array_equal(as_np(score), sc.astype(np.float32)), splits
 
 
+def test_more_splits_than_tiles(dev, tuning):
+    """n = 33 is two tiles: with 16 column splits forced, 14 of every panel's parts are empty and their waves write lists
+    of padding alone.  Integer scores, so both calls must give the oracle's bits"""
+    runs = []
+    for splits in (1, 16):
+        tuning("topk_splits", splits)
+        runs.append(_exact_case(33, 3, 5, dev, seed=33))
+    assert torch.equal(runs[0][1], runs[1][1]) and torch.equal(runs[0][0].view(torch.int32), runs[1][0].view(torch.int32))
+
+
 def test_single_member_graph_scope_equals_batch_scope(dev):
     import gae_dgl_amd as G
     g = load_golden("sym200")

@@ -205,6 +205,29 @@ def test_short_lists_merge_the_same_for_any_split(dev):
             assert np.array_equal(got_v.astype(np.float64), want_v), (metric, splits)
 
 
+@pytest.mark.parametrize("k", [5, 64])
+@pytest.mark.parametrize("n", [1, 17, 33])
+def test_more_splits_than_tiles(dev, n, k):
+    """16 column splits over a database of one or two tiles of 32 rows: the parts are whole tiles, so all but one or two
+    of them are empty (pb = pe = n) and their blocks write lists of padding alone; at k = 64 no query has k candidates.
+    On the exact grid every call must give the reference's bits, and so the bits of one split"""
+    rng = np.random.default_rng(n * 100 + k)
+    m, d = 33, 3
+    Q, X = grid(rng, m, d), grid(rng, n, d)
+    searches = [(Q, X, 0)] + ([(X, X, 1)] if n == m else [])           # (queries, database, same-index flag)
+    for A, B, flag in searches:
+        Ad, Bd = strided(A, 5, dev), strided(B, 2, dev)
+        for metric in ("l2", "dot"):
+            want_i, want_v = R.knn(A, B, k, metric, exclude_same=bool(flag))
+            one = raw_knn(Ad, Bd, k, metric, flags=flag, splits=1)
+            many = raw_knn(Ad, Bd, k, metric, flags=flag, splits=16)
+            for got_i, got_v in (one, many):
+                assert np.array_equal(got_i, want_i), (metric, flag)
+                assert np.array_equal(got_v.astype(np.float64), want_v), (metric, flag)
+            assert np.array_equal(one[1].view(np.int32), many[1].view(np.int32)), (metric, flag)
+            assert (want_i[:, min(n - flag, k):] == -1).all() and (want_i[:, :min(n - flag, k)] >= 0).all()
+
+
 # ------------------------------------------------------------------ 6. non-finite values
 @pytest.mark.parametrize("metric", ["l2", "dot"])
 def test_non_finite_rows_are_never_returned(dev, metric):

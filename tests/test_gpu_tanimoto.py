@@ -143,6 +143,26 @@ def test_same_bits_for_any_split_stride_and_run(dev):
         assert torch.equal(r.index, self0.index) and torch.equal(r.value, self0.value)
 
 
+@pytest.mark.parametrize("k", [5, 64])
+@pytest.mark.parametrize("n", [1, 17, 33])
+def test_more_splits_than_tiles(dev, n, k):
+    """16 column splits over a database of one to three tiles of 16 rows: the parts are whole tiles, so all but one to
+    three of them are empty (pb = pe = n) and their blocks write lists of padding alone; at k = 64 no query has k
+    candidates.  Every call must give the reference's bits, and so the bits of one split"""
+    rng = np.random.default_rng(n * 100 + k)
+    m, W = 33, 3
+    Q, X = bit_rows(rng, m, W), bit_rows(rng, n, W)
+    X[::4] = X[0]                                                      # ties: the index rule decides across the parts
+    searches = [(Q, X, 0)] + ([(X, X, 1)] if n == m else [])           # (queries, database, same-index flag)
+    for A, B, flag in searches:
+        Ad, Bd = strided(A, 5, dev), strided(B, 2, dev)
+        want = R.tanimoto_knn(A, B, k, exclude_same=bool(flag))
+        one = raw_tanimoto(Ad, Bd, k, flags=flag, splits=1)
+        many = raw_tanimoto(Ad, Bd, k, flags=flag, splits=16)
+        assert same_bits(one, want) and same_bits(many, want) and same_bits(one, many), flag
+        assert (want[0][:, min(n - flag, k):] == -1).all() and (want[0][:, :min(n - flag, k)] >= 0).all()
+
+
 def test_no_fallback_and_argument_errors(dev):
     from gae_dgl_amd import ops
     from gae_dgl_amd._lib import GaeHipError

@@ -51,6 +51,9 @@ def call(lib, *, ldq=8, m=4, ldx=8, n=10, d=8, k=3, metric=0, flags=0, splits=0,
     (dict(X=None), E_NULL, "X is NULL"),
     (dict(ws=None), E_NULL, "workspace is NULL"),
     (dict(ws_bytes=16), E_WORKSPACE, "workspace of 16 bytes"),
+    # two bad arguments: the one that is checked first is the one reported
+    (dict(d=257, ldq=300, ldx=300, k=65, ldo=65), E_RANGE, "d = 257 outside 1..256"),
+    (dict(metric=2, flags=2), E_RANGE, "unknown metric 2"),
 ])
 def test_argument_errors_come_before_any_access(lib, kw, code, text):
     rc, msg = call(lib, **kw)

@@ -78,6 +78,10 @@ SIZES = {
         (1, 1, 1, 1, 0): 768, (1128, 1128, 48, 10, 0): 456192, (19717, 19717, 16, 64, 16): 161601024,
         (7, 249455, 256, 64, 0): 1055488,
     },
+    "gae_tanimoto_knn_workspace_bytes": {            # from commit 6aa1ace, which added K34 (m, n, n_words, k, splits)
+        (1, 1, 1, 1, 0): 768, (1128, 1128, 32, 10, 0): 456192, (19717, 19717, 32, 64, 16): 161601024,
+        (7, 249455, 64, 64, 0): 1055488, (4096, 249455, 32, 64, 0): 34552576,
+    },
     "gae_ridge_workspace_bytes": {(0, 1, 1, 1): 512, (1128, 48, 1, 5): 102400, (249455, 128, 8, 32): 76153856},
     "gae_forest_workspace_bytes": {
         (1, 1, 1, 1, 1, 1, 2): 4352,
