@@ -51,6 +51,11 @@ SPECTRAL_ERR_INDEX = 1
 SPECTRAL_KEY_XOR = 0x5851F42D4C957F2D
 SPECTRAL_STATUS_WORDS = 8         # gae_spectral_status: int64 info, n_converged, n_spmm, nonfinite, errors; double theta_1,
                                   # theta_k, res_max
+NEIGHBOUR_SCALE_BITS, NEIGHBOUR_TABLE_SLOTS, NEIGHBOUR_MAX_K, NEIGHBOUR_MAX_WEIGHTS = 32, 1024, 64, 2    # GAE_NEIGHBOUR_*
+NEIGHBOUR_STATUS_WORDS = 4        # int64 error bits, short rows, long rows of the last top-k, reserved
+NEIGHBOUR_CN, NEIGHBOUR_JACCARD, NEIGHBOUR_AA, NEIGHBOUR_RA = 0, 1, 2, 3
+NEIGHBOUR_EXCLUDE_EDGES = 1
+NEIGHBOUR_ERR_COLUMN, NEIGHBOUR_ERR_ORDER, NEIGHBOUR_ERR_QUERY, NEIGHBOUR_ERR_TABLE, NEIGHBOUR_ERR_INDPTR = 1, 2, 4, 8, 16
 TSNE_STATUS_WORDS = 8             # gae_tsne_status: int64 done, iteration, nonfinite, ticket; double p_log_d, log_z, grad2, z
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
@@ -259,6 +264,11 @@ SIGNATURES = {
                                       _p, _i64, _p]),
     "gae_tanimoto_knn_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _int]),
     "gae_tanimoto_knn": (_int, [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _int, _int, _p, _p, _i64, _p, _i64, _p]),
+    "gae_neighbour_degrees": (_int, [_p, _p, _i64, _i64, _p, _p, _p]),
+    "gae_neighbour_pairs": (_int, [_p, _p, _i64, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
+    "gae_neighbour_topk_workspace_bytes": (_i64, [_i64, _i64]),
+    "gae_neighbour_topk": (_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _int, _p, _i64, _p, _int, _i64, _p, _p, _p, _p, _p, _i64,
+                                  _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

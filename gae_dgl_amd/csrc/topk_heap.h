@@ -14,6 +14,8 @@ namespace topk {
 
 // (s, j) is better than (t, q): the total order of the output (score descending, then j ascending)
 __device__ __forceinline__ bool better(float s, int j, float t, int q) { return s > t || (s == t && j < q); }
+// the same order over an integer key (K36: an int64 count or sum, or the bits of a non-negative fp64 quotient)
+__device__ __forceinline__ bool better(int64_t s, int j, int64_t t, int q) { return s > t || (s == t && j < q); }
 
 // LDS of one wave: ls [k][64] and lj [k][64], the lists of its 64 lanes, and scr [16][64], the scratch rows of offer_tile
 constexpr int lists_bytes(int k) { return (2 * k + 16) * 256; }

@@ -82,6 +82,14 @@ def evaluate(Z, split):
     return {"auc": roc_auc(p, q), "ap": average_precision(p, q)}
 
 
+def evaluate_scores(pos_scores, neg_scores):
+    """{"auc", "ap"} of scores that are already per pair (a heuristic of ops.neighbour_scores, any monotone score): the
+    ROC-AUC and AP ``evaluate`` reports for an embedding, ties at their average rank"""
+    p, q = torch.as_tensor(pos_scores).reshape(-1), torch.as_tensor(neg_scores).reshape(-1)
+    q = q.to(p.device)
+    return {"auc": roc_auc(p, q), "ap": average_precision(p, q)}
+
+
 def recall_at_k(index, pos_pairs):
     """fraction of the held-out positive pairs (i, j) (``pos_pairs`` [2, m]) found by a top-k list: j in row i of
     ``index`` [n, k] or i in row j (a link is undirected).  Duplicate pairs -- also (i, j) next to (j, i) -- count

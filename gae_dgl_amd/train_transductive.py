@@ -11,6 +11,7 @@ epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
       [--map_out map.npz [--map_perplexity P] [--map_iters T] [--map_seed S] [--map_init random|pca]]
       [--pca K [--pca_out pca.npz]]
       [--spectral K [--spectral_self_loops] [--spectral_scaling none|degree|value] [--spectral_seed N] [--spectral_out sc.npz]]
+      [--heuristics [cn|jaccard|aa|ra|pa ...] [--heuristics_out pairs.npz]]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -23,6 +24,8 @@ import torch
 from gae_dgl_amd import DGLGraph
 from gae_dgl_amd.data import load_data, register_data_args
 from gae_dgl_amd.gae import GAE
+
+HEURISTIC_KINDS = ("cn", "jaccard", "aa", "ra", "pa")
 
 
 def build_parser():
@@ -127,6 +130,14 @@ def build_parser():
     ap.add_argument("--spectral_seed", type=int, default=None, metavar="N", help="with --spectral: the seed of the start block (default 0)")
     ap.add_argument("--spectral_out", default=None, metavar="PATH",
                     help="with --spectral: write PATH (.npz with 'embedding' fp32 [N, K], 'vectors' fp64, 'values', 'residuals')")
+    ap.add_argument("--heuristics", nargs="*", choices=HEURISTIC_KINDS, default=None, metavar="KIND",
+                    help="with --eval: the neighbourhood baselines of a link-prediction table -- common neighbours (cn), "
+                         "jaccard, Adamic-Adar (aa), resource allocation (ra), preferential attachment (pa); no KIND: all "
+                         "five -- of the val / test pairs on the TRAINING graph (ops.neighbour_scores), ROC-AUC | AP beside "
+                         "the model's lines; with --topk K also their test recall@K (ops.neighbour_topk; not for pa)")
+    ap.add_argument("--heuristics_out", default=None, metavar="PATH",
+                    help="with --heuristics: write the per-pair tables to PATH (.npz: '{val,test}_{pos,neg}_pairs' int64 "
+                         "[2, m] and '{val,test}_{pos,neg}_KIND' for common, deg_i, deg_j and every KIND)")
     return ap
 
 
@@ -198,6 +209,11 @@ def parse_args(argv=None):
             ap.error("--spectral needs --eval (it scores the held-out edges)")
         if args.spectral_seed is not None and args.spectral_seed < 0:
             ap.error(f"--spectral_seed {args.spectral_seed}: N must be at least 0")
+    if args.heuristics is None:
+        if args.heuristics_out is not None:
+            ap.error("--heuristics_out needs --heuristics")
+    elif not args.eval:
+        ap.error("--heuristics needs --eval (it scores the held-out edges)")
     return args
 
 
@@ -431,6 +447,33 @@ def main(argv=None):
         if args.spectral_out is not None:
             np.savez(args.spectral_out, embedding=sc.embedding.cpu().numpy(), vectors=sc.vectors.cpu().numpy(),
                      values=sc.values.cpu().numpy(), residuals=sc.residuals.cpu().numpy())
+    if args.heuristics is not None:
+        import numpy as np
+        kinds = list(dict.fromkeys(args.heuristics)) or list(HEURISTIC_KINDS)
+        weights = ops.neighbour_weights(g)                 # the training graph: held-out edges are not in it
+        main.last_heuristics = {}
+        tables = {}
+        for name, split in held_out.items():
+            ns = {part: ops.neighbour_scores(g, torch.as_tensor(split[part], device=device), weights=weights)
+                  for part in ("pos", "neg")}
+            for part in ("pos", "neg"):
+                tables[f"{name}_{part}_pairs"] = np.asarray(split[part], np.int64)
+                for field in ["common", "deg_i", "deg_j"] + kinds:
+                    tables[f"{name}_{part}_{field}"] = getattr(ns[part], field).cpu().numpy()
+            for kind in kinds:
+                scores = metrics.evaluate_scores(getattr(ns["pos"], kind), getattr(ns["neg"], kind))
+                print(f"{kind} {name} ROC-AUC: {scores['auc']:.4f} | AP: {scores['ap']:.4f}")
+                main.last_heuristics[(kind, name)] = scores
+        if args.topk is not None:
+            for kind in kinds:
+                if kind == "pa":                           # not a local score: no top-k
+                    continue
+                top = ops.neighbour_topk(g, args.topk, kind, weights=weights)
+                recall = metrics.recall_at_k(top.index, held_out["test"]["pos"])
+                print(f"{kind} test recall@{args.topk}: {recall:.4f}")
+                main.last_heuristics[(kind, "recall")] = recall
+        if args.heuristics_out is not None:
+            np.savez(args.heuristics_out, **tables)
     return [float(l) for l in losses]
 
 

@@ -1382,6 +1382,68 @@ int gae_tanimoto_knn(const int32_t *Q, int64_t ldq, int64_t m, const int32_t *X,
                      int64_t k, int flags, int splits, int32_t *index_out, float *value_out, int64_t ldo, void *workspace,
                      int64_t workspace_bytes, void *stream);
 
+/* ---- K35 / K36: neighbourhood link-prediction baselines (ops.neighbour_scores, ops.neighbour_topk)
+ * Common neighbours, Jaccard, Adamic-Adar, resource allocation and preferential attachment over a graph, without the
+ * n x n two-hop matrix and without a float being accumulated anywhere.
+ * GRAPH   the library's CSR: int32 indptr [n + 1], indices [nnz]; rows ascending, duplicates kept.  The graph must be
+ *   SYMMETRIC (every edge listed in both directions); the wrapper checks, the kernels rely on it.  n < 2^30, nnz < 2^31.
+ * NEIGHBOUR SETS  Gamma(i) is the set of DISTINCT columns of row i other than i: duplicate edges and self-loops do not
+ *   count.  deg(i) = |Gamma(i)|.
+ * PER PAIR (i, j)   common = |Gamma(i) & Gamma(j)|;  wsum_c = sum over w in Gamma(i) & Gamma(j) of W[w, c], for nw <= 2
+ *   caller-supplied int64 weight columns W [n, nw] (row-major, dense).  The kernels know nothing about logarithms: they
+ *   add integers.  i == j is allowed and gives common = deg(i).
+ * WEIGHTS (built by the wrapper; the kernels take any int64)  fixed point with GAE_NEIGHBOUR_SCALE_BITS = 32 fraction
+ *   bits, from a host table over the degrees 0 .. max degree in numpy fp64:  aa_q[d] = rint(2^32 / log(d)) for d >= 2, else
+ *   0;  ra_q[d] = rint(2^32 / d) for d >= 1, else 0;  the table is gathered on the device by deg.  Every weight is below
+ *   2^32.53 and common below 2^30, so every sum is below 2^63: overflow cannot happen.
+ * SCORES (one stated operation each, formed by the wrapper)  cn = common;  jaccard = double(common) / double(deg_i +
+ *   deg_j - common), 0 when the union is 0;  aa = double(aa_sum) * 2^-32, ra = double(ra_sum) * 2^-32;  pa = deg_i * deg_j
+ *   (int64).
+ * TOP-K  candidates of query row i: every j with j != i and common(i, j) >= 1, minus the j in Gamma(i) under
+ *   GAE_NEIGHBOUR_EXCLUDE_EDGES.  kind: GAE_NEIGHBOUR_CN / _JACCARD / _AA / _RA (pa is not a local score: GAE_E_RANGE).
+ *   ORDER  larger value first, then lower j (better() of csrc/topk_heap.h).  The value compared is the integer common (cn)
+ *   or wsum (aa, ra: the one weight column w, node v's weight at w[v * ldw]) and the fp64 quotient for jaccard.  1 <= k <=
+ *   64.  A row with fewer than k candidates pads its tail with index -1, common 0, wsum 0.
+ *   ROUTES  a plan launch computes B_i = sum over w in Gamma(i) of rowlen(w) and lists the rows with 2 B_i <= table_slots
+ *   as short (an LDS hash table keyed by j, integer LDS atomics, probes bounded by the table size), the others as long
+ *   (windows of table_slots candidate columns with dense LDS accumulators, every Gamma(w) entered by binary search).
+ *   The selection is by rank under the total order, so both routes, every table_slots and every run give the same bits.
+ *   table_slots: 0 = GAE_NEIGHBOUR_TABLE_SLOTS, else a power of two in 64 .. 2048 (else GAE_E_RANGE).
+ *   rows int32 [m] or NULL (then m rows: query q is node q).  index_out, common_out int32 [m, k], wsum_out int64 [m, k],
+ *   dense.  deg int32 [n] from gae_neighbour_degrees.
+ * STATUS  int64 [GAE_NEIGHBOUR_STATUS_WORDS] on the device, zeroed by the caller and read once at the end: word 0 the
+ *   error bits or-ed in -- GAE_NEIGHBOUR_ERR_COLUMN (a column outside [0, n)), _ERR_ORDER (a row that is not ascending),
+ *   _ERR_INDPTR (a row pointer outside [0, nnz] or descending), all three from gae_neighbour_degrees; _ERR_QUERY (a query
+ *   index outside [0, n): that pair's common is -1, that row is padding), _ERR_TABLE (a full hash table: cannot happen on a
+ *   graph without the other bits); words 1 and 2 the short and the long rows of the last gae_neighbour_topk.
+ * SAFETY  a bad row pointer reads as an empty row, a bad column is never used as an index, every loop is bounded: nothing
+ *   outside the arrays is read or written whatever the graph holds.
+ * Argument errors are returned before anything is dereferenced or launched: negative sizes, n >= 2^30, nnz >= 2^31, m
+ * beyond its range (GAE_E_SIZE); nw outside 0..2, k outside 1..64, an unknown kind or flag bit, a bad table_slots
+ * (GAE_E_RANGE); NULL indptr / status / indices (nnz > 0) / deg (n > 0) / pairs and outputs (m > 0) / W (nw, n > 0) / w
+ * (aa, ra) / workspace (GAE_E_NULL); a short workspace (GAE_E_WORKSPACE).  gae_neighbour_topk_workspace_bytes is a pure
+ * host function, positive and non-decreasing in m: O(m) bytes, the two work lists. */
+enum { GAE_NEIGHBOUR_SCALE_BITS = 32, GAE_NEIGHBOUR_TABLE_SLOTS = 1024, GAE_NEIGHBOUR_MAX_K = 64,
+       GAE_NEIGHBOUR_MAX_WEIGHTS = 2, GAE_NEIGHBOUR_STATUS_WORDS = 4 };
+enum { GAE_NEIGHBOUR_CN = 0, GAE_NEIGHBOUR_JACCARD = 1, GAE_NEIGHBOUR_AA = 2, GAE_NEIGHBOUR_RA = 3 };
+enum { GAE_NEIGHBOUR_EXCLUDE_EDGES = 1 };
+enum { GAE_NEIGHBOUR_ERR_COLUMN = 1, GAE_NEIGHBOUR_ERR_ORDER = 2, GAE_NEIGHBOUR_ERR_QUERY = 4, GAE_NEIGHBOUR_ERR_TABLE = 8,
+       GAE_NEIGHBOUR_ERR_INDPTR = 16 };
+
+int gae_neighbour_degrees(const int32_t *indptr, const int32_t *indices, int64_t n, int64_t nnz, int32_t *deg,
+                          int64_t *status, void *stream);
+
+int gae_neighbour_pairs(const int32_t *indptr, const int32_t *indices, int64_t n, int64_t nnz, const int32_t *pair_i,
+                        const int32_t *pair_j, int64_t m, const int64_t *W, int64_t nw, int32_t *common_out,
+                        int64_t *wsum_out, int64_t *status, void *stream);
+
+int64_t gae_neighbour_topk_workspace_bytes(int64_t n, int64_t m);
+
+int gae_neighbour_topk(const int32_t *indptr, const int32_t *indices, int64_t n, int64_t nnz, const int32_t *rows,
+                       int64_t m, int64_t k, int kind, const int64_t *w, int64_t ldw, const int32_t *deg, int flags,
+                       int64_t table_slots, int32_t *index_out, int32_t *common_out, int64_t *wsum_out, int64_t *status,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
 int gae_x_decoder_bce_finalize(const gae_bce_tail *tail, void *stream);
