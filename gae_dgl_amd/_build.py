@@ -13,7 +13,7 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(LIBDIR, "libgae_hip.so")
 SOURCES = ["api.hip", "csr_build.hip", "plan_build.hip", "spmm.hip", "spmm_ell.hip", "dense.hip", "xw.hip", "tall.hip", "spfeat.hip", "decoder_bce.hip", "optim.hip", "readout.hip", "bce_dense.hip", "decoder_graphs.hip", "decoder_topk.hip", "decoder_sampled.hip",
-           "decoder_rank.hip", "decoder_threshold.hip", "embed.hip", "embed_bwd.hip", "kmeans.hip", "knn.hip", "ridge.hip", "forest.hip", "mlp.hip", "logreg.hip", "tsne.hip", "boost.hip", "pca.hip", "spectral.hip", "fingerprint.hip", "tanimoto.hip", "neighbours.hip"]
+           "decoder_rank.hip", "decoder_threshold.hip", "embed.hip", "embed_bwd.hip", "kmeans.hip", "knn.hip", "ridge.hip", "forest.hip", "mlp.hip", "logreg.hip", "tsne.hip", "boost.hip", "pca.hip", "spectral.hip", "fingerprint.hip", "tanimoto.hip", "neighbours.hip", "deepwalk.hip"]
 ARCH = "gfx950"
 # per-file extra flags.  decoder_bce: let MFMA accumulators live in VGPRs (gfx950 has a unified file) so the
 # VALU epilogue of every tile does not pay one v_accvgpr_read per logit.
@@ -25,6 +25,7 @@ ARCH = "gfx950"
 # pca: the same -- centring and every Jacobi rotation are restated by numpy operation for operation.
 # spectral: the same -- every chain of K32 is restated by numpy; products are fused exactly where fma is written.
 # neighbours: the same -- its one float operation, the fp64 quotient of the Jaccard key, is restated by numpy.
+# deepwalk: the same -- the coefficients, the fixed-point scatter and the Adagrad rule of K38 are restated by numpy.
 EXTRA_FLAGS = {"decoder_bce.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "decoder_rank.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "decoder_threshold.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
@@ -36,7 +37,8 @@ EXTRA_FLAGS = {"decoder_bce.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "boost.hip": ["-ffp-contract=off"],
                "pca.hip": ["-ffp-contract=off"],
                "spectral.hip": ["-ffp-contract=off"],
-               "neighbours.hip": ["-ffp-contract=off"]}
+               "neighbours.hip": ["-ffp-contract=off"],
+               "deepwalk.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -56,6 +56,11 @@ NEIGHBOUR_STATUS_WORDS = 4        # int64 error bits, short rows, long rows of t
 NEIGHBOUR_CN, NEIGHBOUR_JACCARD, NEIGHBOUR_AA, NEIGHBOUR_RA = 0, 1, 2, 3
 NEIGHBOUR_EXCLUDE_EDGES = 1
 NEIGHBOUR_ERR_COLUMN, NEIGHBOUR_ERR_ORDER, NEIGHBOUR_ERR_QUERY, NEIGHBOUR_ERR_TABLE, NEIGHBOUR_ERR_INDPTR = 1, 2, 4, 8, 16
+DEEPWALK_STATUS_WORDS, DEEPWALK_MAX_LENGTH = 4, 65536                  # GAE_DEEPWALK_*
+SGNS_MAX_LENGTH, SGNS_MAX_DIM, SGNS_MAX_NEGATIVES, SGNS_SCALE_BITS = 64, 128, 1024, 32    # GAE_SGNS_*
+DEEPWALK_ERR_COLUMN, DEEPWALK_ERR_INDPTR, DEEPWALK_ERR_START, DEEPWALK_ERR_RANGE = 1, 2, 4, 8
+DEEPWALK_ERR_NODE, DEEPWALK_ERR_ORDER, DEEPWALK_ERR_NONFINITE = 16, 32, 64
+DEEPWALK_WALK_DRAW, SGNS_NEG_DRAW, SGNS_INIT_DRAW = 0x3700000000, 0x3800000000, 0x3900000000
 TSNE_STATUS_WORDS = 8             # gae_tsne_status: int64 done, iteration, nonfinite, ticket; double p_log_d, log_z, grad2, z
 
 _i32, _i64, _u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
@@ -269,6 +274,12 @@ SIGNATURES = {
     "gae_neighbour_topk_workspace_bytes": (_i64, [_i64, _i64]),
     "gae_neighbour_topk": (_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _int, _p, _i64, _p, _int, _i64, _p, _p, _p, _p, _p, _i64,
                                   _p]),
+    "gae_random_walks": (_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _u64, _p, _p, _p]),
+    "gae_sgns_init": (_int, [_p, _i64, _i64, _u64, _f, _p]),
+    "gae_sgns_walk_order": (_int, [_i64, _u64, _i64, _p, _p]),
+    "gae_sgns_accumulate": (_int, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _u64, _i64, _p, _p, _p,
+                                   _p, _p, _p]),
+    "gae_sgns_update": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _f, _f, _p, _p]),
     "gae_embed_graphs_usable": (_int, [_i64, _i64, _p, _i64]),
     "gae_embed_graphs": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _int,
                                 _p, _i64, _p, _i64, _p]),

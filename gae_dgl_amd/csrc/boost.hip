@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include "forest_cells.h"
+#include "sigma64.h"
 
 namespace {
 
@@ -90,45 +91,10 @@ __device__ __forceinline__ void mark_bad(const Args &a, int m)
 }
 
 // ------------------------------------------------------------------------------------------------------ sigma
-// exp(-a) for 0 <= a <= 40, the stated sequence: k = rint(-a / ln 2), r = (-a - k ln2_hi) - k ln2_lo (|r| <= 0.3466), the
-// degree-13 Taylor polynomial of exp in Horner form, times 2^k built from its bits (exact)
-constexpr double kInvLn2 = 1.44269504088896338700e+00, kLn2Hi = 6.93147180369123816490e-01,
-                 kLn2Lo = 1.90821492927058770002e-10, kClamp = 40.0;
-
-__device__ __forceinline__ double exp_neg(double a)
-{
-    const double t = -a;
-    const double k = rint(t * kInvLn2);
-    const double r = (t - k * kLn2Hi) - k * kLn2Lo;
-    double p = 1.0 / 6227020800.0;
-    p = p * r + 1.0 / 479001600.0;
-    p = p * r + 1.0 / 39916800.0;
-    p = p * r + 1.0 / 3628800.0;
-    p = p * r + 1.0 / 362880.0;
-    p = p * r + 1.0 / 40320.0;
-    p = p * r + 1.0 / 5040.0;
-    p = p * r + 1.0 / 720.0;
-    p = p * r + 1.0 / 120.0;
-    p = p * r + 1.0 / 24.0;
-    p = p * r + 1.0 / 6.0;
-    p = p * r + 0.5;
-    p = p * r + 1.0;
-    p = p * r + 1.0;
-    return p * __longlong_as_double((i64(1023) + i64(k)) << 52);
-}
-
-__device__ __forceinline__ double clamp_abs(double F)
-{
-    const double a = fabs(F);
-    return a < kClamp ? a : kClamp;        // (a NaN takes the clamp)
-}
-
-// sigma(F) from e = exp(-min(|F|, 40)): q = e / (1 + e) is sigma(-|F|), the other side is 1 - q
-__device__ __forceinline__ double sigma_of(double F, double e)
-{
-    const double q = e / (1.0 + e);
-    return F >= 0.0 ? 1.0 - q : q;
-}
+// the stated fp64 sequence of sigma64.h (shared with K38): exp(-min(|F|, 40)), then q = e / (1 + e) or 1 - q
+using gae::sigma64::clamp_abs;
+using gae::sigma64::exp_neg;
+using gae::sigma64::sigma_of;
 
 // ------------------------------------------------------------------------------------------------------ a round
 __device__ __forceinline__ double leaf_weight(const Args &a, i64 G, i64 H, double lr, double lam)

@@ -26,6 +26,7 @@
 // plus 2 . 136 scaling values, 2 . 256 targets, 256 row ids and 16 words: 130 KB at 128 -> 128 -> 8, 38 KB at 48 -> 100 -> 1.
 // A shape whose sum passes 160 KB (two hidden layers of 128 behind 128 features) is refused by the workspace query.
 #include "common.h"
+#include "feistel.h"
 
 namespace {
 
@@ -265,23 +266,7 @@ __global__ __launch_bounds__(kThreads) void mlp_check_kernel(const FitArgs a)
     if (!ok) gae::add_count(&a.status->nonfinite_rows, 1);
 }
 
-// position p of epoch `epoch` -> an index of [0, ntr): four Feistel rounds on 2 `half` bits, cycle-walked
-__device__ __forceinline__ uint32_t shuffled(uint32_t p, uint32_t ntr, int half, uint64_t seed, uint32_t epoch)
-{
-    const uint32_t mask = (1u << half) - 1u;
-    uint32_t v = p;
-    do {
-        uint32_t hi = v >> half, lo = v & mask;
-        for (uint32_t r = 0; r < 4; ++r) {
-            uint32_t c[4];
-            gae::philox4x32_10((uint64_t(r) << 32) | lo, (uint64_t(1) << 32) + epoch, seed, c);
-            const uint32_t nx = hi ^ (c[0] & mask);
-            hi = lo; lo = nx;
-        }
-        v = (hi << half) | lo;
-    } while (v >= ntr);
-    return v;
-}
+using gae::feistel::shuffled;
 
 struct Rule {
     int solver;

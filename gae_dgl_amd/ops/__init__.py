@@ -5,7 +5,7 @@ hand-written HIP kernels from libgae_hip.so on PyTorch's current HIP stream.
 There is no CPU / eager fallback -- a CPU tensor raises.
 
 A package since round 6 (one 2 355-line module before): `_base` (plumbing, step context), `structure`, `aggregate`, `dense`,
-`vgae_heads`, `loss`, `graph_loss`, `topk`, `rank`, `threshold`, `sampled`, `embed`, `score`, `cluster`, `knn`, `ridge`, `forest`, `mlp`, `logreg`, `tsne`, `boost`, `pca`, `spectral`, `fingerprint`, `tanimoto`, `neighbours`, `layers`, `wide`.  Every name of the former module is re-exported here; the submodules resolve each
+`vgae_heads`, `loss`, `graph_loss`, `topk`, `rank`, `threshold`, `sampled`, `embed`, `score`, `cluster`, `knn`, `ridge`, `forest`, `mlp`, `logreg`, `tsne`, `boost`, `pca`, `spectral`, `fingerprint`, `tanimoto`, `neighbours`, `deepwalk`, `layers`, `wide`.  Every name of the former module is re-exported here; the submodules resolve each
 other through THIS namespace at call time, so `ops.FLAG = ...` and patched functions behave as they did."""
 from .. import _lib
 from .._lib import ACT_IDENTITY, ACT_RELU, BF16, F32, GaeHipError
@@ -35,6 +35,7 @@ from .spectral import *  # noqa: F401,F403
 from .fingerprint import *  # noqa: F401,F403
 from .tanimoto import *  # noqa: F401,F403
 from .neighbours import *  # noqa: F401,F403
+from .deepwalk import *  # noqa: F401,F403
 from .layers import *  # noqa: F401,F403
 from .wide import *  # noqa: F401,F403
 from ._base import _vp, _raw_stream, _stream_handle, _stream, _ptr, _gpu, _rowmajor, _f32, _dtype_code, _WS_CACHE, _STEP_STACK, _STEP_LOCK, _NO_STEP, _StackView, _step_stack, _workspace, _on_device  # noqa: F401

@@ -12,6 +12,8 @@ epochs, ``pos_weight`` from the dense label (train_transductive.py:41,43,49,
       [--pca K [--pca_out pca.npz]]
       [--spectral K [--spectral_self_loops] [--spectral_scaling none|degree|value] [--spectral_seed N] [--spectral_out sc.npz]]
       [--heuristics [cn|jaccard|aa|ra|pa ...] [--heuristics_out pairs.npz]]
+      [--deepwalk D [--deepwalk_walks R] [--deepwalk_length L] [--deepwalk_window W] [--deepwalk_epochs E] [--deepwalk_seed S]
+       [--deepwalk_out dw.npz]]
 
 ``--norm both`` applies the ``deg^-1/2`` normalisation the reference computes
 at :55-58 but never feeds to the model (north-star D^-1/2 A D^-1/2); the
@@ -138,6 +140,20 @@ def build_parser():
     ap.add_argument("--heuristics_out", default=None, metavar="PATH",
                     help="with --heuristics: write the per-pair tables to PATH (.npz: '{val,test}_{pos,neg}_pairs' int64 "
                          "[2, m] and '{val,test}_{pos,neg}_KIND' for common, deg_i, deg_j and every KIND)")
+    ap.add_argument("--deepwalk", type=int, default=None, metavar="D",
+                    help="with --eval: the DeepWalk baseline of the GAE tables -- a D-wide skip-gram embedding of random walks "
+                         "over the TRAINING graph (ops.deepwalk: synchronous mini-batch Adagrad with shared negatives, "
+                         "DeepWalk-like), scored like the model's embedding; with --cluster / --classify the same k-means and "
+                         "log-reg lines for it")
+    ap.add_argument("--deepwalk_walks", type=int, default=None, metavar="R", help="with --deepwalk: walks per node (default 10)")
+    ap.add_argument("--deepwalk_length", type=int, default=None, metavar="L", help="with --deepwalk: nodes per walk, 2..64 (default 40)")
+    ap.add_argument("--deepwalk_window", type=int, default=None, metavar="W",
+                    help="with --deepwalk: the skip-gram window, 1..L - 1 (default 5)")
+    ap.add_argument("--deepwalk_epochs", type=int, default=None, metavar="E", help="with --deepwalk: passes over the walks (default 3)")
+    ap.add_argument("--deepwalk_seed", type=int, default=None, metavar="S", help="with --deepwalk: the seed of the walks, the "
+                    "start table, the walk order and the negatives (default 0)")
+    ap.add_argument("--deepwalk_out", default=None, metavar="PATH",
+                    help="with --deepwalk: write PATH (.npz with 'embedding' and 'context' fp32 [N, D], 'walks' int32 and 'counts')")
     return ap
 
 
@@ -214,6 +230,28 @@ def parse_args(argv=None):
             ap.error("--heuristics_out needs --heuristics")
     elif not args.eval:
         ap.error("--heuristics needs --eval (it scores the held-out edges)")
+    if args.deepwalk is None:
+        if any(v is not None for v in (args.deepwalk_walks, args.deepwalk_length, args.deepwalk_window, args.deepwalk_epochs,
+                                       args.deepwalk_seed, args.deepwalk_out)):
+            ap.error("--deepwalk_walks / --deepwalk_length / --deepwalk_window / --deepwalk_epochs / --deepwalk_seed / "
+                     "--deepwalk_out need --deepwalk D")
+    else:
+        if not 1 <= args.deepwalk <= 128:
+            ap.error(f"--deepwalk {args.deepwalk}: D must lie in 1..128")
+        if not args.eval:
+            ap.error("--deepwalk needs --eval (it scores the held-out edges)")
+        if args.deepwalk_walks is not None and args.deepwalk_walks < 1:
+            ap.error(f"--deepwalk_walks {args.deepwalk_walks}: R must be at least 1")
+        length = 40 if args.deepwalk_length is None else args.deepwalk_length
+        if not 2 <= length <= 64:
+            ap.error(f"--deepwalk_length {length}: L must lie in 2..64")
+        window = 5 if args.deepwalk_window is None else args.deepwalk_window
+        if not 1 <= window < length:
+            ap.error(f"--deepwalk_window {window}: W must lie in 1..L - 1 = {length - 1}")
+        if args.deepwalk_epochs is not None and args.deepwalk_epochs < 1:
+            ap.error(f"--deepwalk_epochs {args.deepwalk_epochs}: E must be at least 1")
+        if args.deepwalk_seed is not None and args.deepwalk_seed < 0:
+            ap.error(f"--deepwalk_seed {args.deepwalk_seed}: S must be at least 0")
     return args
 
 
@@ -447,6 +485,40 @@ def main(argv=None):
         if args.spectral_out is not None:
             np.savez(args.spectral_out, embedding=sc.embedding.cpu().numpy(), vectors=sc.vectors.cpu().numpy(),
                      values=sc.values.cpu().numpy(), residuals=sc.residuals.cpu().numpy())
+    if args.deepwalk is not None:
+        import numpy as np
+        D = args.deepwalk
+        dw = ops.deepwalk(g, D, walks_per_node=args.deepwalk_walks or 10, walk_length=args.deepwalk_length or 40,
+                          window=args.deepwalk_window or 5, epochs=args.deepwalk_epochs or 3, seed=args.deepwalk_seed or 0)
+        main.last_deepwalk = {"result": dw}
+        for name, pairs in held_out.items():
+            scores = metrics.evaluate(dw.embedding, pairs)
+            print(f"deepwalk ({D}) {name} ROC-AUC: {scores['auc']:.4f} | AP: {scores['ap']:.4f}")
+            main.last_deepwalk[name] = scores
+        if args.cluster is not None:
+            res = ops.kmeans(dw.embedding, args.cluster, seed=args.cluster_seed or 0)
+            print(f"deepwalk k-means K = {args.cluster}: inertia {res.inertia:.6g} | iterations: {res.n_iter}"
+                  f"{'' if res.converged else ' (not converged)'} | sizes: {res.counts.tolist()}")
+            main.last_deepwalk["cluster"] = {"result": res}
+            if data.labels is not None:
+                cm = metrics.clustering_metrics(res.labels.cpu().numpy(), data.labels)
+                print(f"deepwalk NMI: {cm['nmi']:.4f} | ARI: {cm['ari']:.4f} | ACC: {cm['acc']:.4f}")
+                main.last_deepwalk["cluster"].update(cm)
+        if args.classify is not None and main.last_classify is not None:
+            # the split and the folds of the model's own head, so the two lines compare like with like
+            test = main.last_classify["test"]
+            labels = torch.as_tensor(data.labels, dtype=torch.int64, device=device)
+            F = args.classify_folds or 5
+            res = ops.logreg(dw.embedding, labels, lambdas=args.classify or None, folds=F, fold=fold.to(device))
+            zt = dw.embedding.index_select(0, test.to(device)).contiguous()
+            pred, proba = ops.logreg_predict(zt, res.coef, res.intercept, res.pivot, proba=True)
+            cm = metrics.classification_metrics(pred, labels[test.to(device)], proba, n_classes=res.coef.shape[0])
+            print(f"deepwalk LogReg ({F}-fold CV, lambda = {res.lam:g}) test accuracy: {cm['accuracy']:.4f} | "
+                  f"macro-F1: {cm['macro_f1']:.4f} | log-loss: {cm['log_loss']:.4f}")
+            main.last_deepwalk["classify"] = {"result": res, "metrics": cm, "pred": pred}
+        if args.deepwalk_out is not None:
+            np.savez(args.deepwalk_out, embedding=dw.embedding.cpu().numpy(), context=dw.context.cpu().numpy(),
+                     walks=dw.walks.cpu().numpy(), counts=dw.counts.cpu().numpy())
     if args.heuristics is not None:
         import numpy as np
         kinds = list(dict.fromkeys(args.heuristics)) or list(HEURISTIC_KINDS)

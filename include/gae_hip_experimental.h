@@ -1444,6 +1444,88 @@ int gae_neighbour_topk(const int32_t *indptr, const int32_t *indices, int64_t n,
                        int64_t table_slots, int32_t *index_out, int32_t *common_out, int64_t *wsum_out, int64_t *status,
                        void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- K37 / K38: the DeepWalk baseline (ops.random_walks, ops.sgns_noise_table, ops.sgns_train, ops.deepwalk)
+ * Uniform random walks over a CSR and a skip-gram trainer with negative sampling.  The trainer is SYNCHRONOUS mini-batch
+ * Adagrad with negatives shared per walk -- DeepWalk-like, not a port of word2vec's asynchronous loop (which depends on
+ * the order of its threads): every run gives the same bits, and a numpy restatement of this comment matches them.  No
+ * n x n object is formed, no float atomic is used.  philox(ctr, draw, key) below is philox4x32_10 of csrc/common.h; word
+ * i is its i-th 32-bit output.
+ *
+ * K37 gae_random_walks
+ *   GRAPH  int64 indptr [n + 1], int32 indices [nnz], walked as stored: duplicate entries count with their multiplicity,
+ *     a self-loop is stepped like any entry, a directed graph is walked along whatever the rows list (the library's
+ *     graph.csr() lists, for a node, the SOURCES of its incoming edges: a walk steps against the edge direction; on a
+ *     symmetric graph there is no difference).  n < 2^31; a row holds fewer than 2^32 entries.
+ *   WALKS  starts int32 [m] or NULL (then m <= n and start s is node s); r = walks_per_start; L = length, 1 <= L <= 2^16;
+ *     m r < 2^31.  walks int32 [m r, L], dense.  Walk id w = rep m + s (rep = 0 .. r - 1).  Position 0 is the start.  Step
+ *     t >= 1 from node v: deg = indptr[v + 1] - indptr[v]; word = word (t & 3) of philox(w, GAE_DEEPWALK_WALK_DRAW + (t >>
+ *     2), seed); the walk moves to indices[indptr[v] + ((uint64(word) deg) >> 32)].  Integers only.  deg = 0 ends the walk:
+ *     the remaining positions are -1.
+ *   STATUS  int64 [GAE_DEEPWALK_STATUS_WORDS], zeroed by the caller; word 0 the error bits: GAE_DEEPWALK_ERR_COLUMN (a
+ *     column outside [0, n) was drawn: the walk ends there), _ERR_INDPTR (a row pointer outside [0, nnz], descending, or a
+ *     row of 2^32 entries: read as an empty row), _ERR_START (a start outside [0, n): that walk is all -1).
+ *
+ * K38 gae_sgns_init / gae_sgns_walk_order / gae_sgns_accumulate / gae_sgns_update
+ *   STATE  W (input table, the embedding) and C (context table), fp32 [n, d] dense; the Adagrad sums HW, HC fp32 [n, d];
+ *     the accumulators AW, AC int64 [n, d], zero between batches (the caller zeroes them once, the update leaves zeros).
+ *   LIMITS  1 <= d <= 128; 2 <= L <= 64; 1 <= window < L; M = shared_negatives in {16, 32, 48, 64}; 0 <= K = negatives <=
+ *     1024; n, n_walks < 2^31; 0 <= epoch < 2^31: anything else is GAE_E_RANGE / GAE_E_SIZE, never another route.
+ *   INIT  gae_sgns_init: element e of W (row-major) = (2 u - 1) bound in three fp32 operations (2 u, minus 1, times bound), u
+ *     = float(word >> 8) 2^-24, word = word (e & 3) of philox(e >> 2, GAE_SGNS_INIT_DRAW, seed) (K27's draw).
+ *   ORDER  gae_sgns_walk_order: order[p] = K27's keyed permutation of [0, n_walks) at position p of `epoch` (four Feistel
+ *     rounds on 2 half bits, 4^half >= n_walks, round r: F = word 0 of philox((r << 32) | lo, 2^32 + epoch, seed); (hi, lo)
+ *     <- (lo, hi ^ (F & mask)); cycle-walked until the value is below n_walks).  A batch is `count` consecutive positions
+ *     from `first`.
+ *   PER WALK w = order[position] of the batch (gae_sgns_accumulate):
+ *   1 ROWS  ids = the walk's L nodes; a position is VALID when its id is not -1.  Ww = W[ids], Cw = C[ids]; an invalid
+ *     position stands as a row of +0 (its coefficients are +0 as well: it never changes a chain of finite values).
+ *   2 NEGATIVES  slot s = 0 .. M - 1: (w0, w1, w2, w3) = philox((epoch << 32) | w, GAE_SGNS_NEG_DRAW + (s >> 1), seed); u =
+ *     (uint64(w[2 (s & 1) + 1]) << 32) | w[2 (s & 1)]; target = the high 64 bits of u cum[n]; neg[s] = the largest i of [0,
+ *     n) with cum[i] <= target, by bisection (lo = 0, hi = n; mid = lo + ((hi - lo) >> 1); cum[mid] <= target moves lo, else
+ *     hi; until hi - lo = 1).  cum int64 [n + 1] ascending from 0: a node of zero width is never drawn.  Cn = C[neg].
+ *   3 LOGITS  S = Ww Cw^T (L x L), N = Ww Cn^T (L x M): every element ONE fp32 fma chain from +0 over the feature index
+ *     ascending (v_mfma_f32_16x16x4_f32, K27's contract; the zero padding of d and L to 16 is exact).
+ *   4 COEFFICIENTS  (p, j) is a positive iff 0 < |p - j| <= window and both positions are valid; c(p) = the positives of
+ *     row p.  Gp[p, j] = float(sigma64(-double(S[p, j]))) on positives, +0 elsewhere.  coef(p) = float(K c(p)) / float(M),
+ *     one fp32 division.  Gn[p, s] = -(coef(p) * float(sigma64(double(N[p, s])))), one fp32 product, and +0 where neg[s] ==
+ *     ids[p] or p is invalid.  sigma64 is K30's sigma (its comment above; csrc/sigma64.h).  The M shared negatives weighted
+ *     by K c(p) / M give every positive pair K negatives in expectation.
+ *   5 GRADIENTS  fp32 fma chains from +0 again, masked terms staying in the chain with their +0 coefficient:  dW[p] over the
+ *     contexts j ascending, then the negatives s ascending, of Gp[p, j] Cw[j] and Gn[p, s] Cn[s];  dCw[j] over p ascending of
+ *     Gp[p, j] Ww[p];  dCn[s] over p ascending of Gn[p, s] Ww[p].
+ *   6 SCATTER  every element x of dW, dCw (valid positions) and dCn becomes llrint(double(x) 2^32) (ties to even) and is added
+ *     to AW[ids[p]], AC[ids[j]], AC[neg[s]] by a 64-bit integer atomic: exact and order-free; sums wrap as int64.  |x| >=
+ *     2^20 or a non-finite x sets GAE_DEEPWALK_ERR_RANGE and is not added.
+ *   UPDATE  gae_sgns_update, per element of W and of C whose accumulator a is not 0 (the others are untouched), single
+ *     correctly rounded fp32 operations in this order:  g = float(double(a) 2^-32);  h = fmaf(g, g, h);  s = sqrtf(h) + eps;
+ *     q = g / s;  x = fmaf(lr, q, x);  then a = 0.  (The gradient is that of the log-likelihood: the step ascends.)  A
+ *     non-finite x or h sets GAE_DEEPWALK_ERR_NONFINITE.
+ *   STATUS  the block of K37; further bits: _ERR_RANGE, _ERR_NONFINITE, _ERR_NODE (a walk-table entry outside [-1, n): read
+ *     as -1), _ERR_ORDER (an order entry outside [0, n_walks): that walk is skipped).  The wrapper reads it once per epoch.
+ * Argument errors are returned before anything is dereferenced or launched (GAE_E_SIZE, GAE_E_RANGE, GAE_E_NULL). */
+enum { GAE_DEEPWALK_STATUS_WORDS = 4, GAE_DEEPWALK_MAX_LENGTH = 65536, GAE_SGNS_MAX_LENGTH = 64, GAE_SGNS_MAX_DIM = 128,
+       GAE_SGNS_MAX_NEGATIVES = 1024, GAE_SGNS_SCALE_BITS = 32 };
+enum { GAE_DEEPWALK_ERR_COLUMN = 1, GAE_DEEPWALK_ERR_INDPTR = 2, GAE_DEEPWALK_ERR_START = 4, GAE_DEEPWALK_ERR_RANGE = 8,
+       GAE_DEEPWALK_ERR_NODE = 16, GAE_DEEPWALK_ERR_ORDER = 32, GAE_DEEPWALK_ERR_NONFINITE = 64 };
+#define GAE_DEEPWALK_WALK_DRAW 0x3700000000ull
+#define GAE_SGNS_NEG_DRAW 0x3800000000ull
+#define GAE_SGNS_INIT_DRAW 0x3900000000ull
+
+int gae_random_walks(const int64_t *indptr, const int32_t *indices, int64_t n, int64_t nnz, const int32_t *starts, int64_t m,
+                     int64_t walks_per_start, int64_t length, uint64_t seed, int32_t *walks, int64_t *status, void *stream);
+
+int gae_sgns_init(float *W, int64_t n, int64_t d, uint64_t seed, float bound, void *stream);
+
+int gae_sgns_walk_order(int64_t n_walks, uint64_t seed, int64_t epoch, int32_t *order, void *stream);
+
+int gae_sgns_accumulate(const int32_t *walks, int64_t n_walks, int64_t length, const int32_t *order, int64_t first,
+                        int64_t count, const int64_t *cum, int64_t n, int64_t d, int64_t window, int64_t negatives,
+                        int64_t shared_negatives, uint64_t seed, int64_t epoch, const float *W, const float *C, int64_t *AW,
+                        int64_t *AC, int64_t *status, void *stream);
+
+int gae_sgns_update(float *W, float *C, float *HW, float *HC, int64_t *AW, int64_t *AC, int64_t n, int64_t d, float lr,
+                    float eps, int64_t *status, void *stream);
+
 int gae_x_decoder_bce_defer_finalize(gae_bce_tail *tail_out);
 
 int gae_x_decoder_bce_finalize(const gae_bce_tail *tail, void *stream);
