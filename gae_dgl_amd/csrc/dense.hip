@@ -1750,7 +1750,7 @@ extern "C" int gae_decoder_dense_bwd(const float *G, int64_t ldg, const float *Z
     GAE_REQUIRE(G && Z && dZ, GAE_E_NULL, "gae_decoder_dense_bwd: NULL pointer");
     hipStream_t s = gae::as_stream(stream);
     const AtbPlan pl = atb_plan(n, d, n);
-    const int64_t need = atb_partial_bytes(pl);
+    const int64_t need = atb_partial_bytes(pl) + 256;      // what gae_decoder_dense_bwd_workspace_bytes reports
     GAE_REQUIRE(workspace && workspace_bytes >= need, GAE_E_WORKSPACE,
                 "gae_decoder_dense_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
     int rc;

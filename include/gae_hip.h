@@ -413,7 +413,8 @@ int gae_dropout_mask(float *mask, int64_t n_elems, float p, uint64_t seed, uint6
                      const uint64_t *draw_dev, void *stream);
 int gae_decoder_dense(const float *Z, const float *mask, int64_t ldz, int64_t n, int64_t d,
                       float *out, int64_t ldo, void *stream);
-/* dZ = ((G + G^T) Zt) (.) mask,  G = dL/dlogits [n, n]  (autograd of gae.py:70-71) */
+/* dZ = ((G + G^T) Zt) (.) mask,  G = dL/dlogits [n, n]  (autograd of gae.py:70-71).
+ * workspace: at least gae_decoder_dense_bwd_workspace_bytes(n, d) bytes (GAE_E_WORKSPACE below that). */
 int64_t gae_decoder_dense_bwd_workspace_bytes(int64_t n, int64_t d);
 int gae_decoder_dense_bwd(const float *G, int64_t ldg, const float *Z, const float *mask,
                           int64_t ldz, int64_t n, int64_t d, float *dZ, int64_t lddz,
